@@ -9,8 +9,15 @@ Contract (driver):  python bench.py --gpus N --steps K --warmup W
   LOCAL_RANK / WORLD_SIZE / MASTER_* set) it is one rank per GPU; WORLD_SIZE must equal --gpus.
   Rank 0 prints ONE JSON line.
 
---config selects the BASELINE.json configuration (all print the same JSON shape with "roofline",
-"cpu_baseline" and an in-run "parity" block against the C oracle):
+A plain run does only what the headline figure needs: set-up, W warm-up steps, the K timed steps,
+the JSON line (metric, value, unit, ms_per_step, ...).  --dump-outputs DIR also writes what the
+timed path computed in its last timed step as DIR/<name>.npy (float32 / float64, at most 64 MB;
+inputs are seeded, so two builds can be compared output for output).  Everything else below -
+CPU baseline, parity, roofline, single_stream, sustained, instrumented, other_configs and the
+one-GPU figure of the N-GPU workload - is measured with --full only.
+
+--config selects the BASELINE.json configuration (with --full all print the same JSON shape with
+"roofline", "cpu_baseline" and an in-run "parity" block against the C oracle):
   replay     (default) configs[1]: a 1k-scan replay, 360 beams, ICP.process + Mapping.update per
              scan into a 400x400 @ 0.05 m grid; a step is --traj = 32 independent replays of that
              trajectory in one slam_replay_dev call (a map each).  With N > 1: configs[3], one
@@ -134,7 +141,12 @@ def parse():
     ap.add_argument("--sustain-seconds", type=float, default=None,
                     help="length of the sustained continuation behind the K steps (default: 3 s for the headline replay configuration, so that "
                          "a 5-second utilisation sampler sees the GPU busy; 0.5 s for every other measurement)")
-    ap.add_argument("--check", action="store_true", help="(kept for compatibility: the parity block is always on)")
+    ap.add_argument("--check", action="store_true", help="(kept for compatibility: the parity block is always on with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline K steps: CPU baseline, in-run parity, roofline, one-lane repeat, sustained continuation, "
+                         "other configurations (the --no-* options above switch parts of it off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last timed step as DIR/<name>.npy (float32 / float64, at most 64 MB)")
     args = ap.parse_args()
     cfg = CONFIGS[args.config]
     if args.scans is None:
@@ -352,6 +364,28 @@ def lane_stream(torch, local, idx, n_lanes):
     return _LANE_STREAMS[key]
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_MAP_BYTES = 48 << 20       # the occupancy maps' share of it (poses, transforms and iteration counts take the rest)
+
+
+def map_sample(n_maps, cells):
+    """Indices of the maps --dump-outputs writes (as float32): all of them if they fit in DUMP_MAP_BYTES, else a fixed
+    seeded sample of as many as fit."""
+    k = max(1, min(n_maps, DUMP_MAP_BYTES // (4 * cells)))
+    return np.arange(n_maps) if k == n_maps else np.sort(np.random.default_rng(0).choice(n_maps, k, replace=False))
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy (float64 as computed, everything else as float32)."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64 if v.dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py: --dump-outputs would write %.1f MB, more than %d MB" % (total / 1e6, DUMP_LIMIT_BYTES >> 20))
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+
+
 class ReplayWorkload:
     """configs[1] / [3] / [4]: per lane a DeviceReplay + map + pmap; a step runs on lane slot % lanes."""
     family_kernels = {"icp": "k_icp", "grid": "k_grid_update_win", "compose": "k_pose_compose", "finalize": "k_grid_finalize"}
@@ -432,6 +466,14 @@ class ReplayWorkload:
             d.update(ln.grid.read(l, want=("pass", "hit")))
             dev.append(d)
         return dev
+
+    def outputs(self):
+        """What a caller of the last step receives: poses [L, n_scan-1, 3], transforms [L, n_scan-1, 3, 3], iteration counts
+        [L, n_scan-1] and the finalized maps (pmap, 0 / 50 / 100) of the trajectories pmap_index names."""
+        ln = self.last_lane()
+        poses, T, iters = ln.dr.results()
+        idx = map_sample(self.traj, self.args.grid * self.args.grid)
+        return {"poses": poses, "T": T, "iters": iters, "pmap": ln.pmap.cpu().numpy()[idx], "pmap_index": idx}
 
     def parity(self, dev):
         """EVERY trajectory of the last step against the oracle (the L trajectories of a step replay the same scans: the
@@ -558,6 +600,16 @@ class ParticleWorkload:
         self.visits = sum(ln.grid.visits() for ln in self.lanes) / max(self.done, 1)     # per step (the maps are never reset)
         return {"poses": t["poses"].cpu().numpy(), "T": t["T"].cpu().numpy(), "iters": self.iters}
 
+    def outputs(self):
+        """What a caller of the last step receives: poses [P, 3], transforms [P, 9], iteration counts [P] and the live pmaps
+        (accumulated over every step of that lane) of the particles pmap_index names."""
+        ln = self.lanes[(self.done - 1) % len(self.lanes)]
+        for c in self.contexts():
+            c.check_status()
+        idx = map_sample(self.P, self.args.grid * self.args.grid)
+        return {"poses": ln.t["poses"].cpu().numpy(), "T": ln.t["T"].cpu().numpy(), "iters": ln.t["iters"].cpu().numpy(),
+                "pmap": np.stack([ln.grid.read(int(p))["pmap"] for p in idx]), "pmap_index": idx}
+
     def parity(self, dev):
         from oracle import checks
         a, P = self.args, self.P
@@ -613,9 +665,10 @@ def config_args(base, name):
     return a
 
 
-def measure(args, env, collective=True, want_single=True, want_sustained=True):
+def measure(args, env, collective=True, want_single=True, want_sustained=True, full=True, dump=None):
     """One workload of --config: warm-up, the timed K steps (barrier + synchronize on both sides, MAX over ranks),
-    the sustained continuation, the one-lane repeat.  Returns a dict of raw results; nothing is printed."""
+    the sustained continuation, the one-lane repeat.  Returns a dict of raw results; nothing is printed.
+    full=False: warm-up and the K steps only.  dump: directory for the outputs of the last of the K steps (dump_outputs)."""
     slam, torch, dist = env.slam, env.torch, env.dist
     use_dist = env.use_dist and collective
     world = env.world if use_dist else 1
@@ -687,10 +740,12 @@ def measure(args, env, collective=True, want_single=True, want_sustained=True):
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if dump:
+        dump_outputs(dump, wl.outputs())
     res = {"wl": wl, "elapsed": elapsed, "elapsed_local": elapsed_local, "enqueue": enqueue, "fam": fam, "closing_ms": closing_ms,
-           "n_ranks": world, "dev_results": wl.collect(), "single": None, "sustained": None, "fam_note": None,
+           "n_ranks": world, "dev_results": wl.collect() if full else None, "single": None, "sustained": None, "fam_note": None,
            "timing_mask": [dominant] if lean else ("all" if not args.no_timing else []), "instrumented": None, "single_pipelined": None}
-    if args.no_timing:
+    if args.no_timing or not full:
         return res
     if lean:
         # the same K steps once more with events on EVERY family's dispatches (how rounds 1-2 measured `value`): the
@@ -923,6 +978,8 @@ def assemble_line(args, n_ranks, value, ms_per_step, enqueue_ms, closing_ms, wor
                                   (", all_gather of final poses (%s)" % args.gather if use_dist else "")},
         "roofline": roofline,
     }
+    if roofline is None:                            # (a plain run: the roofline is measured with --full)
+        del out["roofline"]
     if timing_mask is not None:
         out["timing_mask"] = timing_mask            # kernel families whose dispatches carried HIP events in the timed K steps
     if instrumented:
@@ -973,7 +1030,7 @@ def _child_leg(extra, roofline=True):
     32 trajectories per call on two other contexts first (dense 1.47-1.56 against 1.65 M scans/s in a process of its own, one
     trajectory on 4 contexts 9.0 against 11.4 M; two-lane legs are not affected) - the figure a user of `bench.py --config dense`
     gets is the one of a fresh process.  This process only waits meanwhile (it starts no other program in place of itself)."""
-    cmd = [sys.executable, os.path.abspath(__file__)] + extra + ["--no-cpu-baseline", "--no-other-configs"]
+    cmd = [sys.executable, os.path.abspath(__file__)] + extra + ["--full", "--no-cpu-baseline", "--no-other-configs"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     p = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900)
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -1053,7 +1110,7 @@ def main():
         torch.cuda.set_device(local)
         # BEFORE the process group exists: rank 0 times its own share of the N-GPU workload alone (same scans, same lanes,
         # no collective), so that the line carries the one-GPU figure of the SAME workload
-        if rank == 0 and not args.no_timing:
+        if rank == 0 and not args.no_timing and args.full:
             env1 = Env(slam, torch, None, 0, 1, local, False)
             r1 = measure(args, env1, collective=False, want_single=True, want_sustained=False)
             same_workload = {"value": r1["wl"].units_per_step * args.steps / r1["elapsed"], "unit": "scans/s", "ms_per_step": r1["elapsed"] / args.steps * 1e3,
@@ -1082,8 +1139,10 @@ def main():
     for li in range(4):                 # the lanes' streams first, before any other stream of the process (see lane_stream)
         lane_stream(torch, local, li, 4)
     env = Env(slam, torch, dist, rank, world, local, use_dist)
-    cpu = cpu_baseline_first(slam, args, rank) if rank == 0 and world == 1 and not args.no_cpu_baseline else None
-    res = measure(args, env, want_single=not args.no_single_stream and not use_dist, want_sustained=not use_dist)
+    cpu = cpu_baseline_first(slam, args, rank) if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline else None
+    # (a plain run stops after the K steps, which carry the same HIP events as with --full: the same headline measurement)
+    res = measure(args, env, want_single=not args.no_single_stream and not use_dist, want_sustained=not use_dist, full=args.full,
+                  dump=args.dump_outputs if rank == 0 else None)
     wl = res["wl"]
     n_ranks = dist.get_world_size() if use_dist else 1
     value = wl.units_per_step * n_ranks * args.steps / res["elapsed"]
@@ -1098,14 +1157,14 @@ def main():
 
     if use_dist and same_workload and rank == 0:
         res["single"] = same_single          # stand-alone kernel durations of the same workload: roofline.frac keeps its meaning under a process group
-    roofline = roofline_of(args, res)
-    parity = wl.parity(res["dev_results"]) if rank == 0 and not args.no_parity else None
+    roofline = roofline_of(args, res) if args.full else None
+    parity = wl.parity(res["dev_results"]) if args.full and rank == 0 and not args.no_parity else None
     single, sustained = res["single"], res["sustained"]
 
     # ---- the other single-GPU configurations of BASELINE.json, briefly, in the same process (outside every timed region
     #      above): configs[2] (particles) and configs[4] (dense), each with its own roofline and parity block ----------
     others = None
-    if args.config == "replay" and not use_dist and not args.no_other_configs and rank == 0:
+    if args.full and args.config == "replay" and not use_dist and not args.no_other_configs and rank == 0:
         res["workload_name"], res["units"], res["lanes"] = wl.workload_name(), wl.units_per_step, len(wl.contexts())
         wl.close()
         del res["wl"], wl

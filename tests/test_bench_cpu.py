@@ -123,3 +123,25 @@ def test_source_stamp_ignores_comments_and_blank_lines(tmp_path, monkeypatch):
     assert bench.source_hash() == h0
     (csrc / "a.hip").write_text("int f(int x)\n{\n    return x + 2;\n}\n")
     assert bench.source_hash() != h0
+
+
+def test_dump_outputs_writes_float_arrays_within_64_mb(tmp_path):
+    """--dump-outputs: every array as <name>.npy in float64 (as computed) or float32, maps as a fixed seeded sample where all of
+    them would not fit, and nothing at all past 64 MB."""
+    import numpy as np
+    import pytest
+    sys.path.insert(0, ROOT)
+    import bench
+    assert np.array_equal(bench.map_sample(32, 400 * 400), np.arange(32))          # the default replay's 32 maps fit
+    idx = bench.map_sample(10000, 400 * 400)                                        # the particles' 10 000 do not
+    assert 1 <= len(idx) and len(idx) * 4 * 400 * 400 <= bench.DUMP_MAP_BYTES and np.all(np.diff(idx) > 0) and idx[-1] < 10000
+    assert np.array_equal(idx, bench.map_sample(10000, 400 * 400))                  # the same sample every run
+    bench.dump_outputs(str(tmp_path / "out"), {"poses": np.full((2, 3), 0.1), "iters": np.arange(4, dtype=np.int32),
+                                               "pmap": np.full((2, 4, 4), 50, dtype=np.int8)})
+    assert sorted(os.listdir(tmp_path / "out")) == ["iters.npy", "pmap.npy", "poses.npy"]
+    poses, iters, pmap = (np.load(tmp_path / "out" / (k + ".npy")) for k in ("poses", "iters", "pmap"))
+    assert poses.dtype == np.float64 and np.all(poses == 0.1)
+    assert iters.dtype == np.float32 and np.array_equal(iters, np.arange(4)) and pmap.dtype == np.float32 and np.all(pmap == 50)
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": np.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1, dtype=np.float32)})
+    assert not (tmp_path / "big").exists()

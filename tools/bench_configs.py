@@ -34,7 +34,7 @@ def via_bench(extra, check=True):
     each with roofline, cpu_baseline and an in-run parity block against the C oracle; this runs
     one of them as a child process and returns its JSON line."""
     import subprocess
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline"] + list(extra)
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline"] + list(extra)
     if not check:
         cmd.append("--no-parity")
     out = subprocess.run(cmd, capture_output=True, text=True, check=True).stdout

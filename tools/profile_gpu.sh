@@ -24,7 +24,7 @@ case $CFG in
   particles) STEPS="--steps 12 --warmup 3"; PSTEPS="--steps 6 --warmup 6";;   # (PMC figures from the later half of the launches: settled maps)
   *)      STEPS="--steps 12 --warmup 3"; PSTEPS="--steps 3 --warmup 1";;
 esac
-COMMON="--config $CFG --no-cpu-baseline --no-single-stream --no-other-configs --sustain-seconds 0 --particle-chunks 1"
+COMMON="--full --config $CFG --no-cpu-baseline --no-single-stream --no-other-configs --sustain-seconds 0 --particle-chunks 1"
 # shellcheck disable=SC2086
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_default" -- python3 "$R/bench.py" $COMMON $STEPS \
     > "$OUT/bench_default_under_rocprof.json" 2> "$OUT/trace_default.err" || { echo "kernel trace (default) failed"; tail -5 "$OUT/trace_default.err"; exit 1; }
@@ -54,5 +54,5 @@ fi
 # the summary first (it puts this run's PMC figures under profiles/ of this copy of the tree), then the plain bench line that
 # reads them, then the summary again to file that line with the rest
 python3 "$R/tools/summarize_profiles.py" "$OUT" "$TAG" "$CFG" > /dev/null
-python3 "$R/bench.py" --config $CFG --no-other-configs $STEPS > "$OUT/bench.json" 2> "$OUT/bench.err" || { echo "bench failed"; tail -5 "$OUT/bench.err"; exit 1; }
+python3 "$R/bench.py" --full --config $CFG --no-other-configs $STEPS > "$OUT/bench.json" 2> "$OUT/bench.err" || { echo "bench failed"; tail -5 "$OUT/bench.err"; exit 1; }
 python3 "$R/tools/summarize_profiles.py" "$OUT" "$TAG" "$CFG"

@@ -24,7 +24,7 @@ def main():
         L, lanes = (int(v) for v in pt.split("x"))
         steps = a.steps or max(8, (48 // L) - (48 // L) % lanes)
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", a.config, "--traj", str(L), "--lanes", str(lanes), "--steps", str(steps),
-               "--warmup", str(max(2, lanes)), "--no-cpu-baseline", "--no-other-configs", "--no-parity", "--sustain-seconds", "0.5"]
+               "--warmup", str(max(2, lanes)), "--full", "--no-cpu-baseline", "--no-other-configs", "--no-parity", "--sustain-seconds", "0.5"]
         if not a.single:
             cmd.append("--no-single-stream")
         cmd += a.extra.split()
