@@ -324,6 +324,25 @@ struct ReplaySource {
     __device__ int scans_per_traj() const { return n_scan - 1; }
     __device__ int own_grid(int l) const { return grid_per_traj ? l : 0; }
     bool maps_are_private() const { return grid_per_traj != 0; }
+    // the same streams from trajectory l0 on; scans k0 .. k0 + cnt - 1 of trajectory 0 (launches split by launch_in_chunks)
+    ReplaySource trajectories_from(int l0) const
+    {
+        ReplaySource r = *this;
+        const size_t k = (size_t)l0 * (n_scan - 1);
+        r.ranges += (size_t)l0 * traj_stride; r.poses += 3 * k;
+        if (centres) r.centres += 2 * k;
+        if (heading_cs) r.heading_cs += 2 * k;
+        return r;
+    }
+    ReplaySource scans_from(int k0, int cnt) const
+    {
+        ReplaySource r = *this;
+        r.ranges += (size_t)k0 * n; r.poses += 3 * (size_t)k0;
+        if (centres) r.centres += 2 * (size_t)k0;
+        if (heading_cs) r.heading_cs += 2 * (size_t)k0;
+        r.n_scan = cnt + 1;
+        return r;
+    }
     __device__ void scan_const(int l, int k, const GridDev &g, ScanConst &sc) const
     {
         const double *pose = poses + 3 * ((size_t)l * (n_scan - 1) + k);
@@ -377,6 +396,14 @@ struct ExplicitSource {
     __device__ int scans_per_traj() const { return B; }
     __device__ int own_grid(int) const { return 0; }
     bool maps_are_private() const { return false; }
+    ExplicitSource trajectories_from(int) const { return *this; }          // (one stream)
+    ExplicitSource scans_from(int k0, int cnt) const
+    {
+        ExplicitSource r = *this;
+        r.ox += (size_t)k0 * n; r.oy += (size_t)k0 * n; r.cx += k0; r.cy += k0;
+        r.B = cnt;
+        return r;
+    }
     __device__ void scan_const(int, int k, const GridDev &g, ScanConst &sc) const
     {
         sc.px = cx[k]; sc.py = cy[k]; sc.c = 1.0; sc.s = 0.0;
@@ -2200,6 +2227,36 @@ bool tiles_apply(const GridDev &g, int n, const int32_t *got, int grid_per_traj,
     return (!got || wedges) && !grid_per_traj && (long)g.xw * g.yw > 8L * kWinCells && n <= kTileMaxBeams;
 }
 
+// The casts for large maps take at most kMaxLaunchGroups groups of scans in one launch (k_tile_cast: a row of gridDim.y per
+// group; k_wedge_cast: a unit number of 20 bits, group x class).  A larger cast goes as successive launches on the same
+// stream, over whole trajectories, or over scan ranges where one trajectory alone has more groups (ranges of whole groups
+// of G scans).  The counters are integer sums and the visit counter one more, so the split gives the maps of one launch
+// bit for bit; `one(src, L, scans, got)` is the launcher of a piece, whose scratch the next piece reuses in stream order.
+constexpr int kMaxLaunchGroups = 65535;
+
+template <class Src, class One>
+static hipError_t launch_in_chunks(const Src &src, int L, int scans, int G, const int32_t *got, One &&one)
+{
+    if (src.maps_are_private()) return hipErrorInvalidValue;        // (the maps travel in `got` here)
+    const int groups_per_traj = (scans + G - 1) / G;
+    if (groups_per_traj <= kMaxLaunchGroups) {
+        const int per = kMaxLaunchGroups / groups_per_traj;
+        for (int l0 = 0; l0 < L; l0 += per) {
+            hipError_t e = one(src.trajectories_from(l0), std::min(per, L - l0), scans, got ? got + l0 : nullptr);
+            if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+    }
+    const int span = kMaxLaunchGroups * G;
+    for (int l = 0; l < L; ++l)
+        for (int k0 = 0; k0 < scans; k0 += span) {
+            const int cnt = std::min(span, scans - k0);
+            hipError_t e = one(src.trajectories_from(l).scans_from(k0, cnt), 1, cnt, got ? got + l : nullptr);
+            if (e != hipSuccess) return e;
+        }
+    return hipSuccess;
+}
+
 template <class Src>
 static hipError_t launch_tiles(const GridDev &g, const Src &src, int L, int scans, int n, int group, void *scratch, hipStream_t s)
 {
@@ -2214,7 +2271,10 @@ static hipError_t launch_tiles(const GridDev &g, const Src &src, int L, int scan
         while (scans % G != 0) --G;
     const int groups_per_traj = (scans + G - 1) / G;
     const long groups = (long)L * groups_per_traj, rays = (long)L * scans * n;
-    if (groups > 65535) return hipErrorInvalidValue;
+    if (groups > kMaxLaunchGroups)
+        return launch_in_chunks(src, L, scans, G, nullptr, [&](const Src &cs, int cl, int cscans, const int32_t *) {
+            return launch_tiles(g, cs, cl, cscans, n, G, scratch, s);
+        });
     TileScratch ts;
     char *p = static_cast<char *>(scratch);
     ts.recs = reinterpret_cast<RayRec *>(p); p += (size_t)rays * sizeof(RayRec);
@@ -2684,9 +2744,13 @@ static hipError_t launch_wedges(const GridDev &g, const Src &src, int L, int sca
     G = std::min(G, std::max(1, 65535 / n));
     G = std::min(G, scans);
     if ((long)G * n > 65535) return hipErrorInvalidValue;   // (ray numbers inside a group are 16-bit: keys[], ws.list[])
+    if (g.xw > 65535 || g.yw > 65535) return hipErrorInvalidValue;   // (end cells travel as 16-bit pairs)
     const int groups_per_traj = (scans + G - 1) / G;
     const long groups = (long)L * groups_per_traj, rays = (long)L * scans * n;
-    if (groups > 65535 || g.xw > 65535 || g.yw > 65535) return hipErrorInvalidValue;   // (end cells travel as 16-bit pairs)
+    if (groups > kMaxLaunchGroups)
+        return launch_in_chunks(src, L, scans, G, got, [&](const Src &cs, int cl, int cscans, const int32_t *cgot) {
+            return launch_wedges(g, cs, cl, cscans, n, G, scratch, s, cgot);
+        });
     WedgeScratch ws;
     char *p = static_cast<char *>(scratch);
     ws.ends = reinterpret_cast<uint32_t *>(p); p += (size_t)rays * 4;

@@ -1305,7 +1305,6 @@ int slam_particles_dev(slam_ctx *c, const float *ranges2, const double *cos_t, c
     size_t ds = dtype_size(dtype);
     REQUIRE(ds, "unknown dtype");
     REQUIRE(!grid || grid->d.G >= P, "the grid object needs one map per particle");
-    REQUIRE(!grid || P <= 65535, "at most 65535 particles per call when ray casting");
     // Chunks (option "particle_chunks", off by default): matcher and pose step of chunk k on the context's stream, its ray
     // cast on a second stream behind an event, beside the matcher of chunk k + 1.  The matcher is bound by vector issue and
     // the ray cast by memory traffic, so the two should share the chip well - they do not (measured, round 4: 10 000
@@ -1463,7 +1462,7 @@ int slam_virtual_scan_dev(slam_ctx *c, const double *ox, const double *oy, int K
 {
     TRY(use(c));
     REQUIRE((K == 0 || (ox && oy)) && poses && ranges_out, "null pointer");
-    REQUIRE(K >= 0 && B > 0 && n > 0 && n <= 8192 && B <= 65535, "bad sizes");
+    REQUIRE(K >= 0 && B > 0 && n > 0 && n <= 8192, "bad sizes");
     REQUIRE(angle_increment != 0.0 && std::isfinite(angle_increment) && std::isfinite(angle_min), "bad angles");
     HIPCHK(launch_virtual_scan(ox, oy, K, poses, B, angle_min, angle_increment, n, ranges_out, c->stream));
     return SLAM_OK;
