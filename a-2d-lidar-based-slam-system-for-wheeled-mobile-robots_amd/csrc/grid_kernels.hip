@@ -107,7 +107,7 @@ __device__ __forceinline__ unsigned wave_sum_u32(unsigned v)
     return v;
 }
 
-// Shared tail of the two update kernels: per-wave aggregation of the origin cell and of
+// Tail of the direct kernel (k_grid_update): per-wave aggregation of the origin cell and of
 // the visit counter, and the sticky status word.
 __device__ __forceinline__ void finish_wave(const GridDev &g, uint32_t *pass, int pcx, int pcy, bool first_pending,
                                             unsigned nvis, int bad)
@@ -122,135 +122,6 @@ __device__ __forceinline__ void finish_wave(const GridDev &g, uint32_t *pass, in
         if (tot) atomicAdd(visit_slot(g.visits), (unsigned long long)tot);
         if (anybad) atomicOr(g.status, anybad);
     }
-}
-
-// Mapping.update for B scans given world-frame endpoints: one workgroup per scan, one
-// lane per beam (a workgroup never spans two scans, so the origin cell is wave-uniform).
-__global__ void __launch_bounds__(256) k_grid_update(GridDev g, const double *__restrict__ ox, const double *__restrict__ oy,
-                                                     const double *__restrict__ cx, const double *__restrict__ cy, int n,
-                                                     const int32_t *__restrict__ gob)
-{
-    __shared__ int first_bad;
-    const int b = blockIdx.x;
-    const int gi = gob ? gob[b] : 0;
-    uint32_t *pass = g.pass + (size_t)gi * g.xw * g.yw, *hit = g.hit + (size_t)gi * g.xw * g.yw;
-    int cbad = 0;                                                    // the origin is the same for every beam;
-    const int pcx = to_cell(cx[b], g.scale, g.off_x, cbad);          // :35  a bad origin only raises if some
-    const int pcy = to_cell(cy[b], g.scale, g.off_y, cbad);          // :36  beam is actually cast
-    // the scan stops at its first beam that Python's int() would raise on (mapping.py:29-36: the beams before it have been
-    // applied when the exception leaves update(), and the error is that beam's): find it before anything is cast
-    if (threadIdx.x == 0) first_bad = INT_MAX;
-    __syncthreads();
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        const double x = ox[(size_t)b * n + i], y = oy[(size_t)b * n + i];
-        if (fabs(x) == INFINITY) continue;                           // mapping.py:30: only ox is tested
-        int bad = cbad;
-        (void)to_cell(x, g.scale, g.off_x, bad);
-        (void)to_cell(y, g.scale, g.off_y, bad);
-        if (bad) atomicMin(&first_bad, i);
-    }
-    __syncthreads();
-    const int stop = first_bad;
-    for (int base = 0; base < n; base += blockDim.x) {
-        int i = base + threadIdx.x;
-        int bad = 0;
-        bool first_pending = false;
-        unsigned nvis = 0;
-        if (i < n && i <= stop) {
-            double x = ox[(size_t)b * n + i], y = oy[(size_t)b * n + i];
-            if (!(fabs(x) == INFINITY)) {                            // mapping.py:30: only ox is tested
-                int pox = to_cell(x, g.scale, g.off_x, bad);        // :33
-                int poy = to_cell(y, g.scale, g.off_y, bad);        // :34
-                bad |= cbad;
-                if (!bad) nvis = cast_ray(pass, hit, g.xw, g.yw, pcx, pcy, pox, poy, first_pending);
-            }
-        }
-        finish_wave(g, pass, pcx, pcy, first_pending, nvis, bad);
-    }
-}
-
-// Replay form: the world-frame endpoints are formed here from the raw ranges and the
-// dead-reckoned pose (slam_ekf.py:89 with u2T of :130-137 and laserToNumpy of :115-123),
-// all in float64 whatever storage type the ICP point buffers use, so cells never depend
-// on that choice.  Block (k-1, l) handles scan k of trajectory l.
-__global__ void __launch_bounds__(256) k_grid_update_replay(GridDev g, const float *__restrict__ ranges,
-                                                            const double *__restrict__ cos_t, const double *__restrict__ sin_t,
-                                                            const double *__restrict__ poses, int n_scan, int n,
-                                                            const int32_t *__restrict__ got)
-{
-    __shared__ int first_bad;
-    const int km1 = blockIdx.x, l = blockIdx.y;
-    const int gi = got ? got[l] : 0;
-    uint32_t *pass = g.pass + (size_t)gi * g.xw * g.yw, *hit = g.hit + (size_t)gi * g.xw * g.yw;
-    const double *pose = poses + 3 * ((size_t)l * (n_scan - 1) + km1);
-    const double px = pose[0], py = pose[1];
-    const double c = cos(pose[2]), s = sin(pose[2]);
-    const float *r = ranges + ((size_t)l * n_scan + km1 + 1) * n;
-    int cbad = 0;
-    const int pcx = to_cell(px, g.scale, g.off_x, cbad);
-    const int pcy = to_cell(py, g.scale, g.off_y, cbad);
-    auto world = [&](int i, double &x, double &y) {
-        double rr = (double)r[i];
-        if (rr == INFINITY) rr = 30.0;                               // slam_ekf.py:119
-        double lx = cos_t[i] * rr, ly = sin_t[i] * rr;               // :122
-        x = c * lx + (-s) * ly + px * 1.0;                           // u2T(pose).dot(pc), :89
-        y = s * lx + c * ly + py * 1.0;
-    };
-    // (the scan stops at its first beam int() would raise on, see k_grid_update)
-    if (threadIdx.x == 0) first_bad = INT_MAX;
-    __syncthreads();
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        double x, y;
-        world(i, x, y);
-        if (fabs(x) == INFINITY) continue;
-        int bad = cbad;
-        (void)to_cell(x, g.scale, g.off_x, bad);
-        (void)to_cell(y, g.scale, g.off_y, bad);
-        if (bad) atomicMin(&first_bad, i);
-    }
-    __syncthreads();
-    const int stop = first_bad;
-    for (int base = 0; base < n; base += blockDim.x) {
-        int i = base + threadIdx.x;
-        int bad = 0;
-        bool first_pending = false;
-        unsigned nvis = 0;
-        if (i < n && i <= stop) {
-            double x, y;
-            world(i, x, y);
-            if (!(fabs(x) == INFINITY)) {
-                int pox = to_cell(x, g.scale, g.off_x, bad);
-                int poy = to_cell(y, g.scale, g.off_y, bad);
-                bad |= cbad;
-                if (!bad) nvis = cast_ray(pass, hit, g.xw, g.yw, pcx, pcy, pox, poy, first_pending);
-            }
-        }
-        finish_wave(g, pass, pcx, pcy, first_pending, nvis, bad);
-    }
-}
-
-static inline int ray_block(int n)
-{
-    int blk = ((n + kWave - 1) / kWave) * kWave;
-    return blk > 256 ? 256 : (blk < kWave ? kWave : blk);
-}
-
-hipError_t launch_grid_update(const GridDev &g, const double *ox, const double *oy, const double *cx, const double *cy,
-                              int B, int n, const int32_t *gob, hipStream_t s)
-{
-    if (g.pmap_live && g.live_dirty) *g.live_dirty = true;
-    SLAM_LAUNCH(k_grid_update, dim3(B), dim3(ray_block(n)), 0, s, g, ox, oy, cx, cy, n, gob);
-    return hipGetLastError();
-}
-
-hipError_t launch_grid_update_replay(const GridDev &g, const float *ranges, const double *cos_t, const double *sin_t,
-                                     const double *poses, int L, int n_scan, int n, const int32_t *got, hipStream_t s)
-{
-    if (n_scan < 2) return hipSuccess;
-    if (g.pmap_live && g.live_dirty) *g.live_dirty = true;
-    SLAM_LAUNCH(k_grid_update_replay, dim3(n_scan - 1, L), dim3(ray_block(n)), 0, s, g, ranges, cos_t, sin_t,
-                       poses, n_scan, n, got);
-    return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------------
@@ -426,6 +297,40 @@ struct ExplicitSource {
         return ray(fetch(l, k, i), sc, g, pox, poy, bad);
     }
 };
+
+// Direct global atomics (Mapping.update as written): block (k, l) casts scan k of trajectory l, one lane per beam (a
+// workgroup never spans two scans, so the origin cell is wave-uniform).  `maps` (nullable) names the map of every scan
+// of explicit endpoints, of every trajectory of a replay.
+template <class Src>
+__global__ void __launch_bounds__(256) k_grid_update(GridDev g, Src src, const int32_t *__restrict__ maps)
+{
+    __shared__ int first_bad;
+    const int k = blockIdx.x, l = blockIdx.y, n = src.n;
+    const int gi = maps ? maps[std::is_same<Src, ExplicitSource>::value ? k : l] : 0;
+    uint32_t *pass = g.pass + (size_t)gi * g.xw * g.yw, *hit = g.hit + (size_t)gi * g.xw * g.yw;
+    ScanConst sc;                                                    // the origin is the same for every beam; a bad
+    src.scan_const(l, k, g, sc);                                     // origin only raises if some beam is actually cast
+    // the scan stops at its first beam that Python's int() would raise on (mapping.py:29-36: the beams before it have been
+    // applied when the exception leaves update(), and the error is that beam's): find it before anything is cast
+    if (threadIdx.x == 0) first_bad = INT_MAX;
+    __syncthreads();
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        int bad = 0, pox, poy;
+        (void)src.ray(l, k, i, sc, g, pox, poy, bad);                // (a skipped beam, mapping.py:30, leaves bad at 0)
+        if (bad) atomicMin(&first_bad, i);
+    }
+    __syncthreads();
+    const int stop = first_bad;
+    for (int base = 0; base < n; base += blockDim.x) {
+        int i = base + threadIdx.x;
+        int bad = 0, pox, poy;
+        bool first_pending = false;
+        unsigned nvis = 0;
+        if (i < n && i <= stop && src.ray(l, k, i, sc, g, pox, poy, bad))
+            nvis = cast_ray(pass, hit, g.xw, g.yw, sc.pcx, sc.pcy, pox, poy, first_pending);
+        finish_wave(g, pass, sc.pcx, sc.pcy, first_pending, nvis, bad);
+    }
+}
 
 // LDS byte address of a pointer into shared memory, and a fire-and-forget 32-bit add at such an address
 typedef __attribute__((address_space(3))) unsigned lds_u32_t;
@@ -1881,40 +1786,6 @@ static int pick_group(int group, long total_scans, int scans_per_traj, int n)
     return group;
 }
 
-hipError_t launch_grid_update_win(const GridDev &g, const double *ox, const double *oy, const double *cx, const double *cy,
-                                  int B, int n, int group, hipStream_t s, int split_pref)
-{
-    int G = pick_group(group, B, B, n);
-    if (G == 0) return launch_grid_update(g, ox, oy, cx, cy, B, n, nullptr, s);
-    ExplicitSource src{ox, oy, cx, cy, B, n};
-    return launch_win(g, src, 1, B, n, G, nullptr, s, split_pref);
-}
-
-hipError_t launch_grid_update_replay_win(const GridDev &g, const float *ranges, const double *cos_t, const double *sin_t,
-                                         const double *poses, int L, int n_scan, int n, const int32_t *got, int group,
-                                         hipStream_t s, int shared_scans, int grid_per_traj, const double *heading_cs, int split_pref)
-{
-    if (n_scan < 2) return hipSuccess;
-    int G = pick_group(group, (long)L * (n_scan - 1), n_scan - 1, n);
-    if (G == 0) {
-        if (shared_scans || grid_per_traj) return hipErrorInvalidValue;   // n too large for the window kernel
-        return launch_grid_update_replay(g, ranges, cos_t, sin_t, poses, L, n_scan, n, got, s);
-    }
-    ReplaySource src{ranges, cos_t, sin_t, poses, n_scan, n, shared_scans ? 0L : (long)n_scan * n, grid_per_traj, nullptr, heading_cs};
-    return launch_win(g, src, L, n_scan - 1, n, G, got, s, split_pref);
-}
-
-// S scans cast from given poses, optionally with ray origins of their own.
-hipError_t launch_grid_update_scans(const GridDev &g, const float *ranges, const double *cos_t, const double *sin_t,
-                                    const double *poses, const double *centres, int S, int n, int group, hipStream_t s, int split_pref)
-{
-    int G = pick_group(group, S, S, n);
-    if (G == 0) return hipErrorInvalidValue;                          // n too large for the window kernel
-    // the replay source reads scan k+1 of a stream of n_scan = S+1: shift the base by one scan
-    ReplaySource src{ranges - n, cos_t, sin_t, poses, S + 1, n, 0L, 0, centres};
-    return launch_win(g, src, 1, S, n, G, nullptr, s, split_pref);
-}
-
 // ---------------------------------------------------------------------------------
 // Tiled ray casting for maps far larger than one LDS window (DESIGN.md "K4 tiles"; the
 // 2000x2000 @ 0.02 m map of BASELINE.json configs[4], where a scan's rays cover ~800 k cells
@@ -2214,17 +2085,10 @@ __global__ void __launch_bounds__(1024) k_tile_cast(GridDev g, TileScratch ts, i
     lds_guard_check(guard, g.status);
 }
 
-size_t tile_scratch_bytes(long rays, long groups)
+static size_t tile_scratch_bytes(long rays, long groups)
 {
     // (groups: an upper bound is enough - one per scan)
     return (size_t)rays * (sizeof(RayRec) + kTileWords * 4 + kTileWords * 2) + (size_t)groups * 16 + 1024;
-}
-
-bool tiles_apply(const GridDev &g, int n, const int32_t *got, int grid_per_traj, int wedges)
-{
-    // maps much larger than a window; a group's ray count must fit the 16-bit counters.  The recorded-walk tiles cast into ONE
-    // shared map; the direction wedges also take a map per trajectory (`got`: dense replays in batches, bench.py --config dense --traj)
-    return (!got || wedges) && !grid_per_traj && (long)g.xw * g.yw > 8L * kWinCells && n <= kTileMaxBeams;
 }
 
 // The casts for large maps take at most kMaxLaunchGroups groups of scans in one launch (k_tile_cast: a row of gridDim.y per
@@ -2299,29 +2163,6 @@ static hipError_t launch_tiles(const GridDev &g, const Src &src, int L, int scan
     hipLaunchKernelGGL(k_tile_cast, dim3(tiles_x * tiles_y, (unsigned)groups), dim3(1024), lds, s, g, ts, tiles_x, G * n, rays);
     if (timed) (void)hipEventRecord(ev1, s);
     return hipGetLastError();
-}
-
-template <class Src>
-static hipError_t launch_wedges(const GridDev &g, const Src &src, int L, int scans, int n, int group, void *scratch, hipStream_t s, const int32_t *got = nullptr);
-
-hipError_t launch_grid_update_tiles(const GridDev &g, const float *ranges, const double *cos_t, const double *sin_t,
-                                    const double *poses, const double *centres, int L, int n_scan, int n, int group,
-                                    void *scratch, hipStream_t s, int wedges, const int32_t *got)
-{
-    if (n_scan < 2) return hipSuccess;
-    ReplaySource src{ranges, cos_t, sin_t, poses, n_scan, n, (long)n_scan * n, 0, centres};
-    if (wedges) return launch_wedges(g, src, L, n_scan - 1, n, group, scratch, s, got);
-    if (got) return hipErrorInvalidValue;                            // (the recorded-walk tiles know one shared map)
-    return launch_tiles(g, src, L, n_scan - 1, n, group, scratch, s);
-}
-
-// explicit world-frame endpoints (Mapping.update's own arguments), B scans into one map
-hipError_t launch_grid_update_tiles_explicit(const GridDev &g, const double *ox, const double *oy, const double *cx,
-                                             const double *cy, int B, int n, int group, void *scratch, hipStream_t s, int wedges)
-{
-    ExplicitSource src{ox, oy, cx, cy, B, n};
-    if (wedges) return launch_wedges(g, src, 1, B, n, group, scratch, s);
-    return launch_tiles(g, src, 1, B, n, group, scratch, s);
 }
 
 // ---------------------------------------------------------------------------------
@@ -2731,7 +2572,7 @@ __global__ void __launch_bounds__(kWedgeThreads, 2 * kWedgeThreads / 256) k_wedg
     lds_guard_check(guard, g.status);
 }
 
-size_t wedge_scratch_bytes(long rays, long scans, long groups)
+static size_t wedge_scratch_bytes(long rays, long scans, long groups)
 {
     return (size_t)rays * 6 + (size_t)scans * 4 + (size_t)groups * (kWedgeClasses + 1) * 4 + (size_t)groups * kWedgeClasses * 8 + (size_t)(rays / kWedgePartMin + 1) * 4 + 4096;
 }
@@ -2774,6 +2615,73 @@ static hipError_t launch_wedges(const GridDev &g, const Src &src, int L, int sca
     SLAM_LAUNCH(k_wedge_order, dim3(1), dim3(1024), 0, s, ws, (int)(groups * kWedgeClasses), part_rays);
     SLAM_LAUNCH(k_wedge_cast, dim3((unsigned)max_parts), dim3(kWedgeThreads), lds_b, s, g, ws, n, G, scans, part_rays);
     return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------
+// Which engine casts a batch of scans.  big: the map has more than eight windows of cells (xw * yw > 8 * kWinCells);
+// wok: the direction wedges take the map (grid_mode != 2, both sides <= 65 535 cells, as the end cells travel as 16-bit
+// pairs).  First match wins:
+//
+//   entry                                  condition                                           path
+//   slam_grid_update[_dev]                 grid_of_batch given                                 Direct (any mode)
+//                                          mode 1, 2 or 4, n <= 8192, (big or mode 2, 4)       Wedges if wok, else Tiles
+//                                          mode != 0, n <= 65 535                              Window
+//                                          otherwise                                           Direct
+//   slam_replay*, slam_grid_update_scans*  mode 1, 2 or 4, n <= 8192, (big or mode 2, 4),      Wedges if wok, else Tiles
+//                                          and with grid_of_traj given also wok
+//                                          mode != 0                                           Window (with centres: one stream)
+//                                          mode 0 with centres                                 SLAM_ERR_INVALID (the caller's)
+//                                          mode 0                                              Direct
+//   slam_particles* with a grid            always, any mode and map size                       Window
+//
+// Window is launch_win, which chooses the owner8 / owner / k_grid_update_win kernels itself.  The replay entries take at
+// most 65 535 beams, so one Window rule serves both forms.  n <= 8192 (kTileMaxBeams): ray numbers inside a group of the
+// tiles and wedges are 16-bit.
+// ---------------------------------------------------------------------------------
+constexpr int kTileMaxBeams = 8192;
+
+CastPath plan_cast(const GridDev &g, int mode, const CastRequest &r)
+{
+    if (r.particles) return CastPath::Window;
+    if (r.ox && r.maps) return CastPath::Direct;
+    const bool big = (long)g.xw * g.yw > 8L * kWinCells;
+    const bool wok = mode != 2 && g.xw <= 65535 && g.yw <= 65535;
+    if ((mode == 1 || mode == 2 || mode == 4) && r.n <= kTileMaxBeams && (big || mode == 2 || mode == 4) && (!r.maps || wok))
+        return wok ? CastPath::Wedges : CastPath::Tiles;
+    return mode != 0 && r.n <= 65535 ? CastPath::Window : CastPath::Direct;
+}
+
+size_t cast_scratch_bytes(CastPath p, const CastRequest &r)
+{
+    // the wedges keep 6 bytes per ray (end cell, sorted ray number), the recorded walks ~400; groups: one per scan bounds them
+    const long rays = (long)r.L * r.scans * r.n, groups = (long)r.L * r.scans;
+    if (p == CastPath::Wedges) return wedge_scratch_bytes(rays, groups, groups);
+    if (p == CastPath::Tiles) return tile_scratch_bytes(rays, groups);
+    return 0;
+}
+
+template <class Src>
+static hipError_t launch_cast(const GridDev &g, CastPath p, const Src &src, const CastRequest &r, void *scratch, hipStream_t s)
+{
+    switch (p) {
+    case CastPath::Wedges: return launch_wedges(g, src, r.L, r.scans, r.n, r.group, scratch, s, r.maps);
+    case CastPath::Tiles: return launch_tiles(g, src, r.L, r.scans, r.n, r.group, scratch, s);
+    case CastPath::Window:
+        return launch_win(g, src, r.L, r.scans, r.n, pick_group(r.group, (long)r.L * r.scans, r.scans, r.n), r.maps, s, r.split);
+    case CastPath::Direct: break;
+    }
+    if (g.pmap_live && g.live_dirty) *g.live_dirty = true;
+    const int block = std::min(256, std::max(kWave, (r.n + kWave - 1) / kWave * kWave));
+    SLAM_LAUNCH((k_grid_update<Src>), dim3(r.scans, r.L), dim3(block), 0, s, g, src, r.maps);
+    return hipGetLastError();
+}
+
+hipError_t launch_cast(const GridDev &g, CastPath p, const CastRequest &r, void *scratch, hipStream_t s)
+{
+    if (r.ox) return launch_cast(g, p, ExplicitSource{r.ox, r.oy, r.cx, r.cy, r.scans, r.n}, r, scratch, s);
+    const ReplaySource src{r.ranges, r.cos_t, r.sin_t, r.poses, r.scans + 1, r.n, r.particles ? 0L : (long)(r.scans + 1) * r.n,
+                           r.particles, r.centres, r.heading_cs};
+    return launch_cast(g, p, src, r, scratch, s);
 }
 
 __global__ void __launch_bounds__(256) k_grid_finalize(const uint32_t *__restrict__ pass, const uint32_t *__restrict__ hit,

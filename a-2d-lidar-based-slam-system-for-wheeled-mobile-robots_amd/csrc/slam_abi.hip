@@ -233,10 +233,6 @@ int use(slam_ctx *c)
     return SLAM_OK;
 }
 
-// maps much larger than a window: direction wedges (grid_mode 1 automatic, 4) unless the recorded-walk tiles are asked
-// for (2) or the map's sides exceed what the wedges' packed end cells hold
-int wedges_ok(const slam_ctx *c, const slam_grid *g) { return c->grid_mode != 2 && g->d.xw <= 65535 && g->d.yw <= 65535; }
-
 // stream of the pipelined map stage
 hipStream_t gs(slam_ctx *c) { return c->pipeline ? c->gstream : c->stream; }
 
@@ -888,17 +884,13 @@ int slam_grid_update_dev(slam_ctx *c, slam_grid *g, const double *ox, const doub
     REQUIRE(B > 0 && n > 0, "sizes must be positive");
     g->pristine = false;
     Timed t(c, SLAM_K_GRID);
-    // (forced tiles / wedges keep the bound of the automatic choice on the beam count: ray numbers inside a group are 16-bit)
-    const bool tiles_ok = !grid_of_batch && (tiles_apply(g->d, n, nullptr, 0) || ((c->grid_mode == 2 || c->grid_mode == 4) && n <= kTileMaxBeams));
-    if ((c->grid_mode == 1 || c->grid_mode == 2 || c->grid_mode == 4) && tiles_ok) {
-        size_t need = wedges_ok(c, g) ? wedge_scratch_bytes((long)B * n, B, B) : tile_scratch_bytes((long)B * n, B);
-        if (need > c->tiles.cap) TRY(arena_reserve(c, c->tiles, need));
-        HIPCHK(launch_grid_update_tiles_explicit(g->d, ox, oy, cx, cy, B, n, c->grid_group, c->tiles.base, c->stream, wedges_ok(c, g)));
-    } else if (c->grid_mode != 0 && !grid_of_batch) {
-        HIPCHK(launch_grid_update_win(g->d, ox, oy, cx, cy, B, n, c->grid_group, c->stream, c->grid_split));
-    } else {
-        HIPCHK(launch_grid_update(g->d, ox, oy, cx, cy, B, n, grid_of_batch, c->stream));
-    }
+    CastRequest r;
+    r.ox = ox; r.oy = oy; r.cx = cx; r.cy = cy; r.scans = B; r.n = n; r.maps = grid_of_batch;
+    r.group = c->grid_group; r.split = c->grid_split;
+    const CastPath path = plan_cast(g->d, c->grid_mode, r);
+    const size_t need = cast_scratch_bytes(path, r);
+    if (need > c->tiles.cap) TRY(arena_reserve(c, c->tiles, need));
+    HIPCHK(launch_cast(g->d, path, r, c->tiles.base, c->stream));
     return SLAM_OK;
 }
 
@@ -922,34 +914,25 @@ int slam_grid_update(slam_ctx *c, slam_grid *g, const double *ox, const double *
     return check_status_sync(c);
 }
 
-// Ray cast of L streams x (n_scan - 1) scans into `g` on stream st, choosing the kernel:
-// grid_mode 0 direct atomics, 1 automatic (LDS window; recorded walks + tiles for maps much
-// larger than a window), 2 always tiles (where they apply), 3 always the window.
+// Ray cast of L streams x (n_scan - 1) scans into `g` on stream st, along the path plan_cast picks for grid_mode
+// (0 direct atomics, 1 automatic, 2 recorded walks + tiles, 3 LDS window, 4 direction wedges).
 static int cast_replay(slam_ctx *c, slam_grid *g, const float *ranges, const double *cos_t, const double *sin_t,
                        const double *poses, const double *centres, int L, int n_scan, int n, const int32_t *got,
                        hipStream_t st)
 {
     g->pristine = false;
-    const bool tiles_ok = tiles_apply(g->d, n, got, 0, wedges_ok(c, g)) ||
-                          ((c->grid_mode == 2 || c->grid_mode == 4) && (!got || (c->grid_mode == 4 && wedges_ok(c, g))) && n <= kTileMaxBeams);
-    if ((c->grid_mode == 1 || c->grid_mode == 2 || c->grid_mode == 4) && tiles_ok) {
-        long rays = (long)L * (n_scan - 1) * n, groups = (long)L * (n_scan - 1);
-        // the wedges keep 6 bytes per ray (end cell, sorted ray number); the recorded walks of grid_mode 2 ~400
-        size_t need = wedges_ok(c, g) ? wedge_scratch_bytes(rays, groups, groups) : tile_scratch_bytes(rays, groups);
-        if (need > c->tiles.cap) {
-            if (c->gstream) HIPCHK(hipStreamSynchronize(c->gstream));
-            TRY(arena_reserve(c, c->tiles, need));
-        }
-        HIPCHK(launch_grid_update_tiles(g->d, ranges, cos_t, sin_t, poses, centres, L, n_scan, n, c->grid_group, c->tiles.base, st, wedges_ok(c, g), got));
-        return SLAM_OK;
+    CastRequest r;
+    r.ranges = ranges; r.cos_t = cos_t; r.sin_t = sin_t; r.poses = poses; r.centres = centres;
+    r.L = L; r.scans = n_scan - 1; r.n = n; r.maps = got;
+    r.group = c->grid_group; r.split = c->grid_split;
+    const CastPath path = plan_cast(g->d, c->grid_mode, r);
+    REQUIRE(path != CastPath::Direct || !centres, "grid_mode 0 has no separate ray origins");
+    const size_t need = cast_scratch_bytes(path, r);
+    if (need > c->tiles.cap) {
+        if (c->gstream) HIPCHK(hipStreamSynchronize(c->gstream));
+        TRY(arena_reserve(c, c->tiles, need));
     }
-    if (c->grid_mode != 0) {
-        if (centres) HIPCHK(launch_grid_update_scans(g->d, ranges + n, cos_t, sin_t, poses, centres, n_scan - 1, n, c->grid_group, st, c->grid_split));
-        else HIPCHK(launch_grid_update_replay_win(g->d, ranges, cos_t, sin_t, poses, L, n_scan, n, got, c->grid_group, st, 0, 0, nullptr, c->grid_split));
-        return SLAM_OK;
-    }
-    REQUIRE(!centres, "grid_mode 0 has no separate ray origins");
-    HIPCHK(launch_grid_update_replay(g->d, ranges, cos_t, sin_t, poses, L, n_scan, n, got, st));
+    HIPCHK(launch_cast(g->d, path, r, c->tiles.base, st));
     return SLAM_OK;
 }
 
@@ -1370,9 +1353,12 @@ int slam_particles_dev(slam_ctx *c, const float *ranges2, const double *cos_t, c
             const size_t off = (size_t)p0 * d.xw * d.yw;
             d.G = pc; d.pass += off; d.hit += off;
             if (d.pmap_live) d.pmap_live += off;
+            CastRequest r;                                             // one scan per hypothesis into its own map (no scratch)
+            r.ranges = ranges2; r.cos_t = cos_t; r.sin_t = sin_t; r.poses = poses_out + 3 * (size_t)p0;
+            r.heading_cs = heading_cs + 2 * (size_t)p0;
+            r.L = pc; r.scans = 1; r.n = n; r.particles = true; r.group = 1;
             Timed t(c, SLAM_K_GRID, nullptr, k == 0);
-            HIPCHK(launch_grid_update_replay_win(d, ranges2, cos_t, sin_t, poses_out + 3 * (size_t)p0, pc, 2, n, nullptr, 1, st,
-                                                 /*shared_scans=*/1, /*grid_per_traj=*/1, heading_cs + 2 * (size_t)p0));
+            HIPCHK(launch_cast(d, plan_cast(d, c->grid_mode, r), r, nullptr, st));
             if (chunks > 1) HIPCHK(hipEventRecord(c->pev_cast[k], c->pstream));
         }
     }

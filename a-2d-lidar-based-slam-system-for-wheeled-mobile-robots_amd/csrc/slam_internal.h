@@ -151,35 +151,25 @@ struct GridDev {
     double free_inc, hit_inc;
 };
 
-hipError_t launch_grid_update(const GridDev &g, const double *ox, const double *oy, const double *cx,
-                              const double *cy, int B, int n, const int32_t *grid_of_batch, hipStream_t s);
-// world points are formed in-kernel from ranges and poses (slam_ekf.py:89): scan k>=1 of
-// trajectory l uses poses[l][k-1].
-hipError_t launch_grid_update_replay(const GridDev &g, const float *ranges, const double *cos_t,
-                                     const double *sin_t, const double *poses, int L, int n_scan, int n,
-                                     const int32_t *grid_of_traj, hipStream_t s);
-// LDS-window variants (group = scans per workgroup, 0 = automatic); they fall back to the
-// direct-atomic kernels when a scan has too many beams for the packed window counters.
-// split_pref: two workgroups per group of scans, one per direction half: -1 = when the launch cannot fill the chip, 0 = never, 1 = always
-hipError_t launch_grid_update_win(const GridDev &g, const double *ox, const double *oy, const double *cx,
-                                  const double *cy, int B, int n, int group, hipStream_t s, int split_pref = -1);
-hipError_t launch_grid_update_replay_win(const GridDev &g, const float *ranges, const double *cos_t,
-                                         const double *sin_t, const double *poses, int L, int n_scan, int n,
-                                         const int32_t *grid_of_traj, int group, hipStream_t s, int shared_scans = 0,
-                                         int grid_per_traj = 0, const double *heading_cs = nullptr, int split_pref = -1);
-hipError_t launch_grid_update_scans(const GridDev &g, const float *ranges, const double *cos_t, const double *sin_t,
-                                    const double *poses, const double *centres, int S, int n, int group, hipStream_t s, int split_pref = -1);
-// Tiled path for maps much larger than an LDS window (single shared map, ReplaySource only).
-constexpr int kTileMaxBeams = 8192;      // beams per scan the tiled / wedge paths take (ray numbers inside a group are 16-bit)
-size_t tile_scratch_bytes(long rays, long groups);
-size_t wedge_scratch_bytes(long rays, long scans, long groups);
-bool tiles_apply(const GridDev &g, int n, const int32_t *got, int grid_per_traj, int wedges = 0);
-// got: nullable [L] map of every trajectory (wedges only; the recorded-walk tiles cast into one shared map)
-hipError_t launch_grid_update_tiles(const GridDev &g, const float *ranges, const double *cos_t, const double *sin_t,
-                                    const double *poses, const double *centres, int L, int n_scan, int n, int group,
-                                    void *scratch, hipStream_t s, int wedges = 0, const int32_t *got = nullptr);
-hipError_t launch_grid_update_tiles_explicit(const GridDev &g, const double *ox, const double *oy, const double *cx,
-                                             const double *cy, int B, int n, int group, void *scratch, hipStream_t s, int wedges = 0);
+// A ray cast of a batch of scans: plan_cast picks the engine, cast_scratch_bytes is the device scratch launch_cast then needs
+// at `scratch` (0 for Direct and Window).  The request holds either explicit world-frame endpoints (ox != nullptr:
+// Mapping.update's own arguments, `scans` scans of one stream) or a replay: scan k of trajectory l is
+// ranges[(l * (scans + 1) + k + 1) * n], cast from poses[l][k] (slam_ekf.py:89).
+enum class CastPath { Direct, Window, Tiles, Wedges };
+struct CastRequest {
+    const double *ox = nullptr, *oy = nullptr, *cx = nullptr, *cy = nullptr;      // [scans][n], [scans]
+    const float *ranges = nullptr;
+    const double *cos_t = nullptr, *sin_t = nullptr, *poses = nullptr;
+    const double *centres = nullptr;       // nullable [L][scans][2]: ray origins that are not the pose (one stream)
+    const double *heading_cs = nullptr;    // nullable [L][scans][2]: cos / sin of the poses' headings
+    int L = 1, scans = 0, n = 0;
+    const int32_t *maps = nullptr;         // nullable: the map of every scan (explicit) or trajectory (replay)
+    bool particles = false;                // every trajectory reads the same two scans and casts into map l of its own
+    int group = 0, split = -1;             // scans per workgroup (0: automatic); window split in two (-1: automatic, 0, 1)
+};
+CastPath plan_cast(const GridDev &g, int grid_mode, const CastRequest &r);
+size_t cast_scratch_bytes(CastPath p, const CastRequest &r);
+hipError_t launch_cast(const GridDev &g, CastPath p, const CastRequest &r, void *scratch, hipStream_t s);
 hipError_t launch_grid_finalize(const GridDev &g, int g0, int gcount, int8_t *pmap, hipStream_t s);
 hipError_t launch_grid_datamap(const GridDev &g, int gi, double *datamap, hipStream_t s);
 hipError_t launch_grid_transpose(const int8_t *pmap, int xw, int yw, int8_t *data, hipStream_t s);

@@ -3,9 +3,9 @@
 Mirrors W12m/mapping.py:8-51: ``Mapping(xw, yw, xyreso)`` holds ``pmap`` (50 = unknown,
 0 = free, 100 = occupied) and ``datamap``; ``update(ox, oy, center_x, center_y)`` casts one
 ray per beam from the centre to each world-frame endpoint and returns the live ``pmap``.
-The rays are walked by libslamhip's ``k_grid_update`` kernel (float-error Bresenham,
-integer pass / hit counters) through ``slam_grid_update``; ``pmap`` comes from
-``slam_grid_read``.
+The rays are walked by libslamhip's ray-cast kernels (float-error Bresenham, integer
+pass / hit counters; ``plan_cast`` picks which) through ``slam_grid_update``; ``pmap``
+comes from ``slam_grid_read``.
 
 Fidelity notes:
 * the reference converts world coordinates with ``int(10 * (x + 10))`` whatever ``xyreso``
