@@ -10,6 +10,8 @@ zjwzcx/A-2D-LiDAR-based-SLAM-System-for-Wheeled-Mobile-Robots:
     SLAM_EKF   laserCallback glue (scan matching + map building); landmarks=True: the whole W12
                node with Extraction and the landmark EKF on the host
     Localization  updateMap / laserEstimation / calc_map_observation (scan-to-map, W9)
+    dwa        dwa_control / Config / RobotType (course_agv_nav DWA local planner), batched as
+               DeviceDWA / dwa_batch_host; LocalPlanner: the local planner node without ROS
 
 plus the batched forms used by bench.py (``replay``) and the multi-GPU sharding helper
 (``dist``).  Importing the package never computes anything; every operator raises if
@@ -17,10 +19,13 @@ libslamhip.so or the GPU is missing (there is no CPU implementation in the produ
 """
 from . import _abi, dist, param, synthetic
 from ._abi import Context, LibraryMissing, SlamError, default_context
+from . import dwa
 from .bresenham import bresenham, rasterize
+from .dwa import DeviceDWA, dwa_batch_host, dwa_control
 from .ekf_lm import EKF
 from .extraction import Extraction, LandMarkSet
 from .icp import ICP, scan_to_pc
+from .local_planner import LocalPlanner
 from .localization import Localization
 from .mapping import Mapping
 from .replay import DeviceGrid, DeviceReplay, icp_batch_host, particles_host, prior_matrices, replay_host
@@ -29,4 +34,4 @@ from .synthetic import LaserScan
 
 __all__ = ["ICP", "Mapping", "Localization", "EKF", "Extraction", "LandMarkSet", "bresenham", "rasterize", "SLAM_EKF", "LaserScan", "Context", "default_context",
            "DeviceGrid", "DeviceReplay", "replay_host", "icp_batch_host", "particles_host", "prior_matrices", "scan_to_pc", "SlamError",
-           "LibraryMissing", "param", "synthetic"]
+           "LibraryMissing", "param", "synthetic", "dwa", "dwa_control", "DeviceDWA", "dwa_batch_host", "LocalPlanner"]

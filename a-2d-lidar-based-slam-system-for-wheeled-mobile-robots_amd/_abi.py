@@ -11,6 +11,7 @@ package raises instead of computing anything on the host.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import re
 import threading
@@ -87,6 +88,11 @@ _SIGS = {
     "slam_map_observation": ([_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _d, _d, _i, _d, _vp, _vp], _i),
     "slam_map_observation_dev": ([_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _d, _d, _i, _d, _vp, _vp, _vp, _vp], _i),
     "slam_replay_dev": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i),
+    "slam_dwa": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp], _i),
+    "slam_dwa_dev": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp], _i),
+    "slam_dwa_scans": ([_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _d, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp], _i),
+    "slam_dwa_scans_dev": ([_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _d, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp], _i),
+    "slam_dwa_shape": ([_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)], _i),
 }
 
 
@@ -232,3 +238,10 @@ def trig_tables(angle_min, angle_max, n):
     (icp.py:227-228): numpy.linspace then numpy.cos / numpy.sin."""
     ang = np.linspace(angle_min, angle_max, n)
     return np.ascontiguousarray(np.cos(ang)), np.ascontiguousarray(np.sin(ang))
+
+
+def beam_tables(angle_min, angle_increment, n):
+    """cos/sin of the beam angles as LocalPlanner.laserCallback forms them
+    (local_planner.py:64-68): a = angle_min + angle_increment * i, then math.cos / math.sin."""
+    a = [angle_min + angle_increment * i for i in range(n)]
+    return (np.array([math.cos(v) for v in a], dtype=np.float64), np.array([math.sin(v) for v in a], dtype=np.float64))

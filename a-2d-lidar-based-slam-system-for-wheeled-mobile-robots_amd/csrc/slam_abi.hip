@@ -379,6 +379,73 @@ int check_status_sync(slam_ctx *c)
         if (rc_ != SLAM_OK) return rc_;                                                                \
     } while (0)
 
+// ---- DWA local planner -------------------------------------------------------------------
+// Config checks and launch shape shared by the DWA entry points (slam_dwa_shape documents them).
+constexpr int kDwaMaxRows = 65536;
+constexpr long kDwaMaxSamples = 1L << 20;
+
+// Bound of np.arange(lo, hi, reso) over every state: lo >= spec_lo, hi <= spec_hi and
+// hi - lo <= 2 * accel * dt up to rounding (calc_dynamic_window, dwa.py:65-83).
+long dwa_axis_cap(double spec_lo, double spec_hi, double accel_dt, double reso)
+{
+    double width = std::fmin(spec_hi - spec_lo, 2.0 * accel_dt);
+    if (!(width > 0.0)) return 0;
+    double n = std::ceil(width / reso) + 2.0;
+    return n > (double)kDwaMaxSamples ? kDwaMaxSamples + 1 : (long)n;
+}
+
+int dwa_config(const double *config, DwaConfig *cfg, int *rows, int *nv_cap, int *nw_cap)
+{
+    if (!config) return fail(SLAM_ERR_INVALID, "slam_dwa: config is null");
+    for (int i = 0; i < SLAM_DWA_CONFIG_LEN; ++i)
+        if (!std::isfinite(config[i])) return fail(SLAM_ERR_INVALID, "slam_dwa: config[%d] is not finite", i);
+    DwaConfig c;
+    static_assert(sizeof(DwaConfig) == SLAM_DWA_CONFIG_LEN * sizeof(double), "config layout");
+    memcpy(&c, config, sizeof c);
+    if (!(c.dt > 0.0) || !(c.v_reso > 0.0) || !(c.yawrate_reso > 0.0))
+        return fail(SLAM_ERR_INVALID, "slam_dwa: dt, v_reso and yawrate_reso must be > 0");
+    if (c.robot_type != 0.0 && c.robot_type != 1.0) return fail(SLAM_ERR_INVALID, "slam_dwa: robot_type must be 0 or 1");
+    // predict_trajectory's loop (dwa.py:118-122), time accumulated in float64
+    int steps = 0;
+    for (double t = 0.0; t <= c.predict_time; t += c.dt)
+        if (++steps >= kDwaMaxRows) return fail(SLAM_ERR_INVALID, "slam_dwa: more than %d trajectory rows", kDwaMaxRows);
+    if (steps == 0) return fail(SLAM_ERR_INVALID, "slam_dwa: predict_time < 0 leaves no trajectory step");
+    long nv = dwa_axis_cap(c.min_speed, c.max_speed, c.max_accel * c.dt, c.v_reso);
+    long nw = dwa_axis_cap(-c.max_yawrate, c.max_yawrate, c.max_dyawrate * c.dt, c.yawrate_reso);
+    if (nv * nw > kDwaMaxSamples) return fail(SLAM_ERR_INVALID, "slam_dwa: window of up to %ld x %ld samples (> 2^20)", nv, nw);
+    if (cfg) *cfg = c;
+    *rows = steps + 1;
+    *nv_cap = (int)nv;
+    *nw_cap = (int)nw;
+    return SLAM_OK;
+}
+
+struct DwaOut {
+    double *u, *cost;
+    int32_t *index, *counts;
+    double *costs;
+    int s_cap;
+    double *traj;
+};
+
+int dwa_launch(slam_ctx *c, DwaArgs &a, const double *config, const DwaOut &o)
+{
+    REQUIRE(a.states && a.goals && o.u && o.cost && o.index, "null pointer");
+    REQUIRE(a.B > 0, "B must be > 0");
+    REQUIRE(!o.costs || o.s_cap > 0, "costs_out needs s_cap > 0");
+    TRY(dwa_config(config, &a.cfg, &a.rows, &a.nv_cap, &a.nw_cap));
+    a.u_out = o.u;
+    a.cost_out = o.cost;
+    a.index_out = o.index;
+    a.counts_out = o.counts;
+    a.costs_out = o.costs;
+    a.s_cap = o.s_cap;
+    a.traj_out = o.traj;
+    a.status = c->status;
+    HIPCHK(launch_dwa(a, c->stream));
+    return SLAM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1543,6 +1610,130 @@ int slam_map_observation(slam_ctx *c, const double *ox, const double *oy, int K,
     if (iters_out) D2H(iters_out, d_it, (size_t)B * 4);
     HIPCHK(hipStreamSynchronize(c->stream));
     return SLAM_OK;
+}
+
+/* ---- DWA local planner ------------------------------------------------------------------ */
+
+int slam_dwa_shape(const double *config, int *rows_out, int *nv_cap_out, int *nw_cap_out)
+{
+    if (!rows_out || !nv_cap_out || !nw_cap_out) return fail(SLAM_ERR_INVALID, "slam_dwa_shape: null pointer");
+    return dwa_config(config, nullptr, rows_out, nv_cap_out, nw_cap_out);
+}
+
+int slam_dwa_dev(slam_ctx *c, const double *states, const double *goals, const double *obstacles, const int32_t *counts,
+                 int M, int shared, const double *config, int B, double *u_out, double *cost_out, int32_t *index_out,
+                 int32_t *counts_out, double *costs_out, int s_cap, double *traj_out)
+{
+    TRY(use(c));
+    REQUIRE(obstacles, "null pointer");
+    REQUIRE(M > 0, "M must be > 0 (np.min of an empty obstacle set raises, dwa.py:157)");
+    DwaArgs a;
+    a.states = states;
+    a.goals = goals;
+    a.obs = obstacles;
+    a.ob_stride = shared ? 0 : 2L * M;
+    a.M = M;
+    a.counts = counts;
+    a.count_stride = shared ? 0 : 1;
+    a.B = B;
+    a.tile_cap = M < kDwaTile ? M : kDwaTile;
+    return dwa_launch(c, a, config, DwaOut{u_out, cost_out, index_out, counts_out, costs_out, s_cap, traj_out});
+}
+
+// Host forms: stage states, goals, the obstacle input (`in`: obstacles or ranges, in_bytes), the scans form's cos / sin
+// tables (`extra`) and counts, run the device form, copy back.
+static int dwa_host(slam_ctx *c, const double *states, const double *goals, int B, const double *config, size_t in_bytes,
+                    const void *in, const int32_t *counts, int ncounts, double *u_out, double *cost_out,
+                    int32_t *index_out, int32_t *counts_out, double *costs_out, int s_cap, double *traj_out,
+                    const double *extra, size_t extra_bytes, bool scans, int M, int n, int shared, double threshold)
+{
+    TRY(use(c));
+    REQUIRE(states && goals && in && u_out && cost_out && index_out, "null pointer");
+    REQUIRE(B > 0, "B must be > 0");
+    REQUIRE(!costs_out || s_cap > 0, "costs_out needs s_cap > 0");
+    int rows = 0, nvc = 0, nwc = 0;
+    TRY(dwa_config(config, nullptr, &rows, &nvc, &nwc));
+    const size_t Bz = (size_t)B;
+    const size_t traj_bytes = traj_out ? Bz * rows * 40 : 0, costs_bytes = costs_out ? Bz * s_cap * 8 : 0;
+    TRY(arena_reserve(c, c->staging, align_up(Bz * 40) + align_up(Bz * 16) + align_up(in_bytes) + align_up(extra_bytes) +
+                                         align_up((size_t)ncounts * 4) + align_up(Bz * 16) + align_up(Bz * 8) + align_up(Bz * 4) +
+                                         align_up(Bz * 8) + align_up(costs_bytes) + align_up(traj_bytes) + 4096));
+    double *d_st = carve<double>(c->staging, Bz * 5), *d_g = carve<double>(c->staging, Bz * 2);
+    char *d_in = carve<char>(c->staging, in_bytes);
+    double *d_ex = carve<double>(c->staging, extra_bytes / 8);
+    int32_t *d_k = carve<int32_t>(c->staging, ncounts);
+    double *d_u = carve<double>(c->staging, Bz * 2), *d_c = carve<double>(c->staging, Bz);
+    int32_t *d_i = carve<int32_t>(c->staging, Bz), *d_n = carve<int32_t>(c->staging, Bz * 2);
+    double *d_cs = carve<double>(c->staging, costs_bytes / 8), *d_t = carve<double>(c->staging, traj_bytes / 8);
+    TRY(copy_in(c, {{d_st, (void *)states, Bz * 40}, {d_g, (void *)goals, Bz * 16}, {d_in, (void *)in, in_bytes},
+                    {d_ex, (void *)extra, extra_bytes}, {d_k, (void *)counts, (size_t)ncounts * 4}}));
+    if (scans)
+        TRY(slam_dwa_scans_dev(c, d_st, d_g, reinterpret_cast<const float *>(d_in), n, shared, d_ex, d_ex + n, threshold,
+                               config, B, d_u, d_c, d_i, counts_out ? d_n : nullptr, costs_out ? d_cs : nullptr, s_cap,
+                               traj_out ? d_t : nullptr));
+    else
+        TRY(slam_dwa_dev(c, d_st, d_g, reinterpret_cast<const double *>(d_in), counts ? d_k : nullptr, M, shared, config, B,
+                         d_u, d_c, d_i, counts_out ? d_n : nullptr, costs_out ? d_cs : nullptr, s_cap,
+                         traj_out ? d_t : nullptr));
+    TRY(copy_out_sync(c, {{d_u, u_out, Bz * 16}, {d_c, cost_out, Bz * 8}, {d_i, index_out, Bz * 4},
+                          {d_n, counts_out, counts_out ? Bz * 8 : 0}, {d_cs, costs_out, costs_bytes}, {d_t, traj_out, traj_bytes}}));
+    return check_status_sync(c);
+}
+
+int slam_dwa(slam_ctx *c, const double *states, const double *goals, const double *obstacles, const int32_t *counts,
+             int M, int shared, const double *config, int B, double *u_out, double *cost_out, int32_t *index_out,
+             int32_t *counts_out, double *costs_out, int s_cap, double *traj_out)
+{
+    REQUIRE(M > 0, "M must be > 0 (np.min of an empty obstacle set raises, dwa.py:157)");
+    REQUIRE(B > 0, "B must be > 0");
+    const int sets = shared ? 1 : B;
+    if (counts)
+        for (int b = 0; b < sets; ++b)
+            if (counts[b] < 1 || counts[b] > M)
+                return fail(SLAM_ERR_INVALID, "slam_dwa: counts[%d] = %d outside [1, M = %d] (np.min of an empty set raises, dwa.py:157)",
+                            b, counts[b], M);
+    return dwa_host(c, states, goals, B, config, (size_t)sets * 2 * M * 8, obstacles, counts, counts ? sets : 0, u_out,
+                    cost_out, index_out, counts_out, costs_out, s_cap, traj_out, nullptr, 0, false, M, 0, shared, 0.0);
+}
+
+int slam_dwa_scans_dev(slam_ctx *c, const double *states, const double *goals, const float *ranges, int n, int shared,
+                       const double *cos_t, const double *sin_t, double threshold, const double *config, int B,
+                       double *u_out, double *cost_out, int32_t *index_out, int32_t *counts_out, double *costs_out,
+                       int s_cap, double *traj_out)
+{
+    TRY(use(c));
+    REQUIRE(ranges && cos_t && sin_t, "null pointer");
+    REQUIRE(n > 0 && n <= kDwaMaxBeams, "n must be in [1, 4095]");
+    REQUIRE(!std::isnan(threshold), "threshold is NaN");
+    DwaArgs a;
+    a.states = states;
+    a.goals = goals;
+    a.ranges = ranges;
+    a.cos_t = cos_t;
+    a.sin_t = sin_t;
+    a.scan_stride = shared ? 0 : n;
+    a.n = n;
+    a.threshold = threshold;
+    a.B = B;
+    a.tile_cap = n + 1;
+    return dwa_launch(c, a, config, DwaOut{u_out, cost_out, index_out, counts_out, costs_out, s_cap, traj_out});
+}
+
+int slam_dwa_scans(slam_ctx *c, const double *states, const double *goals, const float *ranges, int n, int shared,
+                   const double *cos_t, const double *sin_t, double threshold, const double *config, int B,
+                   double *u_out, double *cost_out, int32_t *index_out, int32_t *counts_out, double *costs_out,
+                   int s_cap, double *traj_out)
+{
+    REQUIRE(ranges && cos_t && sin_t, "null pointer");
+    REQUIRE(n > 0 && n <= kDwaMaxBeams, "n must be in [1, 4095]");
+    REQUIRE(B > 0, "B must be > 0");
+    REQUIRE(!std::isnan(threshold), "threshold is NaN");
+    std::vector<double> trig((size_t)2 * n);
+    memcpy(trig.data(), cos_t, (size_t)n * 8);
+    memcpy(trig.data() + n, sin_t, (size_t)n * 8);
+    return dwa_host(c, states, goals, B, config, (size_t)(shared ? 1 : B) * n * 4, ranges, nullptr, 0, u_out, cost_out,
+                    index_out, counts_out, costs_out, s_cap, traj_out, trig.data(), trig.size() * 8, true, 0, n, shared,
+                    threshold);
 }
 
 }  // extern "C"

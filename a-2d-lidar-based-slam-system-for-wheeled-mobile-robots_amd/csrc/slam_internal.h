@@ -184,4 +184,43 @@ hipError_t launch_virtual_scan(const double *ox, const double *oy, int K, const 
 hipError_t launch_ranges64_to_points(const double *ranges, const double *cos_t, const double *sin_t, int B, int n,
                                      double *pts, hipStream_t s);
 
+// ---- DWA local planner (dwa_kernels.hip) ----------------------------------------------
+// The fields of SLAM_DWA_CONFIG_LEN in the order include/slam_hip.h documents (dwa.py:23-45).
+struct DwaConfig {
+    double max_speed, min_speed, max_yawrate, max_accel, max_dyawrate, dt, v_reso, yawrate_reso, predict_time,
+        to_goal_cost_gain, speed_cost_gain, obstacle_cost_gain, robot_type, robot_radius, robot_width, robot_length;
+};
+constexpr int kDwaTile = 4096;               // obstacles staged in LDS at a time (16 B each)
+constexpr int kDwaMaxBeams = kDwaTile - 1;   // scans form: the sentinel and every beam fit one tile
+constexpr long kDwaMaxGroups = 1L << 20;     // workgroups per launch; more planners are taken grid-stride
+struct DwaArgs {
+    const double *states, *goals;            // [B][5], [B][2]
+    // explicit obstacles: [.][2][M] (x row, then y row), ob_stride doubles between planners (0: one shared set);
+    // counts nullable ([.] with count_stride 0 or 1): planner b uses min(counts[b], M) of them
+    const double *obs = nullptr;
+    long ob_stride = 0;
+    int M = 0;
+    const int32_t *counts = nullptr;
+    long count_stride = 0;
+    // scans form (ranges != nullptr): [.][n] float32, scan_stride floats between planners (0: shared)
+    const float *ranges = nullptr;
+    const double *cos_t = nullptr, *sin_t = nullptr;
+    long scan_stride = 0;
+    int n = 0;
+    double threshold = 0.0;
+    long B = 0;
+    int rows = 0;                            // trajectory rows: 1 + the passes of the predict_time loop
+    int nv_cap = 0, nw_cap = 0;              // bound on the sample axes for this config (slam_dwa_shape)
+    int tile_cap = 0;                        // obstacles per LDS tile
+    DwaConfig cfg;
+    double *u_out, *cost_out;                // [B][2], [B]
+    int32_t *index_out;                      // [B]
+    int32_t *counts_out = nullptr;           // nullable [B][2]
+    double *costs_out = nullptr;             // nullable [B][s_cap]
+    int s_cap = 0;
+    double *traj_out = nullptr;              // nullable [B][rows][5]
+    int *status = nullptr;
+};
+hipError_t launch_dwa(const DwaArgs &a, hipStream_t s);
+
 }  // namespace slam

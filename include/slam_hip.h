@@ -329,6 +329,67 @@ int slam_map_observation_dev(slam_ctx *ctx, const double *ox, const double *oy, 
                              const double *sin_t, double angle_min, double angle_increment, int max_iter, double tol,
                              double *vranges_ws, double *vpts_ws, double *T_out, int32_t *iters_out);
 
+/* ---- DWA local planner --------------------------------------------------------------- */
+/* NAV = "W12_LiDAR SLAM/w12-mapping/course_agv_nav/scripts".  Replaces dwa_control(x, config,
+ * goal, ob) (NAV/dwa.py:10-16, with calc_dynamic_window :65-83 and calc_control_and_trajectory
+ * :85-113) for B planners in one launch; the local planner node runs it on every control step
+ * (NAV/local_planner.py:135-150).
+ * config: double[SLAM_DWA_CONFIG_LEN], the fields of Config (NAV/dwa.py:23-45) in this order:
+ *   max_speed, min_speed, max_yawrate, max_accel, max_dyawrate, dt, v_reso, yawrate_reso,
+ *   predict_time, to_goal_cost_gain, speed_cost_gain, obstacle_cost_gain,
+ *   robot_type (0 = RobotType.circle, 1 = RobotType.rectangle), robot_radius, robot_width, robot_length.
+ *   Every value must be finite; dt, v_reso and yawrate_reso must be > 0 (the reference loops
+ *   forever or raises) and predict_time >= 0 (else its trajectory has no last row).
+ * Semantics are the reference's as it executes (DESIGN.md "DWA local planner"):
+ *  - samples: numpy float arange of both window axes, v outer: sample s = iv * nw + iw (:95-96);
+ *  - rollout: row 0 = the state, then one row per pass of `while time <= predict_time`
+ *    (time accumulated in float64, :115-124); each step yaw, then x, then y (:57-63);
+ *  - rectangle robots collide iff some (row, obstacle) pair has |tx-ox| <= robot_length/2 and
+ *    |ty-oy| <= robot_width/2 in the PLANNING frame: the reference's rotation is a no-op
+ *    (`np.reshape(-1, 1)` is [-1], :138) and is reproduced, not fixed; circle robots iff some
+ *    hypot <= robot_radius; the obstacle cost is inf on collision, else 1 / min hypot (:126-160);
+ *  - final cost to_goal + speed + obstacle gains, summed left to right (0 * inf = NaN, :101-105);
+ *  - selection as `if min_cost >= final_cost` from inf (:108): NaN never wins, ties go to the
+ *    LARGER index; no winner (empty window, all NaN): u = (0, 0), index -1, cost inf;
+ *  - a state whose v or omega is not finite plans an empty window (the reference raises for inf).
+ * states [B][5] (x, y, yaw, v, omega); goals [B][2].  obstacles: [B][2][M] structure-of-arrays
+ * (M x values, then M y values: the layout slam_map_obstacles_dev writes with oy = ox + M), or one
+ * shared [2][M] set when shared != 0.  counts: NULL (every planner uses M obstacles) or [B]
+ * (one value when shared): planner b uses the first min(counts[b], M).  The host form rejects a
+ * count outside [1, M] (np.min of an empty set raises in the reference); in the device form a
+ * count < 1 gives index -1.
+ * Outputs: u_out [B][2], cost_out [B] (the winner's final cost), index_out [B];
+ * nullable: counts_out [B][2] (nv, nw), costs_out [B][s_cap] (every sample's final cost; samples
+ * at s >= s_cap are not written), traj_out [B][rows][5] (the winner's trajectory; with no winner
+ * row 0 is the state and the other rows NaN).  rows and the sample bound come from slam_dwa_shape.
+ * Obstacle sets of any size are staged through LDS in tiles; B is bounded by memory. */
+#define SLAM_DWA_CONFIG_LEN 16
+int slam_dwa(slam_ctx *ctx, const double *states, const double *goals, const double *obstacles, const int32_t *counts,
+             int M, int shared, const double *config, int B, double *u_out, double *cost_out, int32_t *index_out,
+             int32_t *counts_out, double *costs_out, int s_cap, double *traj_out);
+int slam_dwa_dev(slam_ctx *ctx, const double *states, const double *goals, const double *obstacles,
+                 const int32_t *counts, int M, int shared, const double *config, int B, double *u_out,
+                 double *cost_out, int32_t *index_out, int32_t *counts_out, double *costs_out, int s_cap,
+                 double *traj_out);
+/* The same with the obstacles of LocalPlanner.laserCallback (NAV/local_planner.py:57-68)
+ * formed inside the launch: the sentinel (100, 100), then (cos_t[i] * r, sin_t[i] * r) for every
+ * beam i with r < threshold (inf and NaN ranges drop out).  ranges [B][n] float32 (one shared
+ * scan when shared != 0), n <= 4095; cos_t, sin_t [n] = cos / sin(angle_min + angle_increment * i)
+ * computed by the caller; threshold = max_speed * predict_time in the reference (:34). */
+int slam_dwa_scans(slam_ctx *ctx, const double *states, const double *goals, const float *ranges, int n, int shared,
+                   const double *cos_t, const double *sin_t, double threshold, const double *config, int B,
+                   double *u_out, double *cost_out, int32_t *index_out, int32_t *counts_out, double *costs_out,
+                   int s_cap, double *traj_out);
+int slam_dwa_scans_dev(slam_ctx *ctx, const double *states, const double *goals, const float *ranges, int n,
+                       int shared, const double *cos_t, const double *sin_t, double threshold, const double *config,
+                       int B, double *u_out, double *cost_out, int32_t *index_out, int32_t *counts_out,
+                       double *costs_out, int s_cap, double *traj_out);
+/* Host only, no context: validate a config (as above) and return the trajectory rows of
+ * predict_trajectory (NAV/dwa.py:115-124) and upper bounds of the two sample axes over every
+ * state (nv <= nv_cap, nw <= nw_cap; size costs_out with s_cap = nv_cap * nw_cap).  Configs whose
+ * rows exceed 65 536 or whose nv_cap * nw_cap exceeds 2^20 are rejected (SLAM_ERR_INVALID). */
+int slam_dwa_shape(const double *config, int *rows_out, int *nv_cap_out, int *nw_cap_out);
+
 #ifdef __cplusplus
 }
 #endif
