@@ -3,6 +3,7 @@
 // host; without a gfx950 device every entry point fails.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -39,9 +40,17 @@ int fail(int code, const char *fmt, ...)
         if (e_ != hipSuccess) return fail(SLAM_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));       \
     } while (0)
 
-#define REQUIRE(cond, msg)                                                                             \
+// REQUIRE_IN: a check written once for an entry point and its host / device twin reports the name it was called by
+#define REQUIRE_IN(fn, cond, msg)                                                                      \
     do {                                                                                               \
-        if (!(cond)) return fail(SLAM_ERR_INVALID, "%s: %s", __func__, msg);                           \
+        if (!(cond)) return fail(SLAM_ERR_INVALID, "%s: %s", fn, msg);                                 \
+    } while (0)
+#define REQUIRE(cond, msg) REQUIRE_IN(__func__, cond, msg)
+
+#define TRY(expr)                                                                                      \
+    do {                                                                                               \
+        int rc_ = (expr);                                                                              \
+        if (rc_ != SLAM_OK) return rc_;                                                                \
     } while (0)
 
 size_t dtype_size(int dtype)
@@ -281,64 +290,103 @@ bool ensure_pinned(slam_ctx *c)
     return true;
 }
 
-// Host <-> staging copies of an entry point.  The pieces lie in ONE arena in ascending order, so
-// when they are small (a drop-in call: one scan pair, one scan) they cross the bus in one copy
-// through the page-locked block, laid out like the device pieces; otherwise one copy per piece.
-struct Seg {
-    void *dev;
-    void *host;          // source (copy_in) or destination (copy_out_sync); null pieces are skipped
-    size_t bytes;
-};
+// Device copies of the arguments of a host-pointer entry point.  The entry point declares its
+// pieces once, in order; upload() reserves exactly their aligned sum in the staging arena, sets
+// every device pointer and copies the inputs in; download() copies the outputs back and ends with
+// a stream synchronise (so the page-locked block is free at the next call).  The pieces lie in
+// ONE arena in ascending order, so when those of one direction are small (a drop-in call: one
+// scan pair, one scan) they cross the bus in one copy through the page-locked block, laid out
+// like the device pieces; otherwise one copy per piece.
+class Staging {
+public:
+    explicit Staging(slam_ctx *c) : c_(c) {}
+    // an input copied from `host`; absent (null device pointer) when `host` is null
+    template <typename T> Staging &in(T *&dev, const T *host, size_t n) { return add(dev, n, host, nullptr, !host); }
+    // an output copied back to `host`; absent when `host` is null
+    template <typename T> Staging &out(T *&dev, T *host, size_t n) { return add(dev, n, nullptr, host, !host); }
+    // an output the device form always needs: copied back only when `host` is non-null
+    template <typename T> Staging &out_always(T *&dev, T *host, size_t n) { return add(dev, n, nullptr, host, false); }
+    // device-only workspace
+    template <typename T> Staging &work(T *&dev, size_t n) { return add(dev, n, nullptr, nullptr, false); }
 
-int copy_in(slam_ctx *c, std::initializer_list<Seg> segs)
-{
-    char *lo = nullptr, *hi = nullptr;
-    for (const Seg &g : segs) {
-        if (!g.host || !g.bytes) continue;
-        if (!g.dev) return fail(SLAM_ERR_NOMEM, "internal: workspace");
-        char *d = static_cast<char *>(g.dev);
-        if (!lo || d < lo) lo = d;
-        if (!hi || d + g.bytes > hi) hi = d + g.bytes;
-    }
-    if (!lo) return SLAM_OK;
-    const size_t span = (size_t)(hi - lo);
-    if (span <= kPinnedBytes / 2 && ensure_pinned(c)) {
-        for (const Seg &g : segs)
-            if (g.host && g.bytes) memcpy(c->pinned + (static_cast<char *>(g.dev) - lo), g.host, g.bytes);
-        HIPCHK(hipMemcpyAsync(lo, c->pinned, span, hipMemcpyHostToDevice, c->stream));
-        return SLAM_OK;
-    }
-    for (const Seg &g : segs)
-        if (g.host && g.bytes) HIPCHK(hipMemcpyAsync(g.dev, g.host, g.bytes, hipMemcpyHostToDevice, c->stream));
-    return SLAM_OK;
-}
-
-int copy_out_sync(slam_ctx *c, std::initializer_list<Seg> segs)
-{
-    char *lo = nullptr, *hi = nullptr;
-    for (const Seg &g : segs) {
-        if (!g.host || !g.bytes) continue;
-        if (!g.dev) return fail(SLAM_ERR_NOMEM, "internal: workspace");
-        char *d = static_cast<char *>(g.dev);
-        if (!lo || d < lo) lo = d;
-        if (!hi || d + g.bytes > hi) hi = d + g.bytes;
-    }
-    if (lo) {
-        const size_t span = (size_t)(hi - lo);
-        if (span <= kPinnedBytes / 2 && ensure_pinned(c)) {
-            char *h = c->pinned + kPinnedBytes / 2;
-            HIPCHK(hipMemcpyAsync(h, lo, span, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipStreamSynchronize(c->stream));
-            for (const Seg &g : segs)
-                if (g.host && g.bytes) memcpy(g.host, h + (static_cast<char *>(g.dev) - lo), g.bytes);
+    int upload()
+    {
+        if (overflow_) return fail(SLAM_ERR_NOMEM, "internal: more than %d staging pieces", kMaxPieces);
+        TRY(arena_reserve(c_, c_->staging, size_));
+        char *d = c_->staging.base;
+        for (int i = 0; i < n_; ++i) p_[i].set(p_[i].dev, d + p_[i].off);
+        size_t lo, hi;
+        if (!span(true, lo, hi)) return SLAM_OK;
+        if (hi - lo <= kPinnedBytes / 2 && ensure_pinned(c_)) {
+            for (int i = 0; i < n_; ++i)
+                if (p_[i].src) memcpy(c_->pinned + (p_[i].off - lo), p_[i].src, p_[i].bytes);
+            HIPCHK(hipMemcpyAsync(d + lo, c_->pinned, hi - lo, hipMemcpyHostToDevice, c_->stream));
             return SLAM_OK;
         }
-        for (const Seg &g : segs)
-            if (g.host && g.bytes) HIPCHK(hipMemcpyAsync(g.host, g.dev, g.bytes, hipMemcpyDeviceToHost, c->stream));
+        for (int i = 0; i < n_; ++i)
+            if (p_[i].src) HIPCHK(hipMemcpyAsync(d + p_[i].off, p_[i].src, p_[i].bytes, hipMemcpyHostToDevice, c_->stream));
+        return SLAM_OK;
     }
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return SLAM_OK;
-}
+
+    int download()
+    {
+        char *d = c_->staging.base;
+        size_t lo, hi;
+        if (span(false, lo, hi) && hi - lo <= kPinnedBytes / 2 && ensure_pinned(c_)) {
+            char *h = c_->pinned + kPinnedBytes / 2;
+            HIPCHK(hipMemcpyAsync(h, d + lo, hi - lo, hipMemcpyDeviceToHost, c_->stream));
+            HIPCHK(hipStreamSynchronize(c_->stream));
+            for (int i = 0; i < n_; ++i)
+                if (p_[i].dst) memcpy(p_[i].dst, h + (p_[i].off - lo), p_[i].bytes);
+            return SLAM_OK;
+        }
+        for (int i = 0; i < n_; ++i)
+            if (p_[i].dst) HIPCHK(hipMemcpyAsync(p_[i].dst, d + p_[i].off, p_[i].bytes, hipMemcpyDeviceToHost, c_->stream));
+        HIPCHK(hipStreamSynchronize(c_->stream));
+        return SLAM_OK;
+    }
+
+private:
+    struct Piece {
+        void *dev;                            // the entry point's device pointer (a T *), set by upload()
+        void (*set)(void *dev, char *p);
+        const void *src;                      // host source of an input (null: nothing to copy in)
+        void *dst;                            // host destination of an output (null: nothing to copy back)
+        size_t off, bytes;
+    };
+    static constexpr int kMaxPieces = 12;
+
+    template <typename T> static void set_ptr(void *dev, char *p) { *static_cast<T **>(dev) = reinterpret_cast<T *>(p); }
+    template <typename T> Staging &add(T *&dev, size_t n, const void *src, void *dst, bool absent)
+    {
+        dev = nullptr;
+        if (absent) return *this;
+        if (n_ == kMaxPieces) overflow_ = true;
+        if (overflow_) return *this;
+        const size_t bytes = n * sizeof(T);
+        p_[n_++] = Piece{&dev, &set_ptr<T>, bytes ? src : nullptr, bytes ? dst : nullptr, size_, bytes};
+        size_ += align_up(bytes);
+        return *this;
+    }
+    // byte range [lo, hi) of the arena that the copies of one direction cover; false: nothing to copy
+    bool span(bool in, size_t &lo, size_t &hi) const
+    {
+        lo = size_;
+        hi = 0;
+        for (int i = 0; i < n_; ++i)
+            if (in ? p_[i].src != nullptr : p_[i].dst != nullptr) {
+                lo = std::min(lo, p_[i].off);
+                hi = std::max(hi, p_[i].off + p_[i].bytes);
+            }
+        return lo < hi;
+    }
+
+    slam_ctx *c_;
+    Piece p_[kMaxPieces];
+    int n_ = 0;
+    bool overflow_ = false;
+    size_t size_ = 0;
+};
 
 // entry points that touch a map on the MAIN stream call this first
 int grid_on_main(slam_ctx *c)
@@ -371,13 +419,7 @@ int check_status_sync(slam_ctx *c)
     return status_to_code(st);
 }
 
-#define H2D(dst, src, bytes) HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream))
 #define D2H(dst, src, bytes) HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream))
-#define TRY(expr)                                                                                      \
-    do {                                                                                               \
-        int rc_ = (expr);                                                                              \
-        if (rc_ != SLAM_OK) return rc_;                                                                \
-    } while (0)
 
 // ---- DWA local planner -------------------------------------------------------------------
 // Config checks and launch shape shared by the DWA entry points (slam_dwa_shape documents them).
@@ -428,12 +470,17 @@ struct DwaOut {
     double *traj;
 };
 
-int dwa_launch(slam_ctx *c, DwaArgs &a, const double *config, const DwaOut &o)
+// Checks of every DWA entry point; fills the config and launch shape of `a`.
+int check_dwa(const char *fn, const double *states, const double *goals, const double *config, int B, const DwaOut &o, DwaArgs &a)
 {
-    REQUIRE(a.states && a.goals && o.u && o.cost && o.index, "null pointer");
-    REQUIRE(a.B > 0, "B must be > 0");
-    REQUIRE(!o.costs || o.s_cap > 0, "costs_out needs s_cap > 0");
-    TRY(dwa_config(config, &a.cfg, &a.rows, &a.nv_cap, &a.nw_cap));
+    REQUIRE_IN(fn, states && goals && o.u && o.cost && o.index, "null pointer");
+    REQUIRE_IN(fn, B > 0, "B must be > 0");
+    REQUIRE_IN(fn, !o.costs || o.s_cap > 0, "costs_out needs s_cap > 0");
+    return dwa_config(config, &a.cfg, &a.rows, &a.nv_cap, &a.nw_cap);
+}
+
+int dwa_launch(slam_ctx *c, DwaArgs &a, const DwaOut &o)
+{
     a.u_out = o.u;
     a.cost_out = o.cost;
     a.index_out = o.index;
@@ -675,13 +722,20 @@ int slam_debug_records(slam_ctx *c, void *out, int max_records)
 
 /* ---- ICP ------------------------------------------------------------------------ */
 
+static int check_scan_to_points(const char *fn, const float *ranges, const double *cos_t, const double *sin_t, int B, int n,
+                                int dtype, const void *pts_out)
+{
+    REQUIRE_IN(fn, ranges && cos_t && sin_t && pts_out, "null pointer");
+    REQUIRE_IN(fn, B > 0 && n > 0, "B and n must be positive");
+    REQUIRE_IN(fn, dtype_size(dtype), "unknown dtype");
+    return SLAM_OK;
+}
+
 int slam_scan_to_points_dev(slam_ctx *c, const float *ranges, const double *cos_t, const double *sin_t, int B, int n,
                             int clip_inf, int dtype, void *pts_out)
 {
     TRY(use(c));
-    REQUIRE(ranges && cos_t && sin_t && pts_out, "null pointer");
-    REQUIRE(B > 0 && n > 0, "B and n must be positive");
-    REQUIRE(dtype_size(dtype), "unknown dtype");
+    TRY(check_scan_to_points(__func__, ranges, cos_t, sin_t, B, n, dtype, pts_out));
     Timed t(c, SLAM_K_POINTS);
     HIPCHK(launch_scan_to_points(ranges, cos_t, sin_t, (long)B * n, n, clip_inf, dtype, pts_out, c->stream));
     return SLAM_OK;
@@ -691,29 +745,31 @@ int slam_scan_to_points(slam_ctx *c, const float *ranges, const double *cos_t, c
                         int clip_inf, int dtype, void *pts_out)
 {
     TRY(use(c));
-    REQUIRE(ranges && cos_t && sin_t && pts_out, "null pointer");
-    REQUIRE(B > 0 && n > 0, "B and n must be positive");
-    size_t ds = dtype_size(dtype);
-    REQUIRE(ds, "unknown dtype");
-    size_t nr = (size_t)B * n;
-    TRY(arena_reserve(c, c->staging, align_up(nr * 4) + 2 * align_up((size_t)n * 8) + align_up(2 * nr * ds) + 1024));
-    float *d_r = carve<float>(c->staging, nr);
-    double *d_c = carve<double>(c->staging, n), *d_s = carve<double>(c->staging, n);
-    char *d_p = carve<char>(c->staging, 2 * nr * ds);
-    TRY(copy_in(c, {{d_r, const_cast<float *>(ranges), nr * 4}, {d_c, const_cast<double *>(cos_t), (size_t)n * 8},
-                    {d_s, const_cast<double *>(sin_t), (size_t)n * 8}}));
+    TRY(check_scan_to_points(__func__, ranges, cos_t, sin_t, B, n, dtype, pts_out));
+    const size_t nr = (size_t)B * n;
+    float *d_r; double *d_c, *d_s; char *d_p;
+    Staging s(c);
+    s.in(d_r, ranges, nr).in(d_c, cos_t, n).in(d_s, sin_t, n).out(d_p, static_cast<char *>(pts_out), 2 * nr * dtype_size(dtype));
+    TRY(s.upload());
     TRY(slam_scan_to_points_dev(c, d_r, d_c, d_s, B, n, clip_inf, dtype, d_p));
-    return copy_out_sync(c, {{d_p, pts_out, 2 * nr * ds}});
+    return s.download();
+}
+
+static int check_nn(const char *fn, const void *src, const void *tar, int B, int n_src, int n_tar, int dtype,
+                    const double *dist, const int32_t *idx)
+{
+    REQUIRE_IN(fn, src && tar && dist && idx, "null pointer");
+    REQUIRE_IN(fn, B > 0 && n_src > 0 && n_tar > 0, "sizes must be positive");
+    REQUIRE_IN(fn, dtype_size(dtype), "unknown dtype");
+    REQUIRE_IN(fn, n_tar <= 8192, "n_tar too large for the LDS-resident target (max 8192 points)");
+    return SLAM_OK;
 }
 
 int slam_nn_dev(slam_ctx *c, const void *src, const void *tar, int B, int n_src, int n_tar, int dtype, double *dist,
                 int32_t *idx)
 {
     TRY(use(c));
-    REQUIRE(src && tar && dist && idx, "null pointer");
-    REQUIRE(B > 0 && n_src > 0 && n_tar > 0, "sizes must be positive");
-    REQUIRE(dtype_size(dtype), "unknown dtype");
-    REQUIRE(n_tar <= 8192, "n_tar too large for the LDS-resident target (max 8192 points)");
+    TRY(check_nn(__func__, src, tar, B, n_src, n_tar, dtype, dist, idx));
     Timed t(c, SLAM_K_NN);
     HIPCHK(launch_nn(src, tar, B, n_src, n_tar, dtype, dist, idx, c->stream));
     return SLAM_OK;
@@ -723,29 +779,28 @@ int slam_nn(slam_ctx *c, const void *src, const void *tar, int B, int n_src, int
             int32_t *idx)
 {
     TRY(use(c));
-    REQUIRE(src && tar && dist && idx, "null pointer");
-    REQUIRE(B > 0 && n_src > 0 && n_tar > 0, "sizes must be positive");
-    size_t ds = dtype_size(dtype);
-    REQUIRE(ds, "unknown dtype");
-    size_t bs = (size_t)B * 2 * n_src * ds, bt = (size_t)B * 2 * n_tar * ds, q = (size_t)B * n_src;
-    TRY(arena_reserve(c, c->staging, align_up(bs) + align_up(bt) + align_up(q * 8) + align_up(q * 4) + 1024));
-    char *d_s = carve<char>(c->staging, bs), *d_t = carve<char>(c->staging, bt);
-    double *d_d = carve<double>(c->staging, q);
-    int32_t *d_i = carve<int32_t>(c->staging, q);
-    H2D(d_s, src, bs);
-    H2D(d_t, tar, bt);
+    TRY(check_nn(__func__, src, tar, B, n_src, n_tar, dtype, dist, idx));
+    const size_t ds = dtype_size(dtype), q = (size_t)B * n_src;
+    char *d_s, *d_t; double *d_d; int32_t *d_i;
+    Staging s(c);
+    s.in(d_s, static_cast<const char *>(src), q * 2 * ds).in(d_t, static_cast<const char *>(tar), (size_t)B * 2 * n_tar * ds);
+    s.out(d_d, dist, q).out(d_i, idx, q);
+    TRY(s.upload());
     TRY(slam_nn_dev(c, d_s, d_t, B, n_src, n_tar, dtype, d_d, d_i));
-    D2H(dist, d_d, q * 8);
-    D2H(idx, d_i, q * 4);
-    HIPCHK(hipStreamSynchronize(c->stream));
+    return s.download();
+}
+
+static int check_kabsch2d(const char *fn, const double *src, const double *tar, int B, int n, const double *T_out)
+{
+    REQUIRE_IN(fn, src && tar && T_out, "null pointer");
+    REQUIRE_IN(fn, B > 0 && n > 0, "sizes must be positive");
     return SLAM_OK;
 }
 
 int slam_kabsch2d_dev(slam_ctx *c, const double *src, const double *tar, int B, int n, double *T_out)
 {
     TRY(use(c));
-    REQUIRE(src && tar && T_out, "null pointer");
-    REQUIRE(B > 0 && n > 0, "sizes must be positive");
+    TRY(check_kabsch2d(__func__, src, tar, B, n, T_out));
     Timed t(c, SLAM_K_KABSCH);
     HIPCHK(launch_kabsch(src, tar, B, n, T_out, c->stream));
     return SLAM_OK;
@@ -754,17 +809,24 @@ int slam_kabsch2d_dev(slam_ctx *c, const double *src, const double *tar, int B, 
 int slam_kabsch2d(slam_ctx *c, const double *src, const double *tar, int B, int n, double *T_out)
 {
     TRY(use(c));
-    REQUIRE(src && tar && T_out, "null pointer");
-    REQUIRE(B > 0 && n > 0, "sizes must be positive");
-    size_t bp = (size_t)B * 2 * n * 8;
-    TRY(arena_reserve(c, c->staging, 2 * align_up(bp) + align_up((size_t)B * 72) + 1024));
-    double *d_s = carve<double>(c->staging, (size_t)B * 2 * n), *d_t = carve<double>(c->staging, (size_t)B * 2 * n);
-    double *d_T = carve<double>(c->staging, (size_t)B * 9);
-    H2D(d_s, src, bp);
-    H2D(d_t, tar, bp);
+    TRY(check_kabsch2d(__func__, src, tar, B, n, T_out));
+    double *d_s, *d_t, *d_T;
+    Staging s(c);
+    s.in(d_s, src, (size_t)B * 2 * n).in(d_t, tar, (size_t)B * 2 * n).out(d_T, T_out, (size_t)B * 9);
+    TRY(s.upload());
     TRY(slam_kabsch2d_dev(c, d_s, d_t, B, n, d_T));
-    D2H(T_out, d_T, (size_t)B * 72);
-    HIPCHK(hipStreamSynchronize(c->stream));
+    return s.download();
+}
+
+static int check_icp_batch(const char *fn, const void *tar, const void *src, int B, int n_tar, int n_src, int dtype,
+                           int max_iter, const double *T_out)
+{
+    REQUIRE_IN(fn, tar && src && T_out, "null pointer");
+    REQUIRE_IN(fn, B > 0 && n_src > 0 && n_tar > 0, "sizes must be positive");
+    REQUIRE_IN(fn, max_iter >= 0, "max_iter must be >= 0");
+    REQUIRE_IN(fn, dtype_size(dtype), "unknown dtype");
+    REQUIRE_IN(fn, n_src <= 8192, "n_src > 8192 not supported");
+    REQUIRE_IN(fn, n_tar <= 8192, "n_tar too large for the LDS-resident target (max 8192 points)");
     return SLAM_OK;
 }
 
@@ -773,12 +835,7 @@ int slam_icp_batch_dev(slam_ctx *c, const void *tar, const void *src, int B, int
                        int32_t *iters_out, double *mean_err_out)
 {
     TRY(use(c));
-    REQUIRE(tar && src && T_out, "null pointer");
-    REQUIRE(B > 0 && n_src > 0 && n_tar > 0, "sizes must be positive");
-    REQUIRE(max_iter >= 0, "max_iter must be >= 0");
-    REQUIRE(dtype_size(dtype), "unknown dtype");
-    REQUIRE(n_src <= 8192, "n_src > 8192 not supported");
-    REQUIRE(n_tar <= 8192, "n_tar too large for the LDS-resident target (max 8192 points)");
+    TRY(check_icp_batch(__func__, tar, src, B, n_tar, n_src, dtype, max_iter, T_out));
     IcpArgs a;
     a.tar = tar; a.src = src; a.prior = prior;
     a.ranges = nullptr; a.cos_t = a.sin_t = nullptr; a.tar_scan_stride = a.src_scan_stride = 0;
@@ -798,29 +855,30 @@ int slam_icp_batch(slam_ctx *c, const void *tar, const void *src, int B, int n_t
                    double *mean_err_out)
 {
     TRY(use(c));
-    REQUIRE(tar && src && T_out, "null pointer");
-    REQUIRE(B > 0 && n_src > 0 && n_tar > 0, "sizes must be positive");
-    size_t ds = dtype_size(dtype);
-    REQUIRE(ds, "unknown dtype");
-    size_t bt = (size_t)(tar_shared ? 1 : B) * 2 * n_tar * ds, bs = (size_t)(src_shared ? 1 : B) * 2 * n_src * ds;
-    TRY(arena_reserve(c, c->staging, align_up(bt) + align_up(bs) + align_up((size_t)B * 48) + align_up((size_t)B * 72) +
-                                         align_up((size_t)B * 4) + align_up((size_t)B * 8) + 2048));
-    char *d_t = carve<char>(c->staging, bt), *d_s = carve<char>(c->staging, bs);
-    double *d_p = prior ? carve<double>(c->staging, (size_t)B * 6) : nullptr;
-    double *d_T = carve<double>(c->staging, (size_t)B * 9);
-    int32_t *d_i = carve<int32_t>(c->staging, B);
-    double *d_e = carve<double>(c->staging, B);
-    TRY(copy_in(c, {{d_t, const_cast<void *>(tar), bt}, {d_s, const_cast<void *>(src), bs},
-                    {d_p, const_cast<double *>(prior), prior ? (size_t)B * 48 : 0}}));
+    TRY(check_icp_batch(__func__, tar, src, B, n_tar, n_src, dtype, max_iter, T_out));
+    const size_t ds = dtype_size(dtype);
+    char *d_t, *d_s; double *d_p, *d_T, *d_e; int32_t *d_i;
+    Staging s(c);
+    s.in(d_t, static_cast<const char *>(tar), (size_t)(tar_shared ? 1 : B) * 2 * n_tar * ds)
+        .in(d_s, static_cast<const char *>(src), (size_t)(src_shared ? 1 : B) * 2 * n_src * ds)
+        .in(d_p, prior, (size_t)B * 6);
+    s.out(d_T, T_out, (size_t)B * 9).out_always(d_i, iters_out, B).out_always(d_e, mean_err_out, B);
+    TRY(s.upload());
     TRY(slam_icp_batch_dev(c, d_t, d_s, B, n_tar, n_src, dtype, tar_shared, src_shared, d_p, max_iter, tol, d_T, d_i, d_e));
-    return copy_out_sync(c, {{d_T, T_out, (size_t)B * 72}, {d_i, iters_out, (size_t)B * 4}, {d_e, mean_err_out, (size_t)B * 8}});
+    return s.download();
+}
+
+static int check_pose_compose(const char *fn, const double *T, const double *pose0, int L, int n, const double *poses_out)
+{
+    REQUIRE_IN(fn, T && pose0 && poses_out, "null pointer");
+    REQUIRE_IN(fn, L > 0 && n > 0, "sizes must be positive");
+    return SLAM_OK;
 }
 
 int slam_pose_compose_dev(slam_ctx *c, const double *T, const double *pose0, int L, int n, double *poses_out)
 {
     TRY(use(c));
-    REQUIRE(T && pose0 && poses_out, "null pointer");
-    REQUIRE(L > 0 && n > 0, "sizes must be positive");
+    TRY(check_pose_compose(__func__, T, pose0, L, n, poses_out));
     Timed t(c, SLAM_K_COMPOSE);
     HIPCHK(launch_pose_compose(T, pose0, L, n, poses_out, c->stream));
     return SLAM_OK;
@@ -829,18 +887,14 @@ int slam_pose_compose_dev(slam_ctx *c, const double *T, const double *pose0, int
 int slam_pose_compose(slam_ctx *c, const double *T, const double *pose0, int L, int n, double *poses_out)
 {
     TRY(use(c));
-    REQUIRE(T && pose0 && poses_out, "null pointer");
-    REQUIRE(L > 0 && n > 0, "sizes must be positive");
-    size_t nt = (size_t)L * n;
-    TRY(arena_reserve(c, c->staging, align_up(nt * 72) + align_up((size_t)L * 24) + align_up(nt * 24) + 1024));
-    double *d_T = carve<double>(c->staging, nt * 9), *d_0 = carve<double>(c->staging, (size_t)L * 3);
-    double *d_P = carve<double>(c->staging, nt * 3);
-    H2D(d_T, T, nt * 72);
-    H2D(d_0, pose0, (size_t)L * 24);
+    TRY(check_pose_compose(__func__, T, pose0, L, n, poses_out));
+    const size_t nt = (size_t)L * n;
+    double *d_T, *d_0, *d_P;
+    Staging s(c);
+    s.in(d_T, T, nt * 9).in(d_0, pose0, (size_t)L * 3).out(d_P, poses_out, nt * 3);
+    TRY(s.upload());
     TRY(slam_pose_compose_dev(c, d_T, d_0, L, n, d_P));
-    D2H(poses_out, d_P, nt * 24);
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return SLAM_OK;
+    return s.download();
 }
 
 /* ---- occupancy grid --------------------------------------------------------------- */
@@ -942,13 +996,20 @@ int slam_grid_reset(slam_ctx *c, slam_grid *g)
     return SLAM_OK;
 }
 
+static int check_grid_update(const char *fn, const slam_grid *g, const double *ox, const double *oy, const double *cx,
+                             const double *cy, int B, int n)
+{
+    REQUIRE_IN(fn, g && ox && oy && cx && cy, "null pointer");
+    REQUIRE_IN(fn, B > 0 && n > 0, "sizes must be positive");
+    return SLAM_OK;
+}
+
 int slam_grid_update_dev(slam_ctx *c, slam_grid *g, const double *ox, const double *oy, const double *cx, const double *cy,
                          int B, int n, const int32_t *grid_of_batch)
 {
     TRY(use(c));
     TRY(grid_on_main(c));
-    REQUIRE(g && ox && oy && cx && cy, "null pointer");
-    REQUIRE(B > 0 && n > 0, "sizes must be positive");
+    TRY(check_grid_update(__func__, g, ox, oy, cx, cy, B, n));
     g->pristine = false;
     Timed t(c, SLAM_K_GRID);
     CastRequest r;
@@ -965,18 +1026,14 @@ int slam_grid_update(slam_ctx *c, slam_grid *g, const double *ox, const double *
                      int B, int n, const int32_t *grid_of_batch)
 {
     TRY(use(c));
-    REQUIRE(g && ox && oy && cx && cy, "null pointer");
-    REQUIRE(B > 0 && n > 0, "sizes must be positive");
+    TRY(check_grid_update(__func__, g, ox, oy, cx, cy, B, n));
     if (grid_of_batch)
         for (int b = 0; b < B; ++b) REQUIRE(grid_of_batch[b] >= 0 && grid_of_batch[b] < g->d.G, "grid_of_batch out of range");
-    size_t np = (size_t)B * n;
-    TRY(arena_reserve(c, c->staging, 2 * align_up(np * 8) + 2 * align_up((size_t)B * 8) + align_up((size_t)B * 4) + 2048));
-    double *d_x = carve<double>(c->staging, np), *d_y = carve<double>(c->staging, np);
-    double *d_cx = carve<double>(c->staging, B), *d_cy = carve<double>(c->staging, B);
-    int32_t *d_g = grid_of_batch ? carve<int32_t>(c->staging, B) : nullptr;
-    TRY(copy_in(c, {{d_x, const_cast<double *>(ox), np * 8}, {d_y, const_cast<double *>(oy), np * 8},
-                    {d_cx, const_cast<double *>(cx), (size_t)B * 8}, {d_cy, const_cast<double *>(cy), (size_t)B * 8},
-                    {d_g, const_cast<int32_t *>(grid_of_batch), grid_of_batch ? (size_t)B * 4 : 0}}));
+    const size_t np = (size_t)B * n;
+    double *d_x, *d_y, *d_cx, *d_cy; int32_t *d_g;
+    Staging s(c);
+    s.in(d_x, ox, np).in(d_y, oy, np).in(d_cx, cx, B).in(d_cy, cy, B).in(d_g, grid_of_batch, B);
+    TRY(s.upload());
     TRY(slam_grid_update_dev(c, g, d_x, d_y, d_cx, d_cy, B, n, d_g));
     return check_status_sync(c);
 }
@@ -1003,13 +1060,20 @@ static int cast_replay(slam_ctx *c, slam_grid *g, const float *ranges, const dou
     return SLAM_OK;
 }
 
+static int check_grid_update_scans(const char *fn, const slam_grid *g, const float *ranges, const double *cos_t,
+                                   const double *sin_t, const double *poses, int S, int n)
+{
+    REQUIRE_IN(fn, g && ranges && cos_t && sin_t && poses, "null pointer");
+    REQUIRE_IN(fn, S > 0 && n > 0 && n <= 65535, "bad sizes");
+    return SLAM_OK;
+}
+
 int slam_grid_update_scans_dev(slam_ctx *c, slam_grid *g, const float *ranges, const double *cos_t, const double *sin_t,
                                const double *poses, const double *centres, int S, int n)
 {
     TRY(use(c));
     TRY(grid_on_main(c));
-    REQUIRE(g && ranges && cos_t && sin_t && poses, "null pointer");
-    REQUIRE(S > 0 && n > 0 && n <= 65535, "bad sizes");
+    TRY(check_grid_update_scans(__func__, g, ranges, cos_t, sin_t, poses, S, n));
     Timed t(c, SLAM_K_GRID);
     // scan k of cast_replay's stream is ranges[k + 1]: shift the base by one scan
     return cast_replay(c, g, ranges - n, cos_t, sin_t, poses, centres, 1, S + 1, n, nullptr, c->stream);
@@ -1019,20 +1083,11 @@ int slam_grid_update_scans(slam_ctx *c, slam_grid *g, const float *ranges, const
                            const double *poses, const double *centres, int S, int n)
 {
     TRY(use(c));
-    REQUIRE(g && ranges && cos_t && sin_t && poses, "null pointer");
-    REQUIRE(S > 0 && n > 0 && n <= 65535, "bad sizes");
-    size_t nr = (size_t)S * n;
-    TRY(arena_reserve(c, c->staging, align_up(nr * 4) + 2 * align_up((size_t)n * 8) + align_up((size_t)S * 24) +
-                                         align_up((size_t)S * 16) + 2048));
-    float *d_r = carve<float>(c->staging, nr);
-    double *d_c = carve<double>(c->staging, n), *d_s = carve<double>(c->staging, n);
-    double *d_p = carve<double>(c->staging, (size_t)S * 3);
-    double *d_o = centres ? carve<double>(c->staging, (size_t)S * 2) : nullptr;
-    H2D(d_r, ranges, nr * 4);
-    H2D(d_c, cos_t, (size_t)n * 8);
-    H2D(d_s, sin_t, (size_t)n * 8);
-    H2D(d_p, poses, (size_t)S * 24);
-    if (centres) H2D(d_o, centres, (size_t)S * 16);
+    TRY(check_grid_update_scans(__func__, g, ranges, cos_t, sin_t, poses, S, n));
+    float *d_r; double *d_c, *d_s, *d_p, *d_o;
+    Staging s(c);
+    s.in(d_r, ranges, (size_t)S * n).in(d_c, cos_t, n).in(d_s, sin_t, n).in(d_p, poses, (size_t)S * 3).in(d_o, centres, (size_t)S * 2);
+    TRY(s.upload());
     TRY(slam_grid_update_scans_dev(c, g, d_r, d_c, d_s, d_p, d_o, S, n));
     return check_status_sync(c);
 }
@@ -1183,42 +1238,40 @@ int slam_bresenham_batch(slam_ctx *c, const int32_t *starts, const int32_t *ends
         if (cells_out && (offsets[b] < 0 || offsets[b] + len > total_cells))
             return fail(SLAM_ERR_INVALID, "line %d does not fit cells_out", b);
     }
-    size_t tc = cells_out ? (size_t)total_cells : 0;
-    TRY(arena_reserve(c, c->staging, 2 * align_up((size_t)B * 8) + align_up((size_t)B * 8) + align_up((size_t)B * 4) +
-                                         align_up(tc * 8) + 2048));
-    int32_t *d_s = carve<int32_t>(c->staging, (size_t)B * 2), *d_e = carve<int32_t>(c->staging, (size_t)B * 2);
-    int64_t *d_o = carve<int64_t>(c->staging, B);
-    int32_t *d_l = carve<int32_t>(c->staging, B);
-    int32_t *d_c = cells_out ? carve<int32_t>(c->staging, tc * 2) : nullptr;
-    H2D(d_s, starts, (size_t)B * 8);
-    H2D(d_e, ends, (size_t)B * 8);
-    if (cells_out) H2D(d_o, offsets, (size_t)B * 8);
+    int32_t *d_s, *d_e, *d_l, *d_c; int64_t *d_o;
+    Staging s(c);
+    s.in(d_s, starts, (size_t)B * 2).in(d_e, ends, (size_t)B * 2).in(d_o, cells_out ? offsets : nullptr, B);
+    s.out(d_l, lens_out, B).out(d_c, cells_out, cells_out ? (size_t)total_cells * 2 : 0);
+    TRY(s.upload());
     {
         Timed t(c, SLAM_K_BRESENHAM);
         HIPCHK(launch_bresenham(d_s, d_e, B, d_o, d_l, d_c, c->stream));
     }
-    D2H(lens_out, d_l, (size_t)B * 4);
-    if (cells_out && tc) D2H(cells_out, d_c, tc * 8);
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return SLAM_OK;
+    return s.download();
 }
 
 /* ---- fused replay ------------------------------------------------------------------ */
+
+static int check_replay(const char *fn, const float *ranges, const double *cos_t, const double *sin_t, int L, int n_scan,
+                        int n, int dtype, int max_iter, const double *pose0, const double *poses_out)
+{
+    REQUIRE_IN(fn, ranges && cos_t && sin_t && pose0 && poses_out, "null pointer");
+    REQUIRE_IN(fn, L > 0 && n_scan >= 2 && n > 0, "need L > 0, n_scan >= 2, n > 0");
+    REQUIRE_IN(fn, max_iter >= 0, "max_iter must be >= 0");
+    REQUIRE_IN(fn, dtype_size(dtype), "unknown dtype");
+    REQUIRE_IN(fn, n <= 8192, "n too large (max 8192 beams)");
+    REQUIRE_IN(fn, (long)L * (n_scan - 1) < (1L << 31), "too many scan pairs for one launch");
+    return SLAM_OK;
+}
 
 int slam_replay_dev(slam_ctx *c, const float *ranges, const double *cos_t, const double *sin_t, int L, int n_scan, int n,
                     int dtype, int max_iter, double tol, const double *pose0, slam_grid *grid, const int32_t *grid_of_traj,
                     void *pts_ws, double *poses_out, double *T_out, int32_t *iters_out)
 {
     TRY(use(c));
-    REQUIRE(ranges && cos_t && sin_t && pose0 && poses_out, "null pointer");
+    TRY(check_replay(__func__, ranges, cos_t, sin_t, L, n_scan, n, dtype, max_iter, pose0, poses_out));
     (void)pts_ws;   // kept in the ABI; the point buffers are no longer materialised
-    REQUIRE(L > 0 && n_scan >= 2 && n > 0, "need L > 0, n_scan >= 2, n > 0");
-    REQUIRE(max_iter >= 0, "max_iter must be >= 0");
-    size_t ds = dtype_size(dtype);
-    REQUIRE(ds, "unknown dtype");
-    REQUIRE(n <= 8192, "n too large (max 8192 beams)");
     const long pairs = (long)L * (n_scan - 1);
-    REQUIRE(pairs < (1L << 31), "too many scan pairs for one launch");
     const bool piped = c->pipeline && grid;     // three stages on three streams: ICP | compose | map
     double *T = T_out;
     if (!T) {
@@ -1313,48 +1366,46 @@ int slam_replay(slam_ctx *c, const float *ranges, const double *cos_t, const dou
                 double *poses_out, double *T_out, int32_t *iters_out)
 {
     TRY(use(c));
-    REQUIRE(ranges && cos_t && sin_t && pose0 && poses_out, "null pointer");
-    REQUIRE(L > 0 && n_scan >= 2 && n > 0, "need L > 0, n_scan >= 2, n > 0");
-    size_t ds = dtype_size(dtype);
-    REQUIRE(ds, "unknown dtype");
+    TRY(check_replay(__func__, ranges, cos_t, sin_t, L, n_scan, n, dtype, max_iter, pose0, poses_out));
     if (grid && grid_of_traj)
         for (int l = 0; l < L; ++l) REQUIRE(grid_of_traj[l] >= 0 && grid_of_traj[l] < grid->d.G, "grid_of_traj out of range");
-    size_t nr = (size_t)L * n_scan * n, pairs = (size_t)L * (n_scan - 1);
-    TRY(arena_reserve(c, c->staging, align_up(nr * 4) + 2 * align_up((size_t)n * 8) + align_up((size_t)L * 24) +
-                                         align_up(pairs * 72) + align_up(pairs * 24) + align_up(pairs * 4) +
-                                         align_up((size_t)L * 4) + 4096));
-    float *d_r = carve<float>(c->staging, nr);
-    double *d_c = carve<double>(c->staging, n), *d_s = carve<double>(c->staging, n);
-    double *d_0 = carve<double>(c->staging, (size_t)L * 3);
-    int32_t *d_g = (grid && grid_of_traj) ? carve<int32_t>(c->staging, L) : nullptr;
-    double *d_T = carve<double>(c->staging, pairs * 9), *d_P = carve<double>(c->staging, pairs * 3);
-    int32_t *d_it = carve<int32_t>(c->staging, pairs);
-    TRY(copy_in(c, {{d_r, const_cast<float *>(ranges), nr * 4}, {d_c, const_cast<double *>(cos_t), (size_t)n * 8},
-                    {d_s, const_cast<double *>(sin_t), (size_t)n * 8}, {d_0, const_cast<double *>(pose0), (size_t)L * 24},
-                    {d_g, const_cast<int32_t *>(grid_of_traj), d_g ? (size_t)L * 4 : 0}}));
+    const size_t pairs = (size_t)L * (n_scan - 1);
+    float *d_r; double *d_c, *d_s, *d_0, *d_T, *d_P; int32_t *d_g, *d_it;
+    Staging s(c);
+    s.in(d_r, ranges, (size_t)L * n_scan * n).in(d_c, cos_t, n).in(d_s, sin_t, n).in(d_0, pose0, (size_t)L * 3)
+        .in(d_g, grid ? grid_of_traj : nullptr, L);
+    s.out_always(d_T, T_out, pairs * 9).out(d_P, poses_out, pairs * 3).out_always(d_it, iters_out, pairs);
+    TRY(s.upload());
     TRY(slam_replay_dev(c, d_r, d_c, d_s, L, n_scan, n, dtype, max_iter, tol, d_0, grid, d_g, nullptr, d_P, d_T, d_it));
     // "pipeline" option with a map: compose ran on cstream and the ray cast on gstream (which
     // waited for compose): the copies below are issued on the main stream, which must first see
     // both (join_from_grid records on gstream, i.e. after ev_pose of cstream).
     TRY(join_from_grid(c));
-    TRY(copy_out_sync(c, {{d_P, poses_out, pairs * 24}, {d_T, T_out, pairs * 72}, {d_it, iters_out, pairs * 4}}));
+    TRY(s.download());
     return check_status_sync(c);
 }
 
 /* ---- particle hypotheses ----------------------------------------------------------- */
+
+static int check_particles(const char *fn, const float *ranges2, const double *cos_t, const double *sin_t, int n, int dtype,
+                           const double *pose_prev, int P, int max_iter, const slam_grid *grid, const double *poses_out)
+{
+    REQUIRE_IN(fn, ranges2 && cos_t && sin_t && pose_prev && poses_out, "null pointer");
+    REQUIRE_IN(fn, P > 0 && n > 0 && n <= 8192, "need P > 0 and 0 < n <= 8192");
+    REQUIRE_IN(fn, max_iter >= 0, "max_iter must be >= 0");
+    REQUIRE_IN(fn, dtype_size(dtype), "unknown dtype");
+    REQUIRE_IN(fn, !grid || grid->d.G >= P, "the grid object needs one map per particle");
+    return SLAM_OK;
+}
 
 int slam_particles_dev(slam_ctx *c, const float *ranges2, const double *cos_t, const double *sin_t, int n, int dtype,
                        const double *prior, const double *pose_prev, int P, int max_iter, double tol, slam_grid *grid,
                        void *pts_ws, double *poses_out, double *T_out, int32_t *iters_out)
 {
     TRY(use(c));
-    REQUIRE(ranges2 && cos_t && sin_t && pose_prev && poses_out && T_out, "null pointer");
+    REQUIRE(T_out, "null pointer");
+    TRY(check_particles(__func__, ranges2, cos_t, sin_t, n, dtype, pose_prev, P, max_iter, grid, poses_out));
     (void)pts_ws;   // kept in the ABI; the point buffers are no longer materialised
-    REQUIRE(P > 0 && n > 0 && n <= 8192, "need P > 0 and 0 < n <= 8192");
-    REQUIRE(max_iter >= 0, "max_iter must be >= 0");
-    size_t ds = dtype_size(dtype);
-    REQUIRE(ds, "unknown dtype");
-    REQUIRE(!grid || grid->d.G >= P, "the grid object needs one map per particle");
     // Chunks (option "particle_chunks", off by default): matcher and pose step of chunk k on the context's stream, its ray
     // cast on a second stream behind an event, beside the matcher of chunk k + 1.  The matcher is bound by vector issue and
     // the ray cast by memory traffic, so the two should share the chip well - they do not (measured, round 4: 10 000
@@ -1446,46 +1497,36 @@ int slam_particles(slam_ctx *c, const float *ranges2, const double *cos_t, const
                    double *poses_out, double *T_out, int32_t *iters_out)
 {
     TRY(use(c));
-    REQUIRE(ranges2 && cos_t && sin_t && pose_prev && poses_out, "null pointer");
-    REQUIRE(P > 0 && n > 0, "sizes must be positive");
-    size_t ds = dtype_size(dtype);
-    REQUIRE(ds, "unknown dtype");
-    TRY(arena_reserve(c, c->staging, align_up((size_t)2 * n * 4) + 2 * align_up((size_t)n * 8) + align_up((size_t)P * 48) +
-                                         align_up((size_t)P * 24) * 2 + align_up(4 * (size_t)n * ds) + align_up((size_t)P * 72) +
-                                         align_up((size_t)P * 4) + 4096));
-    float *d_r = carve<float>(c->staging, 2 * (size_t)n);
-    double *d_c = carve<double>(c->staging, n), *d_s = carve<double>(c->staging, n);
-    double *d_pr = prior ? carve<double>(c->staging, (size_t)P * 6) : nullptr;
-    double *d_p0 = carve<double>(c->staging, (size_t)P * 3), *d_P = carve<double>(c->staging, (size_t)P * 3);
-    char *d_pts = carve<char>(c->staging, 4 * (size_t)n * ds);
-    double *d_T = carve<double>(c->staging, (size_t)P * 9);
-    int32_t *d_it = carve<int32_t>(c->staging, P);
-    H2D(d_r, ranges2, 2 * (size_t)n * 4);
-    H2D(d_c, cos_t, (size_t)n * 8);
-    H2D(d_s, sin_t, (size_t)n * 8);
-    if (prior) H2D(d_pr, prior, (size_t)P * 48);
-    H2D(d_p0, pose_prev, (size_t)P * 24);
-    TRY(slam_particles_dev(c, d_r, d_c, d_s, n, dtype, d_pr, d_p0, P, max_iter, tol, grid, d_pts, d_P, d_T, d_it));
-    D2H(poses_out, d_P, (size_t)P * 24);
-    if (T_out) D2H(T_out, d_T, (size_t)P * 72);
-    if (iters_out) D2H(iters_out, d_it, (size_t)P * 4);
+    TRY(check_particles(__func__, ranges2, cos_t, sin_t, n, dtype, pose_prev, P, max_iter, grid, poses_out));
+    float *d_r; double *d_c, *d_s, *d_pr, *d_p0, *d_P, *d_T; int32_t *d_it;
+    Staging s(c);
+    s.in(d_r, ranges2, 2 * (size_t)n).in(d_c, cos_t, n).in(d_s, sin_t, n).in(d_pr, prior, (size_t)P * 6).in(d_p0, pose_prev, (size_t)P * 3);
+    s.out(d_P, poses_out, (size_t)P * 3).out_always(d_T, T_out, (size_t)P * 9).out_always(d_it, iters_out, P);
+    TRY(s.upload());
+    TRY(slam_particles_dev(c, d_r, d_c, d_s, n, dtype, d_pr, d_p0, P, max_iter, tol, grid, nullptr, d_P, d_T, d_it));
+    TRY(s.download());
     return check_status_sync(c);
 }
 
 /* ---- scan-to-map observation ------------------------------------- */
 
+static int check_map_obstacles(const char *fn, const int8_t *map, int width, int height, const double *ox, const double *oy,
+                               int cap, const int *count)
+{
+    REQUIRE_IN(fn, map && ox && oy && count, "null pointer");
+    REQUIRE_IN(fn, width > 0 && height > 0 && cap >= 0, "bad sizes");
+    return SLAM_OK;
+}
+
 int slam_map_obstacles(slam_ctx *c, const int8_t *map, int width, int height, int wire_layout, double resolution,
                        double origin_x, double origin_y, double *ox, double *oy, int cap, int *count_out)
 {
     TRY(use(c));
-    REQUIRE(map && ox && oy && count_out, "null pointer");
-    REQUIRE(width > 0 && height > 0 && cap >= 0, "bad sizes");
-    size_t cells = (size_t)width * height;
-    TRY(arena_reserve(c, c->staging, align_up(cells) + 2 * align_up((size_t)cap * 8) + 1024));
-    int8_t *d_m = carve<int8_t>(c->staging, cells);
-    double *d_x = carve<double>(c->staging, cap), *d_y = carve<double>(c->staging, cap);
-    int *d_k = carve<int>(c->staging, 1);
-    H2D(d_m, map, cells);
+    TRY(check_map_obstacles(__func__, map, width, height, ox, oy, cap, count_out));
+    int8_t *d_m; double *d_x, *d_y; int *d_k;
+    Staging s(c);
+    s.in(d_m, map, (size_t)width * height).work(d_x, cap).work(d_y, cap).work(d_k, 1);
+    TRY(s.upload());
     HIPCHK(launch_map_obstacles(d_m, width, height, wire_layout, resolution, origin_x, origin_y, d_x, d_y, cap, d_k, c->stream));
     int k = 0;
     D2H(&k, d_k, sizeof(int));
@@ -1504,9 +1545,17 @@ int slam_map_obstacles_dev(slam_ctx *c, const int8_t *map, int width, int height
                            double origin_x, double origin_y, double *ox, double *oy, int cap, int *count_dev)
 {
     TRY(use(c));
-    REQUIRE(map && ox && oy && count_dev, "null pointer");
-    REQUIRE(width > 0 && height > 0 && cap >= 0, "bad sizes");
+    TRY(check_map_obstacles(__func__, map, width, height, ox, oy, cap, count_dev));
     HIPCHK(launch_map_obstacles(map, width, height, wire_layout, resolution, origin_x, origin_y, ox, oy, cap, count_dev, c->stream));
+    return SLAM_OK;
+}
+
+static int check_virtual_scan(const char *fn, const double *ox, const double *oy, int K, const double *poses, int B,
+                              double angle_min, double angle_increment, int n)
+{
+    REQUIRE_IN(fn, (K == 0 || (ox && oy)) && poses, "null pointer");
+    REQUIRE_IN(fn, K >= 0 && B > 0 && n > 0 && n <= 8192, "bad sizes");
+    REQUIRE_IN(fn, angle_increment != 0.0 && std::isfinite(angle_increment) && std::isfinite(angle_min), "bad angles");
     return SLAM_OK;
 }
 
@@ -1514,9 +1563,8 @@ int slam_virtual_scan_dev(slam_ctx *c, const double *ox, const double *oy, int K
                           double angle_min, double angle_increment, int n, double *ranges_out)
 {
     TRY(use(c));
-    REQUIRE((K == 0 || (ox && oy)) && poses && ranges_out, "null pointer");
-    REQUIRE(K >= 0 && B > 0 && n > 0 && n <= 8192, "bad sizes");
-    REQUIRE(angle_increment != 0.0 && std::isfinite(angle_increment) && std::isfinite(angle_min), "bad angles");
+    REQUIRE(ranges_out, "null pointer");
+    TRY(check_virtual_scan(__func__, ox, oy, K, poses, B, angle_min, angle_increment, n));
     HIPCHK(launch_virtual_scan(ox, oy, K, poses, B, angle_min, angle_increment, n, ranges_out, c->stream));
     return SLAM_OK;
 }
@@ -1525,16 +1573,21 @@ int slam_virtual_scan(slam_ctx *c, const double *ox, const double *oy, int K, co
                       double angle_increment, int n, double *ranges_out)
 {
     TRY(use(c));
-    REQUIRE((K == 0 || (ox && oy)) && poses && ranges_out, "null pointer");
-    REQUIRE(K >= 0 && B > 0 && n > 0, "bad sizes");
-    TRY(arena_reserve(c, c->staging, 2 * align_up((size_t)K * 8) + align_up((size_t)B * 24) + align_up((size_t)B * n * 8) + 2048));
-    double *d_x = carve<double>(c->staging, K), *d_y = carve<double>(c->staging, K);
-    double *d_p = carve<double>(c->staging, (size_t)B * 3), *d_r = carve<double>(c->staging, (size_t)B * n);
-    if (K) { H2D(d_x, ox, (size_t)K * 8); H2D(d_y, oy, (size_t)K * 8); }
-    H2D(d_p, poses, (size_t)B * 24);
+    REQUIRE(ranges_out, "null pointer");
+    TRY(check_virtual_scan(__func__, ox, oy, K, poses, B, angle_min, angle_increment, n));
+    double *d_x, *d_y, *d_p, *d_r;
+    Staging s(c);
+    s.in(d_x, ox, K).in(d_y, oy, K).in(d_p, poses, (size_t)B * 3).out(d_r, ranges_out, (size_t)B * n);
+    TRY(s.upload());
     TRY(slam_virtual_scan_dev(c, d_x, d_y, K, d_p, B, angle_min, angle_increment, n, d_r));
-    D2H(ranges_out, d_r, (size_t)B * n * 8);
-    HIPCHK(hipStreamSynchronize(c->stream));
+    return s.download();
+}
+
+static int check_scan_to_points_f64(const char *fn, const double *ranges, const double *cos_t, const double *sin_t, int B,
+                                    int n, const double *pts_out)
+{
+    REQUIRE_IN(fn, ranges && cos_t && sin_t && pts_out, "null pointer");
+    REQUIRE_IN(fn, B > 0 && n > 0, "bad sizes");
     return SLAM_OK;
 }
 
@@ -1542,8 +1595,7 @@ int slam_scan_to_points_f64_dev(slam_ctx *c, const double *ranges, const double 
                                 double *pts_out)
 {
     TRY(use(c));
-    REQUIRE(ranges && cos_t && sin_t && pts_out, "null pointer");
-    REQUIRE(B > 0 && n > 0, "bad sizes");
+    TRY(check_scan_to_points_f64(__func__, ranges, cos_t, sin_t, B, n, pts_out));
     HIPCHK(launch_ranges64_to_points(ranges, cos_t, sin_t, B, n, pts_out, c->stream));
     return SLAM_OK;
 }
@@ -1552,19 +1604,22 @@ int slam_scan_to_points_f64(slam_ctx *c, const double *ranges, const double *cos
                             double *pts_out)
 {
     TRY(use(c));
-    REQUIRE(ranges && cos_t && sin_t && pts_out, "null pointer");
-    REQUIRE(B > 0 && n > 0, "bad sizes");
-    TRY(arena_reserve(c, c->staging, align_up((size_t)B * n * 8) + 2 * align_up((size_t)n * 8) + align_up((size_t)B * 2 * n * 8) + 2048));
-    double *d_r = carve<double>(c->staging, (size_t)B * n);
-    double *d_c = carve<double>(c->staging, n), *d_s = carve<double>(c->staging, n);
-    double *d_p = carve<double>(c->staging, (size_t)B * 2 * n);
-    H2D(d_r, ranges, (size_t)B * n * 8);
-    H2D(d_c, cos_t, (size_t)n * 8);
-    H2D(d_s, sin_t, (size_t)n * 8);
+    TRY(check_scan_to_points_f64(__func__, ranges, cos_t, sin_t, B, n, pts_out));
+    double *d_r, *d_c, *d_s, *d_p;
+    Staging s(c);
+    s.in(d_r, ranges, (size_t)B * n).in(d_c, cos_t, n).in(d_s, sin_t, n).out(d_p, pts_out, (size_t)B * 2 * n);
+    TRY(s.upload());
     TRY(slam_scan_to_points_f64_dev(c, d_r, d_c, d_s, B, n, d_p));
-    D2H(pts_out, d_p, (size_t)B * 2 * n * 8);
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return SLAM_OK;
+    return s.download();
+}
+
+static int check_map_observation(const char *fn, const double *ox, const double *oy, int K, const double *poses,
+                                 const double *src, int B, int n, const double *cos_t, const double *sin_t, double angle_min,
+                                 double angle_increment, int max_iter, const double *T_out)
+{
+    REQUIRE_IN(fn, src && cos_t && sin_t && T_out, "null pointer");
+    REQUIRE_IN(fn, max_iter >= 0, "max_iter must be >= 0");
+    return check_virtual_scan(fn, ox, oy, K, poses, B, angle_min, angle_increment, n);
 }
 
 int slam_map_observation_dev(slam_ctx *c, const double *ox, const double *oy, int K, const double *poses, const double *src,
@@ -1573,8 +1628,8 @@ int slam_map_observation_dev(slam_ctx *c, const double *ox, const double *oy, in
                              double *T_out, int32_t *iters_out)
 {
     TRY(use(c));
-    REQUIRE(poses && src && cos_t && sin_t && vranges_ws && vpts_ws && T_out, "null pointer");
-    REQUIRE(B > 0 && n > 0 && n <= 8192, "bad sizes");
+    REQUIRE(vranges_ws && vpts_ws, "null pointer");
+    TRY(check_map_observation(__func__, ox, oy, K, poses, src, B, n, cos_t, sin_t, angle_min, angle_increment, max_iter, T_out));
     TRY(slam_virtual_scan_dev(c, ox, oy, K, poses, B, angle_min, angle_increment, n, vranges_ws));
     HIPCHK(launch_ranges64_to_points(vranges_ws, cos_t, sin_t, B, n, vpts_ws, c->stream));
     return slam_icp_batch_dev(c, vpts_ws, src, B, n, n, SLAM_F64, 0, src_shared, nullptr, max_iter, tol, T_out, iters_out,
@@ -1586,30 +1641,16 @@ int slam_map_observation(slam_ctx *c, const double *ox, const double *oy, int K,
                          double angle_increment, int max_iter, double tol, double *T_out, int32_t *iters_out)
 {
     TRY(use(c));
-    REQUIRE((K == 0 || (ox && oy)) && poses && src && cos_t && sin_t && T_out, "null pointer");
-    REQUIRE(K >= 0 && B > 0 && n > 0, "bad sizes");
-    size_t bs = (size_t)(src_shared ? 1 : B) * 2 * n * 8;
-    TRY(arena_reserve(c, c->staging, 2 * align_up((size_t)K * 8) + align_up((size_t)B * 24) + align_up(bs) + 2 * align_up((size_t)n * 8) +
-                                         align_up((size_t)B * n * 8) + align_up((size_t)B * 2 * n * 8) + align_up((size_t)B * 72) +
-                                         align_up((size_t)B * 4) + 4096));
-    double *d_x = carve<double>(c->staging, K), *d_y = carve<double>(c->staging, K);
-    double *d_p = carve<double>(c->staging, (size_t)B * 3);
-    double *d_s = carve<double>(c->staging, bs / 8);
-    double *d_c = carve<double>(c->staging, n), *d_sn = carve<double>(c->staging, n);
-    double *d_vr = carve<double>(c->staging, (size_t)B * n), *d_vp = carve<double>(c->staging, (size_t)B * 2 * n);
-    double *d_T = carve<double>(c->staging, (size_t)B * 9);
-    int32_t *d_it = carve<int32_t>(c->staging, B);
-    if (K) { H2D(d_x, ox, (size_t)K * 8); H2D(d_y, oy, (size_t)K * 8); }
-    H2D(d_p, poses, (size_t)B * 24);
-    H2D(d_s, src, bs);
-    H2D(d_c, cos_t, (size_t)n * 8);
-    H2D(d_sn, sin_t, (size_t)n * 8);
+    TRY(check_map_observation(__func__, ox, oy, K, poses, src, B, n, cos_t, sin_t, angle_min, angle_increment, max_iter, T_out));
+    double *d_x, *d_y, *d_p, *d_s, *d_c, *d_sn, *d_vr, *d_vp, *d_T; int32_t *d_it;
+    Staging s(c);
+    s.in(d_x, ox, K).in(d_y, oy, K).in(d_p, poses, (size_t)B * 3).in(d_s, src, (size_t)(src_shared ? 1 : B) * 2 * n)
+        .in(d_c, cos_t, n).in(d_sn, sin_t, n);
+    s.work(d_vr, (size_t)B * n).work(d_vp, (size_t)B * 2 * n).out(d_T, T_out, (size_t)B * 9).out_always(d_it, iters_out, B);
+    TRY(s.upload());
     TRY(slam_map_observation_dev(c, d_x, d_y, K, d_p, d_s, B, n, src_shared, d_c, d_sn, angle_min, angle_increment, max_iter,
                                  tol, d_vr, d_vp, d_T, d_it));
-    D2H(T_out, d_T, (size_t)B * 72);
-    if (iters_out) D2H(iters_out, d_it, (size_t)B * 4);
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return SLAM_OK;
+    return s.download();
 }
 
 /* ---- DWA local planner ------------------------------------------------------------------ */
@@ -1620,14 +1661,22 @@ int slam_dwa_shape(const double *config, int *rows_out, int *nv_cap_out, int *nw
     return dwa_config(config, nullptr, rows_out, nv_cap_out, nw_cap_out);
 }
 
+static int check_dwa_obstacles(const char *fn, const double *states, const double *goals, const double *obstacles, int M,
+                               const double *config, int B, const DwaOut &o, DwaArgs &a)
+{
+    REQUIRE_IN(fn, obstacles, "null pointer");
+    REQUIRE_IN(fn, M > 0, "M must be > 0 (np.min of an empty obstacle set raises, dwa.py:157)");
+    return check_dwa(fn, states, goals, config, B, o, a);
+}
+
 int slam_dwa_dev(slam_ctx *c, const double *states, const double *goals, const double *obstacles, const int32_t *counts,
                  int M, int shared, const double *config, int B, double *u_out, double *cost_out, int32_t *index_out,
                  int32_t *counts_out, double *costs_out, int s_cap, double *traj_out)
 {
     TRY(use(c));
-    REQUIRE(obstacles, "null pointer");
-    REQUIRE(M > 0, "M must be > 0 (np.min of an empty obstacle set raises, dwa.py:157)");
+    const DwaOut o{u_out, cost_out, index_out, counts_out, costs_out, s_cap, traj_out};
     DwaArgs a;
+    TRY(check_dwa_obstacles(__func__, states, goals, obstacles, M, config, B, o, a));
     a.states = states;
     a.goals = goals;
     a.obs = obstacles;
@@ -1637,63 +1686,43 @@ int slam_dwa_dev(slam_ctx *c, const double *states, const double *goals, const d
     a.count_stride = shared ? 0 : 1;
     a.B = B;
     a.tile_cap = M < kDwaTile ? M : kDwaTile;
-    return dwa_launch(c, a, config, DwaOut{u_out, cost_out, index_out, counts_out, costs_out, s_cap, traj_out});
-}
-
-// Host forms: stage states, goals, the obstacle input (`in`: obstacles or ranges, in_bytes), the scans form's cos / sin
-// tables (`extra`) and counts, run the device form, copy back.
-static int dwa_host(slam_ctx *c, const double *states, const double *goals, int B, const double *config, size_t in_bytes,
-                    const void *in, const int32_t *counts, int ncounts, double *u_out, double *cost_out,
-                    int32_t *index_out, int32_t *counts_out, double *costs_out, int s_cap, double *traj_out,
-                    const double *extra, size_t extra_bytes, bool scans, int M, int n, int shared, double threshold)
-{
-    TRY(use(c));
-    REQUIRE(states && goals && in && u_out && cost_out && index_out, "null pointer");
-    REQUIRE(B > 0, "B must be > 0");
-    REQUIRE(!costs_out || s_cap > 0, "costs_out needs s_cap > 0");
-    int rows = 0, nvc = 0, nwc = 0;
-    TRY(dwa_config(config, nullptr, &rows, &nvc, &nwc));
-    const size_t Bz = (size_t)B;
-    const size_t traj_bytes = traj_out ? Bz * rows * 40 : 0, costs_bytes = costs_out ? Bz * s_cap * 8 : 0;
-    TRY(arena_reserve(c, c->staging, align_up(Bz * 40) + align_up(Bz * 16) + align_up(in_bytes) + align_up(extra_bytes) +
-                                         align_up((size_t)ncounts * 4) + align_up(Bz * 16) + align_up(Bz * 8) + align_up(Bz * 4) +
-                                         align_up(Bz * 8) + align_up(costs_bytes) + align_up(traj_bytes) + 4096));
-    double *d_st = carve<double>(c->staging, Bz * 5), *d_g = carve<double>(c->staging, Bz * 2);
-    char *d_in = carve<char>(c->staging, in_bytes);
-    double *d_ex = carve<double>(c->staging, extra_bytes / 8);
-    int32_t *d_k = carve<int32_t>(c->staging, ncounts);
-    double *d_u = carve<double>(c->staging, Bz * 2), *d_c = carve<double>(c->staging, Bz);
-    int32_t *d_i = carve<int32_t>(c->staging, Bz), *d_n = carve<int32_t>(c->staging, Bz * 2);
-    double *d_cs = carve<double>(c->staging, costs_bytes / 8), *d_t = carve<double>(c->staging, traj_bytes / 8);
-    TRY(copy_in(c, {{d_st, (void *)states, Bz * 40}, {d_g, (void *)goals, Bz * 16}, {d_in, (void *)in, in_bytes},
-                    {d_ex, (void *)extra, extra_bytes}, {d_k, (void *)counts, (size_t)ncounts * 4}}));
-    if (scans)
-        TRY(slam_dwa_scans_dev(c, d_st, d_g, reinterpret_cast<const float *>(d_in), n, shared, d_ex, d_ex + n, threshold,
-                               config, B, d_u, d_c, d_i, counts_out ? d_n : nullptr, costs_out ? d_cs : nullptr, s_cap,
-                               traj_out ? d_t : nullptr));
-    else
-        TRY(slam_dwa_dev(c, d_st, d_g, reinterpret_cast<const double *>(d_in), counts ? d_k : nullptr, M, shared, config, B,
-                         d_u, d_c, d_i, counts_out ? d_n : nullptr, costs_out ? d_cs : nullptr, s_cap,
-                         traj_out ? d_t : nullptr));
-    TRY(copy_out_sync(c, {{d_u, u_out, Bz * 16}, {d_c, cost_out, Bz * 8}, {d_i, index_out, Bz * 4},
-                          {d_n, counts_out, counts_out ? Bz * 8 : 0}, {d_cs, costs_out, costs_bytes}, {d_t, traj_out, traj_bytes}}));
-    return check_status_sync(c);
+    return dwa_launch(c, a, o);
 }
 
 int slam_dwa(slam_ctx *c, const double *states, const double *goals, const double *obstacles, const int32_t *counts,
              int M, int shared, const double *config, int B, double *u_out, double *cost_out, int32_t *index_out,
              int32_t *counts_out, double *costs_out, int s_cap, double *traj_out)
 {
-    REQUIRE(M > 0, "M must be > 0 (np.min of an empty obstacle set raises, dwa.py:157)");
-    REQUIRE(B > 0, "B must be > 0");
+    TRY(use(c));
+    DwaArgs a;
+    TRY(check_dwa_obstacles(__func__, states, goals, obstacles, M, config, B,
+                            DwaOut{u_out, cost_out, index_out, counts_out, costs_out, s_cap, traj_out}, a));
     const int sets = shared ? 1 : B;
     if (counts)
         for (int b = 0; b < sets; ++b)
             if (counts[b] < 1 || counts[b] > M)
                 return fail(SLAM_ERR_INVALID, "slam_dwa: counts[%d] = %d outside [1, M = %d] (np.min of an empty set raises, dwa.py:157)",
                             b, counts[b], M);
-    return dwa_host(c, states, goals, B, config, (size_t)sets * 2 * M * 8, obstacles, counts, counts ? sets : 0, u_out,
-                    cost_out, index_out, counts_out, costs_out, s_cap, traj_out, nullptr, 0, false, M, 0, shared, 0.0);
+    const size_t Bz = (size_t)B;
+    double *d_st, *d_g, *d_ob, *d_u, *d_c, *d_cs, *d_t; int32_t *d_k, *d_i, *d_n;
+    Staging s(c);
+    s.in(d_st, states, Bz * 5).in(d_g, goals, Bz * 2).in(d_ob, obstacles, (size_t)sets * 2 * M).in(d_k, counts, sets);
+    s.out(d_u, u_out, Bz * 2).out(d_c, cost_out, Bz).out(d_i, index_out, Bz).out(d_n, counts_out, Bz * 2)
+        .out(d_cs, costs_out, Bz * s_cap).out(d_t, traj_out, Bz * a.rows * 5);
+    TRY(s.upload());
+    TRY(slam_dwa_dev(c, d_st, d_g, d_ob, d_k, M, shared, config, B, d_u, d_c, d_i, d_n, d_cs, s_cap, d_t));
+    TRY(s.download());
+    return check_status_sync(c);
+}
+
+static int check_dwa_scans(const char *fn, const double *states, const double *goals, const float *ranges, int n,
+                           const double *cos_t, const double *sin_t, double threshold, const double *config, int B,
+                           const DwaOut &o, DwaArgs &a)
+{
+    REQUIRE_IN(fn, ranges && cos_t && sin_t, "null pointer");
+    REQUIRE_IN(fn, n > 0 && n <= kDwaMaxBeams, "n must be in [1, 4095]");
+    REQUIRE_IN(fn, !std::isnan(threshold), "threshold is NaN");
+    return check_dwa(fn, states, goals, config, B, o, a);
 }
 
 int slam_dwa_scans_dev(slam_ctx *c, const double *states, const double *goals, const float *ranges, int n, int shared,
@@ -1702,10 +1731,9 @@ int slam_dwa_scans_dev(slam_ctx *c, const double *states, const double *goals, c
                        int s_cap, double *traj_out)
 {
     TRY(use(c));
-    REQUIRE(ranges && cos_t && sin_t, "null pointer");
-    REQUIRE(n > 0 && n <= kDwaMaxBeams, "n must be in [1, 4095]");
-    REQUIRE(!std::isnan(threshold), "threshold is NaN");
+    const DwaOut o{u_out, cost_out, index_out, counts_out, costs_out, s_cap, traj_out};
     DwaArgs a;
+    TRY(check_dwa_scans(__func__, states, goals, ranges, n, cos_t, sin_t, threshold, config, B, o, a));
     a.states = states;
     a.goals = goals;
     a.ranges = ranges;
@@ -1716,7 +1744,7 @@ int slam_dwa_scans_dev(slam_ctx *c, const double *states, const double *goals, c
     a.threshold = threshold;
     a.B = B;
     a.tile_cap = n + 1;
-    return dwa_launch(c, a, config, DwaOut{u_out, cost_out, index_out, counts_out, costs_out, s_cap, traj_out});
+    return dwa_launch(c, a, o);
 }
 
 int slam_dwa_scans(slam_ctx *c, const double *states, const double *goals, const float *ranges, int n, int shared,
@@ -1724,16 +1752,20 @@ int slam_dwa_scans(slam_ctx *c, const double *states, const double *goals, const
                    double *u_out, double *cost_out, int32_t *index_out, int32_t *counts_out, double *costs_out,
                    int s_cap, double *traj_out)
 {
-    REQUIRE(ranges && cos_t && sin_t, "null pointer");
-    REQUIRE(n > 0 && n <= kDwaMaxBeams, "n must be in [1, 4095]");
-    REQUIRE(B > 0, "B must be > 0");
-    REQUIRE(!std::isnan(threshold), "threshold is NaN");
-    std::vector<double> trig((size_t)2 * n);
-    memcpy(trig.data(), cos_t, (size_t)n * 8);
-    memcpy(trig.data() + n, sin_t, (size_t)n * 8);
-    return dwa_host(c, states, goals, B, config, (size_t)(shared ? 1 : B) * n * 4, ranges, nullptr, 0, u_out, cost_out,
-                    index_out, counts_out, costs_out, s_cap, traj_out, trig.data(), trig.size() * 8, true, 0, n, shared,
-                    threshold);
+    TRY(use(c));
+    DwaArgs a;
+    TRY(check_dwa_scans(__func__, states, goals, ranges, n, cos_t, sin_t, threshold, config, B,
+                        DwaOut{u_out, cost_out, index_out, counts_out, costs_out, s_cap, traj_out}, a));
+    const size_t Bz = (size_t)B;
+    float *d_r; double *d_st, *d_g, *d_ct, *d_sn, *d_u, *d_c, *d_cs, *d_t; int32_t *d_i, *d_n;
+    Staging s(c);
+    s.in(d_st, states, Bz * 5).in(d_g, goals, Bz * 2).in(d_r, ranges, (size_t)(shared ? 1 : B) * n).in(d_ct, cos_t, n).in(d_sn, sin_t, n);
+    s.out(d_u, u_out, Bz * 2).out(d_c, cost_out, Bz).out(d_i, index_out, Bz).out(d_n, counts_out, Bz * 2)
+        .out(d_cs, costs_out, Bz * s_cap).out(d_t, traj_out, Bz * a.rows * 5);
+    TRY(s.upload());
+    TRY(slam_dwa_scans_dev(c, d_st, d_g, d_r, n, shared, d_ct, d_sn, threshold, config, B, d_u, d_c, d_i, d_n, d_cs, s_cap, d_t));
+    TRY(s.download());
+    return check_status_sync(c);
 }
 
 }  // extern "C"

@@ -51,6 +51,16 @@ def test_invalid_arguments_are_rejected(env):
         L.slam_set_option(h, b"no_such_option", 1.0),
         L.slam_set_option(h, b"grid_mode", 7.0),
         L.slam_bresenham_batch(h, None, None, 1, None, None, None, 0),
+        # host forms past the device limits, with correctly sized host arrays: rejected before anything is staged
+        L.slam_nn(h, A.ptr(np.zeros(8)), A.ptr(np.zeros(2 * 8193)), 1, 4, 8193, A.F64, A.ptr(np.zeros(4)),
+                  A.ptr(np.zeros(4, dtype=np.int32))),
+        L.slam_icp_batch(h, A.ptr(np.zeros(8)), A.ptr(np.zeros(2 * 8193)), 1, 4, 8193, A.F64, 0, 0, None, 5, 1e-3,
+                         A.ptr(np.zeros(9)), None, None),
+        L.slam_replay(h, A.ptr(np.zeros(2 * 8193, dtype=np.float32)), A.ptr(np.zeros(8193)), A.ptr(np.zeros(8193)), 1, 2,
+                      8193, A.F64, 5, 1e-3, A.ptr(np.zeros(3)), None, None, A.ptr(np.zeros(3)), None, None),
+        L.slam_particles(h, A.ptr(np.zeros(16, dtype=np.float32)), A.ptr(np.zeros(8)), A.ptr(np.zeros(8)), 8, A.F64, None,
+                         A.ptr(np.zeros(6)), 2, 5, 1e-3, g._h, A.ptr(np.zeros(6)), None, None),   # 1 map, P = 2
+        L.slam_virtual_scan(h, A.ptr(d), A.ptr(d), 4, A.ptr(np.zeros(3)), 1, 0.0, 0.1, 8193, A.ptr(np.zeros(8193))),
     ]
     assert all(rc == A.ERR_INVALID for rc in bad), bad
     assert L.slam_last_error()                                   # a message is kept
