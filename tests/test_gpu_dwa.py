@@ -117,6 +117,7 @@ def check_against_oracle(r, b, x, c, goal, ob):
         assert len(f) > 1 and f[1] - f[0] <= 1e-12 * max(abs(f[0]), 1.0), (b, r["index"][b], want["index"])
     else:
         assert np.array_equal(r["u"][b], want["u"])
+    return want
 
 
 @pytest.mark.parametrize("rt", [dwa_ref.RECTANGLE, dwa_ref.CIRCLE])
