@@ -12,6 +12,8 @@ zjwzcx/A-2D-LiDAR-based-SLAM-System-for-Wheeled-Mobile-Robots:
     Localization  updateMap / laserEstimation / calc_map_observation (scan-to-map, W9)
     dwa        dwa_control / Config / RobotType (course_agv_nav DWA local planner), batched as
                DeviceDWA / dwa_batch_host; LocalPlanner: the local planner node without ROS
+    global_planner  find_path(...).start_find() / GlobalPlanner (course_agv_nav A*), batched as
+               DeviceAStar / astar_host
 
 plus the batched forms used by bench.py (``replay``) and the multi-GPU sharding helper
 (``dist``).  Importing the package never computes anything; every operator raises if
@@ -24,6 +26,8 @@ from .bresenham import bresenham, rasterize
 from .dwa import DeviceDWA, dwa_batch_host, dwa_control
 from .ekf_lm import EKF
 from .extraction import Extraction, LandMarkSet
+from . import global_planner
+from .global_planner import DeviceAStar, GlobalPlanner, astar_host, find_path, inflate_host
 from .icp import ICP, scan_to_pc
 from .local_planner import LocalPlanner
 from .localization import Localization
@@ -34,4 +38,5 @@ from .synthetic import LaserScan
 
 __all__ = ["ICP", "Mapping", "Localization", "EKF", "Extraction", "LandMarkSet", "bresenham", "rasterize", "SLAM_EKF", "LaserScan", "Context", "default_context",
            "DeviceGrid", "DeviceReplay", "replay_host", "icp_batch_host", "particles_host", "prior_matrices", "scan_to_pc", "SlamError",
-           "LibraryMissing", "param", "synthetic", "dwa", "dwa_control", "DeviceDWA", "dwa_batch_host", "LocalPlanner"]
+           "LibraryMissing", "param", "synthetic", "dwa", "dwa_control", "DeviceDWA", "dwa_batch_host", "LocalPlanner",
+           "global_planner", "find_path", "GlobalPlanner", "DeviceAStar", "astar_host", "inflate_host"]

@@ -93,6 +93,10 @@ _SIGS = {
     "slam_dwa_scans": ([_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _d, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp], _i),
     "slam_dwa_scans_dev": ([_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _d, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp], _i),
     "slam_dwa_shape": ([_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)], _i),
+    "slam_astar": ([_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp], _i),
+    "slam_astar_dev": ([_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp], _i),
+    "slam_astar_inflate": ([_vp, _vp, _i, _i, _i, _i, _i, _i, _vp], _i),
+    "slam_astar_inflate_dev": ([_vp, _vp, _i, _i, _i, _i, _i, _i, _vp], _i),
 }
 
 

@@ -493,6 +493,70 @@ int dwa_launch(slam_ctx *c, DwaArgs &a, const DwaOut &o)
     return SLAM_OK;
 }
 
+// ---- A* global planner -------------------------------------------------------------------
+// Checks shared by the A* entry points (include/slam_hip.h documents them).
+int check_astar_maps(const char *fn, const int8_t *maps, int G, int H, int W, int span, int r)
+{
+    REQUIRE_IN(fn, maps, "null pointer");
+    REQUIRE_IN(fn, G > 0 && H > 0 && W > 0, "G, H and W must be > 0");
+    REQUIRE_IN(fn, (long)H * W < (1L << 31), "H * W must be < 2^31");
+    REQUIRE_IN(fn, H <= W, "H > W (find_path's state_map is W x W, global_planner.py:136)");
+    REQUIRE_IN(fn, r >= 0, "r must be >= 0");
+    REQUIRE_IN(fn, span >= 0 && span <= H, "span must be in [0, min(H, W)] (the inflation loop indexes past the map, global_planner.py:150-155)");
+    REQUIRE_IN(fn, span <= kAstarMaxSpan, "span must be <= 4096");
+    return SLAM_OK;
+}
+
+int check_astar(const char *fn, const int8_t *maps, int G, int H, int W, int span, int r, const int32_t *starts,
+                const int32_t *goals, const int32_t *map_of_query, int B, int path_cap, const int32_t *status,
+                const int32_t *path_len, const int32_t *path, const int32_t *expansions)
+{
+    TRY(check_astar_maps(fn, maps, G, H, W, span, r));
+    REQUIRE_IN(fn, starts && goals && status && path_len && expansions, "null pointer");
+    REQUIRE_IN(fn, B > 0, "B must be > 0");
+    REQUIRE_IN(fn, path_cap >= 0 && (path_cap == 0 || path), "path_cap must be >= 0, path_out non-null when it is > 0");
+    REQUIRE_IN(fn, map_of_query || G == 1 || G == B, "map_of_query is NULL but G is neither 1 nor B");
+    return SLAM_OK;
+}
+
+// Inflation of G maps into `inflated` and, when `a` is non-null, the search of its queries over them.  The
+// workspace (trigger rows, the inflated maps when the caller keeps none, the search slots) is the scratch arena.
+int astar_run(slam_ctx *c, const int8_t *maps, int G, int H, int W, int wire, int span, int r, int8_t *inflated,
+              AstarArgs *a)
+{
+    TRY(grid_on_main(c));
+    const size_t cells = (size_t)H * W;
+    const size_t dil_words = (size_t)G * span * ((span + 63) / 64);     // trigger rows: G x span rows of 64-column words
+    const size_t dil = dil_words * sizeof(unsigned long long);
+    const size_t infl = inflated ? 0 : (size_t)G * cells;
+    long slots = 0;
+    if (a) {
+        slots = a->B < kAstarMaxSlots ? a->B : kAstarMaxSlots;
+        const long fit = (long)(kAstarSlotBudget / (cells * kAstarSlotBytesPerCell));
+        if (slots > fit) slots = fit > 0 ? fit : 1;
+    }
+    const size_t sc = (size_t)slots * cells;
+    TRY(arena_reserve(c, c->scratch, align_up(dil) + align_up(infl) + align_up(sc) + 4 * align_up(sc * 4) +
+                                         align_up(sc * 8) + 4096));
+    unsigned long long *d_dil = carve<unsigned long long>(c->scratch, dil_words);
+    if (!inflated) inflated = carve<int8_t>(c->scratch, infl);
+    if (!d_dil || !inflated) return SLAM_ERR_NOMEM;
+    HIPCHK(launch_astar_inflate(maps, G, H, W, wire, span, r, d_dil, inflated, c->status, c->stream));
+    if (!a) return SLAM_OK;
+    a->imaps = inflated;
+    a->slots = (int)slots;
+    a->state = carve<uint8_t>(c->scratch, sc);
+    a->pos = carve<int32_t>(c->scratch, sc);
+    a->ocell = carve<int32_t>(c->scratch, sc);
+    a->og = carve<int32_t>(c->scratch, sc);
+    a->closed = carve<int32_t>(c->scratch, sc);
+    a->okey = carve<unsigned long long>(c->scratch, sc);
+    if (!a->state || !a->pos || !a->ocell || !a->og || !a->closed || !a->okey) return SLAM_ERR_NOMEM;
+    HIPCHK(hipMemsetAsync(a->state, 0, sc, c->stream));
+    HIPCHK(launch_astar(*a, c->stream));
+    return SLAM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1764,6 +1828,81 @@ int slam_dwa_scans(slam_ctx *c, const double *states, const double *goals, const
         .out(d_cs, costs_out, Bz * s_cap).out(d_t, traj_out, Bz * a.rows * 5);
     TRY(s.upload());
     TRY(slam_dwa_scans_dev(c, d_st, d_g, d_r, n, shared, d_ct, d_sn, threshold, config, B, d_u, d_c, d_i, d_n, d_cs, s_cap, d_t));
+    TRY(s.download());
+    return check_status_sync(c);
+}
+
+/* ---- A* global planner ------------------------------------------------------------------ */
+
+int slam_astar_dev(slam_ctx *c, const int8_t *maps, int G, int H, int W, int wire_layout, int span, int r,
+                   const int32_t *starts, const int32_t *goals, const int32_t *map_of_query, int B, int path_cap,
+                   int32_t *status_out, int32_t *path_len_out, int32_t *path_out, int32_t *expansions_out,
+                   int8_t *inflated_out)
+{
+    TRY(use(c));
+    TRY(check_astar(__func__, maps, G, H, W, span, r, starts, goals, map_of_query, B, path_cap, status_out, path_len_out,
+                    path_out, expansions_out));
+    AstarArgs a{};
+    a.G = G;
+    a.H = H;
+    a.W = W;
+    a.starts = starts;
+    a.goals = goals;
+    a.map_of_query = map_of_query;
+    a.B = B;
+    a.path_cap = path_cap;
+    a.status = status_out;
+    a.path_len = path_len_out;
+    a.path = path_out;
+    a.expansions = expansions_out;
+    return astar_run(c, maps, G, H, W, wire_layout, span, r, inflated_out, &a);
+}
+
+int slam_astar(slam_ctx *c, const int8_t *maps, int G, int H, int W, int wire_layout, int span, int r,
+               const int32_t *starts, const int32_t *goals, const int32_t *map_of_query, int B, int path_cap,
+               int32_t *status_out, int32_t *path_len_out, int32_t *path_out, int32_t *expansions_out,
+               int8_t *inflated_out)
+{
+    TRY(use(c));
+    TRY(check_astar(__func__, maps, G, H, W, span, r, starts, goals, map_of_query, B, path_cap, status_out, path_len_out,
+                    path_out, expansions_out));
+    if (map_of_query)
+        for (int b = 0; b < B; ++b)
+            if (map_of_query[b] < 0 || map_of_query[b] >= G)
+                return fail(SLAM_ERR_INVALID, "slam_astar: map_of_query[%d] = %d outside [0, G = %d)", b, map_of_query[b], G);
+    const size_t Bz = (size_t)B, maps_n = (size_t)G * H * W;
+    int8_t *d_m, *d_inf; int32_t *d_s, *d_g, *d_q, *d_st, *d_len, *d_p, *d_e;
+    Staging s(c);
+    s.in(d_m, maps, maps_n).in(d_s, starts, Bz * 2).in(d_g, goals, Bz * 2).in(d_q, map_of_query, Bz);
+    s.out_always(d_st, status_out, Bz).out_always(d_len, path_len_out, Bz).out(d_p, path_out, Bz * path_cap * 2)
+        .out_always(d_e, expansions_out, Bz).out(d_inf, inflated_out, maps_n);
+    TRY(s.upload());
+    TRY(slam_astar_dev(c, d_m, G, H, W, wire_layout, span, r, d_s, d_g, d_q, B, path_cap, d_st, d_len, d_p, d_e, d_inf));
+    TRY(s.download());
+    return check_status_sync(c);
+}
+
+int slam_astar_inflate_dev(slam_ctx *c, const int8_t *maps, int G, int H, int W, int wire_layout, int span, int r,
+                           int8_t *inflated_out)
+{
+    TRY(use(c));
+    TRY(check_astar_maps(__func__, maps, G, H, W, span, r));
+    REQUIRE(inflated_out, "null pointer");
+    return astar_run(c, maps, G, H, W, wire_layout, span, r, inflated_out, nullptr);
+}
+
+int slam_astar_inflate(slam_ctx *c, const int8_t *maps, int G, int H, int W, int wire_layout, int span, int r,
+                       int8_t *inflated_out)
+{
+    TRY(use(c));
+    TRY(check_astar_maps(__func__, maps, G, H, W, span, r));
+    REQUIRE(inflated_out, "null pointer");
+    const size_t maps_n = (size_t)G * H * W;
+    int8_t *d_m, *d_o;
+    Staging s(c);
+    s.in(d_m, maps, maps_n).out_always(d_o, inflated_out, maps_n);
+    TRY(s.upload());
+    TRY(slam_astar_inflate_dev(c, d_m, G, H, W, wire_layout, span, r, d_o));
     TRY(s.download());
     return check_status_sync(c);
 }

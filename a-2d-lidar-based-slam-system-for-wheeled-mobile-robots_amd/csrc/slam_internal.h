@@ -223,4 +223,29 @@ struct DwaArgs {
 };
 hipError_t launch_dwa(const DwaArgs &a, hipStream_t s);
 
+// ---- A* global planner (astar_kernels.hip) ----------------------------------------------
+constexpr int kAstarMaxSpan = 4096;          // inflated extent: one 64-column word per lane of the row walk
+constexpr int kAstarMaxSlots = 4096;         // resident waves of the search (one workspace slot each)
+constexpr size_t kAstarSlotBudget = 1ull << 30;   // bytes of search workspace a call may take
+// per cell of a slot: state byte, open-list position, entry cell, entry g, closed list (int32 each), entry key
+constexpr size_t kAstarSlotBytesPerCell = 1 + 4 * 4 + 8;
+struct AstarArgs {
+    const int8_t *imaps;                     // inflated row-major maps [G][H][W]
+    int G, H, W;
+    const int32_t *starts, *goals;           // [B][2] (row, col) before find_path's -1
+    const int32_t *map_of_query;             // nullable [B]; NULL: map 0 (G == 1) or map b (G == B)
+    long B;
+    int path_cap;
+    int32_t *status, *path_len, *path, *expansions;   // [B], [B], [B][path_cap][2], [B]
+    // workspace: `slots` slots of H * W cells each; state bytes zero on entry
+    int slots;
+    uint8_t *state;
+    int32_t *pos, *ocell, *og, *closed;
+    unsigned long long *okey;
+};
+// dil: workspace [G][span][(span + 63) / 64] words; out: inflated row-major maps [G][H][W]
+hipError_t launch_astar_inflate(const int8_t *maps, int G, int H, int W, int wire, int span, int r,
+                                unsigned long long *dil, int8_t *out, int *status, hipStream_t s);
+hipError_t launch_astar(const AstarArgs &a, hipStream_t s);
+
 }  // namespace slam

@@ -390,6 +390,58 @@ int slam_dwa_scans_dev(slam_ctx *ctx, const double *states, const double *goals,
  * rows exceed 65 536 or whose nv_cap * nw_cap exceeds 2^20 are rejected (SLAM_ERR_INVALID). */
 int slam_dwa_shape(const double *config, int *rows_out, int *nv_cap_out, int *nw_cap_out);
 
+/* ---- A* global planner --------------------------------------------------------------- */
+/* NAV as above.  Replaces find_path(map, start, goal).start_find() (NAV/global_planner.py:133-238)
+ * for B queries over G maps in one call; the global planner node runs it on every goal
+ * (NAV/global_planner.py:87-98).  Semantics are the reference's as it executes (DESIGN.md "A* global planner"):
+ *  - maps: G int8 maps of H rows x W columns (row = y, column = x); wire_layout != 0: OccupancyGrid
+ *    order data[y*W + x] (what map_callback reshapes, :61-70), else [x][y] (Mapping.pmap order,
+ *    what slam_grid_live_pmap holds).  100 and -1 are obstacles, 0 is free, any other value
+ *    (99, SLAM_EKF's 50 for unknown cells) is neither;
+ *  - inflation (:148-155, with 129 -> span and 2 -> r): the in-place loop over rows and columns
+ *    [r, span - r) writing 99 over the (2r+1)^2 window of every cell that still holds 100 or -1
+ *    when the loop reaches it - a greedy set, not a dilation; inflating twice changes nothing;
+ *  - start / goal [B][2] (row, col) as find_path receives them: it subtracts 1 from both (:137-142);
+ *  - search (:157-238): 8 moves of cost 10, h = 10 * Manhattan distance, neighbours row offset
+ *    outer, column offset inner; an open cell is replaced in place only if its f is strictly
+ *    larger; the pop is the first open-list entry of the smallest f below 100 000, else entry 0;
+ *    the goal is tested when popped.
+ * Per query: status_out [B] (SLAM_ASTAR_*), path_len_out [B] (cells of the path, also when
+ * TRUNCATED), path_out [B][path_cap][2] (row, col) start -> goal (nullable when path_cap is 0; the
+ * entries past a query's path are not written),
+ * expansions_out [B] = len(close_list) (the start plus every non-goal pop; for NO_PATH and EDGE the
+ * cells closed before the search stopped).  inflated_out: nullable [G][H][W] row-major, the map
+ * start_find leaves in GlobalPlanner.map.
+ * Rejected up front (SLAM_ERR_INVALID): span > min(H, W) (the reference raises IndexError),
+ * H > W (its state_map is W x W), r < 0, span < 0 or span > 4096, H * W >= 2^31, map_of_query NULL
+ * with G != 1 and G != B; the host form also rejects a map_of_query entry outside [0, G) (the
+ * device form reports SLAM_ASTAR_BAD_MAP).  Workspace: G * (H * W + span * (span + 63) / 8) bytes
+ * and up to 1 GB of search slots (25 bytes per cell each), on the context. */
+enum {
+    SLAM_ASTAR_OK = 0,
+    SLAM_ASTAR_INVALID_START = 1,   /* the start cell is not 0 after inflation: `return "None"` (:157-159)   */
+    SLAM_ASTAR_INVALID_GOAL = 2,    /* the goal cell is not 0 after inflation: `return "None"` (:160-162)    */
+    SLAM_ASTAR_NO_PATH = 3,         /* the open list ran empty, start == goal included: IndexError (:172)    */
+    SLAM_ASTAR_EDGE = 4,            /* an expansion would index outside [0,H) x [0,W), or the shifted start or
+                                       goal lies outside: the reference wraps a -1 index or raises IndexError */
+    SLAM_ASTAR_TRUNCATED = 5,       /* path longer than path_cap: the first path_cap cells written           */
+    SLAM_ASTAR_BAD_MAP = 6          /* device form: map_of_query entry outside [0, G)                        */
+};
+int slam_astar(slam_ctx *ctx, const int8_t *maps, int G, int H, int W, int wire_layout, int span, int r,
+               const int32_t *starts, const int32_t *goals, const int32_t *map_of_query, int B, int path_cap,
+               int32_t *status_out, int32_t *path_len_out, int32_t *path_out, int32_t *expansions_out,
+               int8_t *inflated_out);
+int slam_astar_dev(slam_ctx *ctx, const int8_t *maps, int G, int H, int W, int wire_layout, int span, int r,
+                   const int32_t *starts, const int32_t *goals, const int32_t *map_of_query, int B, int path_cap,
+                   int32_t *status_out, int32_t *path_len_out, int32_t *path_out, int32_t *expansions_out,
+                   int8_t *inflated_out);
+/* The inflation alone (:148-155): the map start_find leaves behind in GlobalPlanner.map (the
+ * reference mutates it in place), inflated_out [G][H][W] row-major; same checks as slam_astar. */
+int slam_astar_inflate(slam_ctx *ctx, const int8_t *maps, int G, int H, int W, int wire_layout, int span, int r,
+                       int8_t *inflated_out);
+int slam_astar_inflate_dev(slam_ctx *ctx, const int8_t *maps, int G, int H, int W, int wire_layout, int span, int r,
+                           int8_t *inflated_out);
+
 #ifdef __cplusplus
 }
 #endif
