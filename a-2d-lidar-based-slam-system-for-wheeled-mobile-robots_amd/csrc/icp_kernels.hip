@@ -348,6 +348,10 @@ __device__ __forceinline__ NNHit nn_exact(const double2 *tab, bool padded, int n
     return NNHit{md2, mj};
 }
 
+// STRIDE: LDS slots per block of the image the search reads - kNNStride for the padded one, kNNBlock for the unpadded
+// copy (the one-wave shape of k_icp stages no padded one: same candidates in the same order, bank conflicts where lanes
+// scan different blocks).
+template <int STRIDE = kNNStride>
 __device__ __forceinline__ void nn_search(const double2 *__restrict__ tarL, const Box *__restrict__ boxes,
                                           const Box *__restrict__ boxes4, int nblocks, int n_tar, double sx, double sy,
                                           int seed, bool first_iter, bool active, double &best_d2, int &best_j, bool &amb)
@@ -357,12 +361,12 @@ __device__ __forceinline__ void nn_search(const double2 *__restrict__ tarL, cons
     if (first_iter) {
         // no previous match yet: the same-index guess can be far off, so take the best of the
         // guess's whole block as the bound (16 evaluations that save several block scans)
-        const double2 *t = tarL + (seed >> 4) * kNNStride;
+        const double2 *t = tarL + (seed >> 4) * STRIDE;
         U = INFINITY;
 #pragma unroll
         for (int k = 0; k < kNNBlock; ++k) U = fmin(U, dist2(sx, sy, t[k].x, t[k].y));   // fmin ignores NaN
     } else {
-        double2 ts = tarL[tslot(seed)];
+        double2 ts = tarL[STRIDE == kNNBlock ? seed : tslot(seed)];
         U = dist2(sx, sy, ts.x, ts.y);
     }
     // (a block is marked if its box comes within the bound WIDENED by a class of equal distances: a point that
@@ -394,7 +398,7 @@ __device__ __forceinline__ void nn_search(const double2 *__restrict__ tarL, cons
             if (mask != 0u) {
                 const int blk = base + __ffs((int)mask) - 1;
                 mask &= mask - 1u;
-                const double2 *t = tarL + blk * kNNStride;
+                const double2 *t = tarL + blk * STRIDE;
                 const double before = b.d2;
                 int kk = 0;
 #pragma unroll
@@ -702,20 +706,15 @@ struct Cloud {
     }
 };
 
-// Is the target a usable scan?  Beam directions must be unit vectors, ordered by angle with
-// neighbours less than 30 degrees apart, spanning at most one turn (plus half a beam), and no
-// range may be negative.  One workgroup-wide pass over the trig tables per pair (they are shared
-// by all pairs of a launch and sit in L2).  Every wave leaves its part in slots[wave]: [0] smallest
-// cross product of neighbouring directions as float bits (a lower bound of their angle: asin(x) >= x),
-// [1] upper bound of the span it saw (float bits), [2] ok flag; polar_combine() puts them together behind
-// a barrier.  (No atomics, no initialisation to order against: the probe runs ahead of the pair's first
-// barrier, its loads in flight together with those that stage the target.)
+// A wave's part of the probe below, the same in all its lanes: smallest cross product of neighbouring directions (float
+// bits), upper bound of the span it saw (rounded up once here; whoever combines the parts rounds the total up once more),
+// "saw a bad beam".
 template <typename T>
-__device__ __forceinline__ void polar_probe(const Cloud<T> &tar, int n_tar, unsigned *slots)
+__device__ __forceinline__ void polar_probe_wave(const Cloud<T> &tar, int n_tar, unsigned &mn, float &sum, bool &wave_bad)
 {
     // per-lane partials, one butterfly per wave
-    unsigned mn = 0x7f800000u;
-    float sum = 0.0f;
+    mn = 0x7f800000u;
+    sum = 0.0f;
     bool bad = false;
     for (int j = threadIdx.x; j < n_tar; j += blockDim.x) {
         const double c0 = tar.cos_t[j], s0 = tar.sin_t[j];
@@ -736,11 +735,29 @@ __device__ __forceinline__ void polar_probe(const Cloud<T> &tar, int n_tar, unsi
         mn = min(mn, (unsigned)__shfl_xor((int)mn, off));
         sum += __shfl_xor(sum, off);
     }
-    const bool wave_bad = __any(bad);
+    wave_bad = __any(bad);
+    sum *= 1.00001f;
+}
+
+// Is the target a usable scan?  Beam directions must be unit vectors, ordered by angle with
+// neighbours less than 30 degrees apart, spanning at most one turn (plus half a beam), and no
+// range may be negative.  One workgroup-wide pass over the trig tables per pair (they are shared
+// by all pairs of a launch and sit in L2).  Every wave leaves its part in slots[wave]: [0] smallest
+// cross product of neighbouring directions as float bits (a lower bound of their angle: asin(x) >= x),
+// [1] upper bound of the span it saw (float bits), [2] ok flag; polar_combine() puts them together behind
+// a barrier.  (No atomics, no initialisation to order against: the probe runs ahead of the pair's first
+// barrier, its loads in flight together with those that stage the target.)
+template <typename T>
+__device__ __forceinline__ void polar_probe(const Cloud<T> &tar, int n_tar, unsigned *slots)
+{
+    unsigned mn;
+    float sum;
+    bool wave_bad;
+    polar_probe_wave(tar, n_tar, mn, sum, wave_bad);
     if ((threadIdx.x & 63) == 0) {
         unsigned *s = slots + 4 * (threadIdx.x >> 6);
         s[0] = mn;
-        s[1] = __float_as_uint(sum * 1.00001f);
+        s[1] = __float_as_uint(sum);
         s[2] = wave_bad ? 0u : 1u;
     }
 }
@@ -765,6 +782,15 @@ __device__ __forceinline__ PolarProbe polar_combine(const unsigned *slots, int n
     return r;
 }
 
+// What a barrier is to a workgroup of ONE wave: LDS operations of a wave execute in the order they are issued, so a value
+// one lane stored is there for another lane's later read - the compiler only has to keep that order.
+__device__ __forceinline__ void wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 template <typename T>
 __device__ __forceinline__ void stage_points(const Cloud<T> &tar, int n_tar, double2 *tarL, double2 *tarP = nullptr)
 {
@@ -778,6 +804,9 @@ __device__ __forceinline__ void stage_points(const Cloud<T> &tar, int n_tar, dou
     if (tarP && threadIdx.x < kPolarTail) tarP[n_tar + threadIdx.x] = make_double2(qnan, qnan);
 }
 
+// (STRIDE as in nn_search.  From the unpadded image, where the blocks of neighbouring lanes lie a whole turn of the
+// banks apart, lane b reads its block's points starting at point b: minimum and maximum do not depend on the order.)
+template <int STRIDE = kNNStride, bool ONE_WAVE = false>
 __device__ __forceinline__ void stage_boxes(int n_tar, const double2 *tarL, Box *boxes, Box *boxes4)
 {
     const int nb = nn_blocks(n_tar);
@@ -786,14 +815,14 @@ __device__ __forceinline__ void stage_boxes(int n_tar, const double2 *tarL, Box 
         if (b < nb) {
 #pragma unroll
             for (int k = 0; k < kNNBlock; ++k) {
-                double2 t = tarL[b * kNNStride + k];
+                double2 t = tarL[b * STRIDE + (STRIDE == kNNBlock ? (k + b) & (kNNBlock - 1) : k)];
                 bx.x0 = fmin(bx.x0, t.x); bx.x1 = fmax(bx.x1, t.x);  // fmin / fmax ignore NaN
                 bx.y0 = fmin(bx.y0, t.y); bx.y1 = fmax(bx.y1, t.y);
             }
         }
         boxes[b] = bx;
     }
-    __syncthreads();
+    if (ONE_WAVE) wave_sync(); else __syncthreads();
     for (int b = threadIdx.x; b < nn_boxes4(n_tar); b += blockDim.x) {
         Box bx = boxes[4 * b];
 #pragma unroll
@@ -1241,6 +1270,344 @@ __device__ __forceinline__ bool icp_pair(const IcpArgs &a, const int b, char *sm
     return !EXACT && (nwaves > 1 ? geo[5] != 0u : amb_mask != 0ull);
 }
 
+// ---------------------------------------------------------------------------------
+// The same solve by ONE wave per pair, six queries a lane (n_src <= 384): the shape of launches that fill the chip many
+// times over, where a launch's duration is the instructions its pairs issue and not a pair's own latency.  Nothing is
+// handed between waves: no barrier, the sums are one transposed wave reduction and lane reads, rotation, translation and
+// convergence test are computed once per pair.  What a lane keeps from one iteration to the next is a query's moving
+// point and its last match (five registers a query): a match's contribution to the sums is added as soon as the match is
+// known (later iterations), or formed from the match's index (first iteration, behind the listed queries' search: the
+// square of the distance is that of the query to the match as the search computed it, the same operations on the same
+// bits); the originals are formed again from the source for the final transform.  LDS holds the unpadded image of the
+// target (NaN points up to a whole block and behind the last beam), the boxes and a list for a quarter of the queries:
+// 8.6 KB for 360 beams, so that registers (128: four waves per SIMD) and not LDS bound the pairs resident on a CU.  The
+// box search (1.3 % of the queries) reads the unpadded image.  Same candidates in the same order under the same rules as
+// icp_pair: matches and iteration counts are those of every other shape, sums are added in another order.
+// ---------------------------------------------------------------------------------
+constexpr int kWaveQpt = 6;
+constexpr int kWaveRound = 4 * 1024;          // pairs resident at once in this shape: 4 per SIMD, 1 024 SIMDs
+__host__ __device__ inline int icp_wave_points(int n_tar)
+{
+    const int whole = nn_blocks(n_tar) * kNNBlock, tail = n_tar + kPolarTail;
+    return whole > tail ? whole : tail;
+}
+__host__ __device__ inline size_t icp_wave_lds_bytes(int n_tar, int cap)
+{
+    return (size_t)icp_wave_points(n_tar) * sizeof(double2) + (size_t)(nn_boxes_padded(n_tar) + nn_boxes4(n_tar)) * sizeof(Box) +
+           (size_t)cap * (sizeof(double2) + sizeof(int));
+}
+
+template <typename T, bool EXACT>
+__device__ __forceinline__ bool icp_pair_wave(const IcpArgs &a, const int b, char *smem)
+{
+    constexpr int QPT = kWaveQpt;
+    const int n_src = a.n_src, n_tar = a.n_tar, nblocks = nn_blocks(n_tar), lane = threadIdx.x;
+    double2 *tarP = reinterpret_cast<double2 *>(smem);                                           // [icp_wave_points]
+    Box *boxes = reinterpret_cast<Box *>(tarP + icp_wave_points(n_tar));                         // [padded to x4]
+    Box *boxes4 = boxes + nn_boxes_padded(n_tar);                                                // one per 4 blocks
+    double2 *qlist = reinterpret_cast<double2 *>(boxes4 + nn_boxes4(n_tar));                     // [a.team_cap] nn_listed
+    int *qseed = reinterpret_cast<int *>(qlist + a.team_cap);                                    // [a.team_cap]
+    char *guard = reinterpret_cast<char *>(qseed + a.team_cap);
+    lds_guard_fill(guard);
+
+    const long be = (long)b + (a.ppt ? b / a.ppt : 0);
+    Cloud<T> tar{nullptr, nullptr, a.cos_t, a.sin_t, n_tar}, src{nullptr, nullptr, a.cos_t, a.sin_t, n_src};
+    if (a.ranges) {
+        tar.ranges = a.ranges + be * a.tar_scan_stride;
+        src.ranges = a.ranges + be * a.src_scan_stride + n_tar;      // the scan after the target's
+    } else {
+        tar.pts = static_cast<const T *>(a.tar) + be * a.tar_stride;
+        src.pts = static_cast<const T *>(a.src) + be * a.src_stride;
+    }
+    // source point i as the solve starts from it (the prior applied); a lane without one starts from the origin's image
+    auto source = [&](int i, bool have) __attribute__((always_inline)) -> double2 {
+        double2 pt = have ? src.at(i) : make_double2(0.0, 0.0);
+        if (a.prior) {
+            const double *p = a.prior + 6 * (long)b;
+            pt = make_double2(p[0] * pt.x + p[1] * pt.y + p[2], p[3] * pt.x + p[4] * pt.y + p[5]);
+        }
+        return pt;
+    };
+
+    // the source points first: their loads are in flight together with those that stage the target
+    double sx[QPT], sy[QPT];
+    int seed[QPT];
+    bool src_differs = false;
+    {
+        const double2 p0 = source(0, true);                          // collapsed sets: see icp_pair
+#pragma unroll
+        for (int q = 0; q < QPT; ++q) {
+            const int i = lane + q * kWave;
+            const double2 pt = source(i, i < n_src);
+            sx[q] = pt.x; sy[q] = pt.y;
+            seed[q] = min(i, n_tar - 1);             // first guess: the same beam index
+            src_differs |= i < n_src && !(pt.x == p0.x && pt.y == p0.y);
+        }
+    }
+    {
+        const double qnan = __longlong_as_double(0x7ff8000000000000LL);
+        for (int j = lane; j < icp_wave_points(n_tar); j += kWave) tarP[j] = j < n_tar ? tar.at(j) : make_double2(qnan, qnan);
+    }
+    // the target is a scan with usable beam geometry: nearest neighbours by beam window (nn_polar)
+    PolarGeo pg;
+    {
+        bool polar = false;
+        float dmin = 1.0f;
+        if (a.ranges) {
+            unsigned mn;
+            float sum;
+            bool bad;
+            polar_probe_wave(tar, n_tar, mn, sum, bad);
+            dmin = __uint_as_float((unsigned)__builtin_amdgcn_readfirstlane((int)mn));
+            // (the total rounded up once more, as polar_combine does with the sum of the waves' parts: the same test as icp_pair's)
+            const float span = __uint_as_float((unsigned)__builtin_amdgcn_readfirstlane((int)__float_as_uint(sum * 1.00001f)));
+            polar = !bad && n_tar >= 2 && dmin >= 1e-5f && dmin < 1.0f && span <= 6.2831855f + 0.5f * dmin;   // as icp_pair
+        }
+        pg.inv_db = polar ? __fdividef(1.000002f, dmin) : 0.0f;
+        pg.slack = StoreSlack<T>::ang;
+    }
+    const bool src_collapsed = !__any(src_differs);
+    wave_sync();
+    stage_boxes<kNNBlock, true>(n_tar, tarP, boxes, boxes4);
+    wave_sync();
+
+    const double dn = (double)n_src;
+    const LaneSel ls = lane_sel(lane);
+    double pre_error = 0.0, mean_error = 0.0, pcx = 0.0, pcy = 0.0, ca0x = 0.0, ca0y = 0.0;   // (ca0: centroid of the source before it moves)
+    int iters = 0;
+    unsigned long long amb_mask = 0ull;   // lanes that saw a best undercut its predecessor by less than a class of equal distances (see icp_pair)
+
+    // nearest target of query q (icp.py:67): its index - or, for a first-iteration query put on the list, -1 - its place there -
+    // and the square of its distance
+    auto nearest = [&](const int q, const bool okq, const bool first, const bool listing, int &nlisted, double &d2, int &j)
+                       __attribute__((always_inline)) {
+        if (EXACT) {
+            const NNHit h = nn_exact(tarP, false, okq ? n_tar : 0, sx[q], sy[q]);
+            d2 = h.d2; j = h.j;
+        } else if (pg.inv_db > 0.0f) {                               // wave-uniform: the target is a scan
+            bool big, amb_lane;
+            unsigned long long am;
+            nn_polar<4, false>(tarP, n_tar, sx[q], sy[q], seed[q], okq, pg, listing ? kPolarMaxFirst : kPolarMax, d2, j, big, amb_lane, am);
+            (void)amb_lane;
+            amb_mask |= am;
+            if (listing) {
+                const unsigned long long bm = __ballot(big);
+                if (bm != 0ull) {
+                    const int pos = nlisted + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bm, 0u));
+                    nlisted += (int)__popcll(bm);
+                    if (big && pos < a.team_cap) {
+                        qlist[pos] = make_double2(sx[q], sy[q]);
+                        qseed[pos] = seed[q];
+                        j = -1 - pos;
+                        big = false;                                 // (a list that is full leaves the rest to the box search)
+                    }
+                }
+            }
+            if (__any(big)) {
+                double d2b; int jb; bool ambb;
+                nn_search<kNNBlock>(tarP, boxes, boxes4, nblocks, n_tar, sx[q], sy[q], seed[q], first, big, d2b, jb, ambb);
+                d2 = big ? d2b : d2;
+                j = big ? jb : j;
+                amb_mask |= __ballot(big && ambb);
+            }
+        } else {
+            bool ambs;
+            nn_search<kNNBlock>(tarP, boxes, boxes4, nblocks, n_tar, sx[q], sy[q], seed[q], first, okq, d2, j, ambs);
+            amb_mask |= __ballot(ambs);
+        }
+    };
+    // every source point matched to ONE target point (same coordinates)?  As icp_pair: settled on one lane of the first
+    // query where some lane there is matched to another beam whose point differs, else every match is compared.
+    struct Same { double m0x, m0y; bool found, differs; };
+    auto same_step = [&](const int q, const bool okq, const double2 m, Same &s) __attribute__((always_inline)) {
+        if (q == 0) {
+            s.m0x = readlane_f64(m.x, 0); s.m0y = readlane_f64(m.y, 0);
+            s.found = s.differs = false;
+            const int j0 = __builtin_amdgcn_readfirstlane(seed[0]);
+            const unsigned long long other = __ballot(okq && seed[0] != j0);
+            if (other != 0ull) {
+                const int l = __ffsll((long long)other) - 1;
+                const double ox = readlane_f64(m.x, l), oy = readlane_f64(m.y, l);
+                s.found = !(ox == s.m0x && oy == s.m0y);
+            }
+        }
+        if (!s.found) s.differs |= okq && !(m.x == s.m0x && m.y == s.m0y);
+    };
+    // src = T.src (:71), the convergence test (:76-77); (cbx, cby): the centroid the source now has (up to rounding)
+    auto advance = [&](const Rigid2 &r, const double cbx, const double cby) __attribute__((always_inline)) -> bool {
+#pragma unroll
+        for (int q = 0; q < QPT; ++q) {
+            const double nx = r.c * sx[q] + (-r.s) * sy[q] + r.tx;
+            const double ny = r.s * sx[q] + r.c * sy[q] + r.ty;
+            sx[q] = nx; sy[q] = ny;
+        }
+        pcx = cbx; pcy = cby;
+        ++iters;
+        if (fabs(pre_error - mean_error) < a.tol) return true;
+        pre_error = mean_error;
+        return false;
+    };
+    // the first iteration: centroids, then centred products, as the reference (icp.py:154-160); the only one that lists queries
+    auto first_iteration = [&]() __attribute__((always_inline)) -> bool {
+        const bool listing = !EXACT && a.team_cap > 0 && pg.inv_db > 0.0f;
+        int nlisted = 0;
+#pragma unroll
+        for (int q = 0; q < QPT; ++q) {
+            if (q * kWave >= n_src) continue;                        // wave-uniform
+            double d2; int j;
+            nearest(q, lane + q * kWave < n_src, true, listing, nlisted, d2, j);
+            seed[q] = j;
+        }
+        if (listing) {
+            wave_sync();
+            nn_listed<4>(tarP, n_tar, pg, qlist, qseed, min(nlisted, a.team_cap));
+            wave_sync();
+#pragma unroll
+            for (int q = 0; q < QPT; ++q) {
+                if (q * kWave >= n_src) continue;
+                bool flagged = false;
+                if (seed[q] < 0) {
+                    const int jf = __double2loint(qlist[-1 - seed[q]].y);
+                    flagged = jf < 0;
+                    seed[q] = jf & 0x7fffffff;
+                }
+                amb_mask |= __ballot(flagged);
+            }
+        }
+        double v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        Same same{0.0, 0.0, false, false};
+#pragma unroll
+        for (int q = 0; q < QPT; ++q) {
+            if (q * kWave >= n_src) continue;
+            const bool okq = lane + q * kWave < n_src;
+            const double2 m = tarP[seed[q]];
+            const double d2 = dist2(sx[q], sy[q], m.x, m.y);         // what the search found for this match
+            const double dq = (d2 < INFINITY) ? sqrt(d2) : 0.0;      // never-won query: distance 0 (:97)
+            same_step(q, okq, m, same);
+            if (okq) { v[0] += sx[q]; v[1] += sy[q]; v[2] += m.x; v[3] += m.y; v[4] += dq; }
+        }
+        const double qv = wave_reduce8(v, ls) / dn;                  // icp.py:154-155, :75
+        const double cax = readlane_f64(qv, 0), cay = readlane_f64(qv, 1), cbx = readlane_f64(qv, 2), cby = readlane_f64(qv, 3);
+        mean_error = readlane_f64(qv, 7);                            // value 4 lives in lane 7
+        const bool tar_collapsed = !(same.found || __any(same.differs));
+        double w[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int q = 0; q < QPT; ++q) {
+            if (q * kWave >= n_src) continue;
+            if (lane + q * kWave < n_src) {
+                const double2 m = tarP[seed[q]];
+                const double aax = sx[q] - cax, aay = sy[q] - cay, bbx = m.x - cbx, bby = m.y - cby;
+                w[0] += bbx * aax; w[1] += bbx * aay; w[2] += bby * aax; w[3] += bby * aay;   // :160
+            }
+        }
+        const double tot = wave_reduce4(w, ls);
+        w[0] = readlane_f64(tot, 0); w[1] = readlane_f64(tot, 1); w[2] = readlane_f64(tot, 2); w[3] = readlane_f64(tot, 3);
+        if (tar_collapsed || src_collapsed) w[0] = w[1] = w[2] = w[3] = 0.0;
+        ca0x = cax; ca0y = cay;
+        return advance(kabsch_from_sums_wave(cax, cay, cbx, cby, w[0], w[1], w[2], w[3], lane), cbx, cby);    // :69
+    };
+    // a later iteration: sums and products about the previous matches' centroid in one reduction (see icp_pair)
+    auto iteration = [&]() __attribute__((always_inline)) -> bool {
+        double u[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        Same same{0.0, 0.0, false, false};
+        int none = 0;
+#pragma unroll
+        for (int q = 0; q < QPT; ++q) {
+            if (q * kWave >= n_src) continue;                        // wave-uniform
+            const bool okq = lane + q * kWave < n_src;
+            double d2; int j;
+            nearest(q, okq, false, false, none, d2, j);
+            seed[q] = j;                                             // next iteration's guess
+            const double2 m = tarP[j];
+            const double dq = (d2 < INFINITY) ? sqrt(d2) : 0.0;
+            same_step(q, okq, m, same);
+            if (okq) {
+                const double dax = sx[q] - pcx, day = sy[q] - pcy, dbx = m.x - pcx, dby = m.y - pcy;
+                u[0] += dax; u[1] += day; u[2] += dbx; u[3] += dby; u[4] += dq;
+                u[5] = fma(dbx, dax, fma(dby, day, u[5])); u[6] = fma(dby, dax, fma(-dbx, day, u[6]));
+            }
+        }
+        const double tot = wave_reduce8(u, ls);
+        const double qv = tot / dn;                                  // icp.py:154-155, :75
+        const double qax = readlane_f64(qv, 0), qay = readlane_f64(qv, 1);
+        const double cax = pcx + qax, cay = pcy + qay;
+        const double cbx = pcx + readlane_f64(qv, 2), cby = pcy + readlane_f64(qv, 3);
+        mean_error = readlane_f64(qv, 7);                            // value 4 lives in lane 7, values 5, 6 in lanes 6, 5
+        const double sbx = readlane_f64(tot, 2), sby = readlane_f64(tot, 3);
+        double wa = readlane_f64(tot, 6) - (sbx * qax + sby * qay);  // A
+        double wb = readlane_f64(tot, 5) - (sby * qax - sbx * qay);  // B
+        if (!(same.found || __any(same.differs)) || src_collapsed) wa = wb = 0.0;
+        return advance(kabsch_from_sums_wave(cax, cay, cbx, cby, wa, 0.0, wb, 0.0, lane), cbx, cby);          // :69
+    };
+    if (a.max_iter > 0 && !first_iteration())
+        for (int it = 1; it < a.max_iter; ++it)
+            if (iteration()) break;
+
+    // final T = getTransform(A_original, src_final) (icp.py:81), as icp_pair; the originals are formed again from the source
+    Rigid2 r;
+    if (iters > 0) {
+        double u[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int q = 0; q < QPT; ++q) {
+            if (q * kWave >= n_src) continue;
+            const int i = lane + q * kWave;
+            if (i < n_src) {
+                const double2 o = source(i, true);
+                const double dsx = sx[q] - pcx, dsy = sy[q] - pcy, dax = o.x - ca0x, day = o.y - ca0y;
+                u[0] += dsx; u[1] += dsy;
+                u[2] += dsx * dax + dsy * day; u[3] += dsy * dax - dsx * day;
+            }
+        }
+        const double tot = wave_reduce4(u, ls);
+        const double qv = tot / dn;
+        const double csx = pcx + readlane_f64(qv, 0), csy = pcy + readlane_f64(qv, 1);
+        double wa = readlane_f64(tot, 2), wb = readlane_f64(tot, 3);
+        if (src_collapsed) wa = wb = 0.0;
+        r = kabsch_from_sums_wave(ca0x, ca0y, csx, csy, wa, 0.0, wb, 0.0, lane);
+    } else {
+        // no iteration (max_iter 0): the source has not moved, both sets are the originals; centroids, then centred products
+        double v[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int q = 0; q < QPT; ++q)
+            if (lane + q * kWave < n_src) { v[0] += sx[q]; v[1] += sy[q]; v[2] += sx[q]; v[3] += sy[q]; }
+        const double qv = wave_reduce4(v, ls) / dn;
+        const double cax = readlane_f64(qv, 0), cay = readlane_f64(qv, 1), cbx = readlane_f64(qv, 2), cby = readlane_f64(qv, 3);
+        double w[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int q = 0; q < QPT; ++q) {
+            if (lane + q * kWave < n_src) {
+                const double aax = sx[q] - cax, aay = sy[q] - cay, bbx = sx[q] - cbx, bby = sy[q] - cby;
+                w[0] += bbx * aax; w[1] += bbx * aay; w[2] += bby * aax; w[3] += bby * aay;
+            }
+        }
+        const double tot = wave_reduce4(w, ls);
+        w[0] = readlane_f64(tot, 0); w[1] = readlane_f64(tot, 1); w[2] = readlane_f64(tot, 2); w[3] = readlane_f64(tot, 3);
+        if (src_collapsed) w[0] = w[1] = w[2] = w[3] = 0.0;
+        r = kabsch_from_sums_wave(cax, cay, cbx, cby, w[0], w[1], w[2], w[3], lane);
+    }
+    if (lane == 0) {
+        double *To = a.T_out + 9 * (long)b;
+        To[0] = r.c; To[1] = -r.s; To[2] = r.tx;
+        To[3] = r.s; To[4] = r.c;  To[5] = r.ty;
+        To[6] = 0.0; To[7] = 0.0;  To[8] = 1.0;
+        if (a.iters_out) a.iters_out[b] = iters;
+        if (a.err_out) a.err_out[b] = mean_error;
+    }
+    lds_guard_check(guard, a.status);
+    return !EXACT && amb_mask != 0ull;
+}
+
+// the replay's map counters, cleared on the way (16 bytes a lane, fire and forget) instead of by a fill kernel of
+// its own ahead of this launch: one dispatch less on the replay's stream
+__device__ __forceinline__ void icp_clear_on_the_way(const IcpArgs &a)
+{
+    if (!a.zero_ptr) return;
+    uint4 *p = static_cast<uint4 *>(a.zero_ptr);
+    const size_t n16 = a.zero_bytes >> 4;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += (size_t)gridDim.x * blockDim.x) p[i] = make_uint4(0u, 0u, 0u, 0u);
+    if (blockIdx.x == 0 && threadIdx.x < ((a.zero_bytes & 15) >> 2)) static_cast<unsigned *>(a.zero_ptr)[(n16 << 2) + threadIdx.x] = 0u;
+}
+
 // k_icp: one workgroup per pair.  None of the pairs of noisy scans and a few per cent of those with quantised ranges
 // need the second pass (icp_pair<EXACT>); the workgroup of such a pair runs it right away - until round 3 a
 // second launch did, which cost every batch 4 us whether or not a pair was flagged.  The second pass overwrites
@@ -1249,17 +1616,24 @@ template <typename T, int QPT, int UNROLL>
 __global__ void __launch_bounds__(1024) k_icp(IcpArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    if (a.zero_ptr) {
-        // the replay's map counters, cleared on the way (16 bytes a lane, fire and forget) instead of by a fill kernel of
-        // its own ahead of this launch: one dispatch less on the replay's stream
-        uint4 *p = static_cast<uint4 *>(a.zero_ptr);
-        const size_t n16 = a.zero_bytes >> 4;
-        for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += (size_t)gridDim.x * blockDim.x) p[i] = make_uint4(0u, 0u, 0u, 0u);
-        if (blockIdx.x == 0 && threadIdx.x < ((a.zero_bytes & 15) >> 2)) static_cast<unsigned *>(a.zero_ptr)[(n16 << 2) + threadIdx.x] = 0u;
-    }
+    icp_clear_on_the_way(a);
     if (icp_pair<T, QPT, UNROLL, false>(a, blockIdx.x, smem)) {
         __syncthreads();                                             // the second pass re-uses the LDS
         icp_pair<T, QPT, 2, true>(a, blockIdx.x, smem);
+    }
+}
+
+// k_icp<T>: one WAVE per pair (icp_pair_wave); at most 128 registers, so that four pairs are resident per SIMD.  An overload
+// of the name on purpose: kernel traces, counter summaries and the benchmark's roofline file the scan matcher under k_icp
+// whatever its launch shape, and tell the shapes apart by their template arguments.
+template <typename T>
+__global__ void __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(4))) k_icp(IcpArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    icp_clear_on_the_way(a);
+    if (icp_pair_wave<T, false>(a, blockIdx.x, smem)) {
+        wave_sync();                                                 // the second pass re-uses the LDS
+        icp_pair_wave<T, true>(a, blockIdx.x, smem);
     }
 }
 
@@ -1287,6 +1661,28 @@ static hipError_t launch_icp_t(const IcpArgs &a_in, hipStream_t s)
     int pref = a.qpt_pref > 0 ? a.qpt_pref : (waves_at_two >= 7500 ? 3 : 2);
     if (a.B > 64 && qpt < pref && a.n_src > 64 * pref) qpt = pref;
     if (qpt > 4) qpt = 8;                     // the shapes that exist: 1, 2, 3, 4, 8 queries per lane
+    // One wave per pair with six queries per lane (k_icp<T>): no barriers, the per-iteration fixed work paid once per
+    // pair.  For launches that fill the chip several times over on their own, where instructions are time: the preference
+    // resolves to the full-chip shape (given or automatic) and the batch is at least FOUR rounds of this shape's own
+    // workgroups - 4 resident per SIMD on 1 024 SIMDs, 16 384 pairs.  A launch of a round or two ends on its longest pairs,
+    // and a pair is slower alone in this shape (six queries in sequence: 0.28 against 0.20 ms for 999 pairs when it was
+    // first tried, in the era of lone launches), so every smaller launch - the particle batches of 10 000 and their chunks
+    // among them, which were not measured in this shape - keeps the shape it had.  Measured on the benchmark's launches of
+    // 31 968 pairs (7.8 rounds), two contexts: 17.46 against 15.50 M scans/s, a step of 1.831 instead of 2.062 ms
+    // (profiles/icp_one_wave.txt).  Automatic only for scans (the box search of a point cloud would read the unpadded image
+    // throughout) and while 16 pairs fit a CU's LDS.  a.one_wave: -1 = by this rule, 0 = never, 1 = wherever a pair fits
+    // (context option "icp_one_wave").
+    {
+        const int cap = (a.ranges && a.team_mode == 0) ? ((a.n_src + 3) / 4 + 15) / 16 * 16 : 0;   // the list: a quarter of the queries (a fifth is listed on the benchmark scans)
+        const size_t lds = icp_wave_lds_bytes(a.n_tar, cap) + kLdsGuard;
+        const bool fits = a.n_src <= kWave * kWaveQpt && lds <= 64 * 1024;
+        const bool full = pref == 3 && a.B >= 4 * kWaveRound && a.n_src > kWave * 3 && a.ranges && lds <= 10 * 1024;
+        if (fits && (a.one_wave == 1 || (a.one_wave < 0 && full))) {
+            a.team_cap = cap;
+            SLAM_LAUNCH((k_icp<T>), dim3(a.B), dim3(kWave), lds, s, a);
+            return hipGetLastError();
+        }
+    }
     const int block = icp_block(a.n_src, qpt);
     const size_t lds_base = nn_lds_bytes(a.n_tar) + icp_red_bytes(block / kWave) + kIcpExtraLds + kLdsGuard;
     // second, unpadded copy of the target for the beam-window search: only for scans, and only while both copies fit
@@ -1314,9 +1710,6 @@ static hipError_t launch_icp_t(const IcpArgs &a_in, hipStream_t s)
         }                                                                                                       \
         SLAM_LAUNCH((k_icp<T, Q, U>), grid, dim3(block), lds, s, a);                                            \
     }
-    // (one wave per pair with six queries per lane - no barriers, the per-iteration fixed work paid
-    // once per pair - was measured: 12 % fewer instructions, but 0.28 instead of 0.20 ms alone and
-    // no faster with replays overlapping: dropped)
     // (candidates per trip of the beam-window search: see nn_polar.  Four
     // per trip are as fast as two when the chip is full and faster when it is not - four overlapping 999-pair
     // replays 8.5 -> 8.9 M scans/s - since the candidates come from the unpadded copy.)

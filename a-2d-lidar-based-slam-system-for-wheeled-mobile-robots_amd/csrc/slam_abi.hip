@@ -99,6 +99,7 @@ struct slam_ctx {
     int grid_split = -1;  // window mode: two workgroups per group, one per direction half (-1: when the launch cannot fill the chip)
     int icp_qpt = 0;      // queries per lane of batched scan matching (0: by batch size)
     int replay_reset = 0; // 1: slam_replay_dev clears its map's counters itself (inside the scan-matching launch)
+    int icp_one_wave = -1; // scan matching with one wave per pair: -1 = where a full-chip launch allows it, 0 = never, 1 = wherever a pair fits
     int icp_team = 0;     // first-iteration queries without a beam window: 0 = listed and searched apart from their lanes (nn_listed), 1 = box search
     // "pipeline" option: the map stage of slam_replay_dev (reset -> ray cast -> finalize) runs on
     // a second stream, so the map stage of one replay overlaps the scan matching of the next.
@@ -684,19 +685,43 @@ int slam_check_status(slam_ctx *c)
     return check_status_sync(c);
 }
 
+// The options' names, the values each takes and the words that say so.  slam_set_option checks name and value against
+// this table before it touches the context: a caller's mistake is named as such whatever the state of the device.
+struct OptionRange {
+    const char *name;
+    bool (*ok)(double);
+    const char *msg;
+};
+static const OptionRange kOptionRanges[] = {
+    {"grid_mode", [](double v) { return v == 0 || v == 1 || v == 2 || v == 3 || v == 4; }, "grid_mode is 0..4"},
+    {"grid_group", [](double v) { return v >= 0 && v <= 64; }, "grid_group in [0, 64]"},
+    {"grid_split", [](double v) { return v == -1 || v == 0 || v == 1; }, "grid_split is -1, 0 or 1"},
+    {"replay_reset", [](double v) { return v == 0 || v == 1; }, "replay_reset is 0 or 1"},
+    {"icp_team", [](double v) { return v == 0 || v == 1; }, "icp_team is 0 or 1"},
+    {"icp_one_wave", [](double v) { return v == -1 || v == 0 || v == 1; }, "icp_one_wave is -1, 0 or 1"},
+    {"particle_chunks", [](double v) { return v >= 0 && v <= 64 && v == (int)v; }, "particle_chunks in [0, 64]"},
+    {"icp_qpt", [](double v) { return v >= 0 && v <= 3; }, "icp_qpt in [0, 3]"},
+    {"pipeline", [](double v) { return v == 0 || v == 1; }, "pipeline is 0 or 1"},
+};
+
 int slam_set_option(slam_ctx *c, const char *name, double value)
 {
-    TRY(use(c));
     REQUIRE(name, "null name");
-    if (!strcmp(name, "grid_mode")) { REQUIRE(value == 0 || value == 1 || value == 2 || value == 3 || value == 4, "grid_mode is 0..4"); c->grid_mode = (int)value; }
-    else if (!strcmp(name, "grid_group")) { REQUIRE(value >= 0 && value <= 64, "grid_group in [0, 64]"); c->grid_group = (int)value; }
-    else if (!strcmp(name, "grid_split")) { REQUIRE(value == -1 || value == 0 || value == 1, "grid_split is -1, 0 or 1"); c->grid_split = (int)value; }
-    else if (!strcmp(name, "replay_reset")) { REQUIRE(value == 0 || value == 1, "replay_reset is 0 or 1"); c->replay_reset = (int)value; }
-    else if (!strcmp(name, "icp_team")) { REQUIRE(value == 0 || value == 1, "icp_team is 0 or 1"); c->icp_team = (int)value; }
-    else if (!strcmp(name, "particle_chunks")) { REQUIRE(value >= 0 && value <= 64 && value == (int)value, "particle_chunks in [0, 64]"); TRY(join_particles(c)); c->particle_chunks = (int)value; }
-    else if (!strcmp(name, "icp_qpt")) { REQUIRE(value >= 0 && value <= 3, "icp_qpt in [0, 3]"); c->icp_qpt = (int)value; }
+    const OptionRange *opt = nullptr;
+    for (const OptionRange &o : kOptionRanges)
+        if (!strcmp(name, o.name)) opt = &o;
+    if (!opt) return fail(SLAM_ERR_INVALID, "unknown option %s", name);
+    REQUIRE(opt->ok(value), opt->msg);
+    TRY(use(c));
+    if (!strcmp(name, "grid_mode")) c->grid_mode = (int)value;
+    else if (!strcmp(name, "grid_group")) c->grid_group = (int)value;
+    else if (!strcmp(name, "grid_split")) c->grid_split = (int)value;
+    else if (!strcmp(name, "replay_reset")) c->replay_reset = (int)value;
+    else if (!strcmp(name, "icp_team")) c->icp_team = (int)value;
+    else if (!strcmp(name, "icp_one_wave")) c->icp_one_wave = (int)value;
+    else if (!strcmp(name, "particle_chunks")) { TRY(join_particles(c)); c->particle_chunks = (int)value; }
+    else if (!strcmp(name, "icp_qpt")) c->icp_qpt = (int)value;
     else if (!strcmp(name, "pipeline")) {
-        REQUIRE(value == 0 || value == 1, "pipeline is 0 or 1");
         TRY(join_from_grid(c));
         if (value == 1 && !c->gstream) {
             HIPCHK(hipStreamCreateWithFlags(&c->gstream, hipStreamNonBlocking));
@@ -709,7 +734,6 @@ int slam_set_option(slam_ctx *c, const char *name, double value)
         c->cast_poses[0] = c->cast_poses[1] = nullptr;
         c->cast_T[0] = c->cast_T[1] = nullptr;
     }
-    else return fail(SLAM_ERR_INVALID, "unknown option %s", name);
     return SLAM_OK;
 }
 
@@ -908,7 +932,7 @@ int slam_icp_batch_dev(slam_ctx *c, const void *tar, const void *src, int B, int
     a.ppt = 0;
     a.B = B; a.n_tar = n_tar; a.n_src = n_src; a.max_iter = max_iter; a.tol = tol;
     a.T_out = T_out; a.iters_out = iters_out; a.err_out = mean_err_out;
-    a.status = c->status; a.qpt_pref = c->icp_qpt; a.team_mode = c->icp_team;
+    a.status = c->status; a.qpt_pref = c->icp_qpt; a.team_mode = c->icp_team; a.one_wave = c->icp_one_wave;
     Timed t(c, SLAM_K_ICP);
     HIPCHK(launch_icp(a, dtype, c->stream));
     return SLAM_OK;
@@ -1376,7 +1400,7 @@ int slam_replay_dev(slam_ctx *c, const float *ranges, const double *cos_t, const
         a.ppt = n_scan - 1;
         a.B = (int)pairs; a.n_tar = n; a.n_src = n; a.max_iter = max_iter; a.tol = tol;
         a.T_out = T; a.iters_out = iters_out; a.err_out = nullptr;
-        a.status = c->status; a.qpt_pref = c->icp_qpt; a.team_mode = c->icp_team;
+        a.status = c->status; a.qpt_pref = c->icp_qpt; a.team_mode = c->icp_team; a.one_wave = c->icp_one_wave;
         if (grid && c->replay_reset) {
             // option "replay_reset": the map starts from zero for this replay.  On one stream the scan-matching launch
             // clears the counters on its way (they are next touched by the ray cast behind it); maps with a live pmap and
@@ -1513,7 +1537,7 @@ int slam_particles_dev(slam_ctx *c, const float *ranges2, const double *cos_t, c
             a.ppt = 0;
             a.B = pc; a.n_tar = n; a.n_src = n; a.max_iter = max_iter; a.tol = tol;
             a.T_out = T_out + 9 * (size_t)p0; a.iters_out = iters_out ? iters_out + p0 : nullptr; a.err_out = nullptr;
-            a.status = c->status; a.team_mode = c->icp_team;
+            a.status = c->status; a.team_mode = c->icp_team; a.one_wave = c->icp_one_wave;
             // (queries per lane by the size of the BATCH: its chunks share the chip with one another's ray casts)
             a.qpt_pref = c->icp_qpt > 0 ? c->icp_qpt : (P >= 2500 ? 3 : 0);
             Timed t(c, SLAM_K_ICP, nullptr, k == 0);

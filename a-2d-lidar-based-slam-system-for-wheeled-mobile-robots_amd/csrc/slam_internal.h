@@ -99,6 +99,7 @@ struct IcpArgs {
     int polar_copy = 0;        // set by launch_icp: the kernel carves the unpadded second copy of the target (nn_polar)
     int team_cap = 0;          // set by launch_icp: room in the LDS list of first-iteration queries without a beam window (nn_listed), 0: none
     int team_mode = 0;         // context option "icp_team": 0 = on where it applies, 1 = off (the box search takes every such query)
+    int one_wave = -1;         // context option "icp_one_wave": -1 = one wave per pair where a full-chip launch allows it, 0 = never, 1 = wherever a pair fits
 };
 
 hipError_t launch_icp(const IcpArgs &a, int dtype, hipStream_t s);

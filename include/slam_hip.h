@@ -82,7 +82,7 @@ int slam_stream_order(slam_ctx *ctx, void *stream, int direction);
  * last call (SLAM_OK, SLAM_ERR_NAN or SLAM_ERR_OVERFLOW). */
 int slam_check_status(slam_ctx *ctx);
 /* Tuning knobs.  Maps, cell indices, nearest-neighbour indices and iteration counts never depend on them; the launch
- * shape of the scan matcher ("icp_qpt", and the batch size itself) decides the order in which a pair's sums are added,
+ * shape of the scan matcher ("icp_qpt", "icp_one_wave", and the batch size itself) decides the order in which a pair's sums are added,
  * so transforms and poses of two shapes agree to rounding (1e-13), not bit for bit.
  * "grid_mode": 1 = automatic (default): ray casting through an LDS window per group of scans,
  *   or - for one shared map much larger than a window - rays dealt by direction and swept in
@@ -97,7 +97,14 @@ int slam_check_status(slam_ctx *ctx);
  * "icp_qpt": queries per lane of batched scan matching, 1..3; 0 = by batch size (two for
  *   launches that cannot fill the chip on their own, three from 2 500 pairs of 360 beams or
  *   834 of 1 080 - 7 500 waves at two queries per lane; callers that overlap several smaller
- *   launches set 3).
+ *   launches set 3).  3 means "the shapes for a full chip": three queries per lane, or - see
+ *   "icp_one_wave" - one wave per pair where the launch is that large on its own.
+ * "icp_one_wave": scan matching by ONE wave per pair, six queries per lane, for pairs of up to 384
+ *   source points: fewer instructions per pair and no barriers, a longer solve of the single pair.
+ *   -1 = automatic (default): where the queries per lane resolve to 3 (given or by batch size), the
+ *   launch holds at least 16 384 pairs (four rounds of the pairs resident in this shape), the clouds
+ *   are scans and 16 pairs fit a compute unit's LDS; 0 = never; 1 = wherever a pair fits.  Same matches and iteration counts;
+ *   transforms agree with the other shapes to rounding, as above.
  * "replay_reset": 1 = slam_replay_dev starts its map from zero (as slam_grid_reset before it would),
  *   clearing the counters inside its scan-matching launch: one dispatch less per replay.  0
  *   (default): the map accumulates across replays until slam_grid_reset.
