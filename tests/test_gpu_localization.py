@@ -50,7 +50,7 @@ def test_update_map_golden(slam, g5):
 def test_update_map_layouts_and_edges(slam):
     rng = np.random.default_rng(3)
     loc = slam.Localization()
-    for (w, h) in ((1, 1), (7, 7), (64, 64), (33, 33)):
+    for (w, h) in ((1, 1), (7, 7), (64, 64), (33, 33), (12, 5)):
         data = rng.choice(np.array([-1, 0, 20, 21, 50, 100], dtype=np.int8), size=w * h)
         loc.updateMap(grid_msg(data, w, h, 0.05, -1.25, 2.5))
         want = on.map_obstacles(data, w, h, 0.05, -1.25, 2.5)
