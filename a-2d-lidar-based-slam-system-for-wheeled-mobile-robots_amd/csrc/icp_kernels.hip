@@ -763,6 +763,15 @@ __device__ __forceinline__ void polar_probe(const Cloud<T> &tar, int n_tar, unsi
 }
 
 struct PolarProbe { float dmin, span; bool ok; };
+// The whole probe from its parts put together, wave-uniform: the span's total is rounded up once more here.
+__device__ __forceinline__ PolarProbe polar_total(unsigned mn, float sum, bool ok)
+{
+    PolarProbe r;
+    r.dmin = __uint_as_float((unsigned)__builtin_amdgcn_readfirstlane((int)mn));
+    r.span = __uint_as_float((unsigned)__builtin_amdgcn_readfirstlane((int)__float_as_uint(sum * 1.00001f)));
+    r.ok = ok;
+    return r;
+}
 __device__ __forceinline__ PolarProbe polar_combine(const unsigned *slots, int nwaves)
 {
     const int lane = threadIdx.x & 63;
@@ -775,11 +784,7 @@ __device__ __forceinline__ PolarProbe polar_combine(const unsigned *slots, int n
         sum += __shfl_xor(sum, off);
         okw &= (unsigned)__shfl_xor((int)okw, off);
     }
-    PolarProbe r;
-    r.dmin = __uint_as_float((unsigned)__builtin_amdgcn_readfirstlane((int)mn));
-    r.span = __uint_as_float((unsigned)__builtin_amdgcn_readfirstlane((int)__float_as_uint(sum * 1.00001f)));
-    r.ok = __builtin_amdgcn_readfirstlane((int)okw) != 0;
-    return r;
+    return polar_total(mn, sum, __builtin_amdgcn_readfirstlane((int)okw) != 0);
 }
 
 // What a barrier is to a workgroup of ONE wave: LDS operations of a wave execute in the order they are issued, so a value
@@ -844,6 +849,306 @@ __device__ __forceinline__ void stage_target(const Cloud<T> &tar, int n_tar, dou
 }
 
 // ---------------------------------------------------------------------------------
+// The rules of the solve, each once, for both launch shapes of k_icp (icp_pair: one workgroup per pair; icp_pair_wave:
+// one wave per pair).  Nothing here knows a shape's LDS layout, how it stages or how it reduces: the pieces take tables,
+// reduced totals and a few scalars.  That the shapes find the same matches, run the same number of iterations and agree
+// on the transform to rounding (they add their sums in different orders) rests on both calling these.
+// ---------------------------------------------------------------------------------
+
+// The two clouds of pair b and the prior its source starts from.
+template <typename T>
+struct PairClouds {
+    Cloud<T> tar, src;
+    const double *prior;       // nullable [B][6]
+    int b;
+    // source point i as the solve starts from it (the prior applied); a lane without one starts from the origin's image
+    __device__ __forceinline__ double2 source(int i, bool have) const
+    {
+        double2 pt = have ? src.at(i) : make_double2(0.0, 0.0);
+        if (prior) {
+            const double *p = prior + 6 * (long)b;
+            pt = make_double2(p[0] * pt.x + p[1] * pt.y + p[2], p[3] * pt.x + p[4] * pt.y + p[5]);
+        }
+        return pt;
+    }
+};
+template <typename T>
+__device__ __forceinline__ PairClouds<T> pair_clouds(const IcpArgs &a, const int b)
+{
+    const long be = (long)b + (a.ppt ? b / a.ppt : 0);
+    PairClouds<T> pc{{nullptr, nullptr, a.cos_t, a.sin_t, a.n_tar}, {nullptr, nullptr, a.cos_t, a.sin_t, a.n_src}, a.prior, b};
+    if (a.ranges) {
+        pc.tar.ranges = a.ranges + be * a.tar_scan_stride;
+        pc.src.ranges = a.ranges + be * a.src_scan_stride + a.n_tar;   // the scan after the target's
+    } else {
+        pc.tar.pts = static_cast<const T *>(a.tar) + be * a.tar_stride;
+        pc.src.pts = static_cast<const T *>(a.src) + be * a.src_stride;
+    }
+    return pc;
+}
+
+// The target is a scan with usable beam geometry (nearest neighbours by beam window, nn_polar) when the probe found
+// nothing bad, the beams lie at least 1e-5 rad apart - closer together they are no usable geometry: the window's index
+// bound (dhi + alpha) * inv_db must stay far inside the int range - and they span at most one turn plus half a beam.
+template <typename T>
+__device__ __forceinline__ PolarGeo polar_geo(const PolarProbe &pp, int n_tar)
+{
+    const float dmin = pp.dmin, span = pp.span;
+    const bool polar = pp.ok && n_tar >= 2 && dmin >= 1e-5f && dmin < 1.0f && span <= 6.2831855f + 0.5f * dmin;
+    PolarGeo pg;
+    pg.inv_db = polar ? __fdividef(1.000002f, dmin) : 0.0f;
+    pg.slack = StoreSlack<T>::ang;
+    return pg;
+}
+
+// The tables a query is searched in.  has_p: tarP is there (unpadded image, NaN points behind the last beam); without it
+// tarB is the padded image and serves every purpose.  Two layouts exist and nn_query relies on it: STRIDE == kNNStride -
+// tarB is the padded image, tarP a second copy or absent; STRIDE == kNNBlock - ONE unpadded image, tarB == tarP, has_p true.
+struct NNTarget {
+    const double2 *tarP;       // the beam-window search's image, or null
+    const double2 *tarB;       // the box search's image: STRIDE slots a block (nn_search)
+    const Box *boxes, *boxes4;
+    int nblocks, n_tar;
+    bool has_p;
+    double2 *qlist;            // the list of first-iteration queries without a usable beam window (nn_listed),
+    int *qseed;                // their guesses,
+    int cap;                   // its room; 0: no list
+    __device__ __forceinline__ double2 at(int j) const { return has_p ? tarP[j] : tarB[tslot(j)]; }
+};
+struct NNQuery {
+    double d2;                 // square of the distance to the nearest target; infinite: the query never won
+    int j;                     // its index
+    int slot;                  // >= 0: the query was put on the list at this place and nn_listed finds its match (listed_result), d2 and j are void
+};
+__device__ __forceinline__ double match_distance(double d2) { return (d2 < INFINITY) ? sqrt(d2) : 0.0; }   // never-won query: distance 0 (icp.py:97)
+
+// Nearest target of one query (icp.py:67).  EXACT: the reference's own loop.  A scan: the beam window around the guess;
+// in a first iteration that lists (`listing`), a query without a usable window goes on the list while there is room -
+// place(mask of such lanes) says where the wave's entries start: the shapes count them differently - and what is still
+// without a window takes the box search.  No scan: the box search.  Every event that can make the order of squares differ
+// from the reference's order of distances (see "Best") is added to amb_mask, the wave-wide mask of lanes that saw one:
+// kept in scalar registers (a per-lane flag cost four vector instructions a query); amb_mask != 0 -> the pair is re-done
+// with EXACT.  note_big(big): the diagnostic build's counter of queries left to the box search.
+template <int UNROLL, int STRIDE, bool EXACT, typename Place, typename NoteBig>
+__device__ __forceinline__ NNQuery nn_query(const NNTarget &t, const PolarGeo &pg, const double sx, const double sy, const int seed, const bool okq,
+                                            const bool first, const bool listing, Place &&place, NoteBig &&note_big, unsigned long long &amb_mask)
+{
+    NNQuery h;
+    h.slot = -1;
+    if (EXACT) {
+        const bool padded = STRIDE == kNNStride && !t.has_p;      // (the unpadded image where there is one: no slot arithmetic)
+        const NNHit e = nn_exact(padded ? t.tarB : t.tarP, padded, okq ? t.n_tar : 0, sx, sy);
+        h.d2 = e.d2; h.j = e.j;
+    } else if (pg.inv_db > 0.0f) {                                   // wave-uniform: the target is a scan
+        bool big, amb_lane;
+        unsigned long long am;
+        nn_polar<UNROLL, false>(t.tarP, t.n_tar, sx, sy, seed, okq, pg, listing ? kPolarMaxFirst : kPolarMax, h.d2, h.j, big, amb_lane, am);
+        (void)amb_lane;
+        amb_mask |= am;
+        if (listing) {
+            const unsigned long long bm = __ballot(big);
+            if (bm != 0ull) {
+                const int pos = place(bm) + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bm, 0u));
+                if (big && pos < t.cap) {
+                    h.slot = pos;
+                    t.qlist[pos] = make_double2(sx, sy);
+                    t.qseed[pos] = seed;
+                    big = false;                                     // (a list that is full leaves the rest to the box search)
+                }
+            }
+        }
+        // The few queries without a good match (newly visible surfaces; they come in runs of
+        // neighbouring beams: measured 1.3 % of the queries, in 10 % of the wave-queries, 8 lanes at
+        // a time) take the box search.  Tried and dropped: scanning the whole cloud for them
+        // with the wave, one query after the other (4.37e7 instead of 4.00e7 instructions per
+        // launch), and searching a lane's queries together in one wave-wide loop (4.55e7).
+        note_big(big);
+        if (__any(big)) {
+            double d2b; int jb; bool ambb;
+            nn_search<STRIDE>(t.tarB, t.boxes, t.boxes4, t.nblocks, t.n_tar, sx, sy, seed, first, big, d2b, jb, ambb);
+            h.d2 = big ? d2b : h.d2;
+            h.j = big ? jb : h.j;
+            amb_mask |= __ballot(big && ambb);
+        }
+    } else {
+        bool ambs;
+        nn_search<STRIDE>(t.tarB, t.boxes, t.boxes4, t.nblocks, t.n_tar, sx, sy, seed, first, okq, h.d2, h.j, ambs);
+        amb_mask |= __ballot(ambs);
+    }
+    return h;
+}
+
+// What nn_listed left for the query listed at `slot` (none: slot < 0, d2 and j stay): square and index; the flag in the
+// index's sign bit goes to amb_mask.  Called by the whole wave.
+__device__ __forceinline__ void listed_result(const double2 *qlist, const int slot, double &d2, int &j, unsigned long long &amb_mask)
+{
+    bool flagged = false;
+    if (slot >= 0) {
+        const double2 rs = qlist[slot];
+        const int jf = __double2loint(rs.y);
+        flagged = jf < 0;
+        j = jf & 0x7fffffff;
+        d2 = rs.x;
+    }
+    amb_mask |= __ballot(flagged);
+}
+
+// Collapsed sets (every point of a set is ONE point): W = BB^T.AA is mathematically zero and
+// the canonical answer is R = I (the SVD of a zero matrix), t = centroid_B - centroid_A.  The
+// reference's centred rows are rounding noise there (np.mean of n equal values is not that
+// value) and its rotation arbitrary: documented deviation, tests/golden/g8_collapsed.npz.
+//
+// Is every query of a wave matched to ONE target point (same coordinates)?  Every match is compared with that of lane 0's
+// first query (which always exists).  The usual case is settled on ONE lane: some first query of the wave is matched to
+// another beam than lane 0's (an integer compare per lane), and that beam's point differs from lane 0's.  Only when no
+// such lane exists, or its point has the same coordinates (targets that coincide: several beams of range 0), every match
+// is compared.  step() for each query of the lane in turn, q = 0 first, by the whole wave.
+struct SameMatch {
+    double m0x, m0y;           // the match of lane 0's first query
+    bool found, differs;
+    __device__ __forceinline__ void step(const int q, const bool okq, const int j, const double mx, const double my)
+    {
+        if (q == 0) {
+            m0x = readlane_f64(mx, 0); m0y = readlane_f64(my, 0);
+            found = differs = false;
+            const int j0 = __builtin_amdgcn_readfirstlane(j);
+            const unsigned long long other = __ballot(okq && j != j0);
+            if (other != 0ull) {
+                const int l = __ffsll((long long)other) - 1;
+                const double ox = readlane_f64(mx, l), oy = readlane_f64(my, l);
+                found = !(ox == m0x && oy == m0y);
+            }
+        }
+        if (!found) differs |= okq && !(mx == m0x && my == m0y);
+    }
+    __device__ __forceinline__ bool wave_differs() const { return found || __any(differs); }
+};
+
+// ---- a query's share of the sums (a: the source point or its original, b: its match or where it moved to)
+// both sets' coordinates: the centroids' sums (icp.py:154-155)
+template <int N>
+__device__ __forceinline__ void add_points(double (&v)[N], double ax, double ay, double bx, double by)
+{
+    v[0] += ax; v[1] += ay; v[2] += bx; v[3] += by;
+}
+// the products of the centred rows (:160)
+__device__ __forceinline__ void add_centred(double (&w)[4], double ax, double ay, double cax, double cay, double bx, double by, double cbx, double cby)
+{
+    const double aax = ax - cax, aay = ay - cay, bbx = bx - cbx, bby = by - cby;
+    w[0] += bbx * aax; w[1] += bbx * aay; w[2] += bby * aax; w[3] += bby * aay;
+}
+// From the second iteration on: ONE pass.  The update of the iteration before moved the source's centroid onto the
+// centroid of its matches (t = c_B - R c_A), so that point p is within rounding of this iteration's source centroid and
+// close to the new matches': sums and products are formed about p and the exact centroids and centred products follow
+// algebraically (one_pass_totals),
+//   c_A = p + S_a / N,  c_B = p + S_b / N,  W = sum (b - p)(a - p)^T - S_b S_a^T / N,
+// with S_a = sum (a - p) at rounding level - the correction is of the order of the last place of W.  The rotation needs
+// W only through A = W00 + W11 and B = W10 - W01 (kabsch_from_sums): the two are summed directly - seven values instead
+// of nine, one exchange level less in the wave reduction.
+__device__ __forceinline__ void add_one_pass(double (&u)[8], double ax, double ay, double bx, double by, double dq, double px, double py)
+{
+    const double dax = ax - px, day = ay - py, dbx = bx - px, dby = by - py;
+    u[0] += dax; u[1] += day; u[2] += dbx; u[3] += dby; u[4] += dq;
+    // (fused: two instructions a sum instead of four - these sums are this kernel's own form of W anyway, K2)
+    u[5] = fma(dbx, dax, fma(dby, day, u[5])); u[6] = fma(dby, dax, fma(-dbx, day, u[6]));
+}
+// the final transform's (final_transform): s the moved source point about p, a its original about the originals' centroid
+__device__ __forceinline__ void add_final(double (&u)[4], double sx, double sy, double px, double py, double ax, double ay, double cax, double cay)
+{
+    const double dsx = sx - px, dsy = sy - py, dax = ax - cax, day = ay - cay;
+    u[0] += dsx; u[1] += dsy;
+    u[2] += dsx * dax + dsy * day; u[3] += dsy * dax - dsx * day;
+}
+
+// ---- from the totals to a transform.  `tot`: what a lane holds behind wave_reduce8 / wave_reduce4 (and the workgroup's
+// cross-wave stage): the total of value k in lane k for k < 4, value 4 in lane 7, values 5, 6 in lanes 6, 5.  All 64 lanes.
+struct Centroids { double ax, ay, bx, by; };
+// what the solve carries from one iteration to the next, beside the points
+// (pc: the centroid the source has, up to rounding, after the last update; ca0: its centroid before it moves)
+struct Solve { double pre_error = 0.0, mean_error = 0.0, pcx = 0.0, pcy = 0.0, ca0x = 0.0, ca0y = 0.0; int iters = 0; };
+
+// centroids from the totals of add_points (and the mean distance from value 4): ONE division sequence for all of them,
+// then the broadcasts (icp.py:154-155, :75)
+__device__ __forceinline__ Centroids centroids_from_totals(double tot, double dn, double *mean_error = nullptr)
+{
+    const double qv = tot / dn;
+    const Centroids c{readlane_f64(qv, 0), readlane_f64(qv, 1), readlane_f64(qv, 2), readlane_f64(qv, 3)};
+    if (mean_error) *mean_error = readlane_f64(qv, 7);
+    return c;
+}
+__device__ __forceinline__ void lanes4(double tot, double (&w)[4])
+{
+    w[0] = readlane_f64(tot, 0); w[1] = readlane_f64(tot, 1); w[2] = readlane_f64(tot, 2); w[3] = readlane_f64(tot, 3);
+}
+// rotation and translation (icp.py:69) from centroids and products; a collapsed set: W = 0
+__device__ __forceinline__ Rigid2 rigid_from_w(const Centroids &c, double w00, double w01, double w10, double w11, bool collapsed, int lane)
+{
+    if (collapsed) w00 = w01 = w10 = w11 = 0.0;
+    return kabsch_from_sums_wave(c.ax, c.ay, c.bx, c.by, w00, w01, w10, w11, lane);
+}
+// the one-pass algebra (add_one_pass): centroids, mean distance, A and B from the seven totals about p = (s.pcx, s.pcy)
+struct OnePass { Centroids c; double A, B; };
+__device__ __forceinline__ OnePass one_pass_totals(double tot, double dn, Solve &s)
+{
+    const double qv = tot / dn;                                      // icp.py:154-155, :75
+    const double qax = readlane_f64(qv, 0), qay = readlane_f64(qv, 1);
+    OnePass o;
+    o.c.ax = s.pcx + qax; o.c.ay = s.pcy + qay;
+    o.c.bx = s.pcx + readlane_f64(qv, 2); o.c.by = s.pcy + readlane_f64(qv, 3);
+    s.mean_error = readlane_f64(qv, 7);
+    const double sbx = readlane_f64(tot, 2), sby = readlane_f64(tot, 3);
+    o.A = readlane_f64(tot, 6) - (sbx * qax + sby * qay);
+    o.B = readlane_f64(tot, 5) - (sby * qax - sbx * qay);
+    return o;
+}
+// final T = getTransform(A_original, src_final) (icp.py:81) when an iteration has run, from the ONE reduction of add_final:
+// the originals' centroid c_A is the first iteration's source centroid (the same sums in the same order - the source had
+// not moved yet), and the last update put the source's centroid on p = (pcx, pcy) up to rounding, so with S = sum (s - p)
+//   c_S = p + S / N,   W = sum (s - p)(a - c_A)^T   (- S . sum (a - c_A)^T / N: rounding level times rounding level),
+// of which the rotation needs A = W00 + W11 and B = W10 - W01 (as in the iterations).
+__device__ __forceinline__ Rigid2 final_transform(double tot, double dn, const Solve &s, bool src_collapsed, int lane)
+{
+    const double qv = tot / dn;
+    const Centroids c{s.ca0x, s.ca0y, s.pcx + readlane_f64(qv, 0), s.pcy + readlane_f64(qv, 1)};
+    return rigid_from_w(c, readlane_f64(tot, 2), 0.0, readlane_f64(tot, 3), 0.0, src_collapsed, lane);
+}
+
+// src = T.src (icp.py:71); (cbx, cby): the centroid the source now has (up to rounding)
+template <int QPT>
+__device__ __forceinline__ void advance(const Rigid2 &r, double cbx, double cby, double (&sx)[QPT], double (&sy)[QPT], Solve &s)
+{
+#pragma unroll
+    for (int q = 0; q < QPT; ++q) {
+        const double nx = r.c * sx[q] + (-r.s) * sy[q] + r.tx;
+        const double ny = r.s * sx[q] + r.c * sy[q] + r.ty;
+        sx[q] = nx; sy[q] = ny;
+    }
+    s.pcx = cbx; s.pcy = cby;
+    ++s.iters;
+}
+// the convergence test behind an update (icp.py:76-77)
+__device__ __forceinline__ bool converged(Solve &s, double tol)
+{
+    if (fabs(s.pre_error - s.mean_error) < tol) return true;
+    s.pre_error = s.mean_error;
+    return false;
+}
+
+__device__ __forceinline__ void store_transform(double *To, const Rigid2 &r)
+{
+    To[0] = r.c; To[1] = -r.s; To[2] = r.tx;
+    To[3] = r.s; To[4] = r.c;  To[5] = r.ty;
+    To[6] = 0.0; To[7] = 0.0;  To[8] = 1.0;
+}
+// a pair's result, by one lane
+__device__ __forceinline__ void store_result(const IcpArgs &a, int b, const Rigid2 &r, const Solve &s)
+{
+    store_transform(a.T_out + 9 * (long)b, r);
+    if (a.iters_out) a.iters_out[b] = s.iters;
+    if (a.err_out) a.err_out[b] = s.mean_error;
+}
+
+// ---------------------------------------------------------------------------------
 // k_icp: ICP.process (icp.py:38-88), one workgroup per pair, QPT queries per lane.
 // ---------------------------------------------------------------------------------
 constexpr int kIcpExtraLds = 32;               // flag words: source set collapsed, count of listed queries, re-do
@@ -857,6 +1162,9 @@ __host__ __device__ inline size_t icp_red_bytes(int nwaves) { return (size_t)2 *
 // EXACT: the second pass over a pair in which the first saw a best undercut its predecessor by less than a class of
 // equal distances (see "Best"): the same solve with the reference's own nearest-neighbour loop (nn_exact).
 // Returns whether the pair needs that second pass (the same value in every lane; false from the second pass).
+// What is this shape's own: the padded image beside the unpadded one, staging and probe by all waves behind barriers, a
+// query's moving point, original, match and distance in registers, sums handed between the waves through LDS (block_total,
+// or the lead wave alone behind a second barrier), the list's count an LDS atomic.
 template <typename T, int QPT, int UNROLL, bool EXACT>
 __device__ __forceinline__ bool icp_pair(const IcpArgs &a, const int b, char *smem)
 {
@@ -880,16 +1188,9 @@ __device__ __forceinline__ bool icp_pair(const IcpArgs &a, const int b, char *sm
     char *guard = reinterpret_cast<char *>(qseed + a.team_cap);
     lds_guard_fill(guard);
 
-    const long be = (long)b + (a.ppt ? b / a.ppt : 0);
     const int n_src = a.n_src, n_tar = a.n_tar;
-    Cloud<T> tar{nullptr, nullptr, a.cos_t, a.sin_t, n_tar}, src{nullptr, nullptr, a.cos_t, a.sin_t, n_src};
-    if (a.ranges) {
-        tar.ranges = a.ranges + be * a.tar_scan_stride;
-        src.ranges = a.ranges + be * a.src_scan_stride + n_tar;      // the scan after the target's
-    } else {
-        tar.pts = static_cast<const T *>(a.tar) + be * a.tar_stride;
-        src.pts = static_cast<const T *>(a.src) + be * a.src_stride;
-    }
+    const PairClouds<T> pc = pair_clouds<T>(a, b);
+    const NNTarget nt{tarP, tarL, boxes, boxes4, nblocks, n_tar, has_p, qlist, qseed, a.team_cap};
 
     if (threadIdx.x == 0) { geo[3] = 1u; geo[4] = 0u; geo[5] = 0u; }
 
@@ -897,56 +1198,31 @@ __device__ __forceinline__ bool icp_pair(const IcpArgs &a, const int b, char *sm
     double sx[QPT], sy[QPT], ax[QPT], ay[QPT];
     int seed[QPT];
     bool ok[QPT];
-#pragma unroll
-    for (int q = 0; q < QPT; ++q) {
-        int i = tid + q * blockDim.x;
-        ok[q] = i < n_src;
-        double2 pt = ok[q] ? src.at(i) : make_double2(0.0, 0.0);
-        double x = pt.x, y = pt.y;
-        if (a.prior) {
-            const double *p = a.prior + 6 * (long)b;
-            double xp = p[0] * x + p[1] * y + p[2];
-            double yp = p[3] * x + p[4] * y + p[5];
-            x = xp; y = yp;
-        }
-        sx[q] = ax[q] = x;
-        sy[q] = ay[q] = y;
-        seed[q] = min(i, n_tar - 1);             // first guess: the same beam index
-    }
     bool src_differs = false;
     {
-        // Collapsed sets (every point of a set is ONE point): W = BB^T.AA is mathematically zero and
-        // the canonical answer is R = I (the SVD of a zero matrix), t = centroid_B - centroid_A.  The
-        // reference's centred rows are rounding noise there (np.mean of n equal values is not that
-        // value) and its rotation arbitrary: documented deviation, tests/golden/g8_collapsed.npz.
-        double2 p0 = src.at(0);
-        if (a.prior) {
-            const double *p = a.prior + 6 * (long)b;
-            p0 = make_double2(p[0] * p0.x + p[1] * p0.y + p[2], p[3] * p0.x + p[4] * p0.y + p[5]);
-        }
+        const double2 p0 = pc.source(0, true);                       // (collapsed sets: see SameMatch)
 #pragma unroll
-        for (int q = 0; q < QPT; ++q) src_differs |= ok[q] && !(ax[q] == p0.x && ay[q] == p0.y);
+        for (int q = 0; q < QPT; ++q) {
+            const int i = tid + q * blockDim.x;
+            ok[q] = i < n_src;
+            const double2 pt = pc.source(i, ok[q]);
+            sx[q] = ax[q] = pt.x;
+            sy[q] = ay[q] = pt.y;
+            seed[q] = min(i, n_tar - 1);             // first guess: the same beam index
+            src_differs |= ok[q] && !(pt.x == p0.x && pt.y == p0.y);
+        }
     }
     ISTAMP(13);
-    stage_points(tar, n_tar, tarL, tarP);
+    stage_points(pc.tar, n_tar, tarL, tarP);
     const bool probed = a.ranges && has_p;
     unsigned *pslots = reinterpret_cast<unsigned *>(cref);           // [nwaves][4]: the iterations use this space later
-    if (probed) polar_probe(tar, n_tar, pslots);
+    if (probed) polar_probe(pc.tar, n_tar, pslots);
     __syncthreads();                                                 // (geo is initialised)
     ISTAMP(10);
     if (src_differs) geo[3] = 0u;
-    // the target is a scan with usable beam geometry: nearest neighbours by beam window (nn_polar)
-    PolarGeo pg;
-    {
-        PolarProbe pp{1.0f, 0.0f, false};
-        if (probed) pp = polar_combine(pslots, nwaves);
-        const float dmin = pp.dmin, span = pp.span;
-        // (beams closer together than 1e-5 rad are no usable geometry: the window's index bound (dhi + alpha) * inv_db
-        // must stay far inside the int range)
-        const bool polar = probed && pp.ok && n_tar >= 2 && dmin >= 1e-5f && dmin < 1.0f && span <= 6.2831855f + 0.5f * dmin;
-        pg.inv_db = polar ? __fdividef(1.000002f, dmin) : 0.0f;
-        pg.slack = StoreSlack<T>::ang;
-    }
+    PolarProbe pp{1.0f, 0.0f, false};
+    if (probed) pp = polar_combine(pslots, nwaves);
+    const PolarGeo pg = polar_geo<T>(pp, n_tar);
     ISTAMP(12);
     stage_boxes(n_tar, tarL, boxes, boxes4);
     ISTAMP(11);
@@ -956,10 +1232,15 @@ __device__ __forceinline__ bool icp_pair(const IcpArgs &a, const int b, char *sm
     const double dn = (double)n_src;
     const LaneSel ls = lane_sel(lane);
     ISTAMP(14);
-    double pre_error = 0.0, mean_error = 0.0, pcx = 0.0, pcy = 0.0, ca0x = 0.0, ca0y = 0.0;   // (ca0: centroid of the source before it moves)
-    int iters = 0, par = 0;
-    unsigned long long amb_mask = 0ull;   // lanes of this wave that saw a best undercut its predecessor by less than a class of equal distances:
-                                          // kept as a wave-wide mask in scalar registers (a per-lane flag cost four vector instructions a query)
+    Solve s;
+    int par = 0;
+    unsigned long long amb_mask = 0ull;
+    // where a wave's entries on the list start: the count is in LDS
+    auto place = [&](const unsigned long long bm) __attribute__((always_inline)) -> int {
+        int base = 0;
+        if (lane == 0) base = (int)atomicAdd(&geo[4], (unsigned)__popcll(bm));
+        return __builtin_amdgcn_readfirstlane(base);
+    };
     // one iteration; FIRST: the instance for iteration 0 (two reductions as the reference; the only one that lists queries
     // for nn_listed), the loop behind it takes the one-pass form; returns true when the solve has converged (icp.py:76-77)
     auto iterate = [&](auto first_tag, const int it) __attribute__((always_inline)) -> bool {
@@ -968,58 +1249,16 @@ __device__ __forceinline__ bool icp_pair(const IcpArgs &a, const int b, char *sm
         double mx[QPT], my[QPT], dq[QPT];
         // first iteration over a scan: queries without a usable beam window are listed (nn_listed)
         const bool team_it = FIRST && !EXACT && a.team_cap > 0 && pg.inv_db > 0.0f;
+        auto note_big = [&](const bool big) __attribute__((always_inline)) { ISTAMP_BIG(it, big); (void)big; };
         int slot[QPT];
 #pragma unroll
         for (int q = 0; q < QPT; ++q) {
-            double d2; int j;
-            slot[q] = -1;
-            if (EXACT) {
-                const NNHit h = nn_exact(has_p ? tarP : tarL, !has_p, ok[q] ? n_tar : 0, sx[q], sy[q]);
-                d2 = h.d2; j = h.j;
-            } else if (pg.inv_db > 0.0f) {                           // wave-uniform: the target is a scan
-                bool big, amb_lane;
-                unsigned long long am;
-                nn_polar<UNROLL, false>(tarP, n_tar, sx[q], sy[q], seed[q], ok[q], pg, team_it ? kPolarMaxFirst : kPolarMax, d2, j,
-                                        big, amb_lane, am);          // icp.py:67
-                (void)amb_lane;
-                amb_mask |= am;
-                if (FIRST && team_it) {
-                    const unsigned long long bm = __ballot(big);
-                    if (bm != 0ull) {
-                        int base = 0;
-                        if (lane == 0) base = (int)atomicAdd(&geo[4], (unsigned)__popcll(bm));
-                        base = __builtin_amdgcn_readfirstlane(base);
-                        const int pos = base + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bm, 0u));
-                        if (big && pos < a.team_cap) {
-                            slot[q] = pos;
-                            qlist[pos] = make_double2(sx[q], sy[q]);
-                            qseed[pos] = seed[q];
-                            big = false;                             // (a list that is full leaves the rest to the box search)
-                        }
-                    }
-                }
-                // The few queries without a good match (newly visible surfaces; they come in runs of
-                // neighbouring beams: measured 1.3 % of the queries, in 10 % of the wave-queries, 8 lanes at
-                // a time) take the box search.  Tried and dropped: scanning the whole cloud for them
-                // with the wave, one query after the other (4.37e7 instead of 4.00e7 instructions per
-                // launch), and searching a lane's queries together in one wave-wide loop (4.55e7).
-                ISTAMP_BIG(it, big);
-                if (__any(big)) {
-                    double d2b; int jb; bool ambb;
-                    nn_search(tarL, boxes, boxes4, nblocks, n_tar, sx[q], sy[q], seed[q], FIRST, big, d2b, jb, ambb);
-                    d2 = big ? d2b : d2;
-                    j = big ? jb : j;
-                    amb_mask |= __ballot(big && ambb);
-                }
-            } else {
-                bool ambs;
-                nn_search(tarL, boxes, boxes4, nblocks, n_tar, sx[q], sy[q], seed[q], FIRST, ok[q], d2, j, ambs);   // icp.py:67
-                amb_mask |= __ballot(ambs);
-            }                                                        // (amb_mask != 0 -> the pair is re-done: icp_pair<EXACT>)
-            seed[q] = j;                                             // next iteration's guess
-            double2 m = has_p ? tarP[j] : tarL[tslot(j)];
+            const NNQuery h = nn_query<UNROLL, kNNStride, EXACT>(nt, pg, sx[q], sy[q], seed[q], ok[q], FIRST, team_it, place, note_big, amb_mask);
+            slot[q] = h.slot;
+            seed[q] = h.j;                                           // next iteration's guess
+            const double2 m = nt.at(h.j);
             mx[q] = m.x; my[q] = m.y;
-            dq[q] = (d2 < INFINITY) ? sqrt(d2) : 0.0;               // never-won query: distance 0 (:97)
+            dq[q] = match_distance(h.d2);
         }
         if (FIRST && team_it) {
             __syncthreads();
@@ -1027,107 +1266,58 @@ __device__ __forceinline__ bool icp_pair(const IcpArgs &a, const int b, char *sm
             __syncthreads();
 #pragma unroll
             for (int q = 0; q < QPT; ++q) {
-                bool flagged = false;
+                double d2 = 0.0;
+                listed_result(qlist, slot[q], d2, seed[q], amb_mask);
                 if (slot[q] >= 0) {
-                    const double2 rs = qlist[slot[q]];
-                    const int jf = __double2loint(rs.y), j = jf & 0x7fffffff;
-                    flagged = jf < 0;
-                    seed[q] = j;
-                    const double2 m = tarP[j];
+                    const double2 m = tarP[seed[q]];
                     mx[q] = m.x; my[q] = m.y;
-                    dq[q] = (rs.x < INFINITY) ? sqrt(rs.x) : 0.0;
+                    dq[q] = match_distance(d2);
                 }
-                amb_mask |= __ballot(flagged);
             }
         }
-        // every source point matched to ONE target point (same coordinates)?  see "collapsed sets" above.  Every wave
-        // compares its matches with that of its first query (which always exists) and leaves point and verdict in LDS
-        // ahead of the iteration's first barrier; behind it the waves' points are compared with one another.
+        // every source point matched to ONE target point?  Every wave leaves the point of its first query and its verdict
+        // (SameMatch) in LDS ahead of the iteration's first barrier; behind it the waves' points are compared with one another.
         par ^= 1;
         double *cr = cref + par * nwaves * 4;
-        bool wave_differs;
-        {
-            const double m0x = readlane_f64(mx[0], 0), m0y = readlane_f64(my[0], 0);
-            // The usual case is settled on ONE lane: some first query of the wave is matched to another beam than lane 0's
-            // (an integer compare per lane), and that beam's point differs from lane 0's.  Only when no such lane exists, or
-            // its point has the same coordinates (targets that coincide: several beams of range 0), every match is compared.
-            const int j0 = __builtin_amdgcn_readfirstlane(seed[0]);
-            const unsigned long long other = __ballot(ok[0] && seed[0] != j0);
-            bool found = false;
-            if (other != 0ull) {
-                const int l = __ffsll((long long)other) - 1;
-                const double ox = readlane_f64(mx[0], l), oy = readlane_f64(my[0], l);
-                found = !(ox == m0x && oy == m0y);
-            }
-            if (found) wave_differs = true;
-            else {
-                bool differs = false;
+        SameMatch same{0.0, 0.0, false, false};
 #pragma unroll
-                for (int q = 0; q < QPT; ++q) differs |= ok[q] && !(mx[q] == m0x && my[q] == m0y);
-                wave_differs = __any(differs);
-            }
-            if (nwaves > 1 && lane == 0) { cr[4 * wave] = m0x; cr[4 * wave + 1] = m0y; cr[4 * wave + 2] = wave_differs ? 1.0 : 0.0; }
-        }
+        for (int q = 0; q < QPT; ++q) same.step(q, ok[q], seed[q], mx[q], my[q]);
+        const bool wave_differs = same.wave_differs();
+        if (nwaves > 1 && lane == 0) { cr[4 * wave] = same.m0x; cr[4 * wave + 1] = same.m0y; cr[4 * wave + 2] = wave_differs ? 1.0 : 0.0; }
         auto targets_collapsed = [&]() -> bool {                     // (call behind the barrier)
             if (nwaves == 1) return !wave_differs;
             const double *mine = cr + 4 * min(lane, nwaves - 1);
             return !__any(mine[2] != 0.0 || !(mine[0] == cr[0] && mine[1] == cr[1]));
         };
-        double cax, cay, cbx, cby, w[4];
+        double cbx, cby;
         Rigid2 r;
         if (FIRST || !kOnePass) {
             // Two passes, as the reference (centroids, then centred products, icp.py:154-160).
-            double v[5] = {0, 0, 0, 0, 0};
+            double v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
             for (int q = 0; q < QPT; ++q)
-                if (ok[q]) { v[0] += sx[q]; v[1] += sy[q]; v[2] += mx[q]; v[3] += my[q]; v[4] += dq[q]; }
+                if (ok[q]) { add_points(v, sx[q], sy[q], mx[q], my[q]); v[4] += dq[q]; }
             ISTAMP(FIRST ? 6 : 1);
-            // sums of the five quantities over the pair (transposed reduction: lane l ends up with the total
-            // of value idx8(l)), ONE division sequence for all of them, then five broadcasts
-            {
-                const double v8[8] = {v[0], v[1], v[2], v[3], v[4], 0.0, 0.0, 0.0};
-                const double tot = block_total(wave_reduce8(v8, ls), ls.idx8, red + par * nwaves * kRedStride, nwaves, wave, lane);
-                const double qv = tot / dn;                          // icp.py:154-155, :75
-                cax = readlane_f64(qv, 0); cay = readlane_f64(qv, 1); cbx = readlane_f64(qv, 2); cby = readlane_f64(qv, 3);
-                mean_error = readlane_f64(qv, 7);                    // value 4 lives in lane 7
-            }
+            // sums of the five quantities over the pair (transposed reduction: lane l ends up with the total of value idx8(l))
+            const Centroids c = centroids_from_totals(block_total(wave_reduce8(v, ls), ls.idx8, red + par * nwaves * kRedStride, nwaves, wave, lane), dn, &s.mean_error);
             ISTAMP(FIRST ? 7 : 2);
             const bool tar_collapsed = targets_collapsed();
-            w[0] = w[1] = w[2] = w[3] = 0.0;
+            double w[4] = {0, 0, 0, 0};
 #pragma unroll
-            for (int q = 0; q < QPT; ++q) {
-                if (ok[q]) {
-                    double aax = sx[q] - cax, aay = sy[q] - cay, bbx = mx[q] - cbx, bby = my[q] - cby;
-                    w[0] += bbx * aax; w[1] += bbx * aay; w[2] += bby * aax; w[3] += bby * aay;   // :160
-                }
-            }
+            for (int q = 0; q < QPT; ++q)
+                if (ok[q]) add_centred(w, sx[q], sy[q], c.ax, c.ay, mx[q], my[q], c.bx, c.by);
             par ^= 1;
-            {
-                const double tot = block_total(wave_reduce4(w, ls), ls.idx4, red + par * nwaves * kRedStride, nwaves, wave, lane);
-                w[0] = readlane_f64(tot, 0); w[1] = readlane_f64(tot, 1); w[2] = readlane_f64(tot, 2); w[3] = readlane_f64(tot, 3);
-            }
+            lanes4(block_total(wave_reduce4(w, ls), ls.idx4, red + par * nwaves * kRedStride, nwaves, wave, lane), w);
             ISTAMP(FIRST ? 8 : 3);
-            if (tar_collapsed || src_collapsed) w[0] = w[1] = w[2] = w[3] = 0.0;
-            if (FIRST) { ca0x = cax; ca0y = cay; }
+            if (FIRST) { s.ca0x = c.ax; s.ca0y = c.ay; }
+            cbx = c.bx; cby = c.by;
+            r = rigid_from_w(c, w[0], w[1], w[2], w[3], tar_collapsed || src_collapsed, lane);
         } else {
-            // From the second iteration on: ONE pass and one barrier.  The update of the iteration before moved the
-            // source's centroid onto the centroid of its matches (t = c_B - R c_A), so that point p is within rounding
-            // of this iteration's source centroid and close to the new matches': sums and products are formed about p
-            // and the exact centroids and centred products follow algebraically,
-            //   c_A = p + S_a / N,  c_B = p + S_b / N,  W = sum (b - p)(a - p)^T - S_b S_a^T / N,
-            // with S_a = sum (a - p) at rounding level - the correction is of the order of the last place of W.
-            // The rotation needs W only through A = W00 + W11 and B = W10 - W01 (kabsch_from_sums): the two are summed
-            // directly - seven values instead of nine, one exchange level less in the wave reduction.
+            // From the second iteration on: ONE pass and one barrier (add_one_pass).
             double u[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
-            for (int q = 0; q < QPT; ++q) {
-                if (ok[q]) {
-                    const double dax = sx[q] - pcx, day = sy[q] - pcy, dbx = mx[q] - pcx, dby = my[q] - pcy;
-                    u[0] += dax; u[1] += day; u[2] += dbx; u[3] += dby; u[4] += dq[q];
-                    // (fused: two instructions a sum instead of four - these sums are this kernel's own form of W anyway, K2)
-                    u[5] = fma(dbx, dax, fma(dby, day, u[5])); u[6] = fma(dby, dax, fma(-dbx, day, u[6]));
-                }
-            }
+            for (int q = 0; q < QPT; ++q)
+                if (ok[q]) add_one_pass(u, sx[q], sy[q], mx[q], my[q], dq[q], s.pcx, s.pcy);
             ISTAMP(1);
             // what follows the sums: the quotients, the rotation, the translation - a hundred instructions on wave-uniform
             // values.  In the launch shapes for a full chip (kLead: three queries per lane and more) the pair's first wave
@@ -1135,18 +1325,10 @@ __device__ __forceinline__ bool icp_pair(const IcpArgs &a, const int b, char *sm
             // slots to other pairs (10 000 pairs: 0.388 -> 0.381 ms); a launch that cannot fill the chip is bound by a pair's
             // own latency, and there every wave computes them for itself behind the ONE barrier.
             auto finish = [&](const double tot) __attribute__((always_inline)) {
-                const double qv = tot / dn;                          // icp.py:154-155, :75
-                const double qax = readlane_f64(qv, 0), qay = readlane_f64(qv, 1);
-                cax = pcx + qax; cay = pcy + qay;
-                cbx = pcx + readlane_f64(qv, 2); cby = pcy + readlane_f64(qv, 3);
-                mean_error = readlane_f64(qv, 7);                    // value 4 lives in lane 7, values 5, 6 in lanes 6, 5
-                const double sbx = readlane_f64(tot, 2), sby = readlane_f64(tot, 3);
-                w[0] = readlane_f64(tot, 6) - (sbx * qax + sby * qay);   // A
-                w[2] = readlane_f64(tot, 5) - (sby * qax - sbx * qay);   // B
-                w[1] = w[3] = 0.0;
+                const OnePass o = one_pass_totals(tot, dn, s);
+                cbx = o.c.bx; cby = o.c.by;
                 ISTAMP(3);
-                if (targets_collapsed() || src_collapsed) w[0] = w[2] = 0.0;
-                r = kabsch_from_sums_wave(cax, cay, cbx, cby, w[0], w[1], w[2], w[3], lane);    // :69
+                r = rigid_from_w(o.c, o.A, 0.0, o.B, 0.0, targets_collapsed() || src_collapsed, lane);
             };
             if (kLead && nwaves > 1) {
                 double *sc = red + par * nwaves * kRedStride;
@@ -1158,7 +1340,7 @@ __device__ __forceinline__ bool icp_pair(const IcpArgs &a, const int b, char *sm
                     if (lane == 0) {
                         double2 *l2 = reinterpret_cast<double2 *>(lead);
                         l2[0] = make_double2(r.c, r.s); l2[1] = make_double2(r.tx, r.ty);
-                        l2[2] = make_double2(cbx, cby); l2[3] = make_double2(mean_error, 0.0);
+                        l2[2] = make_double2(cbx, cby); l2[3] = make_double2(s.mean_error, 0.0);
                     }
                 }
                 __syncthreads();
@@ -1166,24 +1348,14 @@ __device__ __forceinline__ bool icp_pair(const IcpArgs &a, const int b, char *sm
                 const double2 v0 = l2[0], v1 = l2[1], v2 = l2[2], v3 = l2[3];
                 r.c = v0.x; r.s = v0.y; r.tx = v1.x; r.ty = v1.y;
                 cbx = readlane_f64(v2.x, 0); cby = readlane_f64(v2.y, 0);
-                mean_error = readlane_f64(v3.x, 0);
+                s.mean_error = readlane_f64(v3.x, 0);
             } else {
                 finish(block_total<8>(wave_reduce8(u, ls), ls.idx8, red + par * nwaves * kRedStride, nwaves, wave, lane));
             }
         }
-        if (FIRST || !kOnePass) r = kabsch_from_sums_wave(cax, cay, cbx, cby, w[0], w[1], w[2], w[3], lane);    // :69
-#pragma unroll
-        for (int q = 0; q < QPT; ++q) {                              // src = T.src (:71)
-            double nx = r.c * sx[q] + (-r.s) * sy[q] + r.tx;
-            double ny = r.s * sx[q] + r.c * sy[q] + r.ty;
-            sx[q] = nx; sy[q] = ny;
-        }
-        pcx = cbx; pcy = cby;                                        // the centroid the source now has (up to rounding)
-        ++iters;
+        advance(r, cbx, cby, sx, sy, s);
         ISTAMP(FIRST ? 9 : 4);
-        if (fabs(pre_error - mean_error) < a.tol) return true;       // :76-77
-        pre_error = mean_error;
-        return false;
+        return converged(s, a.tol);
     };
     if (a.max_iter > 0 && !iterate(std::true_type{}, 0))
         for (int it = 1; it < a.max_iter; ++it)
@@ -1192,23 +1364,13 @@ __device__ __forceinline__ bool icp_pair(const IcpArgs &a, const int b, char *sm
     // (a pair in which some lane saw a best undercut its predecessor by less than a class of equal distances is
     // re-done: the flag travels through LDS, behind the barriers of the sums below)
     if (!EXACT && amb_mask != 0ull) geo[5] = 1u;
-    // final T = getTransform(A_original, src_final) (icp.py:81).  ONE reduction when an iteration has run: the originals'
-    // centroid c_A is the first iteration's source centroid (the same sums in the same order - the source had not moved yet),
-    // and the last update put the source's centroid on p = (pcx, pcy) up to rounding, so with S = sum (s - p)
-    //   c_S = p + S / N,   W = sum (s - p)(a - c_A)^T   (- S . sum (a - c_A)^T / N: rounding level times rounding level),
-    // of which the rotation needs A = W00 + W11 and B = W10 - W01 (as in the iterations).  Only the pair's first wave goes on
-    // behind the barrier: it alone stores the result.
+    // final T (final_transform).  Only the pair's first wave goes on behind the barrier: it alone stores the result.
     Rigid2 r;
-    if (iters > 0) {
+    if (s.iters > 0) {
         double u[4] = {0, 0, 0, 0};
 #pragma unroll
-        for (int q = 0; q < QPT; ++q) {
-            if (ok[q]) {
-                const double dsx = sx[q] - pcx, dsy = sy[q] - pcy, dax = ax[q] - ca0x, day = ay[q] - ca0y;
-                u[0] += dsx; u[1] += dsy;
-                u[2] += dsx * dax + dsy * day; u[3] += dsy * dax - dsx * day;
-            }
-        }
+        for (int q = 0; q < QPT; ++q)
+            if (ok[q]) add_final(u, sx[q], sy[q], s.pcx, s.pcy, ax[q], ay[q], s.ca0x, s.ca0y);
         par ^= 1;
         const double mine = wave_reduce4(u, ls);
         double tot = mine;
@@ -1220,52 +1382,26 @@ __device__ __forceinline__ bool icp_pair(const IcpArgs &a, const int b, char *sm
             mine_to_finish = __builtin_amdgcn_readfirstlane(wave) == 0;
             if (mine_to_finish) tot = lds_column(sc + ls.idx4, 8, nwaves);
         }
-        if (mine_to_finish) {
-            const double qv = tot / dn;
-            const double csx = pcx + readlane_f64(qv, 0), csy = pcy + readlane_f64(qv, 1);
-            double wa = readlane_f64(tot, 2), wb = readlane_f64(tot, 3);
-            if (src_collapsed) wa = wb = 0.0;
-            r = kabsch_from_sums_wave(ca0x, ca0y, csx, csy, wa, 0.0, wb, 0.0, lane);
-        }
+        if (mine_to_finish) r = final_transform(tot, dn, s, src_collapsed, lane);
     } else {
         // no iteration (max_iter 0): centroids, then centred products, as the reference
         double v[4] = {0, 0, 0, 0};
 #pragma unroll
         for (int q = 0; q < QPT; ++q)
-            if (ok[q]) { v[0] += ax[q]; v[1] += ay[q]; v[2] += sx[q]; v[3] += sy[q]; }
+            if (ok[q]) add_points(v, ax[q], ay[q], sx[q], sy[q]);
         par ^= 1;
-        double cax, cay, cbx, cby;
-        {
-            const double tot = block_total(wave_reduce4(v, ls), ls.idx4, red + par * nwaves * kRedStride, nwaves, wave, lane);
-            const double qv = tot / dn;
-            cax = readlane_f64(qv, 0); cay = readlane_f64(qv, 1); cbx = readlane_f64(qv, 2); cby = readlane_f64(qv, 3);
-        }
+        const Centroids c = centroids_from_totals(block_total(wave_reduce4(v, ls), ls.idx4, red + par * nwaves * kRedStride, nwaves, wave, lane), dn);
         double w[4] = {0, 0, 0, 0};
 #pragma unroll
-        for (int q = 0; q < QPT; ++q) {
-            if (ok[q]) {
-                double aax = ax[q] - cax, aay = ay[q] - cay, bbx = sx[q] - cbx, bby = sy[q] - cby;
-                w[0] += bbx * aax; w[1] += bbx * aay; w[2] += bby * aax; w[3] += bby * aay;
-            }
-        }
+        for (int q = 0; q < QPT; ++q)
+            if (ok[q]) add_centred(w, ax[q], ay[q], c.ax, c.ay, sx[q], sy[q], c.bx, c.by);
         par ^= 1;
-        {
-            const double tot = block_total(wave_reduce4(w, ls), ls.idx4, red + par * nwaves * kRedStride, nwaves, wave, lane);
-            w[0] = readlane_f64(tot, 0); w[1] = readlane_f64(tot, 1); w[2] = readlane_f64(tot, 2); w[3] = readlane_f64(tot, 3);
-        }
-        if (src_collapsed) w[0] = w[1] = w[2] = w[3] = 0.0;
-        r = kabsch_from_sums_wave(cax, cay, cbx, cby, w[0], w[1], w[2], w[3], lane);
+        lanes4(block_total(wave_reduce4(w, ls), ls.idx4, red + par * nwaves * kRedStride, nwaves, wave, lane), w);
+        r = rigid_from_w(c, w[0], w[1], w[2], w[3], src_collapsed, lane);
     }
-    if (tid == 0) {
-        double *To = a.T_out + 9 * (long)b;
-        To[0] = r.c; To[1] = -r.s; To[2] = r.tx;
-        To[3] = r.s; To[4] = r.c;  To[5] = r.ty;
-        To[6] = 0.0; To[7] = 0.0;  To[8] = 1.0;
-        if (a.iters_out) a.iters_out[b] = iters;
-        if (a.err_out) a.err_out[b] = mean_error;
-    }
+    if (tid == 0) store_result(a, b, r, s);
     ISTAMP(5);
-    ISTAMP_END(iters);
+    ISTAMP_END(s.iters);
     lds_guard_check(guard, a.status);
     return !EXACT && (nwaves > 1 ? geo[5] != 0u : amb_mask != 0ull);
 }
@@ -1274,15 +1410,15 @@ __device__ __forceinline__ bool icp_pair(const IcpArgs &a, const int b, char *sm
 // The same solve by ONE wave per pair, six queries a lane (n_src <= 384): the shape of launches that fill the chip many
 // times over, where a launch's duration is the instructions its pairs issue and not a pair's own latency.  Nothing is
 // handed between waves: no barrier, the sums are one transposed wave reduction and lane reads, rotation, translation and
-// convergence test are computed once per pair.  What a lane keeps from one iteration to the next is a query's moving
-// point and its last match (five registers a query): a match's contribution to the sums is added as soon as the match is
-// known (later iterations), or formed from the match's index (first iteration, behind the listed queries' search: the
-// square of the distance is that of the query to the match as the search computed it, the same operations on the same
-// bits); the originals are formed again from the source for the final transform.  LDS holds the unpadded image of the
-// target (NaN points up to a whole block and behind the last beam), the boxes and a list for a quarter of the queries:
-// 8.6 KB for 360 beams, so that registers (128: four waves per SIMD) and not LDS bound the pairs resident on a CU.  The
-// box search (1.3 % of the queries) reads the unpadded image.  Same candidates in the same order under the same rules as
-// icp_pair: matches and iteration counts are those of every other shape, sums are added in another order.
+// convergence test are computed once per pair, the list's count is a register.  What a lane keeps from one iteration to the
+// next is a query's moving point and its last match (five registers a query): a match's contribution to the sums is added
+// as soon as the match is known (later iterations), or formed from the match's index (first iteration, behind the listed
+// queries' search: the square of the distance is that of the query to the match as the search computed it, the same
+// operations on the same bits); the originals are formed again from the source for the final transform.  LDS holds the
+// unpadded image of the target (NaN points up to a whole block and behind the last beam), the boxes and a list for a
+// quarter of the queries: 8.6 KB for 360 beams, so that registers (128: four waves per SIMD) and not LDS bound the pairs
+// resident on a CU.  The box search (1.3 % of the queries) reads the unpadded image.  Sums are added in another order than
+// in the workgroup shape; everything else is the shared pieces above.
 // ---------------------------------------------------------------------------------
 constexpr int kWaveQpt = 6;
 constexpr int kWaveRound = 4 * 1024;          // pairs resident at once in this shape: 4 per SIMD, 1 024 SIMDs
@@ -1310,35 +1446,19 @@ __device__ __forceinline__ bool icp_pair_wave(const IcpArgs &a, const int b, cha
     char *guard = reinterpret_cast<char *>(qseed + a.team_cap);
     lds_guard_fill(guard);
 
-    const long be = (long)b + (a.ppt ? b / a.ppt : 0);
-    Cloud<T> tar{nullptr, nullptr, a.cos_t, a.sin_t, n_tar}, src{nullptr, nullptr, a.cos_t, a.sin_t, n_src};
-    if (a.ranges) {
-        tar.ranges = a.ranges + be * a.tar_scan_stride;
-        src.ranges = a.ranges + be * a.src_scan_stride + n_tar;      // the scan after the target's
-    } else {
-        tar.pts = static_cast<const T *>(a.tar) + be * a.tar_stride;
-        src.pts = static_cast<const T *>(a.src) + be * a.src_stride;
-    }
-    // source point i as the solve starts from it (the prior applied); a lane without one starts from the origin's image
-    auto source = [&](int i, bool have) __attribute__((always_inline)) -> double2 {
-        double2 pt = have ? src.at(i) : make_double2(0.0, 0.0);
-        if (a.prior) {
-            const double *p = a.prior + 6 * (long)b;
-            pt = make_double2(p[0] * pt.x + p[1] * pt.y + p[2], p[3] * pt.x + p[4] * pt.y + p[5]);
-        }
-        return pt;
-    };
+    const PairClouds<T> pc = pair_clouds<T>(a, b);
+    const NNTarget nt{tarP, tarP, boxes, boxes4, nblocks, n_tar, true, qlist, qseed, a.team_cap};
 
     // the source points first: their loads are in flight together with those that stage the target
     double sx[QPT], sy[QPT];
     int seed[QPT];
     bool src_differs = false;
     {
-        const double2 p0 = source(0, true);                          // collapsed sets: see icp_pair
+        const double2 p0 = pc.source(0, true);                       // (collapsed sets: see SameMatch)
 #pragma unroll
         for (int q = 0; q < QPT; ++q) {
             const int i = lane + q * kWave;
-            const double2 pt = source(i, i < n_src);
+            const double2 pt = pc.source(i, i < n_src);
             sx[q] = pt.x; sy[q] = pt.y;
             seed[q] = min(i, n_tar - 1);             // first guess: the same beam index
             src_differs |= i < n_src && !(pt.x == p0.x && pt.y == p0.y);
@@ -1346,26 +1466,17 @@ __device__ __forceinline__ bool icp_pair_wave(const IcpArgs &a, const int b, cha
     }
     {
         const double qnan = __longlong_as_double(0x7ff8000000000000LL);
-        for (int j = lane; j < icp_wave_points(n_tar); j += kWave) tarP[j] = j < n_tar ? tar.at(j) : make_double2(qnan, qnan);
+        for (int j = lane; j < icp_wave_points(n_tar); j += kWave) tarP[j] = j < n_tar ? pc.tar.at(j) : make_double2(qnan, qnan);
     }
-    // the target is a scan with usable beam geometry: nearest neighbours by beam window (nn_polar)
-    PolarGeo pg;
-    {
-        bool polar = false;
-        float dmin = 1.0f;
-        if (a.ranges) {
-            unsigned mn;
-            float sum;
-            bool bad;
-            polar_probe_wave(tar, n_tar, mn, sum, bad);
-            dmin = __uint_as_float((unsigned)__builtin_amdgcn_readfirstlane((int)mn));
-            // (the total rounded up once more, as polar_combine does with the sum of the waves' parts: the same test as icp_pair's)
-            const float span = __uint_as_float((unsigned)__builtin_amdgcn_readfirstlane((int)__float_as_uint(sum * 1.00001f)));
-            polar = !bad && n_tar >= 2 && dmin >= 1e-5f && dmin < 1.0f && span <= 6.2831855f + 0.5f * dmin;   // as icp_pair
-        }
-        pg.inv_db = polar ? __fdividef(1.000002f, dmin) : 0.0f;
-        pg.slack = StoreSlack<T>::ang;
+    PolarProbe pp{1.0f, 0.0f, false};
+    if (a.ranges) {
+        unsigned mn;
+        float sum;
+        bool bad;
+        polar_probe_wave(pc.tar, n_tar, mn, sum, bad);
+        pp = polar_total(mn, sum, !bad);
     }
+    const PolarGeo pg = polar_geo<T>(pp, n_tar);
     const bool src_collapsed = !__any(src_differs);
     wave_sync();
     stage_boxes<kNNBlock, true>(n_tar, tarP, boxes, boxes4);
@@ -1373,90 +1484,24 @@ __device__ __forceinline__ bool icp_pair_wave(const IcpArgs &a, const int b, cha
 
     const double dn = (double)n_src;
     const LaneSel ls = lane_sel(lane);
-    double pre_error = 0.0, mean_error = 0.0, pcx = 0.0, pcy = 0.0, ca0x = 0.0, ca0y = 0.0;   // (ca0: centroid of the source before it moves)
-    int iters = 0;
-    unsigned long long amb_mask = 0ull;   // lanes that saw a best undercut its predecessor by less than a class of equal distances (see icp_pair)
-
-    // nearest target of query q (icp.py:67): its index - or, for a first-iteration query put on the list, -1 - its place there -
-    // and the square of its distance
-    auto nearest = [&](const int q, const bool okq, const bool first, const bool listing, int &nlisted, double &d2, int &j)
-                       __attribute__((always_inline)) {
-        if (EXACT) {
-            const NNHit h = nn_exact(tarP, false, okq ? n_tar : 0, sx[q], sy[q]);
-            d2 = h.d2; j = h.j;
-        } else if (pg.inv_db > 0.0f) {                               // wave-uniform: the target is a scan
-            bool big, amb_lane;
-            unsigned long long am;
-            nn_polar<4, false>(tarP, n_tar, sx[q], sy[q], seed[q], okq, pg, listing ? kPolarMaxFirst : kPolarMax, d2, j, big, amb_lane, am);
-            (void)amb_lane;
-            amb_mask |= am;
-            if (listing) {
-                const unsigned long long bm = __ballot(big);
-                if (bm != 0ull) {
-                    const int pos = nlisted + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bm, 0u));
-                    nlisted += (int)__popcll(bm);
-                    if (big && pos < a.team_cap) {
-                        qlist[pos] = make_double2(sx[q], sy[q]);
-                        qseed[pos] = seed[q];
-                        j = -1 - pos;
-                        big = false;                                 // (a list that is full leaves the rest to the box search)
-                    }
-                }
-            }
-            if (__any(big)) {
-                double d2b; int jb; bool ambb;
-                nn_search<kNNBlock>(tarP, boxes, boxes4, nblocks, n_tar, sx[q], sy[q], seed[q], first, big, d2b, jb, ambb);
-                d2 = big ? d2b : d2;
-                j = big ? jb : j;
-                amb_mask |= __ballot(big && ambb);
-            }
-        } else {
-            bool ambs;
-            nn_search<kNNBlock>(tarP, boxes, boxes4, nblocks, n_tar, sx[q], sy[q], seed[q], first, okq, d2, j, ambs);
-            amb_mask |= __ballot(ambs);
-        }
+    Solve s;
+    unsigned long long amb_mask = 0ull;
+    int nlisted = 0;
+    // where the wave's entries on the list start: the count is a register
+    auto place = [&](const unsigned long long bm) __attribute__((always_inline)) -> int {
+        const int base = nlisted;
+        nlisted += (int)__popcll(bm);
+        return base;
     };
-    // every source point matched to ONE target point (same coordinates)?  As icp_pair: settled on one lane of the first
-    // query where some lane there is matched to another beam whose point differs, else every match is compared.
-    struct Same { double m0x, m0y; bool found, differs; };
-    auto same_step = [&](const int q, const bool okq, const double2 m, Same &s) __attribute__((always_inline)) {
-        if (q == 0) {
-            s.m0x = readlane_f64(m.x, 0); s.m0y = readlane_f64(m.y, 0);
-            s.found = s.differs = false;
-            const int j0 = __builtin_amdgcn_readfirstlane(seed[0]);
-            const unsigned long long other = __ballot(okq && seed[0] != j0);
-            if (other != 0ull) {
-                const int l = __ffsll((long long)other) - 1;
-                const double ox = readlane_f64(m.x, l), oy = readlane_f64(m.y, l);
-                s.found = !(ox == s.m0x && oy == s.m0y);
-            }
-        }
-        if (!s.found) s.differs |= okq && !(m.x == s.m0x && m.y == s.m0y);
-    };
-    // src = T.src (:71), the convergence test (:76-77); (cbx, cby): the centroid the source now has (up to rounding)
-    auto advance = [&](const Rigid2 &r, const double cbx, const double cby) __attribute__((always_inline)) -> bool {
-#pragma unroll
-        for (int q = 0; q < QPT; ++q) {
-            const double nx = r.c * sx[q] + (-r.s) * sy[q] + r.tx;
-            const double ny = r.s * sx[q] + r.c * sy[q] + r.ty;
-            sx[q] = nx; sy[q] = ny;
-        }
-        pcx = cbx; pcy = cby;
-        ++iters;
-        if (fabs(pre_error - mean_error) < a.tol) return true;
-        pre_error = mean_error;
-        return false;
-    };
+    auto no_note = [](bool) {};
     // the first iteration: centroids, then centred products, as the reference (icp.py:154-160); the only one that lists queries
     auto first_iteration = [&]() __attribute__((always_inline)) -> bool {
         const bool listing = !EXACT && a.team_cap > 0 && pg.inv_db > 0.0f;
-        int nlisted = 0;
 #pragma unroll
         for (int q = 0; q < QPT; ++q) {
             if (q * kWave >= n_src) continue;                        // wave-uniform
-            double d2; int j;
-            nearest(q, lane + q * kWave < n_src, true, listing, nlisted, d2, j);
-            seed[q] = j;
+            const NNQuery h = nn_query<4, kNNBlock, EXACT>(nt, pg, sx[q], sy[q], seed[q], lane + q * kWave < n_src, true, listing, place, no_note, amb_mask);
+            seed[q] = h.slot >= 0 ? -1 - h.slot : h.j;               // (a listed query keeps its place on the list here)
         }
         if (listing) {
             wave_sync();
@@ -1465,134 +1510,88 @@ __device__ __forceinline__ bool icp_pair_wave(const IcpArgs &a, const int b, cha
 #pragma unroll
             for (int q = 0; q < QPT; ++q) {
                 if (q * kWave >= n_src) continue;
-                bool flagged = false;
-                if (seed[q] < 0) {
-                    const int jf = __double2loint(qlist[-1 - seed[q]].y);
-                    flagged = jf < 0;
-                    seed[q] = jf & 0x7fffffff;
-                }
-                amb_mask |= __ballot(flagged);
+                double d2 = 0.0;                                     // (formed again below from query and match)
+                listed_result(qlist, -1 - seed[q], d2, seed[q], amb_mask);
             }
         }
         double v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        Same same{0.0, 0.0, false, false};
+        SameMatch same{0.0, 0.0, false, false};
 #pragma unroll
         for (int q = 0; q < QPT; ++q) {
             if (q * kWave >= n_src) continue;
             const bool okq = lane + q * kWave < n_src;
             const double2 m = tarP[seed[q]];
-            const double d2 = dist2(sx[q], sy[q], m.x, m.y);         // what the search found for this match
-            const double dq = (d2 < INFINITY) ? sqrt(d2) : 0.0;      // never-won query: distance 0 (:97)
-            same_step(q, okq, m, same);
-            if (okq) { v[0] += sx[q]; v[1] += sy[q]; v[2] += m.x; v[3] += m.y; v[4] += dq; }
+            const double dq = match_distance(dist2(sx[q], sy[q], m.x, m.y));   // what the search found for this match
+            same.step(q, okq, seed[q], m.x, m.y);
+            if (okq) { add_points(v, sx[q], sy[q], m.x, m.y); v[4] += dq; }
         }
-        const double qv = wave_reduce8(v, ls) / dn;                  // icp.py:154-155, :75
-        const double cax = readlane_f64(qv, 0), cay = readlane_f64(qv, 1), cbx = readlane_f64(qv, 2), cby = readlane_f64(qv, 3);
-        mean_error = readlane_f64(qv, 7);                            // value 4 lives in lane 7
-        const bool tar_collapsed = !(same.found || __any(same.differs));
+        const Centroids c = centroids_from_totals(wave_reduce8(v, ls), dn, &s.mean_error);
+        const bool tar_collapsed = !same.wave_differs();
         double w[4] = {0, 0, 0, 0};
 #pragma unroll
         for (int q = 0; q < QPT; ++q) {
             if (q * kWave >= n_src) continue;
             if (lane + q * kWave < n_src) {
                 const double2 m = tarP[seed[q]];
-                const double aax = sx[q] - cax, aay = sy[q] - cay, bbx = m.x - cbx, bby = m.y - cby;
-                w[0] += bbx * aax; w[1] += bbx * aay; w[2] += bby * aax; w[3] += bby * aay;   // :160
+                add_centred(w, sx[q], sy[q], c.ax, c.ay, m.x, m.y, c.bx, c.by);
             }
         }
-        const double tot = wave_reduce4(w, ls);
-        w[0] = readlane_f64(tot, 0); w[1] = readlane_f64(tot, 1); w[2] = readlane_f64(tot, 2); w[3] = readlane_f64(tot, 3);
-        if (tar_collapsed || src_collapsed) w[0] = w[1] = w[2] = w[3] = 0.0;
-        ca0x = cax; ca0y = cay;
-        return advance(kabsch_from_sums_wave(cax, cay, cbx, cby, w[0], w[1], w[2], w[3], lane), cbx, cby);    // :69
+        lanes4(wave_reduce4(w, ls), w);
+        s.ca0x = c.ax; s.ca0y = c.ay;
+        advance(rigid_from_w(c, w[0], w[1], w[2], w[3], tar_collapsed || src_collapsed, lane), c.bx, c.by, sx, sy, s);
+        return converged(s, a.tol);
     };
-    // a later iteration: sums and products about the previous matches' centroid in one reduction (see icp_pair)
+    // a later iteration: sums and products about the previous matches' centroid in one reduction (add_one_pass)
     auto iteration = [&]() __attribute__((always_inline)) -> bool {
         double u[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        Same same{0.0, 0.0, false, false};
-        int none = 0;
+        SameMatch same{0.0, 0.0, false, false};
 #pragma unroll
         for (int q = 0; q < QPT; ++q) {
             if (q * kWave >= n_src) continue;                        // wave-uniform
             const bool okq = lane + q * kWave < n_src;
-            double d2; int j;
-            nearest(q, okq, false, false, none, d2, j);
-            seed[q] = j;                                             // next iteration's guess
-            const double2 m = tarP[j];
-            const double dq = (d2 < INFINITY) ? sqrt(d2) : 0.0;
-            same_step(q, okq, m, same);
-            if (okq) {
-                const double dax = sx[q] - pcx, day = sy[q] - pcy, dbx = m.x - pcx, dby = m.y - pcy;
-                u[0] += dax; u[1] += day; u[2] += dbx; u[3] += dby; u[4] += dq;
-                u[5] = fma(dbx, dax, fma(dby, day, u[5])); u[6] = fma(dby, dax, fma(-dbx, day, u[6]));
-            }
+            const NNQuery h = nn_query<4, kNNBlock, EXACT>(nt, pg, sx[q], sy[q], seed[q], okq, false, false, place, no_note, amb_mask);
+            seed[q] = h.j;                                           // next iteration's guess
+            const double2 m = tarP[h.j];
+            same.step(q, okq, h.j, m.x, m.y);
+            if (okq) add_one_pass(u, sx[q], sy[q], m.x, m.y, match_distance(h.d2), s.pcx, s.pcy);
         }
-        const double tot = wave_reduce8(u, ls);
-        const double qv = tot / dn;                                  // icp.py:154-155, :75
-        const double qax = readlane_f64(qv, 0), qay = readlane_f64(qv, 1);
-        const double cax = pcx + qax, cay = pcy + qay;
-        const double cbx = pcx + readlane_f64(qv, 2), cby = pcy + readlane_f64(qv, 3);
-        mean_error = readlane_f64(qv, 7);                            // value 4 lives in lane 7, values 5, 6 in lanes 6, 5
-        const double sbx = readlane_f64(tot, 2), sby = readlane_f64(tot, 3);
-        double wa = readlane_f64(tot, 6) - (sbx * qax + sby * qay);  // A
-        double wb = readlane_f64(tot, 5) - (sby * qax - sbx * qay);  // B
-        if (!(same.found || __any(same.differs)) || src_collapsed) wa = wb = 0.0;
-        return advance(kabsch_from_sums_wave(cax, cay, cbx, cby, wa, 0.0, wb, 0.0, lane), cbx, cby);          // :69
+        const OnePass o = one_pass_totals(wave_reduce8(u, ls), dn, s);
+        advance(rigid_from_w(o.c, o.A, 0.0, o.B, 0.0, !same.wave_differs() || src_collapsed, lane), o.c.bx, o.c.by, sx, sy, s);
+        return converged(s, a.tol);
     };
     if (a.max_iter > 0 && !first_iteration())
         for (int it = 1; it < a.max_iter; ++it)
             if (iteration()) break;
 
-    // final T = getTransform(A_original, src_final) (icp.py:81), as icp_pair; the originals are formed again from the source
+    // final T (final_transform); the originals are formed again from the source
     Rigid2 r;
-    if (iters > 0) {
+    if (s.iters > 0) {
         double u[4] = {0, 0, 0, 0};
 #pragma unroll
         for (int q = 0; q < QPT; ++q) {
             if (q * kWave >= n_src) continue;
             const int i = lane + q * kWave;
             if (i < n_src) {
-                const double2 o = source(i, true);
-                const double dsx = sx[q] - pcx, dsy = sy[q] - pcy, dax = o.x - ca0x, day = o.y - ca0y;
-                u[0] += dsx; u[1] += dsy;
-                u[2] += dsx * dax + dsy * day; u[3] += dsy * dax - dsx * day;
+                const double2 o = pc.source(i, true);
+                add_final(u, sx[q], sy[q], s.pcx, s.pcy, o.x, o.y, s.ca0x, s.ca0y);
             }
         }
-        const double tot = wave_reduce4(u, ls);
-        const double qv = tot / dn;
-        const double csx = pcx + readlane_f64(qv, 0), csy = pcy + readlane_f64(qv, 1);
-        double wa = readlane_f64(tot, 2), wb = readlane_f64(tot, 3);
-        if (src_collapsed) wa = wb = 0.0;
-        r = kabsch_from_sums_wave(ca0x, ca0y, csx, csy, wa, 0.0, wb, 0.0, lane);
+        r = final_transform(wave_reduce4(u, ls), dn, s, src_collapsed, lane);
     } else {
         // no iteration (max_iter 0): the source has not moved, both sets are the originals; centroids, then centred products
         double v[4] = {0, 0, 0, 0};
 #pragma unroll
         for (int q = 0; q < QPT; ++q)
-            if (lane + q * kWave < n_src) { v[0] += sx[q]; v[1] += sy[q]; v[2] += sx[q]; v[3] += sy[q]; }
-        const double qv = wave_reduce4(v, ls) / dn;
-        const double cax = readlane_f64(qv, 0), cay = readlane_f64(qv, 1), cbx = readlane_f64(qv, 2), cby = readlane_f64(qv, 3);
+            if (lane + q * kWave < n_src) add_points(v, sx[q], sy[q], sx[q], sy[q]);
+        const Centroids c = centroids_from_totals(wave_reduce4(v, ls), dn);
         double w[4] = {0, 0, 0, 0};
 #pragma unroll
-        for (int q = 0; q < QPT; ++q) {
-            if (lane + q * kWave < n_src) {
-                const double aax = sx[q] - cax, aay = sy[q] - cay, bbx = sx[q] - cbx, bby = sy[q] - cby;
-                w[0] += bbx * aax; w[1] += bbx * aay; w[2] += bby * aax; w[3] += bby * aay;
-            }
-        }
-        const double tot = wave_reduce4(w, ls);
-        w[0] = readlane_f64(tot, 0); w[1] = readlane_f64(tot, 1); w[2] = readlane_f64(tot, 2); w[3] = readlane_f64(tot, 3);
-        if (src_collapsed) w[0] = w[1] = w[2] = w[3] = 0.0;
-        r = kabsch_from_sums_wave(cax, cay, cbx, cby, w[0], w[1], w[2], w[3], lane);
+        for (int q = 0; q < QPT; ++q)
+            if (lane + q * kWave < n_src) add_centred(w, sx[q], sy[q], c.ax, c.ay, sx[q], sy[q], c.bx, c.by);
+        lanes4(wave_reduce4(w, ls), w);
+        r = rigid_from_w(c, w[0], w[1], w[2], w[3], src_collapsed, lane);
     }
-    if (lane == 0) {
-        double *To = a.T_out + 9 * (long)b;
-        To[0] = r.c; To[1] = -r.s; To[2] = r.tx;
-        To[3] = r.s; To[4] = r.c;  To[5] = r.ty;
-        To[6] = 0.0; To[7] = 0.0;  To[8] = 1.0;
-        if (a.iters_out) a.iters_out[b] = iters;
-        if (a.err_out) a.err_out[b] = mean_error;
-    }
+    if (lane == 0) store_result(a, b, r, s);
     lds_guard_check(guard, a.status);
     return !EXACT && amb_mask != 0ull;
 }
@@ -1818,11 +1817,7 @@ __global__ void __launch_bounds__(256) k_kabsch(const double *src, const double 
     block_sum<4>(w, red + 4 * kMaxWaves, nwaves, wave, lane);
     if (same[0] || same[1]) w[0] = w[1] = w[2] = w[3] = 0.0;          // collapsed set: canonical R = I (barriers of block_sum passed)
     if (tid == 0) {
-        Rigid2 r = kabsch_from_sums(cax, cay, cbx, cby, w[0], w[1], w[2], w[3]);
-        double *To = T_out + 9 * (long)b;
-        To[0] = r.c; To[1] = -r.s; To[2] = r.tx;
-        To[3] = r.s; To[4] = r.c;  To[5] = r.ty;
-        To[6] = 0.0; To[7] = 0.0;  To[8] = 1.0;
+        store_transform(T_out + 9 * (long)b, kabsch_from_sums(cax, cay, cbx, cby, w[0], w[1], w[2], w[3]));
     }
 }
 
