@@ -377,7 +377,7 @@ def test_particle_priors_vs_oracle(slam, syn):
 
 def test_pose_compose_vs_oracle(slam):
     rng = np.random.default_rng(3)
-    L, n = 3, 2500     # longer than one 1024-step chunk
+    L, n = 3, 2500     # 40 of the pipeline's 64-step chunks, the last one of 4 steps (chunk edges: test_gpu_operator_bounds.py)
     th = rng.uniform(-0.1, 0.1, size=(L, n))
     T = np.zeros((L, n, 9))
     T[..., 0], T[..., 1], T[..., 2] = np.cos(th), -np.sin(th), rng.normal(0, 0.05, (L, n))
