@@ -97,7 +97,17 @@ _SIGS = {
     "slam_astar_dev": ([_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp], _i),
     "slam_astar_inflate": ([_vp, _vp, _i, _i, _i, _i, _i, _i, _vp], _i),
     "slam_astar_inflate_dev": ([_vp, _vp, _i, _i, _i, _i, _i, _i, _vp], _i),
+    "slam_landmarks": ([_vp, _vp, _vp, _vp, _i, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp], _i),
+    "slam_landmarks_dev": ([_vp, _vp, _vp, _vp, _i, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp], _i),
+    "slam_ekf_lm": ([_vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
+    "slam_ekf_lm_dev": ([_vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
+    "slam_node_replay": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _d, _d, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                          _vp, _vp, _vp, _vp, _vp], _i),
+    "slam_node_replay_dev": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _d, _d, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                              _vp, _vp, _vp, _vp, _vp], _i),
 }
+NODE_OK, NODE_REF_RAISES, NODE_LM_CAP, NODE_OBS_CAP = 0, 1, 2, 3
+EKF_MAX_LM = 32
 
 
 def header_symbols(path=HEADER_PATH):

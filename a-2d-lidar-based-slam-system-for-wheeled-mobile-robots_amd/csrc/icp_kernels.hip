@@ -1657,8 +1657,11 @@ static hipError_t launch_icp_t(const IcpArgs &a_in, hipStream_t s)
     // batch would have at two queries per lane: from 7 500 on - 2 500 pairs of 360 beams, 834 pairs of 1 080 (999 such pairs
     // alone: 0.338 ms with three queries per lane against 0.364 with two) - the chip holds them in more than one round.
     const long waves_at_two = (long)a.B * ((a.n_src + 127) / 128);
-    int pref = a.qpt_pref > 0 ? a.qpt_pref : (waves_at_two >= 7500 ? 3 : 2);
-    if (a.B > 64 && qpt < pref && a.n_src > 64 * pref) qpt = pref;
+    // a.batch_invariant (slam_node_replay_dev): the shape must not follow the batch size, so that a trajectory's transforms
+    // are the same bits whether it runs alone or among thousands - two queries per lane for every B, never the automatic
+    // one-wave shape; an explicit "icp_qpt" / "icp_one_wave" = 1 still holds, for every B alike.
+    int pref = a.qpt_pref > 0 ? a.qpt_pref : (a.batch_invariant ? 2 : waves_at_two >= 7500 ? 3 : 2);
+    if ((a.B > 64 || a.batch_invariant) && qpt < pref && a.n_src > 64 * pref) qpt = pref;
     if (qpt > 4) qpt = 8;                     // the shapes that exist: 1, 2, 3, 4, 8 queries per lane
     // One wave per pair with six queries per lane (k_icp<T>): no barriers, the per-iteration fixed work paid once per
     // pair.  For launches that fill the chip several times over on their own, where instructions are time: the preference
@@ -1675,7 +1678,7 @@ static hipError_t launch_icp_t(const IcpArgs &a_in, hipStream_t s)
         const int cap = (a.ranges && a.team_mode == 0) ? ((a.n_src + 3) / 4 + 15) / 16 * 16 : 0;   // the list: a quarter of the queries (a fifth is listed on the benchmark scans)
         const size_t lds = icp_wave_lds_bytes(a.n_tar, cap) + kLdsGuard;
         const bool fits = a.n_src <= kWave * kWaveQpt && lds <= 64 * 1024;
-        const bool full = pref == 3 && a.B >= 4 * kWaveRound && a.n_src > kWave * 3 && a.ranges && lds <= 10 * 1024;
+        const bool full = !a.batch_invariant && pref == 3 && a.B >= 4 * kWaveRound && a.n_src > kWave * 3 && a.ranges && lds <= 10 * 1024;
         if (fits && (a.one_wave == 1 || (a.one_wave < 0 && full))) {
             a.team_cap = cap;
             SLAM_LAUNCH((k_icp<T>), dim3(a.B), dim3(kWave), lds, s, a);

@@ -355,7 +355,7 @@ private:
         void *dst;                            // host destination of an output (null: nothing to copy back)
         size_t off, bytes;
     };
-    static constexpr int kMaxPieces = 12;
+    static constexpr int kMaxPieces = 16;
 
     template <typename T> static void set_ptr(void *dev, char *p) { *static_cast<T **>(dev) = reinterpret_cast<T *>(p); }
     template <typename T> Staging &add(T *&dev, size_t n, const void *src, void *dst, bool absent)
@@ -1927,6 +1927,189 @@ int slam_astar_inflate(slam_ctx *c, const int8_t *maps, int G, int H, int W, int
     s.in(d_m, maps, maps_n).out_always(d_o, inflated_out, maps_n);
     TRY(s.upload());
     TRY(slam_astar_inflate_dev(c, d_m, G, H, W, wire_layout, span, r, d_o));
+    TRY(s.download());
+    return check_status_sync(c);
+}
+
+/* ---- landmark EKF-SLAM node ----------------------------------------------------------------- */
+
+static int check_landmarks(const char *fn, const float *ranges, const double *cos_t, const double *sin_t, int S, int n,
+                           int lm_cap, const int32_t *count_out, const int32_t *overflow_out, const int32_t *ids_out,
+                           const double *means_out, const double *z_out)
+{
+    REQUIRE_IN(fn, ranges && cos_t && sin_t && count_out && overflow_out && ids_out && means_out && z_out, "null pointer");
+    REQUIRE_IN(fn, S > 0 && n > 0 && n <= kLandmarkMaxBeams, "need S > 0 and 1 <= n <= 4096");
+    REQUIRE_IN(fn, lm_cap >= 1 && lm_cap <= 1024, "need 1 <= lm_cap <= 1024");
+    return SLAM_OK;
+}
+
+int slam_landmarks_dev(slam_ctx *c, const float *ranges, const double *cos_t, const double *sin_t, int S, int n,
+                       double range_threshold, double radius_max_th, int lm_cap, int32_t *count_out, int32_t *overflow_out,
+                       int32_t *ids_out, double *means_out, double *z_out, int32_t *labels_out)
+{
+    TRY(use(c));
+    TRY(check_landmarks(__func__, ranges, cos_t, sin_t, S, n, lm_cap, count_out, overflow_out, ids_out, means_out, z_out));
+    LandmarkArgs a{ranges, cos_t, sin_t, S, n, range_threshold, radius_max_th, lm_cap, count_out, overflow_out, ids_out,
+                   means_out, z_out, labels_out, c->status};
+    HIPCHK(launch_landmarks(a, c->stream));
+    return SLAM_OK;
+}
+
+int slam_landmarks(slam_ctx *c, const float *ranges, const double *cos_t, const double *sin_t, int S, int n,
+                   double range_threshold, double radius_max_th, int lm_cap, int32_t *count_out, int32_t *overflow_out,
+                   int32_t *ids_out, double *means_out, double *z_out, int32_t *labels_out)
+{
+    TRY(use(c));
+    TRY(check_landmarks(__func__, ranges, cos_t, sin_t, S, n, lm_cap, count_out, overflow_out, ids_out, means_out, z_out));
+    const size_t Sz = (size_t)S, slots = Sz * lm_cap;
+    float *d_r; double *d_c, *d_s, *d_m, *d_z; int32_t *d_cnt, *d_of, *d_id, *d_lab;
+    Staging s(c);
+    s.in(d_r, ranges, Sz * n).in(d_c, cos_t, n).in(d_s, sin_t, n);
+    s.out_always(d_cnt, count_out, Sz).out_always(d_of, overflow_out, Sz).out_always(d_id, ids_out, slots)
+        .out_always(d_m, means_out, slots * 2).out_always(d_z, z_out, slots * 2).out(d_lab, labels_out, Sz * (n - 1));
+    TRY(s.upload());
+    TRY(slam_landmarks_dev(c, d_r, d_c, d_s, S, n, range_threshold, radius_max_th, lm_cap, d_cnt, d_of, d_id, d_m, d_z, d_lab));
+    TRY(s.download());
+    return check_status_sync(c);
+}
+
+static int check_ekf_lm(const char *fn, const double *u, const int32_t *step_counts, const int64_t *z_off, const double *z,
+                        int64_t nz, int B, int steps, int max_lm, const double *x_out, const double *P_out,
+                        const int32_t *nlm_out, const int32_t *status_out)
+{
+    REQUIRE_IN(fn, u && step_counts && z_off && x_out && P_out && nlm_out && status_out, "null pointer");
+    REQUIRE_IN(fn, nz >= 0 && (z || nz == 0), "z is null");
+    REQUIRE_IN(fn, B > 0 && steps > 0 && (long)B * steps < (1L << 31), "need B > 0, steps > 0, B * steps < 2^31");
+    REQUIRE_IN(fn, max_lm >= 0 && max_lm <= kEkfMaxLm, "need 0 <= max_lm <= 32");
+    return SLAM_OK;
+}
+
+int slam_ekf_lm_dev(slam_ctx *c, const double *x0, const double *u, const int32_t *step_counts, const int64_t *z_off,
+                    const double *z, int64_t nz, int B, int steps, int max_lm, double *x_out, double *P_out,
+                    int32_t *nlm_out, int32_t *status_out)
+{
+    TRY(use(c));
+    TRY(check_ekf_lm(__func__, u, step_counts, z_off, z, nz, B, steps, max_lm, x_out, P_out, nlm_out, status_out));
+    EkfArgs a{};
+    a.B = B; a.steps_max = steps; a.max_lm = max_lm;
+    a.x0 = x0; a.steps = step_counts; a.u = u; a.z = z; a.z_off = z_off; a.nz = nz;
+    a.x_out = x_out; a.P_out = P_out; a.nlm_hist = nlm_out; a.status_out = status_out; a.status = c->status;
+    HIPCHK(launch_ekf_lm(a, c->stream));
+    return SLAM_OK;
+}
+
+int slam_ekf_lm(slam_ctx *c, const double *x0, const double *u, const int32_t *step_counts, const int64_t *z_off,
+                const double *z, int64_t nz, int B, int steps, int max_lm, double *x_out, double *P_out, int32_t *nlm_out,
+                int32_t *status_out)
+{
+    TRY(use(c));
+    TRY(check_ekf_lm(__func__, u, step_counts, z_off, z, nz, B, steps, max_lm, x_out, P_out, nlm_out, status_out));
+    const size_t Bz = (size_t)B, N = 3 + 2 * (size_t)max_lm, rows = Bz * steps;
+    for (size_t k = 0; k <= rows; ++k)
+        REQUIRE(z_off[k] >= (k ? z_off[k - 1] : 0) && z_off[k] <= nz, "z_off must ascend within [0, nz]");
+    double *d_x0, *d_u, *d_z, *d_x, *d_P; int32_t *d_sc, *d_nlm, *d_st; int64_t *d_off;
+    Staging s(c);
+    s.in(d_x0, x0, Bz * 3).in(d_u, u, rows * 3).in(d_sc, step_counts, Bz).in(d_off, z_off, rows + 1).in(d_z, z, (size_t)nz * 2);
+    s.out_always(d_x, x_out, Bz * N).out_always(d_P, P_out, Bz * N * N).out_always(d_nlm, nlm_out, rows).out_always(d_st, status_out, Bz);
+    TRY(s.upload());
+    TRY(slam_ekf_lm_dev(c, d_x0, d_u, d_sc, d_off, d_z, nz, B, steps, max_lm, d_x, d_P, d_nlm, d_st));
+    TRY(s.download());
+    return check_status_sync(c);
+}
+
+static int check_node_replay(const char *fn, const float *ranges, const double *cos_t, const double *sin_t, int L, int n_scan,
+                             int n, int dtype, int max_iter, int lm_cap, int max_lm, const double *pose0,
+                             const int32_t *kept_out, const int32_t *kept_count_out, const double *xest_out,
+                             const int32_t *nlm_out, const double *x_final_out, const double *P_final_out,
+                             const int32_t *status_out)
+{
+    REQUIRE_IN(fn, ranges && cos_t && sin_t && pose0 && kept_out && kept_count_out && xest_out && nlm_out && x_final_out &&
+                       P_final_out && status_out, "null pointer");
+    REQUIRE_IN(fn, L > 0 && L <= 65535 && n_scan >= 2 && n > 0 && n <= kLandmarkMaxBeams, "need 0 < L <= 65535, n_scan >= 2, 1 <= n <= 4096");
+    REQUIRE_IN(fn, (long)L * n_scan < (1L << 31), "too many scans for one call");
+    REQUIRE_IN(fn, max_iter >= 0, "max_iter must be >= 0");
+    REQUIRE_IN(fn, dtype_size(dtype), "unknown dtype");
+    REQUIRE_IN(fn, lm_cap >= 1 && lm_cap <= 1024, "need 1 <= lm_cap <= 1024");
+    REQUIRE_IN(fn, max_lm >= 0 && max_lm <= kEkfMaxLm, "need 0 <= max_lm <= 32");
+    return SLAM_OK;
+}
+
+int slam_node_replay_dev(slam_ctx *c, const float *ranges, const double *cos_t, const double *sin_t, int L, int n_scan, int n,
+                         int dtype, int max_iter, double tol, double range_threshold, double radius_max_th, int lm_cap,
+                         int max_lm, const double *pose0, slam_grid *grid, const int32_t *grid_of_traj, int32_t *kept_out,
+                         int32_t *kept_count_out, double *xest_out, int32_t *nlm_out, double *x_final_out, double *P_final_out,
+                         double *T_out, int32_t *iters_out, int32_t *status_out)
+{
+    TRY(use(c));
+    TRY(check_node_replay(__func__, ranges, cos_t, sin_t, L, n_scan, n, dtype, max_iter, lm_cap, max_lm, pose0, kept_out,
+                          kept_count_out, xest_out, nlm_out, x_final_out, P_final_out, status_out));
+    const size_t S = (size_t)L * n_scan, pairs = (size_t)L * (n_scan - 1), slots = S * lm_cap;
+    TRY(arena_reserve(c, c->scratch, align_up(S * 4) * 2 + align_up(slots * 4) + 2 * align_up(slots * 16) + align_up(S * n * 4) +
+                                         align_up(pairs * 24) + align_up(pairs * 72) + 4096));
+    int32_t *cnt = carve<int32_t>(c->scratch, S), *ovf = carve<int32_t>(c->scratch, S), *ids = carve<int32_t>(c->scratch, slots);
+    double *means = carve<double>(c->scratch, slots * 2), *z = carve<double>(c->scratch, slots * 2);
+    float *kr = carve<float>(c->scratch, S * n);
+    double *cast_poses = carve<double>(c->scratch, pairs * 3);
+    double *T = T_out ? T_out : carve<double>(c->scratch, pairs * 9);
+    REQUIRE(cnt && ovf && ids && means && z && kr && cast_poses && T, "internal: workspace");
+    {   // 1. extraction of every scan (:79); 2. the kept scans of every trajectory (:74-82), moved to the front
+        LandmarkArgs a{ranges, cos_t, sin_t, (long)S, n, range_threshold, radius_max_th, lm_cap, cnt, ovf, ids, means, z, nullptr, c->status};
+        HIPCHK(launch_landmarks(a, c->stream));
+        HIPCHK(launch_node_keep(cnt, L, n_scan, kept_out, kept_count_out, c->stream));
+        HIPCHK(launch_node_gather(ranges, kept_out, kept_count_out, L, n_scan, n, kr, c->stream));
+    }
+    {   // 3. the scan matcher on (previous kept, current kept) (:109-113)
+        IcpArgs a;
+        a.tar = a.src = nullptr; a.prior = nullptr;
+        a.ranges = kr; a.cos_t = cos_t; a.sin_t = sin_t;
+        a.tar_scan_stride = a.src_scan_stride = n;
+        a.tar_stride = a.src_stride = 0;
+        a.ppt = n_scan - 1;
+        a.B = (int)pairs; a.n_tar = n; a.n_src = n; a.max_iter = max_iter; a.tol = tol;
+        a.T_out = T; a.iters_out = iters_out; a.err_out = nullptr;
+        a.status = c->status; a.qpt_pref = c->icp_qpt; a.team_mode = c->icp_team; a.one_wave = c->icp_one_wave;
+        a.batch_invariant = 1;      // a trajectory's result does not depend on how many run beside it
+        Timed t(c, SLAM_K_ICP);
+        HIPCHK(launch_icp(a, dtype, c->stream));
+    }
+    {   // 4. T2u and 5. the filter (:85-86, :125-128)
+        EkfArgs a{};
+        a.B = L; a.steps_max = n_scan - 1; a.max_lm = max_lm;
+        a.x0 = pose0; a.steps = kept_count_out; a.steps_bias = 1; a.T = T; a.z = z;
+        a.kept = kept_out; a.lm_count = cnt; a.lm_overflow = ovf; a.lm_cap = lm_cap;
+        a.x_out = x_final_out; a.P_out = P_final_out; a.nlm_hist = nlm_out; a.status_out = status_out;
+        a.x_hist = xest_out; a.cast_poses = grid ? cast_poses : nullptr; a.status = c->status;
+        HIPCHK(launch_ekf_lm(a, c->stream));
+    }
+    if (grid) {   // 6. every kept scan cast from its xEst (:88-90)
+        TRY(grid_on_main(c));
+        Timed t(c, SLAM_K_GRID);
+        TRY(cast_replay(c, grid, kr, cos_t, sin_t, cast_poses, nullptr, L, n_scan, n, grid_of_traj, c->stream));
+    }
+    return SLAM_OK;
+}
+
+int slam_node_replay(slam_ctx *c, const float *ranges, const double *cos_t, const double *sin_t, int L, int n_scan, int n,
+                     int dtype, int max_iter, double tol, double range_threshold, double radius_max_th, int lm_cap, int max_lm,
+                     const double *pose0, slam_grid *grid, const int32_t *grid_of_traj, int32_t *kept_out,
+                     int32_t *kept_count_out, double *xest_out, int32_t *nlm_out, double *x_final_out, double *P_final_out,
+                     double *T_out, int32_t *iters_out, int32_t *status_out)
+{
+    TRY(use(c));
+    TRY(check_node_replay(__func__, ranges, cos_t, sin_t, L, n_scan, n, dtype, max_iter, lm_cap, max_lm, pose0, kept_out,
+                          kept_count_out, xest_out, nlm_out, x_final_out, P_final_out, status_out));
+    if (grid && grid_of_traj)
+        for (int l = 0; l < L; ++l) REQUIRE(grid_of_traj[l] >= 0 && grid_of_traj[l] < grid->d.G, "grid_of_traj out of range");
+    const size_t Lz = (size_t)L, S = Lz * n_scan, pairs = Lz * (n_scan - 1), N = 3 + 2 * (size_t)max_lm;
+    float *d_r; double *d_c, *d_s, *d_0, *d_xe, *d_xf, *d_Pf, *d_T; int32_t *d_g, *d_k, *d_kc, *d_nlm, *d_it, *d_st;
+    Staging s(c);
+    s.in(d_r, ranges, S * n).in(d_c, cos_t, n).in(d_s, sin_t, n).in(d_0, pose0, Lz * 3).in(d_g, grid ? grid_of_traj : nullptr, Lz);
+    s.out_always(d_k, kept_out, S).out_always(d_kc, kept_count_out, Lz).out_always(d_xe, xest_out, pairs * 3)
+        .out_always(d_nlm, nlm_out, pairs).out_always(d_xf, x_final_out, Lz * N).out_always(d_Pf, P_final_out, Lz * N * N)
+        .out_always(d_T, T_out, pairs * 9).out(d_it, iters_out, pairs).out_always(d_st, status_out, Lz);
+    TRY(s.upload());
+    TRY(slam_node_replay_dev(c, d_r, d_c, d_s, L, n_scan, n, dtype, max_iter, tol, range_threshold, radius_max_th, lm_cap, max_lm,
+                             d_0, grid, d_g, d_k, d_kc, d_xe, d_nlm, d_xf, d_Pf, d_T, d_it, d_st));
     TRY(s.download());
     return check_status_sync(c);
 }

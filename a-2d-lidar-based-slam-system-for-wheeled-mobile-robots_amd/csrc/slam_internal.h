@@ -100,6 +100,7 @@ struct IcpArgs {
     int team_cap = 0;          // set by launch_icp: room in the LDS list of first-iteration queries without a beam window (nn_listed), 0: none
     int team_mode = 0;         // context option "icp_team": 0 = on where it applies, 1 = off (the box search takes every such query)
     int one_wave = -1;         // context option "icp_one_wave": -1 = one wave per pair where a full-chip launch allows it, 0 = never, 1 = wherever a pair fits
+    int batch_invariant = 0;   // 1: launch_icp picks a shape that does not depend on B (the node replay: results independent of the batch)
 };
 
 hipError_t launch_icp(const IcpArgs &a, int dtype, hipStream_t s);
@@ -248,5 +249,52 @@ struct AstarArgs {
 hipError_t launch_astar_inflate(const int8_t *maps, int G, int H, int W, int wire, int span, int r,
                                 unsigned long long *dil, int8_t *out, int *status, hipStream_t s);
 hipError_t launch_astar(const AstarArgs &a, hipStream_t s);
+
+// ---- landmark extraction, landmark EKF and the node's kept scans (landmark_kernels.hip) ------
+constexpr int kLandmarkMaxBeams = 4096;      // a scan's points and its four index arrays fit LDS (32 B per beam)
+constexpr int kEkfMaxLm = 32;                // 67 x 67 covariance and its per-step copy: 75 KiB of LDS
+constexpr long kLandmarkMaxGroups = 1L << 20;   // workgroups per launch; more scans / trajectories are taken grid-stride
+struct LandmarkArgs {
+    const float *ranges;                     // [S][n]
+    const double *cos_t, *sin_t;             // [n]
+    long S;
+    int n;
+    double range_threshold, radius_max_th;
+    int lm_cap;
+    int32_t *count, *overflow, *ids;         // [S], [S], [S][lm_cap]
+    double *means, *z;                       // [S][lm_cap][2] each
+    int32_t *labels;                         // nullable [S][n-1]
+    int *status;
+};
+struct EkfArgs {
+    long B;
+    int steps_max, max_lm;
+    const double *x0;                        // nullable [B][3]
+    const int32_t *steps;                    // [B]; the trajectory runs steps[b] - steps_bias steps, clamped to [0, steps_max]
+    int steps_bias;
+    const double *u;                         // [B][steps_max][3], or null: taken from T [B][steps_max][9] (T2u)
+    const double *T;
+    const double *z;                         // observation rows (range, bearing)
+    // rows of step (b, s): z_off[b * steps_max + s] .. z_off[.. + 1], clamped to [0, nz] ...
+    const int64_t *z_off;
+    long nz;
+    // ... or (kept != null) the lm_count[scan] rows from scan * lm_cap on, scan = b * (steps_max + 1) + kept[b][s + 1]
+    const int32_t *kept, *lm_count, *lm_overflow;
+    int lm_cap;
+    double *x_out, *P_out;                   // [B][N], [B][N][N], N = 3 + 2 max_lm, zero beyond the state
+    int32_t *nlm_hist;                       // [B][steps_max], -1 for steps that did not happen
+    int32_t *status_out;                     // [B] SLAM_NODE_*
+    int32_t *nlm_out;                        // nullable [B]
+    double *x_hist;                          // nullable [B][steps_max][3], NaN for steps that did not happen
+    double *cast_poses;                      // nullable [B][steps_max][3], (inf, 0, 0) for steps that did not happen
+    int *status;
+};
+size_t landmark_lds_bytes(int n);
+size_t ekf_lds_bytes(int max_lm);
+hipError_t launch_landmarks(const LandmarkArgs &a, hipStream_t s);
+hipError_t launch_ekf_lm(const EkfArgs &a, hipStream_t s);
+hipError_t launch_node_keep(const int32_t *lm_count, int L, int n_scan, int32_t *kept, int32_t *kept_count, hipStream_t s);
+hipError_t launch_node_gather(const float *ranges, const int32_t *kept, const int32_t *kept_count, int L, int n_scan, int n,
+                              float *out, hipStream_t s);
 
 }  // namespace slam

@@ -258,7 +258,8 @@ int slam_bresenham_batch(slam_ctx *ctx, const int32_t *starts, const int32_t *en
 /* ---- fused replay ------------------------------------------------------------------ */
 /* The per-scan unit of BASELINE.json (one ICP.process + one Mapping.update) over L scan
  * streams of n_scan scans: SLAM_EKF.laserCallback (W12m/slam_ekf.py:63-95) without its
- * out-of-scope EKF / landmark steps, the map being cast from the dead-reckoned ICP pose.
+ * out-of-scope EKF / landmark steps, the map being cast from the dead-reckoned ICP pose
+ * (slam_node_replay below is the node with them).
  * ranges [L][n_scan][n] float32; pose0 [L][3]; grid may be NULL (ICP + poses only);
  * grid_of_traj [L] or NULL (all into map 0).
  * poses_out [L][n_scan-1][3]; T_out [L][n_scan-1][9], iters_out [L][n_scan-1] may be NULL.
@@ -448,6 +449,80 @@ int slam_astar_inflate(slam_ctx *ctx, const int8_t *maps, int G, int H, int W, i
                        int8_t *inflated_out);
 int slam_astar_inflate_dev(slam_ctx *ctx, const int8_t *maps, int G, int H, int W, int wire_layout, int span, int r,
                            int8_t *inflated_out);
+
+/* ---- landmark EKF-SLAM node ------------------------------------------- */
+/* Replaces Extraction.process(msg) (W12m/extraction.py:24-89) and SLAM_EKF.observation(lm)
+ * (W12m/slam_ekf.py:96-106) for S scans in one launch.  ranges [S][n] float32, cos_t / sin_t [n] as for
+ * slam_scan_to_points; the points are formed as laserToNumpy does (inf -> 30 m, slam_ekf.py:115-123).
+ * The rules are the reference's as it executes: only the first n-1 points are labelled (:36); the point that
+ * closes a cluster belongs to it and a cluster needs two earlier members to be closed (:41-45); cluster
+ * numbers advance on every gap; a cluster still open at the end is never tested; the gap is
+ * sqrt(dx*dx + dy*dy) < range_threshold (:37) and the extent the largest pairwise distance < radius_max_th
+ * (:47-49).  A NaN range compares false everywhere: it ends a cluster and is no landmark's member.
+ * Per scan: count_out [S] landmarks (at most lm_cap; overflow_out [S] is 1 when the scan had more, the first
+ * lm_cap are kept), ids_out [S][lm_cap] their cluster numbers (-1 in unused slots), means_out [S][lm_cap][2]
+ * the sensor-frame means (running sums in index order, :81-87: bit-equal to the reference), z_out
+ * [S][lm_cap][2] the rows (hypot, pi_2_pi(atan2)) of observation; labels_out: nullable [S][n-1], every
+ * point's cluster number or -1.  1 <= n <= 4096, 1 <= lm_cap <= 1024. */
+int slam_landmarks(slam_ctx *ctx, const float *ranges, const double *cos_t, const double *sin_t, int S, int n,
+                   double range_threshold, double radius_max_th, int lm_cap, int32_t *count_out, int32_t *overflow_out,
+                   int32_t *ids_out, double *means_out, double *z_out, int32_t *labels_out);
+int slam_landmarks_dev(slam_ctx *ctx, const float *ranges, const double *cos_t, const double *sin_t, int S, int n,
+                       double range_threshold, double radius_max_th, int lm_cap, int32_t *count_out,
+                       int32_t *overflow_out, int32_t *ids_out, double *means_out, double *z_out, int32_t *labels_out);
+
+/* Per-trajectory status of the filter and of the node replay below. */
+enum {
+    SLAM_NODE_OK = 0,
+    SLAM_NODE_REF_RAISES = 1,   /* an observation matched the landmark appended in the same call: the reference
+                                   raises ValueError from np.hstack (ekf_lm.py:37-38, its n1 is stale)          */
+    SLAM_NODE_LM_CAP = 2,       /* the state would grow past max_lm landmarks                                   */
+    SLAM_NODE_OBS_CAP = 3       /* node replay: a kept scan had more than lm_cap landmarks                      */
+};
+#define SLAM_EKF_MAX_LM 32
+/* Replaces EKF.estimate(xEst, PEst, z, u) (W12m/ekf_lm.py:15-50) called once per step along B trajectories,
+ * each from xEst = x0[b] (NULL: zeros), PEst = eye(3).  u [B][steps][3]; step_counts [B]: trajectory b runs
+ * min(max(step_counts[b], 0), steps) steps; the observations of step (b, s) are the rows
+ * z[z_off[b * steps + s] .. z_off[b * steps + s + 1]) of z [nz][2] (range, bearing); z_off has B * steps + 1
+ * entries (the device form clamps them to [0, nz]).  The reference's stale n1 is reproduced, not fixed: a
+ * second unmatched observation in one call ends the call before the yaw wrap (:40-42), and from the step at
+ * which the reference raises (SLAM_NODE_REF_RAISES) or the state would pass max_lm (SLAM_NODE_LM_CAP) the
+ * trajectory stops with the state it had BEFORE that step.
+ * 0 <= max_lm <= SLAM_EKF_MAX_LM; N = 3 + 2 * max_lm.  x_out [B][N], P_out [B][N][N] (zero beyond the state),
+ * nlm_out [B][steps] the landmark count after every step (-1: the step did not happen), status_out [B]. */
+int slam_ekf_lm(slam_ctx *ctx, const double *x0, const double *u, const int32_t *step_counts, const int64_t *z_off,
+                const double *z, int64_t nz, int B, int steps, int max_lm, double *x_out, double *P_out,
+                int32_t *nlm_out, int32_t *status_out);
+int slam_ekf_lm_dev(slam_ctx *ctx, const double *x0, const double *u, const int32_t *step_counts, const int64_t *z_off,
+                    const double *z, int64_t nz, int B, int steps, int max_lm, double *x_out, double *P_out,
+                    int32_t *nlm_out, int32_t *status_out);
+
+/* Replaces SLAM_EKF.laserCallback (W12m/slam_ekf.py:63-95) in full - extraction (:79), the skip of a scan
+ * without landmark (:80-82), calc_odometry (:109-113), T2u (:125-128), observation (:96-106), EKF.estimate
+ * (:86) and the map cast from xEst (:88-90) - over L streams of n_scan already-decimated scans,
+ * ranges [L][n_scan][n] float32.  Scan 0 of a stream is its first target whatever it shows; after it only
+ * scans with at least one landmark are KEPT, and the scan matcher's target advances on kept scans only.
+ * Step s of a trajectory matches kept scan s + 1 against kept scan s, filters, and casts kept scan s + 1 from
+ * xEst into map grid_of_traj[l] (NULL: map 0) of `grid` (NULL: no map).  pose0 [L][3]; PEst starts as eye(3).
+ * kept_out [L][n_scan] scan numbers (-1 behind the kept ones), kept_count_out [L]; per step s < kept_count - 1:
+ * xest_out [L][n_scan-1][3] = xEst[:3] (NaN for steps that did not happen), nlm_out [L][n_scan-1] (-1 likewise),
+ * T_out [L][n_scan-1][9] and iters_out [L][n_scan-1] (nullable; entries behind a trajectory's steps are void);
+ * x_final_out [L][N], P_final_out [L][N][N], N = 3 + 2 * max_lm, zero beyond the state; status_out [L]
+ * (SLAM_NODE_*): a trajectory that stops keeps the state, and casts the scans, of the steps before.
+ * L <= 65535, n <= 4096; dtype, max_iter, tol as slam_replay.  The device form does not synchronise.
+ * The scan matcher runs in ONE launch shape whatever L is (two queries per lane, or what "icp_qpt" / "icp_one_wave" = 1
+ * name), so a trajectory's outputs are the same bits alone and in any batch. */
+int slam_node_replay(slam_ctx *ctx, const float *ranges, const double *cos_t, const double *sin_t, int L, int n_scan,
+                     int n, int dtype, int max_iter, double tol, double range_threshold, double radius_max_th,
+                     int lm_cap, int max_lm, const double *pose0, slam_grid *grid, const int32_t *grid_of_traj,
+                     int32_t *kept_out, int32_t *kept_count_out, double *xest_out, int32_t *nlm_out,
+                     double *x_final_out, double *P_final_out, double *T_out, int32_t *iters_out, int32_t *status_out);
+int slam_node_replay_dev(slam_ctx *ctx, const float *ranges, const double *cos_t, const double *sin_t, int L, int n_scan,
+                         int n, int dtype, int max_iter, double tol, double range_threshold, double radius_max_th,
+                         int lm_cap, int max_lm, const double *pose0, slam_grid *grid, const int32_t *grid_of_traj,
+                         int32_t *kept_out, int32_t *kept_count_out, double *xest_out, int32_t *nlm_out,
+                         double *x_final_out, double *P_final_out, double *T_out, int32_t *iters_out,
+                         int32_t *status_out);
 
 #ifdef __cplusplus
 }
