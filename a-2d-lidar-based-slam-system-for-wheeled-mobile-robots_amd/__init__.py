@@ -10,7 +10,8 @@ zjwzcx/A-2D-LiDAR-based-SLAM-System-for-Wheeled-Mobile-Robots:
     SLAM_EKF   laserCallback glue (scan matching + map building); landmarks=True: the whole W12
                node with Extraction and the landmark EKF on the host; batched on the device
                as DeviceNodeReplay / node_replay_host, landmarks_host, ekf_lm_host
-    Localization  updateMap / laserEstimation / calc_map_observation (scan-to-map, W9)
+    Localization  updateMap / laserEstimation / calc_map_observation (scan-to-map, W9); the whole
+               W9 node batched on the device as DeviceLocalizationReplay / loc_replay_host
     dwa        dwa_control / Config / RobotType (course_agv_nav DWA local planner), batched as
                DeviceDWA / dwa_batch_host; LocalPlanner: the local planner node without ROS
     global_planner  find_path(...).start_find() / GlobalPlanner (course_agv_nav A*), batched as
@@ -32,6 +33,7 @@ from .global_planner import DeviceAStar, GlobalPlanner, astar_host, find_path, i
 from .icp import ICP, scan_to_pc
 from .local_planner import LocalPlanner
 from .localization import Localization
+from .loc_replay import DeviceLocalizationReplay, loc_replay_host
 from .mapping import Mapping
 from .node_replay import DeviceNodeReplay, ekf_lm_host, landmarks_host, node_replay_host
 from .replay import DeviceGrid, DeviceReplay, icp_batch_host, particles_host, prior_matrices, replay_host
@@ -42,4 +44,5 @@ __all__ = ["ICP", "Mapping", "Localization", "EKF", "Extraction", "LandMarkSet",
            "DeviceGrid", "DeviceReplay", "replay_host", "icp_batch_host", "particles_host", "prior_matrices", "scan_to_pc", "SlamError",
            "LibraryMissing", "param", "synthetic", "dwa", "dwa_control", "DeviceDWA", "dwa_batch_host", "LocalPlanner",
            "global_planner", "find_path", "GlobalPlanner", "DeviceAStar", "astar_host", "inflate_host",
-           "DeviceNodeReplay", "node_replay_host", "landmarks_host", "ekf_lm_host"]
+           "DeviceNodeReplay", "node_replay_host", "landmarks_host", "ekf_lm_host",
+           "DeviceLocalizationReplay", "loc_replay_host"]

@@ -105,8 +105,13 @@ _SIGS = {
                           _vp, _vp, _vp, _vp, _vp], _i),
     "slam_node_replay_dev": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _d, _d, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                               _vp, _vp, _vp, _vp, _vp], _i),
+    "slam_loc_replay": ([_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _d, _d, _i, _d, _vp, _vp, _vp, _vp,
+                         _vp, _vp, _vp, _vp], _i),
+    "slam_loc_replay_dev": ([_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, C.c_int64, _vp, _vp, _i, _vp, _vp, _d, _d, _i, _d, _vp,
+                             _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i),
 }
 NODE_OK, NODE_REF_RAISES, NODE_LM_CAP, NODE_OBS_CAP = 0, 1, 2, 3
+LOC_OK, LOC_NONFINITE, LOC_BAD_ROUTE = 0, 1, 2
 EKF_MAX_LM = 32
 
 

@@ -355,7 +355,7 @@ private:
         void *dst;                            // host destination of an output (null: nothing to copy back)
         size_t off, bytes;
     };
-    static constexpr int kMaxPieces = 16;
+    static constexpr int kMaxPieces = 24;
 
     template <typename T> static void set_ptr(void *dev, char *p) { *static_cast<T **>(dev) = reinterpret_cast<T *>(p); }
     template <typename T> Staging &add(T *&dev, size_t n, const void *src, void *dst, bool absent)
@@ -2110,6 +2110,110 @@ int slam_node_replay(slam_ctx *c, const float *ranges, const double *cos_t, cons
     TRY(s.upload());
     TRY(slam_node_replay_dev(c, d_r, d_c, d_s, L, n_scan, n, dtype, max_iter, tol, range_threshold, radius_max_th, lm_cap, max_lm,
                              d_0, grid, d_g, d_k, d_kc, d_xe, d_nlm, d_xf, d_Pf, d_T, d_it, d_st));
+    TRY(s.download());
+    return check_status_sync(c);
+}
+
+/* ---- fusion-localization node (W9), batched ------------------------------------------------ */
+
+static int check_loc_replay(const char *fn, const float *ranges, int S, int n_scan, int n, const int32_t *stream_of_traj,
+                            const double *ox, const double *oy, const int64_t *obs_off, int M, int64_t K, int L,
+                            const double *cos_t, const double *sin_t, double angle_min, double angle_increment, int max_iter,
+                            const double *xest_out, const double *xodom_out, const double *P_final_out,
+                            const int32_t *status_out)
+{
+    REQUIRE_IN(fn, ranges && obs_off && cos_t && sin_t && xest_out && xodom_out && P_final_out && status_out, "null pointer");
+    REQUIRE_IN(fn, K >= 0 && (K == 0 || (ox && oy)), "K >= 0 obstacles need ox and oy");
+    REQUIRE_IN(fn, L > 0 && L <= 65535 && n > 0 && n <= kLocMaxBeams && n_scan >= 1, "need 0 < L <= 65535, n_scan >= 1, 1 <= n <= 4096");
+    REQUIRE_IN(fn, S > 0 && M > 0, "need at least one stream and one map");
+    REQUIRE_IN(fn, stream_of_traj || S == L, "without stream_of_traj every trajectory has its own stream: S must equal L");
+    REQUIRE_IN(fn, (long)L * n_scan < (1L << 31) && (long)S * (2L * n_scan - 1) < (1L << 31), "too many scans for one call");
+    REQUIRE_IN(fn, max_iter >= 0, "max_iter must be >= 0");
+    REQUIRE_IN(fn, angle_increment != 0.0 && std::isfinite(angle_increment) && std::isfinite(angle_min), "bad angles");
+    return SLAM_OK;
+}
+
+int slam_loc_replay_dev(slam_ctx *c, const float *ranges, int S, int n_scan, int n, const int32_t *stream_of_traj,
+                        const double *ox, const double *oy, const int64_t *obs_off, int M, int64_t K,
+                        const int32_t *map_of_traj, const double *pose0, int L, const double *cos_t, const double *sin_t,
+                        double angle_min, double angle_increment, int max_iter, double tol, double *xest_out,
+                        double *xodom_out, double *P_final_out, int32_t *status_out, double *T_obs_out,
+                        int32_t *iters_obs_out, double *T_odom_out, double *tar_pts_out)
+{
+    TRY(use(c));
+    TRY(check_loc_replay(__func__, ranges, S, n_scan, n, stream_of_traj, ox, oy, obs_off, M, K, L, cos_t, sin_t, angle_min,
+                         angle_increment, max_iter, xest_out, xodom_out, P_final_out, status_out));
+    const size_t Lz = (size_t)L, pairs = (size_t)S * (2 * (size_t)n_scan - 1);
+    TRY(arena_reserve(c, c->scratch, align_up(pairs * 4 * n * 8) + align_up(pairs * 72) + 2 * align_up(Lz * 2 * n * 8) +
+                                         align_up(Lz * 72) + align_up(Lz * 4) + align_up(Lz * kLocStateDoubles * 8) + 4096));
+    double *pair_pts = carve<double>(c->scratch, pairs * 4 * n), *T_stream = carve<double>(c->scratch, pairs * 9);
+    double *tar = carve<double>(c->scratch, Lz * 2 * n), *src = carve<double>(c->scratch, Lz * 2 * n);
+    double *T_step = carve<double>(c->scratch, Lz * 9);
+    int32_t *it_step = carve<int32_t>(c->scratch, Lz);
+    double *state = carve<double>(c->scratch, Lz * kLocStateDoubles);
+    REQUIRE(pair_pts && T_stream && tar && src && T_step && it_step && state, "internal: workspace");
+    IcpArgs icp;
+    icp.prior = nullptr; icp.ranges = nullptr; icp.cos_t = icp.sin_t = nullptr; icp.tar_scan_stride = icp.src_scan_stride = 0;
+    icp.ppt = 0; icp.n_tar = n; icp.n_src = n; icp.max_iter = max_iter; icp.tol = tol; icp.err_out = nullptr;
+    icp.status = c->status; icp.qpt_pref = c->icp_qpt; icp.team_mode = c->icp_team; icp.one_wave = c->icp_one_wave;
+    icp.batch_invariant = 1;        // a trajectory's result does not depend on how many run beside it
+    {   // the solves that depend on the stream alone, once per stream: every T2 (:100) and T1 of the steps after the first (:78)
+        HIPCHK(launch_loc_stream_pairs(ranges, cos_t, sin_t, S, n_scan, n, pair_pts, c->stream));
+        icp.tar = pair_pts; icp.src = pair_pts + 2 * (size_t)n; icp.tar_stride = icp.src_stride = 4L * n;
+        icp.B = (int)pairs; icp.T_out = T_stream; icp.iters_out = nullptr;
+        Timed t(c, SLAM_K_ICP);
+        HIPCHK(launch_icp(icp, SLAM_F64, c->stream));
+    }
+    LocArgs a{};
+    a.L = L; a.S = S; a.M = M; a.n = n; a.n_scan = n_scan;
+    a.ranges = ranges; a.stream_of_traj = stream_of_traj; a.map_of_traj = map_of_traj;
+    a.ox = ox; a.oy = oy; a.obs_off = obs_off; a.K = K; a.pose0 = pose0; a.cos_t = cos_t; a.sin_t = sin_t;
+    a.angle_min = angle_min; a.angle_increment = angle_increment;
+    a.T_stream = T_stream; a.T_step = T_step; a.iters_step = it_step; a.state = state; a.tar_pts = tar; a.src_pts = src;
+    a.xest_out = xest_out; a.xodom_out = xodom_out; a.P_final_out = P_final_out; a.status_out = status_out;
+    a.T_obs_out = T_obs_out; a.T_odom_out = T_odom_out; a.iters_obs_out = iters_obs_out; a.tar_pts_out = tar_pts_out;
+    a.status = c->status;
+    icp.tar = tar; icp.src = src; icp.tar_stride = icp.src_stride = 2L * n;
+    icp.B = L; icp.T_out = T_step; icp.iters_out = it_step;
+    for (int s = 0; s <= n_scan; ++s) {   // step s: finish step s - 1, then virtual scan at xEst + the scan -> the scan matcher (:152-157)
+        a.step = s; a.body = s < n_scan;
+        HIPCHK(launch_loc_step(a, c->stream));
+        if (!a.body) break;
+        Timed t(c, SLAM_K_ICP);
+        HIPCHK(launch_icp(icp, SLAM_F64, c->stream));
+    }
+    return SLAM_OK;
+}
+
+int slam_loc_replay(slam_ctx *c, const float *ranges, int S, int n_scan, int n, const int32_t *stream_of_traj,
+                    const double *ox, const double *oy, const int64_t *obs_off, int M, const int32_t *map_of_traj,
+                    const double *pose0, int L, const double *cos_t, const double *sin_t, double angle_min,
+                    double angle_increment, int max_iter, double tol, double *xest_out, double *xodom_out,
+                    double *P_final_out, int32_t *status_out, double *T_obs_out, int32_t *iters_obs_out, double *T_odom_out,
+                    double *tar_pts_out)
+{
+    TRY(use(c));
+    REQUIRE(obs_off && M > 0, "need obs_off with M + 1 entries, M >= 1");
+    for (int m = 0; m < M; ++m) REQUIRE(obs_off[m] >= 0 && obs_off[m] <= obs_off[m + 1], "obs_off must ascend from >= 0");
+    const int64_t K = obs_off[M];
+    TRY(check_loc_replay(__func__, ranges, S, n_scan, n, stream_of_traj, ox, oy, obs_off, M, K, L, cos_t, sin_t, angle_min,
+                         angle_increment, max_iter, xest_out, xodom_out, P_final_out, status_out));
+    for (int l = 0; l < L; ++l) {
+        REQUIRE(!stream_of_traj || (stream_of_traj[l] >= 0 && stream_of_traj[l] < S), "stream_of_traj out of range");
+        REQUIRE(!map_of_traj || (map_of_traj[l] >= 0 && map_of_traj[l] < M), "map_of_traj out of range");
+    }
+    const size_t Lz = (size_t)L, steps = Lz * n_scan;
+    float *d_r; double *d_c, *d_s, *d_x, *d_y, *d_0, *d_xe, *d_xo, *d_P, *d_To, *d_Td, *d_tp; int64_t *d_off;
+    int32_t *d_sot, *d_mot, *d_st, *d_it;
+    Staging s(c);
+    s.in(d_r, ranges, (size_t)S * n_scan * n).in(d_c, cos_t, n).in(d_s, sin_t, n).in(d_x, K ? ox : nullptr, K).in(d_y, K ? oy : nullptr, K)
+        .in(d_off, obs_off, (size_t)M + 1).in(d_0, pose0, Lz * 3).in(d_sot, stream_of_traj, Lz).in(d_mot, map_of_traj, Lz);
+    s.out(d_xe, xest_out, steps * 3).out(d_xo, xodom_out, steps * 3).out(d_P, P_final_out, Lz * 9).out(d_st, status_out, Lz)
+        .out(d_To, T_obs_out, steps * 9).out(d_it, iters_obs_out, steps).out(d_Td, T_odom_out, steps * 9)
+        .out(d_tp, tar_pts_out, steps * 2 * n);
+    TRY(s.upload());
+    TRY(slam_loc_replay_dev(c, d_r, S, n_scan, n, d_sot, d_x, d_y, d_off, M, K, d_mot, d_0, L, d_c, d_s, angle_min,
+                            angle_increment, max_iter, tol, d_xe, d_xo, d_P, d_st, d_To, d_it, d_Td, d_tp));
     TRY(s.download());
     return check_status_sync(c);
 }

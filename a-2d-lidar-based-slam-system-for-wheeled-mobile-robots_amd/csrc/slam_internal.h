@@ -186,6 +186,39 @@ hipError_t launch_virtual_scan(const double *ox, const double *oy, int K, const 
 hipError_t launch_ranges64_to_points(const double *ranges, const double *cos_t, const double *sin_t, int B, int n,
                                      double *pts, hipStream_t s);
 
+// ---- batched W9 node (Localization.laserCallback, W9/localization.py:66-126; localization_kernels.hip) ----
+constexpr int kLocMaxBeams = 4096;           // beam bins of a trajectory in LDS (8 B each)
+constexpr int kLocStateDoubles = 16;         // per trajectory: xEst[3], xOdom[3], PEst[9], status
+struct LocArgs {
+    int L, S, M, n, n_scan;
+    int step;                                // the step whose virtual scan and source this call prepares; it finishes step - 1
+    int body;                                // 0: the last call, which only finishes step n_scan - 1
+    const float *ranges;                     // [S][n_scan][n]
+    const int32_t *stream_of_traj, *map_of_traj;   // nullable [L]
+    const double *ox, *oy;                   // [K] every map's obstacles, concatenated
+    const int64_t *obs_off;                  // [M + 1], clamped to [0, K]
+    long K;
+    const double *pose0;                     // nullable [L][3]
+    const double *cos_t, *sin_t;
+    double angle_min, angle_increment;
+    const double *T_stream;                  // [S][2 n_scan - 1][9]: T2 of step s at s, T1 of step s >= 1 at n_scan + s - 1
+    const double *T_step;                    // [L][9] what the scan matcher made of the pair this kernel prepared last
+    const int32_t *iters_step;               // [L]
+    double *state;                           // [L][kLocStateDoubles]
+    double *tar_pts, *src_pts;               // [L][2][n] the pair of the scan matcher launch that follows
+    double *xest_out, *xodom_out;            // [L][n_scan][3]
+    double *P_final_out;                     // [L][9]
+    int32_t *status_out;                     // [L] SLAM_LOC_*
+    double *T_obs_out, *T_odom_out;          // nullable [L][n_scan][9]
+    int32_t *iters_obs_out;                  // nullable [L][n_scan]
+    double *tar_pts_out;                     // nullable [L][n_scan][2][n]
+    int *status;
+};
+hipError_t launch_loc_step(const LocArgs &a, hipStream_t s);
+// the pairs of the stream-only solves as point sets: pairs [S][2 n_scan - 1][2][2][n] (target, then source)
+hipError_t launch_loc_stream_pairs(const float *ranges, const double *cos_t, const double *sin_t, int S, int n_scan, int n,
+                                   double *pairs, hipStream_t s);
+
 // ---- DWA local planner (dwa_kernels.hip) ----------------------------------------------
 // The fields of SLAM_DWA_CONFIG_LEN in the order include/slam_hip.h documents (dwa.py:23-45).
 struct DwaConfig {

@@ -524,6 +524,54 @@ int slam_node_replay_dev(slam_ctx *ctx, const float *ranges, const double *cos_t
                          double *x_final_out, double *P_final_out, double *T_out, int32_t *iters_out,
                          int32_t *status_out);
 
+/* ---- fusion-localization node (W9), batched ---------------------------------------------- */
+/* Per-trajectory status of slam_loc_replay. */
+enum {
+    SLAM_LOC_OK = 0,
+    SLAM_LOC_NONFINITE = 1,     /* a transform of the step was not finite: the reference raises LinAlgError from
+                                   numpy's svd (W12m/icp.py:161 as W9 runs it)                                   */
+    SLAM_LOC_BAD_ROUTE = 2      /* device form: stream_of_traj / map_of_traj entry out of range                  */
+};
+/* Replaces Localization.laserCallback (W9/localization.py:66-126) in full - calc_odometry twice (:78, :100,
+ * :159-168), calc_map_observation (:152-157) with laserEstimation (:128-150) and laserToNumpy (:170-176), the
+ * pose algebra (:79-83, :113-118) and EKF.estimate (W9/ekf.py:17-87) - for L trajectories in lockstep over
+ * streams of n_scan already-decimated scans, ranges [S][n_scan][n] float32 (every scan is one processed
+ * message), n_scan >= 1.  Trajectory l replays stream stream_of_traj[l] (NULL: stream l, and S must equal L)
+ * against the obstacles (ox, oy)[obs_off[m] .. obs_off[m + 1]) of map m = map_of_traj[l] (NULL: map 0);
+ * obs_off has M + 1 ascending entries over one concatenated list of K = obs_off[M] points (K >= 0, a map may
+ * be empty; the device form clamps the entries to [0, K]).  It starts from xEst = xOdom = pose0[l] (NULL:
+ * zeros), PEst = eye(3).  Step s: T1 = ICP.process(previous scan, scan s) - for s = 0 the target is the
+ * map's virtual scan at pose0 (:159-168) - and xOdom = compose(xOdom, T1); T2 = ICP.process(scan s, scan s)
+ * (:100; solved, not assumed); t = the map observation at xEst, z = compose(xEst, t); xEst, PEst =
+ * EKF.estimate(xEst, PEst, z, T2), its 3x3 inverse by elimination with partial pivoting as numpy's.  Points are
+ * cos_t[i] * r, sin_t[i] * r without an inf clip.  T1 of s >= 1 and T2 are solved once per STREAM; T1 of step
+ * 0 is the same pair as t of step 0 (same target, same source) and is solved once.
+ * Outputs: xest_out, xodom_out [L][n_scan][3]; P_final_out [L][9]; status_out [L] (SLAM_LOC_*); nullable:
+ * T_obs_out [L][n_scan][9] (t), iters_obs_out [L][n_scan], T_odom_out [L][n_scan][9] (T1), tar_pts_out
+ * [L][n_scan][2][n] (the target points of every step's map observation, for inspection).  A trajectory one of
+ * whose T1, T2, t is not finite at step s stops there (SLAM_LOC_NONFINITE): it keeps the state it had before
+ * step s (P_final_out), its per-step outputs from s on are NaN, its iteration counts -1 and its tar_pts_out
+ * entries void; the others are unaffected.
+ * L <= 65535, n <= 4096, L * n_scan < 2^31; max_iter, tol as slam_icp_batch.  The host form rejects route
+ * entries out of range; the device form does not synchronise, takes its workspaces from the context
+ * (S (2 n_scan - 1) pairs of point sets, 32 n bytes each, and 32 n bytes per trajectory) and enqueues two
+ * launches per step.  The scan matcher runs in ONE launch shape whatever L and S are (two queries per lane,
+ * or what "icp_qpt" / "icp_one_wave" = 1 name), so a trajectory's outputs are the same bits alone and in any
+ * batch. */
+int slam_loc_replay(slam_ctx *ctx, const float *ranges, int S, int n_scan, int n, const int32_t *stream_of_traj,
+                    const double *ox, const double *oy, const int64_t *obs_off, int M, const int32_t *map_of_traj,
+                    const double *pose0, int L, const double *cos_t, const double *sin_t, double angle_min,
+                    double angle_increment, int max_iter, double tol, double *xest_out, double *xodom_out,
+                    double *P_final_out, int32_t *status_out, double *T_obs_out, int32_t *iters_obs_out,
+                    double *T_odom_out, double *tar_pts_out);
+/* Device form: K is the length of ox / oy (the host form reads it from obs_off[M]). */
+int slam_loc_replay_dev(slam_ctx *ctx, const float *ranges, int S, int n_scan, int n, const int32_t *stream_of_traj,
+                        const double *ox, const double *oy, const int64_t *obs_off, int M, int64_t K,
+                        const int32_t *map_of_traj, const double *pose0, int L, const double *cos_t,
+                        const double *sin_t, double angle_min, double angle_increment, int max_iter, double tol,
+                        double *xest_out, double *xodom_out, double *P_final_out, int32_t *status_out,
+                        double *T_obs_out, int32_t *iters_obs_out, double *T_odom_out, double *tar_pts_out);
+
 #ifdef __cplusplus
 }
 #endif
