@@ -5,7 +5,7 @@
 // Functional spec = the reference's Python (W12m = "W12_LiDAR SLAM/w12-mapping/
 // course_agv_slam/scripts" under /root/reference):
 //   Mapping.update   W12m/mapping.py:22-51    -> cast_ray / k_grid_update*
-//   bresenham        W12m/bresenham.py:2-58   -> ray_setup + the walk loops, k_bresenham
+//   bresenham        W12m/bresenham.py:2-58   -> ray_setup + walk_step (every engine's loop), k_bresenham
 //   pmap threshold   W12m/mapping.py:47-50    -> k_grid_finalize
 //   publishMap       W12m/slam_ekf.py:270-271 -> k_grid_transpose
 //
@@ -18,7 +18,10 @@
 //
 // The ray walk keeps the reference's float64 error accumulation verbatim
 // (error += dy/float(dx); if error >= 0.5: y += ystep; error -= 1.0): 15 % of lines
-// differ from integer Bresenham, so anything else breaks cell parity.
+// differ from integer Bresenham, so anything else breaks cell parity.  The rule lives in ONE
+// place, walk_step(); the engines share two walks built on it - CellWalk (the cell as map coordinates, bounds
+// tested by the caller) and lds_walk (unchecked, the cell as one running LDS byte address) - and the plain
+// x0 + k, y loops call walk_step directly.  To change the walk, change walk_step.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -37,6 +40,13 @@ struct Ray {
     int x0, y0, dx, ystep;   // walk origin (after steep / endpoint swaps), run length, y direction
     double derr;
     bool steep, flag;        // flag: the walk runs end -> start, i.e. path order is reversed (:57-58)
+    // the ray of a lane that has none: no step to walk (dx = -1), every field defined
+    __device__ __forceinline__ static Ray none()
+    {
+        Ray r;
+        r.x0 = r.y0 = 0; r.dx = -1; r.ystep = 1; r.derr = 0.0; r.steep = r.flag = false;
+        return r;
+    }
 };
 
 // bresenham.__init__ up to the loop (bresenham.py:10-43).  Returns false for identical
@@ -56,6 +66,44 @@ __device__ __forceinline__ bool ray_setup(int sx, int sy, int ex, int ey, Ray &r
     r.ystep = sy < ey ? 1 : -1;                                      // :40-43
     return true;
 }
+
+// THE walk step (bresenham.py:51-55), the only copy in this file: every engine's loop calls it once per walk
+// step and moves its own notion of the cell by what it returns (true: y advances by ystep).  The subtraction is
+// branch-free - minus 1.0, or minus 0.0, which is exact - and gives the bits of `if error >= 0.5: error -= 1.0`.
+__device__ __forceinline__ bool walk_step(double &error, double derr)
+{
+    error += derr;                                                   // :51
+    const bool stepy = error >= 0.5;                                 // :53
+    error -= __hiloint2double(stepy ? 0x3ff00000 : 0, 0);            // :55
+    return stepy;
+}
+
+// The checked cell walk: the cell as map coordinates (lx, ly), moved by next(); the caller tests each cell
+// against whatever bounds it has.  stride_k / stride_y give the same increments for a cell kept as ONE linear
+// index over rows of `row` elements (index = lx * row + ly).
+struct CellWalk {
+    int lx, ly;                  // current cell
+    int klast;                   // walk step of the path's LAST cell (bresenham.py:57-58)
+    int ax_x, ax_y, ay_x, ay_y;  // cell step per walk step, and per y step
+    double error, derr;
+    __device__ __forceinline__ explicit CellWalk(const Ray &r)
+    {
+        klast = r.flag ? 0 : r.dx;
+        ax_x = r.steep ? 0 : 1; ax_y = r.steep ? 1 : 0;              // :46-49
+        ay_x = r.steep ? r.ystep : 0; ay_y = r.steep ? 0 : r.ystep;
+        lx = r.steep ? r.y0 : r.x0; ly = r.steep ? r.x0 : r.y0;
+        error = 0.0; derr = r.derr;                                  // :34-35
+    }
+    __device__ __forceinline__ int stride_k(int row) const { return ax_x * row + ax_y; }
+    __device__ __forceinline__ int stride_y(int row) const { return ay_x * row + ay_y; }
+    __device__ __forceinline__ bool next()
+    {
+        const bool stepy = walk_step(error, derr);
+        lx += ax_x + (stepy ? ay_x : 0);
+        ly += ax_y + (stepy ? ay_y : 0);
+        return stepy;
+    }
+};
 
 // World coordinate -> cell index, int(scale * (v + off)) truncated toward zero
 // (mapping.py:33-36).  Flags what Python would raise on (NaN: ValueError, inf: OverflowError).
@@ -94,8 +142,7 @@ __device__ __forceinline__ unsigned cast_ray(uint32_t *__restrict__ pass, uint32
                 atomicAdd(last ? &hit[c] : &pass[c], 1u);            // :42-45
             }
         }
-        error += r.derr;                                             // :51
-        if (error >= 0.5) { y += r.ystep; error -= 1.0; }            // :53-55
+        if (walk_step(error, r.derr)) y += r.ystep;
     }
     return nvis;
 }
@@ -356,6 +403,48 @@ __device__ __forceinline__ int wave_max_i32(int v)
     return v;
 }
 
+// The unchecked LDS walk, shared by every engine whose rays cannot leave their window (a Bresenham path never
+// leaves the box of its ends): no bounds tests, the cell kept as ONE running LDS byte address `a` of its counter
+// (dword = address & ~3, the count's position in it from the low address bits - the same expression for 16-bit
+// and for 8-bit counters, whose callers scale a, da_k and da_y by 2 or by 1), four steps per wave-wide loop
+// test with no lane mask inside, then a tail of up to three.  9 VALU + 1 LDS instructions per step.
+// Adds 1 to the counters of `rem` cells from `a` on and leaves `error` where the walk stands.  `lead_in`: the
+// first walk step is not counted (a reversed path starts on its hit cell).  A lane with rem == 0 and no
+// lead-in does nothing.
+__device__ __forceinline__ void lds_walk(unsigned a, int da_k, int da_y, int rem, double derr, double &error, bool lead_in)
+{
+    auto advance = [&]() {
+        const bool stepy = walk_step(error, derr);
+        a += (unsigned)(da_k + (stepy ? da_y : 0));
+    };
+    auto step = [&]() {
+        lds_add_u32(a & ~3u, 1u << ((a << 3) & 31u));                // mapping.py:43
+        advance();
+    };
+    if (lead_in) advance();
+    for (;;) {
+        const bool full = rem >= 4;
+        if (!__any(full)) break;
+        if (full) { step(); step(); step(); step(); rem -= 4; }
+    }
+#pragma unroll
+    for (int u = 0; u < 3; ++u)
+        if (rem > u) step();
+}
+
+// Rays are handed to waves 64 at a time from an LDS counter, in `order` when the group was sorted.  False: none
+// are left for this wave; else r is the lane's ray, or -1 for a lane beyond the last one.
+__device__ __forceinline__ bool next_rays(int *next_ray, int nrays, const unsigned short *order, int &r)
+{
+    const int lane = threadIdx.x & 63;
+    int base = 0;
+    if (lane == 0) base = atomicAdd(next_ray, kWave);
+    base = __builtin_amdgcn_readfirstlane(base);
+    if (base >= nrays) return false;
+    r = base + lane >= nrays ? -1 : order ? (int)order[base + lane] : base + lane;   // longest rays first when sorted
+    return true;
+}
+
 // Pass 2 of the window kernel: walk a workgroup's rays.  Rays are handed to waves 64 at a
 // time from an LDS counter, in order of decreasing length when the group was sorted in pass 1
 // (a wave runs as long as its longest ray: unsorted, 54 % of the lane-steps were idle).  The walk
@@ -371,68 +460,34 @@ __device__ __forceinline__ unsigned cast_rays(const GridDev &g, const Src &src, 
                                               uint32_t *__restrict__ hit, const int *first_bad)
 {
     unsigned nvis = 0;
-    const int lane = threadIdx.x & 63;
-    for (;;) {
-        int base = 0;
-        if (lane == 0) base = atomicAdd(next_ray, kWave);
-        base = __builtin_amdgcn_readfirstlane(base);
-        if (base >= nrays) break;
-        if (base + lane >= nrays) continue;
-        const int r = order ? (int)order[base + lane] : base + lane;   // longest rays first when sorted
+    for (int r; next_rays(next_ray, nrays, order, r);) {
+        if (r < 0) continue;
         int s = r / n, i = r - s * n, pox, poy, b2 = 0;
         Ray ry;
         if (i >= first_bad[s]) continue;                             // beams from the scan's first bad one on are not cast
         if (!src.ray(l, s0 + s, i, sc[s], g, pox, poy, b2)) continue;
         if (!ray_setup(sc[s].pcx, sc[s].pcy, pox, poy, ry)) continue;
-        const int klast = ry.flag ? 0 : ry.dx;                       // walk step of the path's LAST cell
-        const int ax_x = ry.steep ? 0 : 1, ax_y = ry.steep ? 1 : 0;  // cell step per walk step ...
-        const int ay_x = ry.steep ? ry.ystep : 0, ay_y = ry.steep ? 0 : ry.ystep;   // ... and per y step
-        int lx = ry.steep ? ry.y0 : ry.x0, ly = ry.steep ? ry.x0 : ry.y0;
+        CellWalk w(ry);
         int hx = -1, hy = -1;
-        double error = 0.0;                                           // bresenham.py:34
-        // A ray whose two end cells lie in the window stays in it (a Bresenham path never leaves the box
-        // of its ends): no bounds checks, the cell kept as ONE running halfword index, four steps per
-        // wave-wide loop test.  The path's last cell is the endpoint's cell (mapping.py:44-45); it takes the
-        // hit and no pass count, so the walk leaves it out: a reversed path (flag) starts one step in.
+        // A ray whose two end cells lie in the window stays in it: the unchecked walk (lds_walk).  The path's
+        // last cell is the endpoint's cell (mapping.py:44-45); it takes the hit and no pass count, so the walk
+        // leaves it out: a reversed path (flag) starts one step in.
         const int Hs = 2 * Hp2;
         const bool safe = (unsigned)(sc[s].pcx - wx0) < (unsigned)W && (unsigned)(sc[s].pcy - wy0) < (unsigned)H &&
                     (unsigned)(pox - wx0) < (unsigned)W && (unsigned)(poy - wy0) < (unsigned)H;
         // (a wave that also holds rays which leave the window walks all its rays the checked way: two loops
         // one after the other made the slowest workgroups - those whose half does not fit - slower)
         if (!__any(!safe)) {
-            {
-                // the cell as the LDS byte address of its 16-bit counter: dword = address & ~3, the count's
-                // position in it from address bit 1 (9 VALU + 1 LDS instructions per step; 14 + 1 + the
-                // per-step lane mask before)
-                unsigned a2 = lds_addr(win) + 2u * (unsigned)((lx - wx0) * Hs + (ly - wy0));
-                const int da_k = 2 * (ry.steep ? 1 : Hs), da_y = 2 * (ry.steep ? ry.ystep * Hs : ry.ystep);
-                int rem = ry.dx;                                      // pass cells: all but the path's last
-                auto advance = [&]() {
-                    error += ry.derr;                                 // bresenham.py:51
-                    const bool stepy = error >= 0.5;                  // :53
-                    a2 += (unsigned)(da_k + (stepy ? da_y : 0));
-                    error -= __hiloint2double(stepy ? 0x3ff00000 : 0, 0);   // :55 (minus 1.0, or minus 0.0: exact)
-                };
-                if (ry.flag) advance();                               // step 0 is the hit cell: start one step in
-                nvis += (unsigned)ry.dx + 1u;                         // every cell of the path is in the map
-                auto step = [&]() {
-                    lds_add_u32(a2 & ~3u, 1u << ((a2 << 3) & 31u));   // mapping.py:43
-                    advance();
-                };
-                for (;;) {                                            // four steps per wave-wide test, no lane mask inside
-                    const bool full = rem >= 4;
-                    if (!__any(full)) break;
-                    if (full) { step(); step(); step(); step(); rem -= 4; }
-                }
-#pragma unroll
-                for (int u = 0; u < 3; ++u)
-                    if (rem > u) step();
-                atomicAdd(&hit[(size_t)pox * g.yw + poy], 1u);        // mapping.py:45
-            }
+            const unsigned a2 = lds_addr(win) + 2u * (unsigned)((w.lx - wx0) * Hs + (w.ly - wy0));   // 16-bit counters
+            nvis += (unsigned)ry.dx + 1u;                             // every cell of the path is in the map
+            // pass cells: all but the path's last
+            lds_walk(a2, 2 * w.stride_k(Hs), 2 * w.stride_y(Hs), ry.dx, w.derr, w.error, ry.flag);
+            atomicAdd(&hit[(size_t)pox * g.yw + poy], 1u);            // mapping.py:45
             continue;
         }
-        for (int k = 0; k <= ry.dx; ++k) {                            // :45
-            bool last = k == klast;
+        for (int k = 0; k <= ry.dx; ++k, w.next()) {                  // bresenham.py:45
+            const int lx = w.lx, ly = w.ly;
+            bool last = k == w.klast;
             unsigned wx = (unsigned)(lx - wx0), wy = (unsigned)(ly - wy0);
             bool inwin = wx < (unsigned)W && wy < (unsigned)H;
             bool inmap = COVERS ? inwin : ((unsigned)lx < (unsigned)g.xw && (unsigned)ly < (unsigned)g.yw);   // mapping.py:41
@@ -440,11 +495,6 @@ __device__ __forceinline__ unsigned cast_rays(const GridDev &g, const Src &src, 
             hx = last ? lx : hx; hy = last ? ly : hy;
             if (inwin && !last) atomicAdd(&win[wx * Hp2 + (wy >> 1)], 1u << ((wy & 1u) * 16u));          // mapping.py:43
             if (!COVERS) { if (inmap && !inwin && !last) atomicAdd(&pass[(size_t)lx * g.yw + ly], 1u); }
-            error += ry.derr;                                         // bresenham.py:51
-            bool stepy = error >= 0.5;                                // :53
-            lx += ax_x + (stepy ? ay_x : 0);
-            ly += ax_y + (stepy ? ay_y : 0);
-            error -= __hiloint2double(stepy ? 0x3ff00000 : 0, 0);    // :55 (minus 1.0, or minus 0.0: exact)
         }
         if ((unsigned)hx < (unsigned)g.xw && (unsigned)hy < (unsigned)g.yw) atomicAdd(&hit[(size_t)hx * g.yw + hy], 1u);   // mapping.py:45
     }
@@ -464,39 +514,24 @@ __device__ __forceinline__ unsigned cast_rays_strip(const GridDev &g, const Src 
                                                     int first_bad)
 {
     unsigned nvis = 0;
-    const int lane = threadIdx.x & 63;
-    for (;;) {
-        int base = 0;
-        if (lane == 0) base = atomicAdd(next_ray, kWave);
-        base = __builtin_amdgcn_readfirstlane(base);
-        if (base >= nrays) break;
-        if (base + lane >= nrays) continue;
-        const int i = order ? (int)order[base + lane] : base + lane;   // longest rays first when sorted
+    for (int i; next_rays(next_ray, nrays, order, i);) {
+        if (i < 0) continue;
         int pox, poy, b2 = 0;
         Ray ry;
         if (i >= first_bad) continue;                                // beams from the first bad one on are not cast
         if (!src.ray(l, s0, i, sc, g, pox, poy, b2)) continue;
         if (max(sc.pcx, pox) < wx0 || min(sc.pcx, pox) >= wx0 + W) continue;   // never enters this strip
         if (!ray_setup(sc.pcx, sc.pcy, pox, poy, ry)) continue;
-        const int klast = ry.flag ? 0 : ry.dx;                       // walk step of the path's LAST cell
-        const int ax_x = ry.steep ? 0 : 1, ax_y = ry.steep ? 1 : 0;  // cell step per walk step ...
-        const int ay_x = ry.steep ? ry.ystep : 0, ay_y = ry.steep ? 0 : ry.ystep;   // ... and per y step
-        int lx = ry.steep ? ry.y0 : ry.x0, ly = ry.steep ? ry.x0 : ry.y0;
-        double error = 0.0;                                           // bresenham.py:34
-        for (int k = 0; k <= ry.dx; ++k) {                            // :45
-            const unsigned wx = (unsigned)(lx - wx0), wy = (unsigned)(ly - wy0);
+        CellWalk w(ry);
+        for (int k = 0; k <= ry.dx; ++k, w.next()) {                  // bresenham.py:45
+            const unsigned wx = (unsigned)(w.lx - wx0), wy = (unsigned)(w.ly - wy0);
             if (wx < (unsigned)W && wy < (unsigned)H) {               // in this strip (every in-map cell of the ray is in some strip)
                 ++nvis;                                               // mapping.py:41
                 unsigned *cell = &win[wx * Hp2 + (wy >> 1)];
                 const unsigned sh = (wy & 1u) * 16u;
-                if (k != klast) atomicAdd(cell, 1u << sh);            // mapping.py:43
-                else { atomicOr(cell, 0x8000u << sh); atomicAdd(&hit[(size_t)lx * g.yw + ly], 1u); }   // :45
+                if (k != w.klast) atomicAdd(cell, 1u << sh);          // mapping.py:43
+                else { atomicOr(cell, 0x8000u << sh); atomicAdd(&hit[(size_t)w.lx * g.yw + w.ly], 1u); }   // :45
             }
-            error += ry.derr;                                         // bresenham.py:51
-            const bool stepy = error >= 0.5;                          // :53
-            lx += ax_x + (stepy ? ay_x : 0);
-            ly += ax_y + (stepy ? ay_y : 0);
-            error -= __hiloint2double(stepy ? 0x3ff00000 : 0, 0);    // :55 (minus 1.0, or minus 0.0: exact)
         }
     }
     return nvis;
@@ -1003,12 +1038,12 @@ struct OwnRay {
     double error, derr;
     __device__ __forceinline__ void start(const Ray &rr, int H)
     {
-        k = 0; kend = rr.dx; klast = rr.flag ? 0 : rr.dx;
-        lx = rr.steep ? rr.y0 : rr.x0;
-        ly = rr.steep ? rr.x0 : rr.y0;
-        dlx_k = rr.steep ? 0 : 1; dlx_y = rr.steep ? rr.ystep : 0;
-        dh_k = rr.steep ? 1 : H;  dh_y = rr.steep ? rr.ystep * H : rr.ystep;
-        error = 0.0; derr = rr.derr;                                  // bresenham.py:34-35
+        const CellWalk w(rr);                                        // (its fields are kept here: the walk is suspended between strips)
+        k = 0; kend = rr.dx; klast = w.klast;
+        lx = w.lx; ly = w.ly;
+        dlx_k = w.ax_x; dlx_y = w.ay_x;
+        dh_k = w.stride_k(H); dh_y = w.stride_y(H);
+        error = w.error; derr = w.derr;
         h = 0;
     }
 };
@@ -1120,8 +1155,7 @@ __device__ __forceinline__ void owner_cast(const GridDev &g, const Src &src, int
 #pragma unroll
     for (int j = 0; j < kOwnerRays; ++j) {
         kind[j] = 0u; pox[j] = poy[j] = 0;
-        Ray rr;
-        rr.x0 = rr.y0 = 0; rr.dx = -1; rr.ystep = 1; rr.derr = 0.0; rr.steep = rr.flag = false;
+        Ray rr = Ray::none();
         ry[j].start(rr, H);                                          // kend = -1: never active
         const int sr = tid + j * (int)blockDim.x;
         if (sr >= n || strips == 0) continue;
@@ -1173,29 +1207,10 @@ __device__ __forceinline__ void owner_cast(const GridDev &g, const Src &src, int
                 const OwnRay &o = ry[j];
                 const bool mine = kind[j] == 1u && (pox[j] >= c0.pcx ? 1 : 0) == strip;
                 if (!__any(mine)) continue;
-                unsigned a2 = lds_addr(win) + 2u * (unsigned)((o.lx - sx0) * H + (o.ly - wy0));
-                const int da_k = 2 * o.dh_k, da_y = 2 * o.dh_y;
+                const unsigned a2 = lds_addr(win) + 2u * (unsigned)((o.lx - sx0) * H + (o.ly - wy0));
                 double error = 0.0;
-                int rem = mine ? o.kend : 0;                         // pass cells: all but the path's last
-                auto advance = [&]() {
-                    error += o.derr;
-                    const bool stepy = error >= 0.5;
-                    a2 += (unsigned)(da_k + (stepy ? da_y : 0));
-                    error -= __hiloint2double(stepy ? 0x3ff00000 : 0, 0);
-                };
-                if (mine && o.klast == 0) advance();                 // a reversed path: its first walk step is the hit cell
-                auto step = [&]() {
-                    lds_add_u32(a2 & ~3u, 1u << ((a2 << 3) & 31u));   // mapping.py:43
-                    advance();
-                };
-                for (;;) {
-                    const bool full = rem >= 4;
-                    if (!__any(full)) break;
-                    if (full) { step(); step(); step(); step(); rem -= 4; }
-                }
-#pragma unroll
-                for (int u = 0; u < 3; ++u)
-                    if (rem > u) step();
+                // pass cells: all but the path's last; a reversed path's first walk step is the hit cell
+                lds_walk(a2, 2 * o.dh_k, 2 * o.dh_y, mine ? o.kend : 0, o.derr, error, mine && o.klast == 0);
             }
         } else
 #pragma unroll
@@ -1220,11 +1235,9 @@ __device__ __forceinline__ void owner_cast(const GridDev &g, const Src &src, int
                     if (act) {
                         const bool cnt = ((unsigned)(o.lx - sx0) < (unsigned)SW) & (o.k != o.klast);
                         if (cnt) atomicAdd(&win[o.h >> 1], 1u << ((o.h & 1) * 16));   // mapping.py:43
-                        o.error += o.derr;                           // bresenham.py:51
-                        const bool stepy = o.error >= 0.5;           // :53
+                        const bool stepy = walk_step(o.error, o.derr);
                         o.h += o.dh_k + (stepy ? o.dh_y : 0);
                         o.lx += o.dlx_k + (stepy ? o.dlx_y : 0);
-                        o.error -= __hiloint2double(stepy ? 0x3ff00000 : 0, 0);   // :55 (minus 1.0, or minus 0.0: exact)
                         ++o.k;
                     }
                 }
@@ -1250,8 +1263,7 @@ __device__ __forceinline__ void owner_cast(const GridDev &g, const Src &src, int
                         ++nvis;
                         atomicAdd(&win[wx * Hp2 + (wy >> 1)], 1u << ((wy & 1u) * 16u));
                     }
-                    error += rr.derr;
-                    if (error >= 0.5) { y += rr.ystep; error -= 1.0; }
+                    if (walk_step(error, rr.derr)) y += rr.ystep;
                 }
             }
         }
@@ -1515,8 +1527,7 @@ __global__ void __launch_bounds__(THREADS, (kOwn8PerCU * THREADS + 255) / 256) k
     const bool have = tid < nv;
     const unsigned e = have ? slots[tid] : 0u;
     const int ex = (int)(e & 0xffffu), ey = (int)(e >> 16);
-    Ray rr;
-    rr.x0 = rr.y0 = 0; rr.dx = 1; rr.ystep = 1; rr.derr = 0.0; rr.steep = rr.flag = false;
+    Ray rr = Ray::none();
     if (have) (void)ray_setup(c0.pcx, c0.pcy, ex, ey, rr);
     const unsigned wbase = lds_addr(win);
     if (have) {                                                      // the path's last cell is the end cell: the hit (mapping.py:44-45)
@@ -1526,30 +1537,9 @@ __global__ void __launch_bounds__(THREADS, (kOwn8PerCU * THREADS + 255) / 256) k
     {
         // the walk (bresenham.py:45-55) without its two end steps: walk step 0 is the origin cell (or, for a
         // reversed path, the hit cell) and step dx the hit cell (or the origin): dx - 1 cells in between
-        const int lx = rr.steep ? rr.y0 : rr.x0, ly = rr.steep ? rr.x0 : rr.y0;
-        unsigned a = wbase + (unsigned)((lx - x0) * Hs + (ly - y4));
-        const int da_k = rr.steep ? 1 : Hs, da_y = rr.steep ? rr.ystep * Hs : rr.ystep;
-        double error = 0.0;                                          // bresenham.py:34
-        int rem = have ? rr.dx - 1 : 0;
-        auto advance = [&]() {
-            error += rr.derr;                                        // :51
-            const bool stepy = error >= 0.5;                         // :53
-            a += (unsigned)(da_k + (stepy ? da_y : 0));
-            error -= __hiloint2double(stepy ? 0x3ff00000 : 0, 0);    // :55 (minus 1.0, or minus 0.0: exact)
-        };
-        auto step = [&]() {
-            lds_add_u32(a & ~3u, 1u << ((a << 3) & 31u));            // mapping.py:43
-            advance();
-        };
-        if (have) advance();
-        for (;;) {                                                   // four steps per wave-wide test, no lane mask inside
-            const bool full = rem >= 4;
-            if (!__any(full)) break;
-            if (full) { step(); step(); step(); step(); rem -= 4; }
-        }
-#pragma unroll
-        for (int u = 0; u < 3; ++u)
-            if (rem > u) step();
+        CellWalk w(rr);
+        const unsigned a = wbase + (unsigned)((w.lx - x0) * Hs + (w.ly - y4));   // byte counters
+        lds_walk(a, w.stride_k(Hs), w.stride_y(Hs), have ? rr.dx - 1 : 0, w.derr, w.error, have);
     }
     __syncthreads();
     STAMP(3);
@@ -1883,10 +1873,7 @@ __global__ void __launch_bounds__(256) k_ray_bits(GridDev g, Src src, TileScratc
                     // the recurrence after them - so there is no lane mask per step)
 #pragma unroll 8
                     for (int b = 0; b < 32; ++b) {
-                        error += derr;                                // bresenham.py:51
-                        const bool stepy = error >= 0.5;              // :53
-                        error -= __hiloint2double(stepy ? 0x3ff00000 : 0, 0);   // :55 (minus 1.0, or minus 0.0: exact)
-                        word |= stepy ? (1u << b) : 0u;
+                        word |= walk_step(error, derr) ? (1u << b) : 0u;
                     }
                     if (nb < 32) word &= (1u << nb) - 1u;
                     pw[k0 >> 5] = (unsigned short)count;
@@ -1908,9 +1895,10 @@ __global__ void __launch_bounds__(256) k_ray_bits(GridDev g, Src src, TileScratc
         }
         if (valid && !plain) {                                       // leaves the map, or too long to record: the step-by-step form
             const bool record = ry.dx < kTileSteps;
-            const int klast = ry.flag ? 0 : ry.dx;
             uint32_t *bw = ts.bits + rid * kTileWords;
             unsigned short *pw = ts.prefix + rid * kTileWords;
+            // (x0 + k, y and walk_step, not CellWalk: with it the compiler allots this kernel 4 more VGPRs)
+            const int klast = ry.flag ? 0 : ry.dx;
             double error = 0.0;
             int y = ry.y0, hx = -1, hy = -1;
             uint32_t word = 0, count = 0;
@@ -1923,9 +1911,7 @@ __global__ void __launch_bounds__(256) k_ray_bits(GridDev g, Src src, TileScratc
                 if (k == klast) { hx = lx; hy = ly; }
                 else if (!record && inmap) atomicAdd(&pass[(size_t)lx * g.yw + ly], 1u);
                 if (k == ry.dx) rec.yend = y;
-                error += ry.derr;
-                bool stepy = error >= 0.5;
-                if (stepy) { y += ry.ystep; error -= 1.0; word |= 1u << (k & 31); ++count; }
+                if (walk_step(error, ry.derr)) { y += ry.ystep; word |= 1u << (k & 31); ++count; }
                 if (record && ((k & 31) == 31 || k == ry.dx)) { bw[k >> 5] = word; word = 0; }
             }
             if ((unsigned)hx < (unsigned)g.xw && (unsigned)hy < (unsigned)g.yw) atomicAdd(&hit[(size_t)hx * g.yw + hy], 1u);
@@ -2276,8 +2262,7 @@ __global__ void __launch_bounds__(1024) k_wedge_sort(GridDev g, Src src, WedgeSc
                 nvis += inmap ? 1u : 0u;
                 if (k == klast) { hx = lx; hy = ly; }
                 else if (inmap) atomicAdd(&pass[(size_t)lx * g.yw + ly], 1u);
-                error += ry.derr;
-                if (error >= 0.5) { y += ry.ystep; error -= 1.0; }
+                if (walk_step(error, ry.derr)) y += ry.ystep;
             }
             if ((unsigned)hx < (unsigned)g.xw && (unsigned)hy < (unsigned)g.yw) atomicAdd(&hit[(size_t)hx * g.yw + hy], 1u);
         }
@@ -2420,8 +2405,7 @@ __global__ void __launch_bounds__(kWedgeThreads, 2 * kWedgeThreads / 256) k_wedg
                 w.x0 = ry.x0; w.y = ry.y0; w.ystep = ry.ystep; w.derr = ry.derr;
                 w.k = 0; w.kend = ry.dx - 1;                             // walk steps 0 .. dx - 1 pass, step dx is the hit ...
                 if (ry.flag) {                                           // ... or, for a reversed path, step 0 is the hit: start one step in
-                    w.error += w.derr;                                   // bresenham.py:51-55
-                    if (w.error >= 0.5) { w.y += w.ystep; w.error -= 1.0; }
+                    if (walk_step(w.error, w.derr)) w.y += w.ystep;
                     w.k = 1; w.kend = ry.dx;
                 }
                 if (w.k <= w.kend) { amin = min(amin, w.x0 + w.k); amax = max(amax, w.x0 + w.kend); }
@@ -2481,8 +2465,7 @@ __global__ void __launch_bounds__(kWedgeThreads, 2 * kWedgeThreads / 256) k_wedg
                     while (w.k <= w.kend && w.x0 + w.k < a_lo + rows) {
                         const int a = w.x0 + w.k;
                         atomicAdd(&pass[steep ? (size_t)w.y * g.yw + a : (size_t)a * g.yw + w.y], 1u);   // mapping.py:43
-                        w.error += w.derr;                               // bresenham.py:51-55
-                        if (w.error >= 0.5) { w.y += w.ystep; w.error -= 1.0; }
+                        if (walk_step(w.error, w.derr)) w.y += w.ystep;
                         ++w.k;
                     }
                 }
@@ -2506,17 +2489,17 @@ __global__ void __launch_bounds__(kWedgeThreads, 2 * kWedgeThreads / 256) k_wedg
                 int rem = (w.k <= w.kend && a_in < a_lo + rows) ? min(w.x0 + w.kend, a_lo + rows - 1) - a_in + 1 : 0;
                 if (!__any(rem > 0)) continue;
                 unsigned a2 = wbase + 2u * (unsigned)((a_in - a_lo) * ca + (w.y - M * a_in - v_lo) * cv);
+                // lds_walk's loop with y carried along, kept here: through lds_walk (y as one more in/out parameter) the
+                // compiler allots this kernel 115 VGPRs instead of 125 and moves the band geometry to the scalar unit
                 const int da_k = 2 * dh_a, da_y = 2 * w.ystep * cv;
-                double error = w.error;
+                double error = w.error;                                  // resumes where the previous band ended
                 int y = w.y;
                 const int took = rem;
                 auto step = [&]() {
                     lds_add_u32(a2 & ~3u, 1u << ((a2 << 3) & 31u));      // mapping.py:43
-                    error += w.derr;                                     // bresenham.py:51
-                    const bool stepy = error >= 0.5;                     // :53
+                    const bool stepy = walk_step(error, w.derr);
                     a2 += (unsigned)(da_k + (stepy ? da_y : 0));
                     y += stepy ? w.ystep : 0;
-                    error -= __hiloint2double(stepy ? 0x3ff00000 : 0, 0);   // :55 (minus 1.0, or minus 0.0: exact)
                 };
                 for (;;) {
                     const bool full = rem >= 4;
@@ -2773,8 +2756,7 @@ __global__ void __launch_bounds__(256) k_bresenham(const int32_t *__restrict__ s
         int j = r.flag ? r.dx - k : k;                               // path.reverse(), :57-58
         out[2 * (size_t)j] = r.steep ? y : x;
         out[2 * (size_t)j + 1] = r.steep ? x : y;
-        error += r.derr;
-        if (error >= 0.5) { y += r.ystep; error -= 1.0; }
+        y += walk_step(error, r.derr) ? r.ystep : 0;
     }
 }
 

@@ -494,6 +494,69 @@ def test_single_scan_byte_window_kernel_cases(slam, case):
     ctx.close()
 
 
+def _short_ray_scene(org, scale, off):
+    """Endpoints 0 .. 9 cells from the cell `org` in each of the eight octants (slopes about 1/2: ties of the
+    error term at 0.5 and lines without one) and along the four axes, as cell offsets and as world coordinates."""
+    offs = []
+    for d in range(10):
+        b = (d + 1) // 2
+        offs += [(sx * d, sy * b) for sx in (1, -1) for sy in (1, -1)] + [(sx * b, sy * d) for sx in (1, -1) for sy in (1, -1)]
+        offs += [(d, 0), (-d, 0), (0, d), (0, -d)]
+    ox = np.array([(org[0] + o[0] + 0.5) / scale - off for o in offs])
+    oy = np.array([(org[1] + o[1] + 0.5) / scale - off for o in offs])
+    return offs, ox, oy, (org[0] + 0.5) / scale - off, (org[1] + 0.5) / scale - off
+
+
+@pytest.mark.parametrize("org", [(32, 32), (3, 60)], ids=["inside", "half_leave_map"])
+def test_short_rays_every_octant_every_engine(slam, org):
+    """One scan of 120 beams that end 0 .. 9 cells from the origin cell in every octant and along the axes, cast into
+    a 64 x 64 map by every engine: grid_mode 0 (direct), 1 (automatic: window), 2 (tiles), 3 (window), 4 (wedges),
+    and as a single scan into a map with a live pmap (byte-window kernel; with the origin at (3, 60), where the
+    octants towards -x and +y leave the map, that kernel hands over to the general owner kernel).  Paths this short
+    are the edges of the shared unchecked walk: the lead-in step of a reversed path and the tail of 0 - 3 steps
+    behind the blocks of four.  Pass / hit counters and pmap equal oracle_np's Mapping.update, two passes."""
+    from oracle import oracle_np as on
+    xw = yw = 64
+    scale, off = 10.0, 1.0
+    offs, ox, oy, cx, cy = _short_ray_scene(org, scale, off)
+    assert len(offs) == 120
+    # the scene holds what it is for (bresenham.py:14-32, ray_setup's rule, from the cells Mapping.update computes):
+    # reversed paths (flag) and forward ones with every run length dx mod 4, steep and not
+    seen = set()
+    pc = (int(scale * (cx + off)), int(scale * (cy + off)))
+    assert pc == org
+    for x, y in zip(ox, oy):
+        sx, sy, ex, ey = pc[0], pc[1], int(scale * (x + off)), int(scale * (y + off))
+        if (sx, sy) == (ex, ey):
+            seen.add("empty")
+            continue
+        steep = abs(ey - sy) > abs(ex - sx)
+        if steep:
+            sx, sy, ex, ey = sy, sx, ey, ex
+        seen.add((sx > ex, abs(ex - sx) % 4, steep))
+    assert "empty" in seen and all((f, m, st) in seen for f in (False, True) for m in range(4) for st in (False, True))
+    want = on.Mapping(xw, yw, 1.0 / scale, scale, off, off)
+    want.update(ox, oy, cx, cy)
+    pass1, hit1, pmap1 = want.pass_cnt.copy(), want.hit_cnt.copy(), want.pmap.copy()
+    want.update(ox, oy, cx, cy)
+    assert pass1.sum() > 100 and (org == (32, 32)) == (hit1.sum() == 108)    # (3, 60): some end cells lie outside the map
+    for mode, live in [(0, False), (1, False), (2, False), (3, False), (4, False), (1, True)]:
+        ctx = slam.Context(0)
+        ctx.set_option("grid_mode", mode)
+        g = slam.DeviceGrid(1, xw, yw, scale, off, off, context=ctx)
+        if live:
+            g.live_pmap()
+        for k, (p_, h_, m_) in enumerate([(pass1, hit1, pmap1), (want.pass_cnt, want.hit_cnt, want.pmap)]):
+            g.update_host(ox, oy, cx, cy)
+            ctx.check_status()
+            r = g.read(0, want=("pmap", "pass", "hit"))
+            assert np.array_equal(r["pass"], p_), (mode, live, k, np.argwhere(r["pass"] != p_)[:8].tolist())
+            assert np.array_equal(r["hit"], h_), (mode, live, k, np.argwhere(r["hit"] != h_)[:8].tolist())
+            assert np.array_equal(r["pmap"], m_), (mode, live, k)
+        g.close()
+        ctx.close()
+
+
 @pytest.mark.parametrize("case", ["random_ranges", "inf_and_tiny", "span_270deg", "span_over_one_turn", "quantised_ties",
                                   "near_origin", "n2", "n9", "n63", "nan_ranges", "f16_random", "f32_room"])
 def test_scan_window_nearest_neighbour_edge_scans(slam, syn, case):
