@@ -1433,6 +1433,35 @@ __host__ __device__ inline size_t icp_wave_lds_bytes(int n_tar, int cap)
            (size_t)cap * (sizeof(double2) + sizeof(int));
 }
 
+// The distance of a match in this shape (match_distance for the lanes that are active here): a float64 square root
+// without the range scaling.  What the compiler makes of sqrt(double) is
+//   s = x < 2^-767 ? 256 : 0;  X = ldexp(x, s);  y = rsq(X);  g = X y;  h = y / 2;  r = fma(-h, g, 1/2);
+//   g = fma(g, r, g);  h = fma(h, r, h);  twice g = fma(fma(-g, g, X), h, g);  result ldexp(g, -s / 2), or X itself when X is
+//   0 or infinite
+// - 18 vector instructions, of which the two ldexp, the selects of s and the class test only serve squares below 2^-767,
+// zero and infinity.  sqrt_unscaled() is that sequence for s = 0, operation for operation (ldexp(x, 0) is x): the same bits
+// as sqrt() for every finite x >= 2^-767 - correctly rounded wherever sqrt() is.  Accepted here: 2^-766 <= x < 2^400, one
+// unsigned compare of the high word (anything negative, NaN, infinite, zero or subnormal lies outside); squares of scan
+// matches lie in [0, 1e4] m^2.  A wave in which an active lane holds anything else - an exact zero, a never-won query's
+// infinity - takes match_distance() as before: wave-uniform, so the usual wave issues the ten instructions alone.
+__device__ __forceinline__ double sqrt_unscaled(double x)
+{
+    const double y = __builtin_amdgcn_rsq(x);
+    double g = x * y, h = y * 0.5;
+    const double r = fma(-h, g, 0.5);
+    g = fma(g, r, g);
+    h = fma(h, r, h);
+    g = fma(fma(-g, g, x), h, g);
+    return fma(fma(-g, g, x), h, g);
+}
+constexpr unsigned kSqrtLoHi = 0x10100000u, kSqrtHiHi = 0x58F00000u;   // high words of 2^-766 and 2^400
+__device__ __forceinline__ double match_distance_wave(double d2)       // by the lanes whose query exists, under their exec mask
+{
+    const bool in = (unsigned)__double2hiint(d2) - kSqrtLoHi < kSqrtHiHi - kSqrtLoHi;
+    if (__any(!in)) return match_distance(d2);
+    return sqrt_unscaled(d2);
+}
+
 template <typename T, bool EXACT>
 __device__ __forceinline__ bool icp_pair_wave(const IcpArgs &a, const int b, char *smem)
 {
@@ -1521,9 +1550,11 @@ __device__ __forceinline__ bool icp_pair_wave(const IcpArgs &a, const int b, cha
             if (q * kWave >= n_src) continue;
             const bool okq = lane + q * kWave < n_src;
             const double2 m = tarP[seed[q]];
-            const double dq = match_distance(dist2(sx[q], sy[q], m.x, m.y));   // what the search found for this match
             same.step(q, okq, seed[q], m.x, m.y);
-            if (okq) { add_points(v, sx[q], sy[q], m.x, m.y); v[4] += dq; }
+            if (okq) {
+                add_points(v, sx[q], sy[q], m.x, m.y);
+                v[4] += match_distance_wave(dist2(sx[q], sy[q], m.x, m.y));   // what the search found for this match
+            }
         }
         const Centroids c = centroids_from_totals(wave_reduce8(v, ls), dn, &s.mean_error);
         const bool tar_collapsed = !same.wave_differs();
@@ -1553,7 +1584,7 @@ __device__ __forceinline__ bool icp_pair_wave(const IcpArgs &a, const int b, cha
             seed[q] = h.j;                                           // next iteration's guess
             const double2 m = tarP[h.j];
             same.step(q, okq, h.j, m.x, m.y);
-            if (okq) add_one_pass(u, sx[q], sy[q], m.x, m.y, match_distance(h.d2), s.pcx, s.pcy);
+            if (okq) add_one_pass(u, sx[q], sy[q], m.x, m.y, match_distance_wave(h.d2), s.pcx, s.pcy);
         }
         const OnePass o = one_pass_totals(wave_reduce8(u, ls), dn, s);
         advance(rigid_from_w(o.c, o.A, 0.0, o.B, 0.0, !same.wave_differs() || src_collapsed, lane), o.c.bx, o.c.by, sx, sy, s);
