@@ -163,15 +163,16 @@ def host_filter(slam, u, z, x0=None):
     return x[:, 0], P, nlm, status
 
 
-def check_filter(slam, cases, max_lm):
+def check_filter(slam, cases, max_lm, host=host_filter):
+    """One slam_ekf_lm call over `cases` against `host` (host_filter, or a function that returns what it would)."""
     out = slam.ekf_lm_host([c["u"] for c in cases], [c["z"] for c in cases], x0=[c.get("x0", (0, 0, 0)) for c in cases],
                            max_lm=max_lm)
     refs = []
     for b, c in enumerate(cases):
         # a trajectory that would pass max_lm stops before that step: the host class runs the steps before it
-        x, P, nlm, status = host_filter(slam, c["u"], c["z"], c.get("x0"))
+        x, P, nlm, status = host(slam, c["u"], c["z"], c.get("x0"))
         if c.get("cap_at") is not None:
-            x, P, nlm, status = host_filter(slam, c["u"][:c["cap_at"]], c["z"][:c["cap_at"]], c.get("x0"))
+            x, P, nlm, status = host(slam, c["u"][:c["cap_at"]], c["z"][:c["cap_at"]], c.get("x0"))
             status = 2
         n = len(x)
         assert out["status"][b] == status, b
