@@ -41,14 +41,17 @@ def stream_solves(ranges, angle_min, angle_max, max_iter=30, tol=0.001):
     return t1, t2
 
 
-def chain(ranges, obstacle, angle_min, angle_max, pose0=(0.0, 0.0, 0.0), max_iter=30, tol=0.001, solves=None, nudge=0.0):
+def chain(ranges, obstacle, angle_min, angle_max, pose0=(0.0, 0.0, 0.0), max_iter=30, tol=0.001, solves=None, nudge=0.0,
+          angle_increment=None):
     """The node over one stream ``ranges [n_scan, n]`` against ``obstacle [2, K]`` from ``pose0``.
     ``solves``: what :func:`stream_solves` returned (computed when None).  ``nudge`` is added to every
-    component of xEst after every step (the stability probe of the tests).  Returns dict of ``xest``,
+    component of xEst after every step (the stability probe of the tests).  ``angle_increment``: the message's
+    own, which bins the virtual scan (localization.py:139) while the points of both scans come from
+    linspace(angle_min, angle_max) (:170-176); None: (angle_max - angle_min) / (n - 1).  Returns dict of ``xest``,
     ``xodom`` [n_scan, 3], ``P`` [3, 3], ``T_obs``, ``T_odom`` [n_scan, 3, 3], ``iters_obs`` [n_scan]."""
     ranges = np.asarray(ranges)
     n_scan, n = ranges.shape
-    inc = (angle_max - angle_min) / (n - 1)
+    inc = (angle_max - angle_min) / (n - 1) if angle_increment is None else float(angle_increment)
     t1s, t2s = solves if solves is not None else stream_solves(ranges, angle_min, angle_max, max_iter, tol)
     xest, xodom, pest = [float(v) for v in pose0], [float(v) for v in pose0], np.eye(3)
     out = {"xest": [], "xodom": [], "T_obs": [], "T_odom": [], "iters_obs": []}
@@ -71,18 +74,27 @@ def chain(ranges, obstacle, angle_min, angle_max, pose0=(0.0, 0.0, 0.0), max_ite
     return o
 
 
-def stable(ranges, obstacle, angle_min, angle_max, pose0=(0.0, 0.0, 0.0), eps=1e-11, bound=1e-10):
+def stable(ranges, obstacle, angle_min, angle_max, pose0=(0.0, 0.0, 0.0), eps=1e-11, bound=1e-10, max_iter=30, tol=0.001,
+           angle_increment=None):
     """(reference run, worst deviation of the runs nudged by +-eps): the chain is discontinuous where an
     obstacle changes its beam bin or a nearest neighbour changes; inputs are usable when the worst
-    deviation stays below ``bound``."""
-    solves = stream_solves(ranges, angle_min, angle_max)
-    ref = chain(ranges, obstacle, angle_min, angle_max, pose0, solves=solves)
+    deviation stays below ``bound``.  The nudge accumulates by eps a step, so a run of n_scan steps is
+    judged against :func:`stable_bound`; the default ``bound`` is that of the 8-step runs at eps = 1e-11."""
+    kw = dict(max_iter=max_iter, tol=tol, angle_increment=angle_increment)
+    solves = stream_solves(ranges, angle_min, angle_max, max_iter, tol)
+    ref = chain(ranges, obstacle, angle_min, angle_max, pose0, solves=solves, **kw)
     worst = 0.0
     for e in (eps, -eps):
-        o = chain(ranges, obstacle, angle_min, angle_max, pose0, solves=solves, nudge=e)
+        o = chain(ranges, obstacle, angle_min, angle_max, pose0, solves=solves, nudge=e, **kw)
         if not np.array_equal(o["iters_obs"], ref["iters_obs"]):
             return ref, float("inf")
         for k in ("xest", "xodom", "P", "T_obs", "T_odom"):
             # the nudge itself moves xest by eps per step; what must not happen is a jump
             worst = max(worst, float(np.max(np.abs(o[k] - ref[k]))))
     return ref, worst
+
+
+def stable_bound(eps, n_scan):
+    """What a run of ``n_scan`` steps nudged by ``eps`` a step may deviate by without a jump: the accumulated
+    nudge is eps * n_scan, the filter and the compositions pass it on with gains near 1; 4x leaves room."""
+    return 4.0 * eps * n_scan

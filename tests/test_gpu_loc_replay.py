@@ -12,12 +12,10 @@ import pytest
 
 import loc_ref
 from conftest import load_golden, pkg
+from loc_cases import AMAX, AMIN, GUARD, make_stream, pick, same_bits
 from oracle import oracle_np as on
 
 pytestmark = pytest.mark.gpu
-AMIN, AMAX = -3.14159, 3.14159
-KEYS = ("xest", "xodom", "P", "status", "T_obs", "iters_obs", "T_odom")
-GUARD = 0x5A                     # the fill of the bounds tests (test_gpu_operator_bounds.py)
 
 
 @pytest.fixture(scope="module")
@@ -35,18 +33,6 @@ def g5():
 @pytest.fixture(scope="module")
 def wall(g5):
     return np.ascontiguousarray(g5["obs_wall"])
-
-
-def make_stream(syn, seed, n, steps=8):
-    """A seeded drive through the empty 10 m x 8 m room whose walls ``obs_wall`` lists -> (ranges [steps, n], pose0)."""
-    rng = np.random.default_rng(seed)
-    p = np.array([rng.uniform(-1, 1), rng.uniform(-1, 1), rng.uniform(-0.5, 0.5)])
-    v, w = rng.uniform(0.02, 0.06), rng.uniform(-0.02, 0.02)
-    poses = [p]
-    for _ in range(steps - 1):
-        p = poses[-1]
-        poses.append(np.array([p[0] + v * np.cos(p[2]), p[1] + v * np.sin(p[2]), p[2] + w]))
-    return syn.scans_from_poses(syn.World(5.0, 4.0, (), 0.0), np.array(poses), n, seed), poses[0]
 
 
 def scan_msg(slam, ranges, n):
@@ -73,16 +59,17 @@ def host_class_run(slam, ranges, obstacle, pose0):
     return out
 
 
-def operator_target_points(slam, obstacle, pose, n):
-    """slam_virtual_scan + slam_scan_to_points_f64 at one pose -> [2, n]."""
+def operator_target_points(slam, obstacle, pose, n, angle_increment=None):
+    """slam_virtual_scan + slam_scan_to_points_f64 at one pose -> [2, n]; ``angle_increment``: the caller's own."""
     loc = slam.Localization()
     loc.obstacle = np.asarray(obstacle, dtype=np.float64).reshape(2, -1)
-    msg = types.SimpleNamespace(ranges=[0.0] * n, angle_min=AMIN, angle_max=AMAX, angle_increment=(AMAX - AMIN) / (n - 1))
+    msg = types.SimpleNamespace(ranges=[0.0] * n, angle_min=AMIN, angle_max=AMAX,
+                                angle_increment=(AMAX - AMIN) / (n - 1) if angle_increment is None else angle_increment)
     r = loc.virtual_ranges(msg, np.asarray(pose, dtype=np.float64).reshape(1, 3))[0]
     return loc.laserToNumpy(types.SimpleNamespace(ranges=r, angle_min=AMIN, angle_max=AMAX))[:2], r
 
 
-def check_targets(slam, o, maps, map_of_traj, pose0, n):
+def check_targets(slam, o, maps, map_of_traj, pose0, n, angle_increment=None):
     """Every step's target points == the existing operators at the xEst the step started from (bit for bit)."""
     L, n_scan = o["xest"].shape[:2]
     for l in range(L):
@@ -90,16 +77,8 @@ def check_targets(slam, o, maps, map_of_traj, pose0, n):
             if s and not np.all(np.isfinite(o["xest"][l, s - 1])):
                 break
             pose = pose0[l] if s == 0 else o["xest"][l, s - 1]
-            want, _ = operator_target_points(slam, maps[map_of_traj[l]], pose, n)
+            want, _ = operator_target_points(slam, maps[map_of_traj[l]], pose, n, angle_increment)
             assert np.array_equal(o["tar_pts"][l, s], want), (l, s)
-
-
-def same_bits(a, b, keys=KEYS):
-    return all(a[k].tobytes() == b[k].tobytes() for k in keys)
-
-
-def pick(o, idx, keys=KEYS):
-    return {k: np.ascontiguousarray(o[k][idx]) for k in keys}
 
 
 # ---- 1. the reference's own run -----------------------------------------------------------------
