@@ -154,6 +154,13 @@ __device__ __forceinline__ unsigned wave_sum_u32(unsigned v)
     return v;
 }
 
+__device__ __forceinline__ int wave_or_i32(int v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v |= __shfl_xor(v, off, kWave);
+    return v;
+}
+
 // Tail of the direct kernel (k_grid_update): per-wave aggregation of the origin cell and of
 // the visit counter, and the sticky status word.
 __device__ __forceinline__ void finish_wave(const GridDev &g, uint32_t *pass, int pcx, int pcy, bool first_pending,
@@ -161,9 +168,7 @@ __device__ __forceinline__ void finish_wave(const GridDev &g, uint32_t *pass, in
 {
     unsigned long long m = __ballot(first_pending);
     unsigned tot = wave_sum_u32(nvis);
-    int anybad = bad;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) anybad |= __shfl_xor(anybad, off, kWave);
+    const int anybad = wave_or_i32(bad);
     if ((threadIdx.x & 63) == 0) {
         if (m) atomicAdd(&pass[(size_t)pcx * g.yw + pcy], (unsigned)__popcll(m));
         if (tot) atomicAdd(visit_slot(g.visits), (unsigned long long)tot);
@@ -188,6 +193,14 @@ __device__ __forceinline__ void finish_wave(const GridDev &g, uint32_t *pass, in
 // origins and endpoints (clamped to the map) when that fits, else a sub-rectangle of it
 // around the first origin; cells of a ray outside the window fall back to direct global
 // atomics, so the result is exact for any window.
+//
+// Which kernel casts a launch (launch_win; first match wins):
+//   the map's only writer (live pmap, one group, one stream or a map per stream), one scan, one hit occupies, rows of a
+//   multiple of 16 cells of which one fits the window, and
+//       at most 384 beams, a re-do list      k_grid_update_owner8, then k_grid_update_owner_redo for what it left
+//       at most 1 024 beams                  k_grid_update_owner (one or two rays per lane)
+//   the map's only writer otherwise          k_grid_update_own (several scans: "grid_group"; more beams; three hit levels)
+//   a map that other workgroups write too    k_grid_update_win (groups of scans of a replay)
 // ---------------------------------------------------------------------------------
 // Between a workgroup's own global atomics and its plain loads of the same cells: every wave waits
 // for its atomics to be acknowledged, then the workgroup barrier.  The map belongs to this
@@ -537,8 +550,22 @@ __device__ __forceinline__ unsigned cast_rays_strip(const GridDev &g, const Src 
     return nvis;
 }
 
-constexpr int kWinPhase = 48 + 64;     // box[]: from here the phases of k_grid_update_win (windows [4][8], phase of a quadrant [4], boundaries in the sorted order [5])
-constexpr int kWinBoxInts = kWinPhase + 48;   // bbox[4], flags; from [16]: the boxes of the four direction quadrants; from [48]: every scan's first bad beam (k_grid_update_win)
+// Control block of a window workgroup, in LDS behind the scan constants.  k_grid_update_win uses all of it, k_grid_update_own
+// what is not about quadrants and phases.
+struct WinCtl {
+    int bbox[4];                     // x0, y0, x1, y1 of everything the group's rays can touch
+    int qbox[4][4];                  // the same for the rays of each direction quadrant
+    int next_ray;                    // rays handed out so far (next_rays)
+    int strips, strip_w;             // single-scan owner form: number of strips of the box and their rows (0: not that form)
+    int phases, parity;              // windows this workgroup fills one after the other; rays shared by beam parity
+    alignas(8) unsigned long long visits;   // of the whole workgroup: ONE global add, at the very end
+    int first_bad[kWinMaxGroup];     // every scan's first beam that Python's int() would raise on
+    int phw[4][8];                   // window of a phase: x0, y0, W, H, covers
+    int phq[4];                      // phase of a quadrant's rays (-1: not this workgroup's)
+    int seg[5];                      // boundaries of the phases in the sorted order
+};
+constexpr int kWinBoxInts = 160;     // ints of LDS set aside for the control block
+static_assert(sizeof(WinCtl) <= kWinBoxInts * 4 && alignof(WinCtl) <= 16, "the control block outgrew its LDS region");
 __host__ __device__ inline size_t win_sc_bytes(int group) { return ((size_t)group * sizeof(ScanConst) + 15) & ~(size_t)15; }
 __host__ __device__ inline int win_sort_cap(long rays) { return rays <= kMaxSortRays ? (int)((rays + 7) & ~7L) : 0; }   // 16-byte multiple
 __host__ __device__ inline size_t win_lds_bytes(int group, int sort_cap, int win_cells)
@@ -556,66 +583,31 @@ inline int win_cells_for(int group, int sort_cap)
     return cells > kWinCells ? (int)cells : kWinCells;
 }
 
-template <class Src>
-__global__ void __launch_bounds__(1024) k_grid_update_win(GridDev g, Src src, int group_size, const int32_t *__restrict__ got,
-                                                          int exclusive, int sort_cap, int win_cells, int split)
+// The LDS regions of a window workgroup, carved for the launch's group size (win_lds_bytes): a small group leaves room
+// for a second workgroup on the CU.
+struct WinLds {
+    ScanConst *sc; WinCtl *ctl; int *hist; unsigned short *order; unsigned *win; char *guard;
+    __device__ __forceinline__ WinLds(char *smem, int group_size, int sort_cap, int win_cells)
+        : sc(reinterpret_cast<ScanConst *>(smem)),                                       // [group_size]
+          ctl(reinterpret_cast<WinCtl *>(smem + win_sc_bytes(group_size))),
+          hist(reinterpret_cast<int *>(ctl) + kWinBoxInts),                              // [4][kSortBins]: (phase, length bin)
+          order(reinterpret_cast<unsigned short *>(hist + 4 * kSortBins)),               // [sort_cap]
+          win(reinterpret_cast<unsigned *>(order + sort_cap)),                           // [W][Hp2] dwords of two 16-bit cells
+          guard(reinterpret_cast<char *>(win) + (size_t)win_cells * 2) {}
+};
+
+// Pass 1 of a window workgroup: the bounding box of everything the group's rays can touch (into bbox, which the caller
+// has set to the empty box), every scan's first bad beam, whose own error is raised, and - when the rays are going to
+// be sorted - park(r, i, casts, quad, lbin) for every ray r (beam i of its scan): whether it has anything to cast, its
+// direction quadrant (bit 0: end cell right of the origin or in its column, bit 1: above it or in its row) and its
+// length bin, longest first.  One barrier, before the errors are raised.
+template <class Src, class Park>
+__device__ __forceinline__ void win_pass1(const GridDev &g, const Src &src, const ScanConst *sc, int l, int s0, int cnt, int n,
+                                          bool sorted, int *bbox, int *first_bad, Park &&park)
 {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    // LDS is carved for this launch's group size (win_lds_bytes): a small group leaves room for a
-    // second workgroup on the CU
-    ScanConst *sc = reinterpret_cast<ScanConst *>(smem);                                  // [group_size]
-    int *box = reinterpret_cast<int *>(smem + win_sc_bytes(group_size));                  // bbox[4], window[4], flags
-    int *hist = box + kWinBoxInts;                                                        // [4][kSortBins]: (phase, length bin)
-    unsigned short *order = reinterpret_cast<unsigned short *>(hist + 4 * kSortBins);     // [sort_cap]
-    unsigned *win = reinterpret_cast<unsigned *>(order + sort_cap);                       // [W][Hp/2] dwords
-    char *guard = reinterpret_cast<char *>(win) + (size_t)win_cells * 2;
-    lds_guard_fill(guard);
-    STAMP_DECL;
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6;
-    const int l = blockIdx.y;
-    // split: TWO workgroups per group of scans, one per direction half - a ray never crosses the column of its origin,
-    // so the rays running towards larger x and those running towards smaller x touch disjoint halves of the group's
-    // box and can be cast by different CUs: each walks its half's rays into its own window and flushes it
-    const int my_half = split ? (int)(blockIdx.x & 1u) : -1;
-    const int s0 = (int)(split ? blockIdx.x >> 1 : blockIdx.x) * group_size;
-    const int cnt = min(group_size, src.scans_per_traj() - s0);
-    const int gi = got ? got[l] : src.own_grid(l);
-    uint32_t *pass = g.pass + (size_t)gi * g.xw * g.yw, *hit = g.hit + (size_t)gi * g.xw * g.yw;
-    const int n = src.n, nrays = cnt * n;
-
-    // exclusive owner of the map + live pmap + rows that are a multiple of 4 cells: the flush is a
-    // plain vectorised read-modify-write of the touched rectangle that also re-thresholds pmap
-    const bool fused = exclusive && g.pmap_live && (g.yw & 3) == 0 && (((size_t)gi * g.xw * g.yw) & 3) == 0;
-    // rows of an even number of cells: two neighbouring counters are one aligned 8-byte word, and the two
-    // 16-bit counts of a window dword are flushed by ONE 64-bit atomic (see the flush)
-    const bool pair64 = (g.yw & 1) == 0 && (((size_t)gi * g.xw * g.yw) & 1) == 0;
-    int *fb = box + 48;                                              // [cnt] first beam of a scan that Python's int() would raise on
-    if (tid < cnt) { src.scan_const(l, s0 + tid, g, sc[tid]); fb[tid] = INT_MAX; }
-    unsigned long long *wg_visits = reinterpret_cast<unsigned long long *>(box + 12);
-    if (tid == 0) {
-        box[0] = box[1] = INT_MAX; box[2] = box[3] = INT_MIN; box[9] = 0; *wg_visits = 0ull;
-        for (int q = 0; q < 4; ++q) { box[16 + 4 * q] = box[17 + 4 * q] = INT_MAX; box[18 + 4 * q] = box[19 + 4 * q] = INT_MIN; }
-        box[34] = 1; box[36] = 0;
-    }
-    const bool sorted = nrays <= sort_cap;
-    // Direction quadrants (DESIGN.md "K4a"): a Bresenham path stays in the box of its two ends, so a ray never crosses the
-    // column or the row of its origin, and the rays of the four direction quadrants (end cell right / left of, above / below
-    // the origin) touch four nearly disjoint parts of the group's bounding box (up to the few cells the origins of the
-    // group's scans differ by).  When the box of a workgroup's rays does not fit the window - a 10 m x 8 m room seen at an
-    // angle spans 250 x 250 cells, 1.5 windows - it is cut at the origins' column, and a half that still does not fit at their
-    // row: every part gets the window to itself, one PHASE after the other; every ray is still walked once, and none of
-    // its cells takes the checked walk with scattered global atomics (round 4 stamps: 44 of a replay's 250 workgroups had a
-    // half that did not fit; their walk took 109 k cycles against 36 k, and the launch lasted as long as they did).
-    const bool quads = sorted && !exclusive;
-    unsigned short *bins = reinterpret_cast<unsigned short *>(win);   // scratch until the window is zeroed
-    for (int k = tid; k < 4 * kSortBins; k += blockDim.x) hist[k] = 0;
-    __syncthreads();
-    STAMP(0);                                   // scan constants
-
-    // pass 1: bounding box of everything the group's rays can touch, and of the four quadrants' rays
-    int bx0 = INT_MAX, by0 = INT_MAX, bx1 = INT_MIN, by1 = INT_MIN, bad = 0;
-    for (int r = tid; r < nrays; r += blockDim.x) {
+    const int tid = threadIdx.x;
+    int bx0 = INT_MAX, by0 = INT_MAX, bx1 = INT_MIN, by1 = INT_MIN;
+    for (int r = tid; r < cnt * n; r += blockDim.x) {
         int s = r / n, i = r - s * n, pox, poy, len = 0, b2 = 0, quad = 0;
         const bool valid = src.ray(l, s0 + s, i, sc[s], g, pox, poy, b2);
         if (valid) {
@@ -627,212 +619,92 @@ __global__ void __launch_bounds__(1024) k_grid_update_win(GridDev g, Src src, in
         }
         // a scan stops at its first beam that Python's int() would raise on (mapping.py:29-36: the beams before
         // it have been applied when the exception leaves update(), and the error is that beam's)
-        if (b2) atomicMin(&fb[s], i);
-        if (sorted) {                                                // bin by (phase,) length, longest first
-            const int lbin = kSortBins - 1 - min(len >> 2, kSortBins - 1);
-            if (quads) {
-                // which phase of which workgroup casts this ray is decided behind the barrier, when the boxes are known
-                // (bits 7-8: quadrant, bit 9: beam parity); rays with nothing to cast are nobody's
-                bins[r] = (valid && len > 0) ? (unsigned short)(lbin | (quad << 7) | ((i & 1) << 9)) : (unsigned short)0xffffu;
-            } else {
-                bins[r] = (unsigned short)lbin;                      // parked in the (not yet zeroed) window
-                atomicAdd(&hist[lbin], 1);
-            }
-        }
+        if (b2) atomicMin(&first_bad[s], i);
+        if (sorted) park(r, i, valid && len > 0, quad, kSortBins - 1 - min(len >> 2, kSortBins - 1));
     }
     bx0 = wave_min_i32(bx0); by0 = wave_min_i32(by0); bx1 = wave_max_i32(bx1); by1 = wave_max_i32(by1);
-    if (lane == 0 && bx0 <= bx1) {
-        atomicMin(&box[0], bx0); atomicMin(&box[1], by0); atomicMax(&box[2], bx1); atomicMax(&box[3], by1);
+    if ((tid & 63) == 0 && bx0 <= bx1) {
+        atomicMin(&bbox[0], bx0); atomicMin(&bbox[1], by0); atomicMax(&bbox[2], bx1); atomicMax(&bbox[3], by1);
     }
     __syncthreads();
-    if (tid < cnt && fb[tid] != INT_MAX) {                           // the first bad beam's own error (NaN or overflow)
+    if (tid < cnt && first_bad[tid] != INT_MAX) {                    // the first bad beam's own error (NaN or overflow)
         int pox, poy, b2 = 0;
-        (void)src.ray(l, s0 + tid, fb[tid], sc[tid], g, pox, poy, b2);
+        (void)src.ray(l, s0 + tid, first_bad[tid], sc[tid], g, pox, poy, b2);
         atomicOr(g.status, b2);
     }
-    int *phw = box + kWinPhase;                                      // [4][8] window of a phase: x0, y0, W, H, covers
-    int *phq = box + kWinPhase + 32;                                 // [4] phase of a quadrant's rays (-1: not this workgroup's)
-    int *seg = box + kWinPhase + 36;                                 // [5] boundaries of the phases in the sorted order
-    if (tid == 0 && quads && box[0] <= box[2]) {
-        // A quadrant's rays lie between the group's origins and the edges of its bounding box on the quadrant's side (every ray
-        // lies in the box of its two ends): the box of quadrant q from the box of everything and the extremes of the origins
-        int ox0 = INT_MAX, oy0 = INT_MAX, ox1 = INT_MIN, oy1 = INT_MIN;
-        for (int k = 0; k < cnt; ++k) { ox0 = min(ox0, sc[k].pcx); ox1 = max(ox1, sc[k].pcx); oy0 = min(oy0, sc[k].pcy); oy1 = max(oy1, sc[k].pcy); }
-        for (int q = 0; q < 4; ++q) {
-            box[16 + 4 * q] = (q & 1) ? max(ox0, box[0]) : box[0]; box[18 + 4 * q] = (q & 1) ? box[2] : min(ox1, box[2]);
-            box[17 + 4 * q] = (q & 2) ? max(oy0, box[1]) : box[1]; box[19 + 4 * q] = (q & 2) ? box[3] : min(oy1, box[3]);
-        }
-    }
-    if (tid == 0 && quads) {
-        // union of the quadrants in mask -> clamped box; false: empty
-        auto box_of = [&](unsigned mask, int *o) -> bool {
-            o[0] = o[1] = INT_MAX; o[2] = o[3] = INT_MIN;
-            for (int q = 0; q < 4; ++q)
-                if ((mask >> q & 1u) && box[16 + 4 * q] <= box[18 + 4 * q]) {
-                    o[0] = min(o[0], box[16 + 4 * q]); o[1] = min(o[1], box[17 + 4 * q]); o[2] = max(o[2], box[18 + 4 * q]); o[3] = max(o[3], box[19 + 4 * q]);
-                }
-            o[0] = max(o[0], 0); o[1] = max(o[1], 0); o[2] = min(o[2], g.xw - 1); o[3] = min(o[3], g.yw - 1);
-            if (pair64) o[1] &= ~1;                                  // the window's dwords line up with 8-byte pairs of counters
-            return o[0] <= o[2] && o[1] <= o[3];
-        };
-        auto fits = [&](unsigned mask) -> bool {
-            int o[4];
-            return !box_of(mask, o) || (long)(o[2] - o[0] + 1) * ((o[3] - o[1] + 2) & ~1) <= win_cells;
-        };
-        // the parts (sets of quadrants) this workgroup casts, one phase each
-        unsigned part[4] = {0u, 0u, 0u, 0u};
-        int nph = 1, parity = 0;
-        if (split) {
-            // Two workgroups per group.  When the group's whole box fits one window, both take that window and share the
-            // rays evenly, by beam parity (neighbouring beams are about equally long; the direction halves of a scan taken
-            // off-centre differ up to 3 : 1 in cells to walk).  Else a workgroup per direction half, cut again at the
-            // origins' row if the half does not fit.
-            const unsigned mine = my_half ? 0xAu : 0x5u;             // quadrants right / left of the origins' column
-            if (fits(0xFu)) { part[0] = 0xFu; parity = 1; }
-            else if (fits(mine)) part[0] = mine;
-            else { part[0] = mine & 0x3u; part[1] = mine & 0xCu; nph = 2; }
-        } else {
-            if (fits(0xFu)) part[0] = 0xFu;
-            else if (fits(0x5u) && fits(0xAu)) { part[0] = 0x5u; part[1] = 0xAu; nph = 2; }
-            else { part[0] = 1u; part[1] = 2u; part[2] = 4u; part[3] = 8u; nph = 4; }
-        }
-        for (int q = 0; q < 4; ++q) phq[q] = -1;
-        for (int ph = 0; ph < nph; ++ph) {
-            for (int q = 0; q < 4; ++q)
-                if (part[ph] >> q & 1u) phq[q] = ph;
-            int o[4], W = 0, H = 0, cov = 1;
-            if (box_of(part[ph], o)) {
-                W = o[2] - o[0] + 1; H = o[3] - o[1] + 1;
-                if ((long)W * ((H + 1) & ~1) > win_cells) {
-                    // still too large: the sub-rectangle next to the origins (the rays start there; clamped into the part's
-                    // box, i.e. in its corner for a quadrant) and the rest by direct atomics
-                    const int Hd = min(H, 192), Wd = min(W, win_cells / ((Hd + 1) & ~1));   // rows are stored padded to an even height
-                    int cx0 = min(max(sc[0].pcx - Wd / 2, o[0]), o[2] - Wd + 1), cy0 = min(max(sc[0].pcy - Hd / 2, o[1]), o[3] - Hd + 1);
-                    if (pair64) cy0 &= ~1;
-                    o[0] = cx0; o[1] = cy0; W = Wd; H = Hd; cov = 0;
-                }
-                // the window is W rows of (H + 1) / 2 dwords: it must fit the win_cells 16-bit cells carved for it.  Should the
-                // sizing above ever be wrong (it once used the unpadded height: a 193 x 191 box wrote 96 dwords past the
-                // window), fall back to no window at all - every cell then takes the direct-atomic path, still exact - and
-                // raise the internal-error status bit.
-                if ((long)W * ((H + 1) >> 1) > win_cells / 2) { atomicOr(g.status, kStatusGuard); W = 0; H = 0; cov = 0; }
-            } else {
-                o[0] = o[1] = 0;
-            }
-            int *w = phw + 8 * ph;
-            w[0] = o[0]; w[1] = o[1]; w[2] = W; w[3] = H; w[4] = cov;
-        }
-        box[34] = nph; box[36] = parity;
-        box[10] = 0; box[11] = 0;
-    }
-    if (tid == 0 && !quads) {
-        int x0 = max(box[0], 0), y0 = max(box[1], 0), x1 = min(box[2], g.xw - 1), y1 = min(box[3], g.yw - 1);
-        int W = 0, H = 0, covers = 1;
-        int fastwin = 0, strip_w = 0;                                // strips of the single-scan owner form
-        if (x0 <= x1 && y0 <= y1) {
-            // Fast owner sweep (see the end of the kernel): one scan, one hit occupies, and the window,
-            // widened to whole 64-byte pieces of the counter rows (16 cells), still holds every cell.
-            if (fused && cnt == 1 && nrays < 32768 && g.hit_levels == 1 && (g.yw & 15) == 0) {
-                const int ya = y0 & ~15, Ha = ((y1 | 15) + 1) - ya, Wb = x1 - x0 + 1;
-                int S = (int)(((long)Wb * Ha + win_cells - 1) / win_cells), Ws = (Wb + S - 1) / S;
-                while ((long)Ws * Ha > win_cells && S < Wb) { ++S; Ws = (Wb + S - 1) / S; }
-                if ((long)Ws * Ha <= win_cells) { y0 = ya; y1 = ya + Ha - 1; fastwin = S; strip_w = Ws; }
-            }
-            if (fused) y0 &= ~3;                                      // quads of the fused flush line up with the window's dwords
-            else if (pair64) y0 &= ~1;                                // the window's dwords line up with 8-byte pairs of counters
-            W = x1 - x0 + 1; H = y1 - y0 + 1;
-            if (!fastwin && (long)W * ((H + 1) & ~1) > win_cells) {   // keep a sub-rectangle around the first origin
-                int Hd = min(H, 192), Wd = min(W, win_cells / ((Hd + 1) & ~1));   // rows are stored padded to an even height
-                int cx0 = min(max(sc[0].pcx - Wd / 2, x0), x1 - Wd + 1), cy0 = min(max(sc[0].pcy - Hd / 2, y0), y1 - Hd + 1);
-                if (fused) cy0 &= ~3;
-                else if (pair64) cy0 &= ~1;
-                x0 = cx0; y0 = cy0; W = Wd; H = Hd;
-                covers = 0;
-            }
-            if ((long)(fastwin ? strip_w : W) * ((H + 1) >> 1) > win_cells / 2) {   // (see above)
-                atomicOr(g.status, kStatusGuard);
-                fastwin = 0;
-                W = 0; H = 0; covers = 0;
-            }
-        }
-        phw[0] = x0; phw[1] = y0; phw[2] = W; phw[3] = H; phw[4] = covers; box[10] = fastwin; box[11] = strip_w;
-        box[34] = 1; box[36] = 0;
-        seg[0] = 0; seg[1] = nrays;
+}
+
+// Counting sort of ray ids by bin (bins[r]; 0xffff: not sorted in), two barriers: exclusive scan of the 64 * kBinsPerLane
+// bins' histogram in wave 0, then every ray claims a slot in its bin.  Order inside a bin is arbitrary; the map update does not
+// depend on ray order.  seg (nullable): where every block of kSortBins bins starts in the order, and where the last one ends.
+template <int kBinsPerLane>
+__device__ __forceinline__ void counting_sort(int *hist, const unsigned short *bins, unsigned short *order, int nrays, int *seg)
+{
+    constexpr int kLanesPerSeg = kSortBins / kBinsPerLane;
+    const int lane = threadIdx.x & 63;
+    if (threadIdx.x < kWave) {
+        int h[kBinsPerLane], tot = 0;
+#pragma unroll
+        for (int u = 0; u < kBinsPerLane; ++u) { h[u] = hist[kBinsPerLane * lane + u]; tot += h[u]; }
+        int inc = tot;
+#pragma unroll
+        for (int off = 1; off < kWave; off <<= 1) { int v = __shfl_up(inc, off, kWave); if (lane >= off) inc += v; }
+        int run = inc - tot;
+        if (seg && lane % kLanesPerSeg == 0) seg[lane / kLanesPerSeg] = run;
+        if (seg && lane == kWave - 1) seg[kWave / kLanesPerSeg] = inc;
+#pragma unroll
+        for (int u = 0; u < kBinsPerLane; ++u) { hist[kBinsPerLane * lane + u] = run; run += h[u]; }
     }
     __syncthreads();
-    STAMP(1);                                   // pass 1: endpoints, bounding boxes, phases
-    int wx0 = phw[0], wy0 = phw[1], W = phw[2], H = phw[3];
-    bool covers = phw[4] != 0;            // the window holds every in-map cell the phase's rays can touch
-    int Hp2 = (H + 1) >> 1;               // dwords per window row
-    const int phases = box[34];
-    if (sorted) {
-        if (quads) {                                                 // this workgroup's rays and their phases
-            const bool parity = box[36] != 0;
-            for (int r = tid; r < nrays; r += blockDim.x) {
-                const unsigned b = bins[r];
-                if (b == 0xffffu) continue;
-                const int ph = phq[(b >> 7) & 3u];
-                const bool mine = ph >= 0 && (!parity || (int)((b >> 9) & 1u) == my_half);
-                const unsigned fin = (unsigned)ph * kSortBins + (b & 127u);
-                bins[r] = mine ? (unsigned short)fin : (unsigned short)0xffffu;
-                if (mine) atomicAdd(&hist[fin], 1);
-            }
-            __syncthreads();
-        }
-        // counting sort of the ray ids by (phase, length bin): exclusive scan of the histogram (wave 0), then every ray
-        // claims a slot in its bin.  Order inside a bin is arbitrary; the map update does not depend on ray order.
-        if (wave == 0) {
-            int h8[8], tot = 0;
-#pragma unroll
-            for (int u = 0; u < 8; ++u) { h8[u] = hist[8 * lane + u]; tot += h8[u]; }
-            int inc = tot;
-#pragma unroll
-            for (int off = 1; off < kWave; off <<= 1) { int v = __shfl_up(inc, off, kWave); if (lane >= off) inc += v; }
-            int run = inc - tot;
-            if (quads && (lane & 15) == 0) seg[lane >> 4] = run;     // first bin of a phase: kSortBins / 8 = 16 lanes per phase
-            if (quads && lane == kWave - 1) seg[4] = inc;
-#pragma unroll
-            for (int u = 0; u < 8; ++u) { hist[8 * lane + u] = run; run += h8[u]; }
-        }
-        __syncthreads();
-        for (int r = tid; r < nrays; r += blockDim.x)
-            if (bins[r] != 0xffffu) order[atomicAdd(&hist[bins[r]], 1)] = (unsigned short)r;
-        __syncthreads();
-    }
-    unsigned nvis = 0;
-    const unsigned short *ord = sorted ? order : nullptr;
-    const int strips = box[10], strip_w = box[11];
-    const bool fast = strips != 0;        // single-scan owner form (the sweep at the end of the kernel)
-    for (int ph = 0; ph < (fast ? 0 : phases); ++ph) {
-        const int seg0 = seg[ph], seg1 = seg[ph + 1];
-        if (seg0 == seg1) continue;                                   // (uniform) a part without rays
-        {
-            const int *o = phw + 8 * ph;
-            wx0 = o[0]; wy0 = o[1]; W = o[2]; H = o[3]; covers = o[4] != 0; Hp2 = (H + 1) >> 1;
-            __syncthreads();                                          // the previous phase's flush has read the window
-            if (tid == 0) box[9] = 0;
-        }
-        for (int w = tid; w < W * Hp2; w += blockDim.x) win[w] = 0u;
-        __syncthreads();
-        STAMP(2);                                   // sort + zero
-        // pass 2: walk the rays (the reference's float-error Bresenham, bresenham.py:45-55)
-        const int *first_bad = fb;
-        if (covers) nvis += cast_rays<true>(g, src, sc, l, s0, n, seg1 - seg0, &box[9], ord ? ord + seg0 : nullptr, win, wx0, wy0, W, H, Hp2, pass, hit, first_bad);
-        else        nvis += cast_rays<false>(g, src, sc, l, s0, n, seg1 - seg0, &box[9], ord ? ord + seg0 : nullptr, win, wx0, wy0, W, H, Hp2, pass, hit, first_bad);
-        __syncthreads();
-        STAMP(3);                                   // walk
+    for (int r = threadIdx.x; r < nrays; r += blockDim.x)
+        if (bins[r] != 0xffffu) order[atomicAdd(&hist[bins[r]], 1)] = (unsigned short)r;
+    __syncthreads();
+}
 
-    // flush: one wave per window row, lanes along y (contiguous in the [x][y] map), two cells per lane
-    // every workgroup flushes the same part of the map: start each one at a different row so
-    // that concurrent flushes do not queue on the same addresses
+// o[4] (x0, y0, x1, y1) clamped to the map, its first row moved down to a multiple of ymask + 1 cells (1: the window's
+// dwords line up with 8-byte pairs of counters, 3: with the quads of the fused sweep).  False: nothing of it is in the map.
+__device__ __forceinline__ bool clamp_box(const GridDev &g, int *o, int ymask)
+{
+    o[0] = max(o[0], 0); o[1] = max(o[1], 0); o[2] = min(o[2], g.xw - 1); o[3] = min(o[3], g.yw - 1);
+    o[1] &= ~ymask;
+    return o[0] <= o[2] && o[1] <= o[3];
+}
+__device__ __forceinline__ bool box_fits(const int *o, int win_cells)   // (rows are stored padded to an even height)
+{
+    return (long)(o[2] - o[0] + 1) * ((o[3] - o[1] + 2) & ~1) <= win_cells;
+}
+
+// The window for the rays of a clamped box o (clamp_box, same ymask; any: its result), into w[5] (x0, y0, W, H, covers):
+// the box itself when it fits win_cells, else a sub-rectangle of it next to the first origin (the rays start there; clamped
+// into the box, i.e. in its corner for a quadrant) - the rest goes by direct atomics.  Nothing in the map: no window.
+__device__ __forceinline__ void fit_window(const GridDev &g, bool any, const int *o, int ymask, const ScanConst &first, int win_cells, int *w)
+{
+    int x0 = any ? o[0] : 0, y0 = any ? o[1] : 0, W = any ? o[2] - o[0] + 1 : 0, H = any ? o[3] - o[1] + 1 : 0, cov = 1;
+    if (any && !box_fits(o, win_cells)) {
+        const int Hd = min(H, 192), Wd = min(W, win_cells / ((Hd + 1) & ~1));   // rows are stored padded to an even height
+        x0 = min(max(first.pcx - Wd / 2, o[0]), o[2] - Wd + 1);
+        y0 = min(max(first.pcy - Hd / 2, o[1]), o[3] - Hd + 1) & ~ymask;
+        W = Wd; H = Hd; cov = 0;
+    }
+    // W rows of (H + 1) / 2 dwords must fit the win_cells 16-bit cells carved for them.  Should the sizing above ever be wrong (it
+    // once used the unpadded height: a 193 x 191 box wrote 96 dwords past the window): no window at all - every cell then takes
+    // the direct-atomic path, still exact - and the internal-error status bit.
+    if ((long)W * ((H + 1) >> 1) > win_cells / 2) { atomicOr(g.status, kStatusGuard); W = 0; H = 0; cov = 0; }
+    w[0] = x0; w[1] = y0; w[2] = W; w[3] = H; w[4] = cov;
+}
+
+// Flush of a window: one wave per window row, lanes along y (contiguous in the [x][y] map), two cells per lane.  Every workgroup
+// flushes the same part of the map: each one starts at a different row so that concurrent flushes do not queue on the same addresses.
+__device__ __forceinline__ void flush_window(const unsigned *win, uint32_t *pass, int yw, int wx0, int wy0, int W, int Hp2, bool pair64)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
     const int rot = W > 0 ? (int)((blockIdx.x * 37u + blockIdx.y * 11u) % (unsigned)W) : 0;
-    for (int rr = wave; rr < (fused ? 0 : W); rr += nwaves) {
+    for (int rr = wave; rr < W; rr += nwaves) {
         const int row = rr + rot < W ? rr + rot : rr + rot - W;
-        size_t gbase = (size_t)(wx0 + row) * g.yw + wy0;
-        // The flush is bound by the chip's rate of global atomics (every workgroup of a replay adds its
-        // ~25 k touched cells to the same map: 6 M atomics per 1 000 scans at 4 scans per group, 20 us
-        // chip-wide): a dword of the window - two cells that are neighbours in the map row - goes out as ONE
-        // 64-bit add of (count0, count1 << 32).  A carry out of the low counter would need 2^32 passes.
+        size_t gbase = (size_t)(wx0 + row) * yw + wy0;
+        // The flush is bound by the chip's rate of global atomics (every workgroup of a replay adds its ~25 k touched cells to the
+        // same map): a dword of the window - two cells that are neighbours in the map row - goes out as ONE 64-bit add of
+        // (count0, count1 << 32).  A carry out of the low counter would need 2^32 passes.
         if (pair64 && (wy0 & 1) == 0) {
             for (int d = lane; d < Hp2; d += kWave) {
                 unsigned v = win[row * Hp2 + d];
@@ -848,157 +720,377 @@ __global__ void __launch_bounds__(1024) k_grid_update_win(GridDev g, Src src, in
             if (p1) atomicAdd(&pass[gbase + 2 * d + 1], p1);          // p1 != 0 implies 2d+1 < H
         }
     }
-    }   // phases
-    // Live pmap: this workgroup is the only writer of its map during the launch, so once its own
-    // atomics (hits, out-of-window passes) have landed it finishes every cell its rays could have
-    // touched - the bounding box of pass 1, clamped to the map - in one sweep: add the window's
-    // pass counts with plain 16-byte read-modify-writes (no flush atomics) and re-threshold pmap,
-    // the finalize pass restricted to what changed.
-    if (fast) {
-        // Single-scan owner form.  Nothing of this map is read that an atomic of this launch wrote:
-        // pass counts come from the window, "a hit fell here" from the window's flag bits (the hit
-        // COUNTERS are bumped by the fire-and-forget atomics of the walk and never read), and the
-        // cell's earlier state from the live pmap itself: with one hit occupying, pmap == 100 says
-        // "hit before or pass >= threshold" and counters only grow, so an occupied cell stays
-        // occupied; otherwise hit == 0 and the new pass count decides (mapping.py:47-50).
-        // The window's rows are whole 64-byte pieces of the counter rows (16 cells = 4 quads = 4
-        // lanes): a piece the scan touched is read and written back whole, an untouched piece is
-        // neither read nor written; pmap is stored only where it changes.  No cell is ever updated
-        // by a global atomic: a bounding box larger than the window is cut into strips of rows, each
-        // walked and swept in turn (a rotated 10 m x 8 m room spans ~250 x 250 cells: two strips).
-        const uint32_t pthr = g.pass_thresh[0];
-        int8_t *pm = g.pmap_live + (size_t)gi * g.xw * g.yw;
-        const int qrow = H >> 2;                                      // H is a multiple of 16 here
-        const unsigned qinv = (unsigned)((0x100000000ull + (unsigned)qrow - 1) / (unsigned)qrow);   // q / qrow == umulhi(q, qinv), q < 2^16
-        constexpr int kBatch = 4;                                     // 16-byte read-modify-writes a lane keeps in flight
-        for (int strip = 0; strip < strips; ++strip) {
-        const int sx0 = wx0 + strip * strip_w, SW = min(strip_w, wx0 + W - sx0), total = SW * qrow;
-        if (strip) __syncthreads();                                   // the previous strip's sweep has read the window
-        for (int w = tid; w < SW * Hp2; w += blockDim.x) win[w] = 0u;
-        if (tid == 0) box[9] = 0;
-        __syncthreads();
-        STAMP(2);                                   // (sort +) zero
-        nvis += cast_rays_strip(g, src, sc[0], l, s0, nrays, &box[9], ord, win, sx0, wy0, SW, H, Hp2, hit, fb[0]);
-        __syncthreads();
-        STAMP(3);                                   // walk
-        for (int q0 = tid; q0 < total; q0 += kBatch * blockDim.x) {
-            uint4 p[kBatch];
-            uint32_t om[kBatch], d0[kBatch], d1[kBatch];
-            size_t at[kBatch];
-            bool live[kBatch];
+}
+
+// Sweep of a strip of the single-scan owner forms (owner_cast, k_grid_update_own; the rule is spelt out above owner_cast): SW
+// window rows of H cells (a multiple of 16: qrow = H / 4 quads, qinv its reciprocal for umulhi) that stand for the map rows from
+// sx0 and the cells from wy0 on; a window cell is a 15-bit pass count and, in bit 15, "a hit of this scan fell here".  4 lanes
+// per 64-byte piece of a counter row: only pieces the scan touched are read and written back; pmap only where it changes.
+__device__ __forceinline__ void sweep_strip(const unsigned *win, uint32_t *pass, int8_t *pm, int yw, int sx0, int wy0, int SW, int H,
+                                            int qrow, unsigned qinv, uint32_t pthr)
+{
+    const int tid = threadIdx.x, lane = tid & 63, Hp2 = H >> 1, total = SW * qrow;
+    constexpr int kBatch = 4;                                     // 16-byte read-modify-writes a lane keeps in flight
+    for (int q0 = tid; q0 < total; q0 += kBatch * blockDim.x) {
+        uint4 p[kBatch];
+        uint32_t om[kBatch], d0[kBatch], d1[kBatch];
+        size_t at[kBatch];
+        bool live[kBatch];
 #pragma unroll
-            for (int u = 0; u < kBatch; ++u) {
-                const int q = q0 + u * (int)blockDim.x;
-                d0[u] = d1[u] = 0u;
-                if (q < total) {
-                    const int r = (int)__umulhi((unsigned)q, qinv), c = q - r * qrow;
-                    const uint2 d = *reinterpret_cast<const uint2 *>(win + (r * Hp2 + 2 * c));
-                    d0[u] = d.x; d1[u] = d.y;
-                    at[u] = (size_t)(sx0 + r) * g.yw + (wy0 + 4 * c);
-                }
-                // the four lanes of a 64-byte piece decide together (total and blockDim are multiples of 4)
-                const unsigned long long m = __ballot((d0[u] | d1[u]) != 0u);
-                live[u] = ((m >> (lane & 60)) & 0xFull) != 0ull;
-                if (live[u]) {
-                    p[u] = *reinterpret_cast<const uint4 *>(pass + at[u]);
-                    om[u] = *reinterpret_cast<const uint32_t *>(pm + at[u]);
-                }
+        for (int u = 0; u < kBatch; ++u) {
+            const int q = q0 + u * (int)blockDim.x;
+            d0[u] = d1[u] = 0u;
+            if (q < total) {
+                const int r = (int)__umulhi((unsigned)q, qinv), c = q - r * qrow;
+                const uint2 d = *reinterpret_cast<const uint2 *>(win + (r * Hp2 + 2 * c));
+                d0[u] = d.x; d1[u] = d.y;
+                at[u] = (size_t)(sx0 + r) * yw + (wy0 + 4 * c);
             }
+            // the four lanes of a piece decide together (total and blockDim are multiples of 4)
+            const unsigned long long m = __ballot((d0[u] | d1[u]) != 0u);
+            live[u] = ((m >> (lane & 60)) & 0xFull) != 0ull;
+            if (live[u]) {
+                p[u] = *reinterpret_cast<const uint4 *>(pass + at[u]);
+                om[u] = *reinterpret_cast<const uint32_t *>(pm + at[u]);
+            }
+        }
 #pragma unroll
-            for (int u = 0; u < kBatch; ++u) {
-                if (!live[u]) continue;
-                const uint32_t c0 = d0[u] & 0x7fffu, c1 = (d0[u] >> 16) & 0x7fffu, c2 = d1[u] & 0x7fffu, c3 = (d1[u] >> 16) & 0x7fffu;
-                p[u].x += c0; p[u].y += c1; p[u].z += c2; p[u].w += c3;
-                *reinterpret_cast<uint4 *>(pass + at[u]) = p[u];
-                if (!(d0[u] | d1[u])) continue;
-                const uint32_t o = om[u];
-                // per byte: 1 where the cell is occupied afterwards - it was (bit 6 is set in 100 only, not
-                // in 0 or 50), a hit fell on it, or its pass count reached the threshold
-                uint32_t occ = (o >> 6) & 0x01010101u;
-                occ |= ((d0[u] >> 15) & 1u) | ((d0[u] >> 31) << 8) | (((d1[u] >> 15) & 1u) << 16) | ((d1[u] >> 31) << 24);
+        for (int u = 0; u < kBatch; ++u) {
+            if (!live[u]) continue;
+            const uint32_t d0v = d0[u], d1v = d1[u];
+            p[u].x += d0v & 0x7fffu; p[u].y += (d0v >> 16) & 0x7fffu; p[u].z += d1v & 0x7fffu; p[u].w += (d1v >> 16) & 0x7fffu;
+            *reinterpret_cast<uint4 *>(pass + at[u]) = p[u];
+            if (!(d0v | d1v)) continue;
+            const uint32_t o = om[u];
+            // one bit per byte (cell): touched by this scan / hit by this scan / occupied before (bit 6
+            // is set in 100 only) / never touched before (bit 4 is set in 50 only)
+            const uint32_t tb = ((d0v & 0xffffu) ? 1u : 0u) | ((d0v >> 16) ? 0x100u : 0u) | ((d1v & 0xffffu) ? 0x10000u : 0u) | ((d1v >> 16) ? 0x1000000u : 0u);
+            const uint32_t fb = ((d0v >> 15) & 1u) | (((d0v >> 31) & 1u) << 8) | (((d1v >> 15) & 1u) << 16) | ((d1v >> 31) << 24);
+            const uint32_t was = (o >> 6) & 0x01010101u, fresh = (o >> 4) & 0x01010101u;
+            const uint32_t pmax = max(max(p[u].x, p[u].y), max(p[u].z, p[u].w));
+            // a byte changes iff the cell was touched, was not occupied, and is fresh (50 -> 0 or 100),
+            // hit now (-> 100) or at / over the pass threshold now (-> 100)
+            if (((tb & ~was) & (fresh | fb)) != 0u || pmax >= pthr) {
+                uint32_t occ = was | fb;
                 occ |= (p[u].x >= pthr ? 1u : 0u) | (p[u].y >= pthr ? 0x100u : 0u) | (p[u].z >= pthr ? 0x10000u : 0u) | (p[u].w >= pthr ? 0x1000000u : 0u);
-                // per byte: 0xff where this scan touched the cell (passed through or hit)
-                const uint32_t tm = ((d0[u] & 0xffffu) ? 0xffu : 0u) | ((d0[u] >> 16) ? 0xff00u : 0u) | ((d1[u] & 0xffffu) ? 0xff0000u : 0u) |
-                                    ((d1[u] >> 16) ? 0xff000000u : 0u);
+                const uint32_t tm = tb * 255u;
                 const uint32_t out = (o & ~tm) | ((occ * 100u) & tm);
                 if (out != o) *reinterpret_cast<uint32_t *>(pm + at[u]) = out;
             }
         }
-        STAMP_SYNC();
-        STAMP(4);                                   // sweep
-        }   // strips
+    }
+}
+
+// Tail of a window workgroup: its visits are summed in LDS (*wg_visits, zeroed at the start) and go out as ONE global add.
+__device__ __forceinline__ void finish_workgroup(const GridDev &g, unsigned long long *wg_visits, unsigned nvis, int tid)
+{
+    const unsigned tot = wave_sum_u32(nvis);
+    if ((tid & 63) == 0 && tot) atomicAdd(wg_visits, (unsigned long long)tot);
+    __syncthreads();
+    if (tid == 0 && *wg_visits) atomicAdd(visit_slot(g.visits), *wg_visits);
+}
+
+// Shared-map form: groups of scans of a replay cast into a map that other workgroups write too.
+template <class Src>
+__global__ void __launch_bounds__(1024) k_grid_update_win(GridDev g, Src src, int group_size, const int32_t *__restrict__ got,
+                                                          int sort_cap, int win_cells, int split)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const WinLds lds(smem, group_size, sort_cap, win_cells);
+    ScanConst *sc = lds.sc; WinCtl *ctl = lds.ctl; int *hist = lds.hist; unsigned *win = lds.win;
+    lds_guard_fill(lds.guard);
+    STAMP_DECL;
+
+    const int tid = threadIdx.x;
+    const int l = blockIdx.y;
+    // split: TWO workgroups per group of scans (see the planner below), each with a window of its own
+    const int my_half = split ? (int)(blockIdx.x & 1u) : -1;
+    const int s0 = (int)(split ? blockIdx.x >> 1 : blockIdx.x) * group_size;
+    const int cnt = min(group_size, src.scans_per_traj() - s0);
+    const int gi = got ? got[l] : src.own_grid(l);
+    uint32_t *pass = g.pass + (size_t)gi * g.xw * g.yw, *hit = g.hit + (size_t)gi * g.xw * g.yw;
+    const int n = src.n, nrays = cnt * n;
+
+    // rows of an even number of cells: two neighbouring counters are one aligned 8-byte word, and the two
+    // 16-bit counts of a window dword are flushed by ONE 64-bit atomic (flush_window)
+    const bool pair64 = (g.yw & 1) == 0 && (((size_t)gi * g.xw * g.yw) & 1) == 0;
+    const int ymask = pair64 ? 1 : 0;
+    if (tid < cnt) { src.scan_const(l, s0 + tid, g, sc[tid]); ctl->first_bad[tid] = INT_MAX; }
+    if (tid == 0) {
+        ctl->bbox[0] = ctl->bbox[1] = INT_MAX; ctl->bbox[2] = ctl->bbox[3] = INT_MIN; ctl->next_ray = 0; ctl->visits = 0ull;
+        for (int q = 0; q < 4; ++q) { ctl->qbox[q][0] = ctl->qbox[q][1] = INT_MAX; ctl->qbox[q][2] = ctl->qbox[q][3] = INT_MIN; }
+        ctl->phases = 1; ctl->parity = 0;
+    }
+    // Direction quadrants (DESIGN.md "K4a"): a ray never crosses the column or the row of its origin, so the rays of the four
+    // direction quadrants (end cell right / left of, above / below the origin) touch four nearly disjoint parts of the group's
+    // bounding box.  When the box of a workgroup's rays does not fit the window it is cut at the origins' column, and a half that
+    // still does not fit at their row: every part gets the window to itself, one PHASE after the other; every ray is still walked
+    // once, and none of its cells takes the checked walk with scattered global atomics.
+    // A group of more than kMaxSortRays rays is neither sorted nor cut: one window, the rays in their own order.
+    const bool sorted = nrays <= sort_cap;
+    unsigned short *bins = reinterpret_cast<unsigned short *>(win);   // scratch until the window is zeroed
+    for (int k = tid; k < 4 * kSortBins; k += blockDim.x) hist[k] = 0;
+    __syncthreads();
+    STAMP(0);                                   // scan constants
+
+    // pass 1: which phase of which workgroup casts a ray is decided behind the barrier, when the boxes are known
+    // (bits 7-8: quadrant, bit 9: beam parity); rays with nothing to cast are nobody's
+    win_pass1(g, src, sc, l, s0, cnt, n, sorted, ctl->bbox, ctl->first_bad, [&](int r, int i, bool casts, int quad, int lbin) {
+        bins[r] = casts ? (unsigned short)(lbin | (quad << 7) | ((i & 1) << 9)) : (unsigned short)0xffffu;
+    });
+    if (tid == 0) {
+        // A quadrant's rays lie between the group's origins and the edges of its bounding box on the quadrant's side (every ray
+        // lies in the box of its two ends): the box of quadrant q from the box of everything and the extremes of the origins
+        const int *bb = ctl->bbox;
+        if (bb[0] <= bb[2]) {
+            int ox0 = INT_MAX, oy0 = INT_MAX, ox1 = INT_MIN, oy1 = INT_MIN;
+            for (int k = 0; k < cnt; ++k) { ox0 = min(ox0, sc[k].pcx); ox1 = max(ox1, sc[k].pcx); oy0 = min(oy0, sc[k].pcy); oy1 = max(oy1, sc[k].pcy); }
+            for (int q = 0; q < 4; ++q) {
+                ctl->qbox[q][0] = (q & 1) ? max(ox0, bb[0]) : bb[0]; ctl->qbox[q][2] = (q & 1) ? bb[2] : min(ox1, bb[2]);
+                ctl->qbox[q][1] = (q & 2) ? max(oy0, bb[1]) : bb[1]; ctl->qbox[q][3] = (q & 2) ? bb[3] : min(oy1, bb[3]);
+            }
+        }
+        // union of the quadrants in mask -> clamped box; false: empty
+        auto box_of = [&](unsigned mask, int *o) -> bool {
+            o[0] = o[1] = INT_MAX; o[2] = o[3] = INT_MIN;
+            for (int q = 0; q < 4; ++q) {
+                const int *b = ctl->qbox[q];
+                if ((mask >> q & 1u) && b[0] <= b[2]) { o[0] = min(o[0], b[0]); o[1] = min(o[1], b[1]); o[2] = max(o[2], b[2]); o[3] = max(o[3], b[3]); }
+            }
+            return clamp_box(g, o, ymask);
+        };
+        auto fits = [&](unsigned mask) -> bool { int o[4]; return !box_of(mask, o) || box_fits(o, win_cells); };
+        // the parts (sets of quadrants) this workgroup casts, one phase each
+        unsigned part[4] = {0u, 0u, 0u, 0u};
+        int nph = 1, parity = 0;
+        if (split) {
+            // Two workgroups per group.  When the group's whole box fits one window, both take that window and share the rays evenly,
+            // by beam parity (neighbouring beams are about equally long; the direction halves of a scan taken off-centre differ up to
+            // 3 : 1 in cells to walk).  Else a workgroup per direction half, cut again at the origins' row if the half does not fit.
+            const unsigned mine = my_half ? 0xAu : 0x5u;             // quadrants right / left of the origins' column
+            if (fits(0xFu)) { part[0] = 0xFu; parity = 1; }
+            else if (fits(mine)) part[0] = mine;
+            else { part[0] = mine & 0x3u; part[1] = mine & 0xCu; nph = 2; }
+        } else {
+            if (!sorted || fits(0xFu)) part[0] = 0xFu;               // (the quadrants together: the box of everything)
+            else if (fits(0x5u) && fits(0xAu)) { part[0] = 0x5u; part[1] = 0xAu; nph = 2; }
+            else { part[0] = 1u; part[1] = 2u; part[2] = 4u; part[3] = 8u; nph = 4; }
+        }
+        for (int q = 0; q < 4; ++q) ctl->phq[q] = -1;
+        for (int ph = 0; ph < nph; ++ph) {
+            for (int q = 0; q < 4; ++q)
+                if (part[ph] >> q & 1u) ctl->phq[q] = ph;
+            int o[4];
+            const bool any = box_of(part[ph], o);
+            fit_window(g, any, o, ymask, sc[0], win_cells, ctl->phw[ph]);
+        }
+        ctl->phases = nph; ctl->parity = parity;
+        if (!sorted) { ctl->seg[0] = 0; ctl->seg[1] = nrays; }       // (else: the counting sort's)
+    }
+    __syncthreads();
+    STAMP(1);                                   // pass 1: endpoints, bounding boxes, phases
+    const int phases = ctl->phases;
+    if (sorted) {                                                    // this workgroup's rays and their phases
+        const bool parity = ctl->parity != 0;
+        for (int r = tid; r < nrays; r += blockDim.x) {
+            const unsigned b = bins[r];
+            if (b == 0xffffu) continue;
+            const int ph = ctl->phq[(b >> 7) & 3u];
+            const bool mine = ph >= 0 && (!parity || (int)((b >> 9) & 1u) == my_half);
+            const unsigned fin = (unsigned)ph * kSortBins + (b & 127u);
+            bins[r] = mine ? (unsigned short)fin : (unsigned short)0xffffu;
+            if (mine) atomicAdd(&hist[fin], 1);
+        }
+        __syncthreads();
+        counting_sort<8>(hist, bins, lds.order, nrays, ctl->seg);    // by (phase, length bin)
+    }
+    unsigned nvis = 0;
+    int W = ctl->phw[0][2], H = ctl->phw[0][3];                      // (after the loop: of the last phase with rays, for the stamps)
+    bool covers = ctl->phw[0][4] != 0;
+    for (int ph = 0; ph < phases; ++ph) {
+        const int seg0 = ctl->seg[ph], seg1 = ctl->seg[ph + 1];
+        if (seg0 == seg1) continue;                                   // (uniform) a part without rays
+        const int *o = ctl->phw[ph];
+        const int wx0 = o[0], wy0 = o[1];
+        W = o[2]; H = o[3]; covers = o[4] != 0;         // the window holds every in-map cell the phase's rays can touch
+        const int Hp2 = (H + 1) >> 1;                   // dwords per window row
+        __syncthreads();                                              // the previous phase's flush has read the window
+        if (tid == 0) ctl->next_ray = 0;
+        for (int w = tid; w < W * Hp2; w += blockDim.x) win[w] = 0u;
+        __syncthreads();
+        STAMP(2);                                   // sort + zero
+        // pass 2: walk the rays (the reference's float-error Bresenham, bresenham.py:45-55)
+        const unsigned short *ord = sorted ? lds.order + seg0 : nullptr;
+        if (covers) nvis += cast_rays<true>(g, src, sc, l, s0, n, seg1 - seg0, &ctl->next_ray, ord, win, wx0, wy0, W, H, Hp2, pass, hit, ctl->first_bad);
+        else        nvis += cast_rays<false>(g, src, sc, l, s0, n, seg1 - seg0, &ctl->next_ray, ord, win, wx0, wy0, W, H, Hp2, pass, hit, ctl->first_bad);
+        __syncthreads();
+        STAMP(3);                                   // walk
+        flush_window(win, pass, g.yw, wx0, wy0, W, Hp2, pair64);
+    }
+    finish_workgroup(g, &ctl->visits, nvis, tid);
+    STAMP(4);                                   // flush
+    STAMP_VAL((ctl->parity << 8) | (covers ? 1 : 0) | (phases << 4) | ((unsigned)(W * ((H + 1) & ~1)) << 12));
+    STAMP_END(5);                               // [5] lifetime, [6] workgroups
+    lds_guard_check(lds.guard, g.status);
+}
+
+// Owner form: the workgroup is the only writer of its map, which has a live pmap, and the launch is not one for the single-scan
+// owner kernels below (several scans in one group: context option "grid_group"; a scan of more than 1 024 beams; three hit levels;
+// rows that are no multiple of 16 cells).  One window, then the workgroup finishes every cell its rays could touch, pmap included.
+template <class Src>
+__global__ void __launch_bounds__(1024) k_grid_update_own(GridDev g, Src src, int group_size, int sort_cap, int win_cells)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const WinLds lds(smem, group_size, sort_cap, win_cells);
+    ScanConst *sc = lds.sc; WinCtl *ctl = lds.ctl; int *hist = lds.hist; unsigned *win = lds.win;
+    lds_guard_fill(lds.guard);
+    STAMP_DECL;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6;
+    const int l = blockIdx.y;
+    const int s0 = (int)blockIdx.x * group_size;
+    const int cnt = min(group_size, src.scans_per_traj() - s0);
+    const int gi = src.own_grid(l);
+    uint32_t *pass = g.pass + (size_t)gi * g.xw * g.yw, *hit = g.hit + (size_t)gi * g.xw * g.yw;
+    int8_t *pm = g.pmap_live + (size_t)gi * g.xw * g.yw;
+    const int n = src.n, nrays = cnt * n;
+
+    // rows that are a multiple of 4 cells: the sweep is a plain vectorised read-modify-write of the touched rectangle
+    // that adds the window's counts itself, so there is no flush
+    const bool fused = (g.yw & 3) == 0 && (((size_t)gi * g.xw * g.yw) & 3) == 0;
+    const bool pair64 = (g.yw & 1) == 0 && (((size_t)gi * g.xw * g.yw) & 1) == 0;   // (see k_grid_update_win)
+    const int ymask = fused ? 3 : pair64 ? 1 : 0;
+    if (tid < cnt) { src.scan_const(l, s0 + tid, g, sc[tid]); ctl->first_bad[tid] = INT_MAX; }
+    if (tid == 0) {
+        ctl->bbox[0] = ctl->bbox[1] = INT_MAX; ctl->bbox[2] = ctl->bbox[3] = INT_MIN; ctl->next_ray = 0; ctl->visits = 0ull;
+        ctl->strips = 0; ctl->strip_w = 0;
+    }
+    const bool sorted = nrays <= sort_cap;
+    unsigned short *bins = reinterpret_cast<unsigned short *>(win);   // scratch until the window is zeroed
+    for (int k = tid; k < kSortBins; k += blockDim.x) hist[k] = 0;
+    __syncthreads();
+    STAMP(0);                                   // scan constants
+
+    win_pass1(g, src, sc, l, s0, cnt, n, sorted, ctl->bbox, ctl->first_bad, [&](int r, int, bool, int, int lbin) {
+        bins[r] = (unsigned short)lbin;                              // parked in the (not yet zeroed) window
+        atomicAdd(&hist[lbin], 1);
+    });
+    if (tid == 0) {
+        int o[4] = {ctl->bbox[0], ctl->bbox[1], ctl->bbox[2], ctl->bbox[3]};
+        int *w = ctl->phw[0];
+        const bool any = clamp_box(g, o, 0);
+        // Single-scan strip form (below): one scan, one hit occupies, and the window, widened to whole 64-byte pieces of the
+        // counter rows (16 cells) and cut into S strips of at most Ws rows, holds every cell.
+        if (any && fused && cnt == 1 && nrays < 32768 && g.hit_levels == 1 && (g.yw & 15) == 0) {
+            const int ya = o[1] & ~15, Ha = ((o[3] | 15) + 1) - ya, Wb = o[2] - o[0] + 1;
+            int S = (int)(((long)Wb * Ha + win_cells - 1) / win_cells), Ws = (Wb + S - 1) / S;
+            while ((long)Ws * Ha > win_cells && S < Wb) { ++S; Ws = (Wb + S - 1) / S; }
+            if ((long)Ws * Ha <= win_cells) { w[0] = o[0]; w[1] = ya; w[2] = Wb; w[3] = Ha; w[4] = 1; ctl->strips = S; ctl->strip_w = Ws; }
+        }
+        if (!ctl->strips) {
+            o[1] &= ~ymask;
+            fit_window(g, any, o, ymask, sc[0], win_cells, w);
+        }
+    }
+    __syncthreads();
+    STAMP(1);                                   // pass 1: endpoints, bounding box, window
+    if (sorted) counting_sort<kSortBins / kWave>(hist, bins, lds.order, nrays, nullptr);   // by length bin
+    const unsigned short *ord = sorted ? lds.order : nullptr;
+    const int wx0 = ctl->phw[0][0], wy0 = ctl->phw[0][1], W = ctl->phw[0][2], H = ctl->phw[0][3];
+    const bool covers = ctl->phw[0][4] != 0;
+    const int Hp2 = (H + 1) >> 1;                                    // dwords per window row
+    const int strips = ctl->strips, strip_w = ctl->strip_w;
+    unsigned nvis = 0;
+    if (strips) {
+        // Single-scan strip form: no cell is updated by a global atomic and nothing an atomic wrote is read (as in owner_cast); a
+        // box larger than the window is cut into strips of rows, each walked (cast_rays_strip) and swept (sweep_strip) in turn
+        const uint32_t pthr = g.pass_thresh[0];
+        const int qrow = H >> 2;                                      // H is a multiple of 16 here
+        const unsigned qinv = (unsigned)((0x100000000ull + (unsigned)qrow - 1) / (unsigned)qrow);   // q / qrow == umulhi(q, qinv), q < 2^16
+        for (int strip = 0; strip < strips; ++strip) {
+            const int sx0 = wx0 + strip * strip_w, SW = min(strip_w, wx0 + W - sx0);
+            if (strip) __syncthreads();                               // the previous strip's sweep has read the window
+            for (int w = tid; w < SW * Hp2; w += blockDim.x) win[w] = 0u;
+            if (tid == 0) ctl->next_ray = 0;
+            __syncthreads();
+            STAMP(2);                                   // (sort +) zero
+            nvis += cast_rays_strip(g, src, sc[0], l, s0, nrays, &ctl->next_ray, ord, win, sx0, wy0, SW, H, Hp2, hit, ctl->first_bad[0]);
+            __syncthreads();
+            STAMP(3);                                   // walk
+            sweep_strip(win, pass, pm, g.yw, sx0, wy0, SW, H, qrow, qinv, pthr);
+            STAMP_SYNC();
+            STAMP(4);                                   // sweep
+        }
         STAMP_COUNT(7, strips);
-    } else if (exclusive && g.pmap_live) {
+    } else {
+        for (int w = tid; w < W * Hp2; w += blockDim.x) win[w] = 0u;
+        __syncthreads();
+        STAMP(2);                                   // sort + zero
+        // pass 2: walk the rays (the reference's float-error Bresenham, bresenham.py:45-55)
+        if (covers) nvis += cast_rays<true>(g, src, sc, l, s0, n, nrays, &ctl->next_ray, ord, win, wx0, wy0, W, H, Hp2, pass, hit, ctl->first_bad);
+        else        nvis += cast_rays<false>(g, src, sc, l, s0, n, nrays, &ctl->next_ray, ord, win, wx0, wy0, W, H, Hp2, pass, hit, ctl->first_bad);
+        __syncthreads();
+        STAMP(3);                                   // walk
+        if (!fused) flush_window(win, pass, g.yw, wx0, wy0, W, Hp2, pair64);
+        // Once its own atomics (hits, out-of-window passes, the flush) have landed, the workgroup finishes every cell its rays could
+        // have touched - the box of pass 1, clamped to the map - in one sweep that re-thresholds pmap.  Plain loads are safe: the
+        // counters were only touched by this workgroup's atomics (done, fenced) and nothing of this map is in this CU's L1.
         owner_fence();
         __syncthreads();
-        const int x0 = max(box[0], 0), y0 = max(box[1], 0), x1 = min(box[2], g.xw - 1), y1 = min(box[3], g.yw - 1);
-        if (x0 <= x1 && y0 <= y1) {
-            const OccRule rule = OccRule::of(g);
-            int8_t *pm = g.pmap_live + (size_t)gi * g.xw * g.yw;
-            // plain loads are safe: the counters were only touched by this workgroup's atomics (done,
-            // fenced) and nothing of this map has been read into this CU's L1 during the launch
-            if (fused) {
-                const int ya = y0 & ~3, qrow = ((y1 | 3) + 1 - ya) >> 2, rows = x1 - x0 + 1;
-                const int total = rows * qrow;
-                // (pm is a char pointer and may alias anything for the compiler: the loads of a batch
-                // are issued before its stores by hand)
-                constexpr int kBatch = 4;                                     // 16-byte read-modify-writes a lane keeps in flight
-                for (int q0 = tid; q0 < total; q0 += kBatch * blockDim.x) {
-                    uint4 p[kBatch], h[kBatch];
-                    size_t at[kBatch];
-                    bool add[kBatch];
+        const int x0 = max(ctl->bbox[0], 0), y0 = max(ctl->bbox[1], 0), x1 = min(ctl->bbox[2], g.xw - 1), y1 = min(ctl->bbox[3], g.yw - 1);
+        const OccRule rule = OccRule::of(g);
+        if (x0 <= x1 && y0 <= y1 && fused) {
+            // the window's pass counts are added here, with plain 16-byte read-modify-writes
+            const int ya = y0 & ~3, qrow = ((y1 | 3) + 1 - ya) >> 2, rows = x1 - x0 + 1;
+            const int total = rows * qrow;
+            // (pm is a char pointer and may alias anything for the compiler: the loads of a batch
+            // are issued before its stores by hand)
+            constexpr int kBatch = 4;                                     // 16-byte read-modify-writes a lane keeps in flight
+            for (int q0 = tid; q0 < total; q0 += kBatch * blockDim.x) {
+                uint4 p[kBatch], h[kBatch];
+                size_t at[kBatch];
+                bool add[kBatch];
 #pragma unroll
-                    for (int u = 0; u < kBatch; ++u) {
-                        int q = min(q0 + u * (int)blockDim.x, total - 1);
-                        int r = q / qrow, c = q - r * qrow;
-                        int x = x0 + r, y = ya + 4 * c;
-                        at[u] = (size_t)x * g.yw + y;
-                        p[u] = *reinterpret_cast<const uint4 *>(pass + at[u]);
-                        h[u] = *reinterpret_cast<const uint4 *>(hit + at[u]);
-                        unsigned wx = (unsigned)(x - wx0), wy = (unsigned)(y - wy0);   // wy is a multiple of 4 when inside
-                        unsigned d0 = 0, d1 = 0;
-                        if (wx < (unsigned)W && wy < (unsigned)H) {
-                            unsigned di = wx * Hp2 + (wy >> 1);
-                            d0 = win[di];
-                            d1 = (wy >> 1) + 1 < (unsigned)Hp2 ? win[di + 1] : 0u;
-                        }
-                        add[u] = (d0 | d1) != 0;
-                        p[u].x += d0 & 0xffffu; p[u].y += d0 >> 16;
-                        p[u].z += d1 & 0xffffu; p[u].w += d1 >> 16;
+                for (int u = 0; u < kBatch; ++u) {
+                    int q = min(q0 + u * (int)blockDim.x, total - 1);
+                    int r = q / qrow, c = q - r * qrow;
+                    int x = x0 + r, y = ya + 4 * c;
+                    at[u] = (size_t)x * g.yw + y;
+                    p[u] = *reinterpret_cast<const uint4 *>(pass + at[u]);
+                    h[u] = *reinterpret_cast<const uint4 *>(hit + at[u]);
+                    unsigned wx = (unsigned)(x - wx0), wy = (unsigned)(y - wy0);   // wy is a multiple of 4 when inside
+                    unsigned d0 = 0, d1 = 0;
+                    if (wx < (unsigned)W && wy < (unsigned)H) {
+                        unsigned di = wx * Hp2 + (wy >> 1);
+                        d0 = win[di];
+                        d1 = (wy >> 1) + 1 < (unsigned)Hp2 ? win[di + 1] : 0u;
                     }
+                    add[u] = (d0 | d1) != 0;
+                    p[u].x += d0 & 0xffffu; p[u].y += d0 >> 16;
+                    p[u].z += d1 & 0xffffu; p[u].w += d1 >> 16;
+                }
 #pragma unroll
-                    for (int u = 0; u < kBatch; ++u) {
-                        if (q0 + u * (int)blockDim.x >= total) continue;
-                        if (add[u]) *reinterpret_cast<uint4 *>(pass + at[u]) = p[u];
-                        uint32_t out = rule.value(p[u].x, h[u].x) | rule.value(p[u].y, h[u].y) << 8 |
-                                       rule.value(p[u].z, h[u].z) << 16 | rule.value(p[u].w, h[u].w) << 24;
-                        *reinterpret_cast<uint32_t *>(pm + at[u]) = out;
-                    }
+                for (int u = 0; u < kBatch; ++u) {
+                    if (q0 + u * (int)blockDim.x >= total) continue;
+                    if (add[u]) *reinterpret_cast<uint4 *>(pass + at[u]) = p[u];
+                    uint32_t out = rule.value(p[u].x, h[u].x) | rule.value(p[u].y, h[u].y) << 8 |
+                                   rule.value(p[u].z, h[u].z) << 16 | rule.value(p[u].w, h[u].w) << 24;
+                    *reinterpret_cast<uint32_t *>(pm + at[u]) = out;
                 }
-            } else {
-                for (int x = x0 + wave; x <= x1; x += nwaves) {
-                    size_t rowb = (size_t)x * g.yw;
-                    for (int y = y0 + lane; y <= y1; y += kWave) pm[rowb + y] = (int8_t)rule.value(pass[rowb + y], hit[rowb + y]);
-                }
+            }
+        } else if (x0 <= x1 && y0 <= y1) {
+            for (int x = x0 + wave; x <= x1; x += nwaves) {
+                size_t rowb = (size_t)x * g.yw;
+                for (int y = y0 + lane; y <= y1; y += kWave) pm[rowb + y] = (int8_t)rule.value(pass[rowb + y], hit[rowb + y]);
             }
         }
     }
-    unsigned tot = wave_sum_u32(nvis);
-    int anybad = bad;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) anybad |= __shfl_xor(anybad, off, kWave);
-    if (lane == 0) {
-        if (tot) atomicAdd(wg_visits, (unsigned long long)tot);      // summed per workgroup in LDS: ONE global add, at the very end
-        if (anybad) atomicOr(g.status, anybad);
-    }
-    __syncthreads();
-    if (tid == 0 && *wg_visits) atomicAdd(visit_slot(g.visits), *wg_visits);
+    finish_workgroup(g, &ctl->visits, nvis, tid);
     STAMP(4);                                   // flush / sweep
-    STAMP_VAL((box[36] << 8) | (covers ? 1 : 0) | (phases << 4) | ((unsigned)(W * ((H + 1) & ~1)) << 12));
+    STAMP_VAL((covers ? 1 : 0) | (1 << 4) | ((unsigned)(W * ((H + 1) & ~1)) << 12));
     STAMP_END(5);                               // [5] lifetime, [6] workgroups
-    lds_guard_check(guard, g.status);
+    lds_guard_check(lds.guard, g.status);
 }
-
 
 // ---------------------------------------------------------------------------------
 // Single-scan owner kernel (DESIGN.md "K4 owner"): ONE scan cast into a map that this workgroup
@@ -1048,29 +1140,40 @@ struct OwnRay {
     }
 };
 
+// Control block of owner_cast, in the LDS region of the window kernels' (WinCtl)
+struct OwnCtl {
+    int bbox[4];                     // x0, y0, x1, y1 of everything the scan's rays can touch
+    int win[4];                      // x0, y0, W, H of the rows and cells the strips cover
+    int halves, split;               // cut at the origin's column `split` instead of into strips
+    int strips, strip_w;
+    alignas(8) unsigned long long visits;   // of the whole workgroup: ONE global add, at the very end
+    int unsafe;                      // some ray leaves the map
+    int first_bad;                   // the scan's first beam that Python's int() would raise on
+};
+static_assert(sizeof(OwnCtl) <= kWinBoxInts * 4, "the control block outgrew its LDS region");
+
 template <class Src, int kOwnerRays>
 __device__ __forceinline__ void owner_cast(const GridDev &g, const Src &src, int sort_cap, int win_cells, const int l)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     ScanConst *sc = reinterpret_cast<ScanConst *>(smem);
-    int *box = reinterpret_cast<int *>(smem + win_sc_bytes(1));
-    int *hist = box + kWinBoxInts;                                   // [2][kSortBins]: (direction half,) length bin
+    OwnCtl *ctl = reinterpret_cast<OwnCtl *>(smem + win_sc_bytes(1));
+    int *hist = reinterpret_cast<int *>(ctl) + kWinBoxInts;          // [2][kSortBins]: (direction half,) length bin
     unsigned short *order = reinterpret_cast<unsigned short *>(hist + 2 * kSortBins);
     unsigned *win = reinterpret_cast<unsigned *>(order + sort_cap);
     char *guard = reinterpret_cast<char *>(win) + (size_t)win_cells * 2;
     lds_guard_fill(guard);
     STAMP_DECL;
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
     const int gi = src.own_grid(l), n = src.n;
     uint32_t *pass = g.pass + (size_t)gi * g.xw * g.yw, *hit = g.hit + (size_t)gi * g.xw * g.yw;
     int8_t *pm = g.pmap_live + (size_t)gi * g.xw * g.yw;
-    unsigned long long *wg_visits = reinterpret_cast<unsigned long long *>(box + 12);
     unsigned short *bins = reinterpret_cast<unsigned short *>(win);   // scratch until the window is first zeroed
 
     if (tid == 0) {
         src.scan_const(l, 0, g, sc[0]);
-        box[0] = box[1] = INT_MAX; box[2] = box[3] = INT_MIN; *wg_visits = 0ull; box[14] = 0; box[15] = INT_MAX;
+        ctl->bbox[0] = ctl->bbox[1] = INT_MAX; ctl->bbox[2] = ctl->bbox[3] = INT_MIN; ctl->visits = 0ull; ctl->unsafe = 0; ctl->first_bad = INT_MAX;
     }
     if (tid < 2 * kSortBins) hist[tid] = 0;
     __syncthreads();
@@ -1089,7 +1192,7 @@ __device__ __forceinline__ void owner_cast(const GridDev &g, const Src &src, int
         // the scan stops at its first beam that Python's int() would raise on (mapping.py:29-36: the
         // beams before it have been applied when the exception leaves update(), and the error is that
         // beam's)
-        if (b2) atomicMin(&box[15], r);
+        if (b2) atomicMin(&ctl->first_bad, r);
         // longest first; rays that run towards larger x behind those that run towards smaller x (see `halves`)
         int bin = kSortBins - 1 - min(len >> 2, kSortBins - 1) + (pox >= c0.pcx ? kSortBins : 0);
         bins[r] = (unsigned short)bin;
@@ -1097,18 +1200,18 @@ __device__ __forceinline__ void owner_cast(const GridDev &g, const Src &src, int
     }
     bx0 = wave_min_i32(bx0); by0 = wave_min_i32(by0); bx1 = wave_max_i32(bx1); by1 = wave_max_i32(by1);
     if (lane == 0 && bx0 <= bx1) {
-        atomicMin(&box[0], bx0); atomicMin(&box[1], by0); atomicMax(&box[2], bx1); atomicMax(&box[3], by1);
+        atomicMin(&ctl->bbox[0], bx0); atomicMin(&ctl->bbox[1], by0); atomicMax(&ctl->bbox[2], bx1); atomicMax(&ctl->bbox[3], by1);
     }
     __syncthreads();
     if (tid == 0) {
-        if (box[15] != INT_MAX) {                                    // the first bad beam's own error (NaN or overflow)
+        if (ctl->first_bad != INT_MAX) {                             // the first bad beam's own error (NaN or overflow)
             int pox, poy, b2 = 0;
-            (void)src.ray(l, 0, box[15], c0, g, pox, poy, b2);
+            (void)src.ray(l, 0, ctl->first_bad, c0, g, pox, poy, b2);
             atomicOr(g.status, b2);
         }
         // window = bounding box clamped to the map, rows widened to whole 16-cell pieces, cut into
         // S strips of at most Ws rows that each fit the window
-        int x0 = max(box[0], 0), y0 = max(box[1], 0), x1 = min(box[2], g.xw - 1), y1 = min(box[3], g.yw - 1);
+        int x0 = max(ctl->bbox[0], 0), y0 = max(ctl->bbox[1], 0), x1 = min(ctl->bbox[2], g.xw - 1), y1 = min(ctl->bbox[3], g.yw - 1);
         int S = 0, Ws = 0, ya = 0, Ha = 0;
         if (x0 <= x1 && y0 <= y1) {
             ya = y0 & ~15; Ha = ((y1 | 15) + 1) - ya;
@@ -1122,26 +1225,14 @@ __device__ __forceinline__ void owner_cast(const GridDev &g, const Src &src, int
         int halves = 0;
         const int split = min(max(c0.pcx, x0), x1);
         if (S >= 2 && (long)max(split - x0 + 1, x1 - split + 1) * Ha <= win_cells) { halves = 1; S = 2; }
-        box[4] = x0; box[5] = ya; box[6] = x1 - x0 + 1; box[7] = Ha; box[10] = S; box[11] = Ws; box[8] = halves; box[9] = split;
+        ctl->win[0] = x0; ctl->win[1] = ya; ctl->win[2] = x1 - x0 + 1; ctl->win[3] = Ha;
+        ctl->strips = S; ctl->strip_w = Ws; ctl->halves = halves; ctl->split = split;
     }
-    if (wave == 0) {                                                 // counting sort by (half, length bin): scan of the histogram
-        int h4[4], tot = 0;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { h4[u] = hist[4 * lane + u]; tot += h4[u]; }
-        int inc = tot;
-#pragma unroll
-        for (int off = 1; off < kWave; off <<= 1) { int v = __shfl_up(inc, off, kWave); if (lane >= off) inc += v; }
-        int run = inc - tot;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { hist[4 * lane + u] = run; run += h4[u]; }
-    }
-    __syncthreads();
-    for (int r = tid; r < n; r += blockDim.x) order[atomicAdd(&hist[bins[r]], 1)] = (unsigned short)r;
-    __syncthreads();
+    counting_sort<2 * kSortBins / kWave>(hist, bins, order, n, nullptr);   // by (half, length bin)
     STAMP(1);
-    const int wx0 = box[4], wy0 = box[5], W = box[6], H = box[7], strips = box[10], strip_w = box[11];
-    const bool halves = box[8] != 0;
-    const int split = box[9];
+    const int wx0 = ctl->win[0], wy0 = ctl->win[1], W = ctl->win[2], H = ctl->win[3], strips = ctl->strips, strip_w = ctl->strip_w;
+    const bool halves = ctl->halves != 0;
+    const int split = ctl->split;
     const int Hp2 = H >> 1;
 
     // this lane's rays: sorted rays tid, tid + blockDim, ...
@@ -1160,7 +1251,7 @@ __device__ __forceinline__ void owner_cast(const GridDev &g, const Src &src, int
         const int sr = tid + j * (int)blockDim.x;
         if (sr >= n || strips == 0) continue;
         int b2 = 0;
-        if ((int)order[sr] >= box[15]) continue;                     // at or after the first bad beam: not cast
+        if ((int)order[sr] >= ctl->first_bad) continue;                    // at or after the first bad beam: not cast
         if (!src.ray(l, 0, (int)order[sr], c0, g, pox[j], poy[j], b2)) continue;
         if (!ray_setup(c0.pcx, c0.pcy, pox[j], poy[j], rr)) continue;          // identical cells: empty path (bresenham.py:10-11)
         const bool inmap = (unsigned)c0.pcx < (unsigned)g.xw && (unsigned)c0.pcy < (unsigned)g.yw &&
@@ -1170,16 +1261,16 @@ __device__ __forceinline__ void owner_cast(const GridDev &g, const Src &src, int
         nvis += (unsigned)rr.dx + 1u;                                // every cell of the path is in the map (mapping.py:41)
         ry[j].start(rr, H);
     }
-    if (unsafe) box[14] = 1;
+    if (unsafe) ctl->unsafe = 1;
     __syncthreads();
-    const bool any_unsafe = box[14] != 0;
+    const bool any_unsafe = ctl->unsafe != 0;
 
     const uint32_t pthr = g.pass_thresh[0];
     const int qrow = H >> 2;                                         // quads per window row (H is a multiple of 16)
     const unsigned qinv = qrow ? (unsigned)((0x100000000ull + (unsigned)qrow - 1) / (unsigned)qrow) : 0u;   // q / qrow == umulhi(q, qinv)
     for (int strip = 0; strip < strips; ++strip) {
         const int sx0 = halves ? (strip ? split : wx0) : wx0 + strip * strip_w;
-        const int SW = halves ? (strip ? wx0 + W - split : split - wx0 + 1) : min(strip_w, wx0 + W - sx0), total = SW * qrow;
+        const int SW = halves ? (strip ? wx0 + W - split : split - wx0 + 1) : min(strip_w, wx0 + W - sx0);
         if (strip) __syncthreads();                                  // the previous strip's sweep has read the window
         {
             uint4 *w4 = reinterpret_cast<uint4 *>(win);
@@ -1269,56 +1360,7 @@ __device__ __forceinline__ void owner_cast(const GridDev &g, const Src &src, int
         }
         __syncthreads();
         STAMP(3);
-        // sweep: 4 lanes per 64-byte piece of a counter row
-        constexpr int kBatch = 4;                                     // 16-byte read-modify-writes a lane keeps in flight
-        for (int q0 = tid; q0 < total; q0 += kBatch * blockDim.x) {
-            uint4 p[kBatch];
-            uint32_t om[kBatch], d0[kBatch], d1[kBatch];
-            size_t at[kBatch];
-            bool live[kBatch];
-#pragma unroll
-            for (int u = 0; u < kBatch; ++u) {
-                const int q = q0 + u * (int)blockDim.x;
-                d0[u] = d1[u] = 0u;
-                if (q < total) {
-                    const int r = (int)__umulhi((unsigned)q, qinv), c = q - r * qrow;
-                    const uint2 d = *reinterpret_cast<const uint2 *>(win + (r * Hp2 + 2 * c));
-                    d0[u] = d.x; d1[u] = d.y;
-                    at[u] = (size_t)(sx0 + r) * g.yw + (wy0 + 4 * c);
-                }
-                // the four lanes of a piece decide together (total and blockDim are multiples of 4)
-                const unsigned long long m = __ballot((d0[u] | d1[u]) != 0u);
-                live[u] = ((m >> (lane & 60)) & 0xFull) != 0ull;
-                if (live[u]) {
-                    p[u] = *reinterpret_cast<const uint4 *>(pass + at[u]);
-                    om[u] = *reinterpret_cast<const uint32_t *>(pm + at[u]);
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < kBatch; ++u) {
-                if (!live[u]) continue;
-                const uint32_t d0v = d0[u], d1v = d1[u];
-                p[u].x += d0v & 0x7fffu; p[u].y += (d0v >> 16) & 0x7fffu; p[u].z += d1v & 0x7fffu; p[u].w += (d1v >> 16) & 0x7fffu;
-                *reinterpret_cast<uint4 *>(pass + at[u]) = p[u];
-                if (!(d0v | d1v)) continue;
-                const uint32_t o = om[u];
-                // one bit per byte (cell): touched by this scan / hit by this scan / occupied before (bit 6
-                // is set in 100 only) / never touched before (bit 4 is set in 50 only)
-                const uint32_t tb = ((d0v & 0xffffu) ? 1u : 0u) | ((d0v >> 16) ? 0x100u : 0u) | ((d1v & 0xffffu) ? 0x10000u : 0u) | ((d1v >> 16) ? 0x1000000u : 0u);
-                const uint32_t fb = ((d0v >> 15) & 1u) | (((d0v >> 31) & 1u) << 8) | (((d1v >> 15) & 1u) << 16) | ((d1v >> 31) << 24);
-                const uint32_t was = (o >> 6) & 0x01010101u, fresh = (o >> 4) & 0x01010101u;
-                const uint32_t pmax = max(max(p[u].x, p[u].y), max(p[u].z, p[u].w));
-                // a byte changes iff the cell was touched, was not occupied, and is fresh (50 -> 0 or 100),
-                // hit now (-> 100) or at / over the pass threshold now (-> 100)
-                if (((tb & ~was) & (fresh | fb)) != 0u || pmax >= pthr) {
-                    uint32_t occ = was | fb;
-                    occ |= (p[u].x >= pthr ? 1u : 0u) | (p[u].y >= pthr ? 0x100u : 0u) | (p[u].z >= pthr ? 0x10000u : 0u) | (p[u].w >= pthr ? 0x1000000u : 0u);
-                    const uint32_t tm = tb * 255u;
-                    const uint32_t out = (o & ~tm) | ((occ * 100u) & tm);
-                    if (out != o) *reinterpret_cast<uint32_t *>(pm + at[u]) = out;
-                }
-            }
-        }
+        sweep_strip(win, pass, pm, g.yw, sx0, wy0, SW, H, qrow, qinv, pthr);
         STAMP_SYNC();
         STAMP(4);
     }
@@ -1327,11 +1369,11 @@ __device__ __forceinline__ void owner_cast(const GridDev &g, const Src &src, int
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) anybad |= __shfl_xor(anybad, off, kWave);
     if (lane == 0) {
-        if (tot) atomicAdd(wg_visits, (unsigned long long)tot);
+        if (tot) atomicAdd(&ctl->visits, (unsigned long long)tot);
         if (anybad) atomicOr(g.status, anybad);
     }
     __syncthreads();
-    if (tid == 0 && *wg_visits) atomicAdd(visit_slot(g.visits), *wg_visits);
+    if (tid == 0 && ctl->visits) atomicAdd(visit_slot(g.visits), ctl->visits);
     STAMP_COUNT(7, strips);
     STAMP_END(5);
     lds_guard_check(guard, g.status);
@@ -1695,8 +1737,8 @@ static hipError_t launch_win(const GridDev &g, const Src &src, int L, int scans,
                              hipStream_t s, int split_pref = -1)
 {
     const size_t lds_max = win_lds_bytes(kWinMaxGroup, kMaxSortRays, kWinCells);
-    {
-        hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(&k_grid_update_win<Src>), (int)lds_max);
+    for (const void *f : {reinterpret_cast<const void *>(&k_grid_update_win<Src>), reinterpret_cast<const void *>(&k_grid_update_own<Src>)}) {
+        hipError_t e = allow_dynamic_lds(f, (int)lds_max);
         if (e != hipSuccess) return e;
     }
     int groups = (scans + group - 1) / group;
@@ -1753,11 +1795,14 @@ static hipError_t launch_win(const GridDev &g, const Src &src, int L, int scans,
     const size_t half_cu = (size_t)(chip.lds_per_cu / 2);
     if (split && wgs <= chip.cus && lds <= half_cu && half_cu + 512 <= (size_t)chip.lds_per_cu) lds = half_cu + 512;
     if (lds > lds_max) {
-        hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(&k_grid_update_win<Src>), (int)lds);
+        const void *f = exclusive ? reinterpret_cast<const void *>(&k_grid_update_own<Src>) : reinterpret_cast<const void *>(&k_grid_update_win<Src>);
+        hipError_t e = allow_dynamic_lds(f, (int)lds);
         if (e != hipSuccess) return e;
     }
-    SLAM_LAUNCH((k_grid_update_win<Src>), dim3(split ? 2 * groups : groups, L), dim3(threads), lds, s, g, src, group, got,
-                exclusive, sort_cap, win_cells, split);
+    // the map's only writer (then there is one group, and no `got`) finishes its cells itself, pmap included
+    if (exclusive) SLAM_LAUNCH((k_grid_update_own<Src>), dim3(groups, L), dim3(threads), lds, s, g, src, group, sort_cap, win_cells);
+    else SLAM_LAUNCH((k_grid_update_win<Src>), dim3(split ? 2 * groups : groups, L), dim3(threads), lds, s, g, src, group, got,
+                     sort_cap, win_cells, split);
     return hipGetLastError();
 }
 
@@ -2617,9 +2662,9 @@ static hipError_t launch_wedges(const GridDev &g, const Src &src, int L, int sca
 //                                          mode 0                                              Direct
 //   slam_particles* with a grid            always, any mode and map size                       Window
 //
-// Window is launch_win, which chooses the owner8 / owner / k_grid_update_win kernels itself.  The replay entries take at
-// most 65 535 beams, so one Window rule serves both forms.  n <= 8192 (kTileMaxBeams): ray numbers inside a group of the
-// tiles and wedges are 16-bit.
+// Window is launch_win; the table in the header of the window section ("Which kernel casts a launch") says which of the
+// window kernels takes it.  The replay entries take at most 65 535 beams, so one Window rule serves both forms.
+// n <= 8192 (kTileMaxBeams): ray numbers inside a group of the tiles and wedges are 16-bit.
 // ---------------------------------------------------------------------------------
 constexpr int kTileMaxBeams = 8192;
 

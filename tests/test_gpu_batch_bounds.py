@@ -8,8 +8,8 @@ large map, and 4) and the recorded-walk tiles (grid_mode 2).  Their workgroup gr
 than 65 535 groups is cast in successive launches of at most 65 535 groups - over whole trajectories, or over scan
 ranges of one trajectory - and must give the counters of one launch bit for bit.
 
-Part B: the batch axis on gridDim.y (k_nn, the ICP launch, k_grid_update_win / _replay, the owner kernels, k_wedge_sort,
-k_ray_bits, k_virtual_scan) with 65 537 rows.
+Part B: the batch axis on gridDim.y (k_nn, the ICP launch, k_grid_update_win, k_grid_update_own and the single-scan
+owner kernels, k_wedge_sort, k_ray_bits, k_virtual_scan) with 65 537 rows.
 
 Counters (pass, hit, pmap) bit-exact, visits equal to the oracle's, iteration counts and NN indices exact, poses and
 transforms to 1e-9."""
