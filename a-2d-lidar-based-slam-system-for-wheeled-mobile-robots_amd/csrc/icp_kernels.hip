@@ -32,12 +32,12 @@
 namespace slam {
 
 #ifdef SLAM_STAMPS_ICP
-__device__ unsigned long long g_polar_lanes[4];
-hipError_t debug_polar_lanes(unsigned long long out[4], bool clear)
+__device__ unsigned long long g_polar_lanes[6];
+hipError_t debug_polar_lanes(unsigned long long out[6], bool clear)
 {
-    hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_polar_lanes), sizeof(unsigned long long) * 4);
+    hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_polar_lanes), sizeof(unsigned long long) * 6);
     if (e == hipSuccess && clear) {
-        const unsigned long long zero[4] = {0ull, 0ull, 0ull, 0ull};
+        const unsigned long long zero[6] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
         e = hipMemcpyToSymbol(HIP_SYMBOL(g_polar_lanes), zero, sizeof zero);
     }
     return e;
@@ -454,10 +454,89 @@ struct PolarGeo {
     float slack;      // angular slack of the stored points (radians)
 };
 
-template <int UNROLL, bool PROBE>
+// ---------------------------------------------------------------------------------
+// A float32 pre-filter for the beam-window scan of the one-wave shape's later iterations (context option
+// "icp_f32_filter"): the trips of nn_polar are nine float64-class instructions a candidate, and nearly every query has ONE
+// candidate that is nearest by far more than float32 can blur.  The trips run on a float32 image of the target and keep
+// the smallest square, the runner-up and the winner's index; float64 still decides: a lane is SETTLED when the smallest
+// square beats the runner-up by more than both can be wrong, then the winner's float64 square is formed from tarP as the
+// float64 scan forms it; a wave with a searching lane that is not settled runs the float64 scan as if nothing had happened.
+//
+// The bound.  s, t: query and target as the float64 scan sees them; fs, ft their float32 roundings (|fs.x - s.x| <=
+// 2^-24 |s.x|, ...); D = |s - t|^2 exactly.  Computed: dx = fl(fs.x - ft.x), dy likewise, d = fl(fma(dy, dy, fl(dx dx))).
+//  - |dx - (s.x - t.x)| <= 2^-24 (|s.x| + |t.x|) + 2^-24 |fs.x - ft.x| <= 2^-23 (1 + 2^-24) (|s.x| + |t.x|), so the vector
+//    (dx, dy) is off by at most E' = (1 + 2^-24) E, E = 2^-23 (|s.x| + |s.y| + |t.x| + |t.y|), and with S = dx^2 + dy^2
+//    exactly: |sqrt(S) - sqrt(D)| <= E'.
+//  - d lies within (1 +- 2^-24)^2 of S; the key k that is compared is d with its two lowest mantissa bits replaced by
+//    the candidate's place in its trip: k <= d < k (1 + 2^-21).  So S lies within (1 +- theta) of k, theta = 2^-20.
+//  - the float64 scan's own square is within 2^-51 of D, and the tie bookkeeping watches a class of 2^-50.
+// The winner (key km) is strictly nearest for the float64 scan, outside any tie class, when for the runner-up's key kr
+//     sqrt(kr (1 - theta)) - E' > (sqrt(km (1 + theta)) + E') (1 + 2^-48):   every other candidate's key is >= kr.
+// Shipped, every rounding pushed outwards (settled()): a = sqrt(km) 1.000002 (theta / 2, the class, v_sqrt_f32's last
+// place), Ef = 2^-23 1.00001 (|fs.x| + |fs.y| + tmax) with tmax >= |t.x| + |t.y| for every target of the pair (found
+// while the image is written, rounded up), b = a + 2 Ef, and  settled <=> b b 1.000002 + 1e-30 < min(kr 0.999998, 1e30).
+// The 1e-30 covers squares that underflow (an absolute 2^-126 instead of a relative error; exact zeros tie), the 1e30
+// keeps a float32 overflow from passing for "far".  The issue of this change words the same bound as err(d) = 2 sqrt(2 d) E
+// + 2 E^2 + 4 2^-24 d, settled when kr - err(kr) > km + err(km); tests/test_f32_filter_bound.py restates both in NumPy
+// float32 and checks them against float64 over random, stepped, tied and far-offset scans.
+// NaN and infinity: a target whose float64 coordinate is NaN (never a winner) is +inf in the image - its square is +inf
+// (or NaN against an infinite query) and its key orders behind every finite one as an unsigned integer, as every NaN
+// pattern does; a lane without a finite winner is not settled; a non-finite tmax or query makes Ef and b infinite.
+// Whatever goes wrong in float32 can only send the wave to the float64 scan.
+// ---------------------------------------------------------------------------------
+struct F32Image {
+    const float2 *img;         // [icp_wave_points]: the target rounded to float32, +inf for NaN and behind the last beam
+    float tmax;                // >= |t.x| + |t.y| of every target with finite float32 coordinates; +inf if one has none
+};
+constexpr unsigned kF32Inf = 0x7f800000u;
+
+struct F32Best {
+    unsigned m, r;             // keys (float32 bits of a square, the low two bits the place in the trip): smallest, runner-up
+    int kb;                    // first index of the trip the smallest came from
+    __device__ __forceinline__ void start() { m = r = kF32Inf; kb = 0; }
+    __device__ __forceinline__ void take(unsigned k)
+    {
+        r = max(min(m, k), min(max(m, k), r));                       // median of three: m <= r throughout
+        m = min(m, k);
+    }
+    __device__ __forceinline__ int index() const { return kb + (int)(m & 3u); }
+    __device__ __forceinline__ bool settled(float fsx, float fsy, float tmax) const
+    {
+        const float km = __uint_as_float(m), kr = __uint_as_float(r);
+        const float a = __builtin_amdgcn_sqrtf(km) * 1.000002f;
+        const float ef = (fabsf(fsx) + fabsf(fsy) + tmax) * (0x1p-23f * 1.00001f);
+        const float b = a + 2.0f * ef;
+        return b * b * 1.000002f + 1e-30f < fminf(kr * 0.999998f, 1e30f);    // NaN: false
+    }
+};
+
+__device__ __forceinline__ unsigned f32_key(float fsx, float fsy, float2 t, unsigned place)
+{
+    const float dx = fsx - t.x, dy = fsy - t.y;
+    return (__float_as_uint(fmaf(dy, dy, dx * dx)) & ~3u) | place;
+}
+
+// nn_polar's scan over [a0, a1] in float32: the same whole trips of four, every lane runs every trip of its wave, a lane
+// past its own range reads the +inf points behind the last beam.
+__device__ __forceinline__ void scan32(const float2 *__restrict__ img, int n_tar, float fsx, float fsy, int a0, int a1, F32Best &b)
+{
+    for (int k = a0; __any(k <= a1); k += 4) {
+        const int kc = k <= a1 ? k : n_tar;
+        const float2 *t = img + kc;
+        const float2 t0 = t[0], t1 = t[1], t2 = t[2], t3 = t[3];
+        const unsigned before = b.m;
+        b.take(f32_key(fsx, fsy, t0, 0u));
+        b.take(f32_key(fsx, fsy, t1, 1u));
+        b.take(f32_key(fsx, fsy, t2, 2u));
+        b.take(f32_key(fsx, fsy, t3, 3u));
+        b.kb = b.m < before ? kc : b.kb;
+    }
+}
+
+template <int UNROLL, bool PROBE, bool F32 = false>
 __device__ __forceinline__ void nn_polar(const double2 *__restrict__ tarP, int n_tar, double sx, double sy, int seed,
                                          bool active, const PolarGeo &geo, int wmax, double &best_d2, int &best_j, bool &big,
-                                         bool &amb, unsigned long long &ambm)
+                                         bool &amb, unsigned long long &ambm, const F32Image f32 = F32Image{nullptr, 0.0f})
 {
     // (seed is a valid target index: the same beam clamped to the target's size before the first iteration, a match after it)
     const float fsx = (float)sx, fsy = (float)sy;
@@ -564,6 +643,33 @@ __device__ __forceinline__ void nn_polar(const double2 *__restrict__ tarP, int n
     Best b;
     b.start();
     const bool wraps = __any(go && ((hi >= n_tar - 2 && lo >= 1) || (lo <= 1 && hi <= n_tar - 2)));
+    if (F32) {
+        // The same ranges and the same whole trips, scanned in float32 first (see "F32Image"): a wave all of whose searching
+        // lanes PROVED their nearest target takes it - its square formed in float64 from the same bits as the scan below
+        // would, and no tie event: the proof leaves none possible - and any other wave scans as it always did.
+        F32Best fb;
+        fb.start();
+        if (wraps) {
+            const int e0 = hi >= n_tar - 2 ? min(hi - (n_tar - 1) + 1, m0 - 1) : -1;
+            scan32(f32.img, n_tar, fsx, fsy, go ? 0 : 1, go ? e0 : 0, fb);
+        }
+        scan32(f32.img, n_tar, fsx, fsy, go ? m0 : 1, go ? m1 : 0, fb);
+        if (wraps) {
+            const int s2 = lo <= 1 ? max(n_tar - 1 + lo - 1, m1 + 1) : n_tar;
+            scan32(f32.img, n_tar, fsx, fsy, go ? s2 : 1, go ? n_tar - 1 : 0, fb);
+        }
+        const bool fell_back = __any(go && !fb.settled(fsx, fsy, f32.tmax));
+        ISTAMP_F32(fell_back);
+        if (!fell_back) {
+            const int j = fb.index();                                // (a lane that is not `go` saw nothing finite: 0)
+            const double2 t = tarP[j];
+            best_d2 = go ? dist2(sx, sy, t.x, t.y) : INFINITY;
+            best_j = j;
+            amb = false;
+            ambm = 0ull;
+            return;
+        }
+    }
     if (wraps) {
         const int e0 = hi >= n_tar - 2 ? min(hi - (n_tar - 1) + 1, m0 - 1) : -1;    // [0, e0]
         scan(go ? 0 : 1, go ? e0 : 0, b);
@@ -913,6 +1019,7 @@ struct NNTarget {
     double2 *qlist;            // the list of first-iteration queries without a usable beam window (nn_listed),
     int *qseed;                // their guesses,
     int cap;                   // its room; 0: no list
+    F32Image f32 = F32Image{nullptr, 0.0f};   // the float32 image of the one-wave shape's later iterations, or none
     __device__ __forceinline__ double2 at(int j) const { return has_p ? tarP[j] : tarB[tslot(j)]; }
 };
 struct NNQuery {
@@ -929,7 +1036,7 @@ __device__ __forceinline__ double match_distance(double d2) { return (d2 < INFIN
 // from the reference's order of distances (see "Best") is added to amb_mask, the wave-wide mask of lanes that saw one:
 // kept in scalar registers (a per-lane flag cost four vector instructions a query); amb_mask != 0 -> the pair is re-done
 // with EXACT.  note_big(big): the diagnostic build's counter of queries left to the box search.
-template <int UNROLL, int STRIDE, bool EXACT, typename Place, typename NoteBig>
+template <int UNROLL, int STRIDE, bool EXACT, bool F32 = false, typename Place, typename NoteBig>
 __device__ __forceinline__ NNQuery nn_query(const NNTarget &t, const PolarGeo &pg, const double sx, const double sy, const int seed, const bool okq,
                                             const bool first, const bool listing, Place &&place, NoteBig &&note_big, unsigned long long &amb_mask)
 {
@@ -942,7 +1049,7 @@ __device__ __forceinline__ NNQuery nn_query(const NNTarget &t, const PolarGeo &p
     } else if (pg.inv_db > 0.0f) {                                   // wave-uniform: the target is a scan
         bool big, amb_lane;
         unsigned long long am;
-        nn_polar<UNROLL, false>(t.tarP, t.n_tar, sx, sy, seed, okq, pg, listing ? kPolarMaxFirst : kPolarMax, h.d2, h.j, big, amb_lane, am);
+        nn_polar<UNROLL, false, F32>(t.tarP, t.n_tar, sx, sy, seed, okq, pg, listing ? kPolarMaxFirst : kPolarMax, h.d2, h.j, big, amb_lane, am, t.f32);
         (void)amb_lane;
         amb_mask |= am;
         if (listing) {
@@ -1427,10 +1534,14 @@ __host__ __device__ inline int icp_wave_points(int n_tar)
     const int whole = nn_blocks(n_tar) * kNNBlock, tail = n_tar + kPolarTail;
     return whole > tail ? whole : tail;
 }
-__host__ __device__ inline size_t icp_wave_lds_bytes(int n_tar, int cap)
+// (f32: the float32 image of the later iterations lies over the first iteration's list, which is dead by then - 360 beams:
+// 8 768 B with a list of 96, 9 792 B with the image of 368 points over it, 16 pairs a CU either way; side by side they
+// would be 11 712 B and 13)
+__host__ __device__ inline size_t icp_wave_lds_bytes(int n_tar, int cap, bool f32)
 {
+    const size_t list = (size_t)cap * (sizeof(double2) + sizeof(int)), image = f32 ? (size_t)icp_wave_points(n_tar) * sizeof(float2) : 0;
     return (size_t)icp_wave_points(n_tar) * sizeof(double2) + (size_t)(nn_boxes_padded(n_tar) + nn_boxes4(n_tar)) * sizeof(Box) +
-           (size_t)cap * (sizeof(double2) + sizeof(int));
+           (list > image ? list : image);
 }
 
 // The distance of a match in this shape (match_distance for the lanes that are active here): a float64 square root
@@ -1462,7 +1573,7 @@ __device__ __forceinline__ double match_distance_wave(double d2)       // by the
     return sqrt_unscaled(d2);
 }
 
-template <typename T, bool EXACT>
+template <typename T, bool EXACT, bool F32>
 __device__ __forceinline__ bool icp_pair_wave(const IcpArgs &a, const int b, char *smem)
 {
     constexpr int QPT = kWaveQpt;
@@ -1472,11 +1583,12 @@ __device__ __forceinline__ bool icp_pair_wave(const IcpArgs &a, const int b, cha
     Box *boxes4 = boxes + nn_boxes_padded(n_tar);                                                // one per 4 blocks
     double2 *qlist = reinterpret_cast<double2 *>(boxes4 + nn_boxes4(n_tar));                     // [a.team_cap] nn_listed
     int *qseed = reinterpret_cast<int *>(qlist + a.team_cap);                                    // [a.team_cap]
-    char *guard = reinterpret_cast<char *>(qseed + a.team_cap);
+    float2 *tarF = reinterpret_cast<float2 *>(qlist);                                            // [icp_wave_points] F32: over the list, after the first iteration
+    char *guard = smem + icp_wave_lds_bytes(n_tar, a.team_cap, F32);
     lds_guard_fill(guard);
 
     const PairClouds<T> pc = pair_clouds<T>(a, b);
-    const NNTarget nt{tarP, tarP, boxes, boxes4, nblocks, n_tar, true, qlist, qseed, a.team_cap};
+    NNTarget nt{tarP, tarP, boxes, boxes4, nblocks, n_tar, true, qlist, qseed, a.team_cap};
 
     // the source points first: their loads are in flight together with those that stage the target
     double sx[QPT], sy[QPT];
@@ -1580,7 +1692,7 @@ __device__ __forceinline__ bool icp_pair_wave(const IcpArgs &a, const int b, cha
         for (int q = 0; q < QPT; ++q) {
             if (q * kWave >= n_src) continue;                        // wave-uniform
             const bool okq = lane + q * kWave < n_src;
-            const NNQuery h = nn_query<4, kNNBlock, EXACT>(nt, pg, sx[q], sy[q], seed[q], okq, false, false, place, no_note, amb_mask);
+            const NNQuery h = nn_query<4, kNNBlock, EXACT, F32 && !EXACT>(nt, pg, sx[q], sy[q], seed[q], okq, false, false, place, no_note, amb_mask);
             seed[q] = h.j;                                           // next iteration's guess
             const double2 m = tarP[h.j];
             same.step(q, okq, h.j, m.x, m.y);
@@ -1590,9 +1702,26 @@ __device__ __forceinline__ bool icp_pair_wave(const IcpArgs &a, const int b, cha
         advance(rigid_from_w(o.c, o.A, 0.0, o.B, 0.0, !same.wave_differs() || src_collapsed, lane), o.c.bx, o.c.by, sx, sy, s);
         return converged(s, a.tol);
     };
-    if (a.max_iter > 0 && !first_iteration())
+    // the float32 image of the target for the later iterations' beam windows (F32Image), over the list the first one is done with
+    auto stage_f32 = [&]() __attribute__((always_inline)) {
+        wave_sync();
+        float tm = 0.0f;
+        for (int j = lane; j < icp_wave_points(n_tar); j += kWave) {
+            const double2 t = tarP[j];                               // (NaN behind the last beam)
+            const float fx = t.x == t.x ? (float)t.x : INFINITY, fy = t.y == t.y ? (float)t.y : INFINITY;
+            tarF[j] = make_float2(fx, fy);
+            if (t.x == t.x && t.y == t.y) tm = fmaxf(tm, fabsf(fx) + fabsf(fy));
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) tm = fmaxf(tm, __shfl_xor(tm, off));
+        nt.f32 = F32Image{tarF, __uint_as_float((unsigned)__builtin_amdgcn_readfirstlane((int)__float_as_uint(tm * 1.000001f)))};
+        wave_sync();
+    };
+    if (a.max_iter > 0 && !first_iteration()) {
+        if (F32 && !EXACT && pg.inv_db > 0.0f && a.max_iter > 1) stage_f32();
         for (int it = 1; it < a.max_iter; ++it)
             if (iteration()) break;
+    }
 
     // final T (final_transform); the originals are formed again from the source
     Rigid2 r;
@@ -1656,14 +1785,15 @@ __global__ void __launch_bounds__(1024) k_icp(IcpArgs a)
 // k_icp<T>: one WAVE per pair (icp_pair_wave); at most 128 registers, so that four pairs are resident per SIMD.  An overload
 // of the name on purpose: kernel traces, counter summaries and the benchmark's roofline file the scan matcher under k_icp
 // whatever its launch shape, and tell the shapes apart by their template arguments.
-template <typename T>
+// F32: the later iterations' beam windows are scanned in float32 first (F32Image; context option "icp_f32_filter").
+template <typename T, bool F32>
 __global__ void __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(4))) k_icp(IcpArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     icp_clear_on_the_way(a);
-    if (icp_pair_wave<T, false>(a, blockIdx.x, smem)) {
+    if (icp_pair_wave<T, false, F32>(a, blockIdx.x, smem)) {
         wave_sync();                                                 // the second pass re-uses the LDS
-        icp_pair_wave<T, true>(a, blockIdx.x, smem);
+        icp_pair_wave<T, true, F32>(a, blockIdx.x, smem);
     }
 }
 
@@ -1707,12 +1837,16 @@ static hipError_t launch_icp_t(const IcpArgs &a_in, hipStream_t s)
     // (context option "icp_one_wave").
     {
         const int cap = (a.ranges && a.team_mode == 0) ? ((a.n_src + 3) / 4 + 15) / 16 * 16 : 0;   // the list: a quarter of the queries (a fifth is listed on the benchmark scans)
-        const size_t lds = icp_wave_lds_bytes(a.n_tar, cap) + kLdsGuard;
+        // a.f32_filter: -1 / 1 = the float32 pre-filter of the later iterations' beam windows (scans only: a point cloud has no
+        // windows), 0 = the float64 scan alone (context option "icp_f32_filter"; no result depends on it)
+        const bool f32 = a.f32_filter != 0 && a.ranges;
+        const size_t lds = icp_wave_lds_bytes(a.n_tar, cap, f32) + kLdsGuard;
         const bool fits = a.n_src <= kWave * kWaveQpt && lds <= 64 * 1024;
-        const bool full = !a.batch_invariant && pref == 3 && a.B >= 4 * kWaveRound && a.n_src > kWave * 3 && a.ranges && lds <= 10 * 1024;
+        const bool full = !a.batch_invariant && pref == 3 && a.B >= 4 * kWaveRound && a.n_src > kWave * 3 && a.ranges && lds - kLdsGuard <= 10 * 1024;   // (the shipped layout's size: the debug build's guard does not choose the shape)
         if (fits && (a.one_wave == 1 || (a.one_wave < 0 && full))) {
             a.team_cap = cap;
-            SLAM_LAUNCH((k_icp<T>), dim3(a.B), dim3(kWave), lds, s, a);
+            if (f32) SLAM_LAUNCH((k_icp<T, true>), dim3(a.B), dim3(kWave), lds, s, a);
+            else SLAM_LAUNCH((k_icp<T, false>), dim3(a.B), dim3(kWave), lds, s, a);
             return hipGetLastError();
         }
     }

@@ -99,6 +99,7 @@ struct slam_ctx {
     int grid_split = -1;  // window mode: two workgroups per group, one per direction half (-1: when the launch cannot fill the chip)
     int icp_qpt = 0;      // queries per lane of batched scan matching (0: by batch size)
     int replay_reset = 0; // 1: slam_replay_dev clears its map's counters itself (inside the scan-matching launch)
+    int icp_f32_filter = -1; // float32 pre-filter of the one-wave shape's beam windows: -1 = the library's choice (on), 0 = off, 1 = on; changes no result
     int icp_one_wave = -1; // scan matching with one wave per pair: -1 = where a full-chip launch allows it, 0 = never, 1 = wherever a pair fits
     int icp_team = 0;     // first-iteration queries without a beam window: 0 = listed and searched apart from their lanes (nn_listed), 1 = box search
     // "pipeline" option: the map stage of slam_replay_dev (reset -> ray cast -> finalize) runs on
@@ -699,6 +700,7 @@ static const OptionRange kOptionRanges[] = {
     {"replay_reset", [](double v) { return v == 0 || v == 1; }, "replay_reset is 0 or 1"},
     {"icp_team", [](double v) { return v == 0 || v == 1; }, "icp_team is 0 or 1"},
     {"icp_one_wave", [](double v) { return v == -1 || v == 0 || v == 1; }, "icp_one_wave is -1, 0 or 1"},
+    {"icp_f32_filter", [](double v) { return v == -1 || v == 0 || v == 1; }, "icp_f32_filter is -1, 0 or 1"},
     {"particle_chunks", [](double v) { return v >= 0 && v <= 64 && v == (int)v; }, "particle_chunks in [0, 64]"},
     {"icp_qpt", [](double v) { return v >= 0 && v <= 3; }, "icp_qpt in [0, 3]"},
     {"pipeline", [](double v) { return v == 0 || v == 1; }, "pipeline is 0 or 1"},
@@ -719,6 +721,7 @@ int slam_set_option(slam_ctx *c, const char *name, double value)
     else if (!strcmp(name, "replay_reset")) c->replay_reset = (int)value;
     else if (!strcmp(name, "icp_team")) c->icp_team = (int)value;
     else if (!strcmp(name, "icp_one_wave")) c->icp_one_wave = (int)value;
+    else if (!strcmp(name, "icp_f32_filter")) c->icp_f32_filter = (int)value;
     else if (!strcmp(name, "particle_chunks")) { TRY(join_particles(c)); c->particle_chunks = (int)value; }
     else if (!strcmp(name, "icp_qpt")) c->icp_qpt = (int)value;
     else if (!strcmp(name, "pipeline")) {
@@ -788,11 +791,11 @@ int slam_debug_read(slam_ctx *c, void *out256, int clear)
 #ifdef SLAM_STAMPS_ICP
 /* diagnostic build: lane efficiency counters of the beam-window search (slam_stamps.h, ISTAMP_SCAN): own candidates and
    candidate slots of the first iteration, of the later ones */
-int slam_debug_lanes(slam_ctx *c, unsigned long long *out4, int clear)
+int slam_debug_lanes(slam_ctx *c, unsigned long long *out6, int clear)
 {
     TRY(use(c));
     HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(slam::debug_polar_lanes(out4, clear != 0));
+    HIPCHK(slam::debug_polar_lanes(out6, clear != 0));
     return SLAM_OK;
 }
 #endif
@@ -932,7 +935,7 @@ int slam_icp_batch_dev(slam_ctx *c, const void *tar, const void *src, int B, int
     a.ppt = 0;
     a.B = B; a.n_tar = n_tar; a.n_src = n_src; a.max_iter = max_iter; a.tol = tol;
     a.T_out = T_out; a.iters_out = iters_out; a.err_out = mean_err_out;
-    a.status = c->status; a.qpt_pref = c->icp_qpt; a.team_mode = c->icp_team; a.one_wave = c->icp_one_wave;
+    a.status = c->status; a.qpt_pref = c->icp_qpt; a.team_mode = c->icp_team; a.one_wave = c->icp_one_wave; a.f32_filter = c->icp_f32_filter;
     Timed t(c, SLAM_K_ICP);
     HIPCHK(launch_icp(a, dtype, c->stream));
     return SLAM_OK;
@@ -1400,7 +1403,7 @@ int slam_replay_dev(slam_ctx *c, const float *ranges, const double *cos_t, const
         a.ppt = n_scan - 1;
         a.B = (int)pairs; a.n_tar = n; a.n_src = n; a.max_iter = max_iter; a.tol = tol;
         a.T_out = T; a.iters_out = iters_out; a.err_out = nullptr;
-        a.status = c->status; a.qpt_pref = c->icp_qpt; a.team_mode = c->icp_team; a.one_wave = c->icp_one_wave;
+        a.status = c->status; a.qpt_pref = c->icp_qpt; a.team_mode = c->icp_team; a.one_wave = c->icp_one_wave; a.f32_filter = c->icp_f32_filter;
         if (grid && c->replay_reset) {
             // option "replay_reset": the map starts from zero for this replay.  On one stream the scan-matching launch
             // clears the counters on its way (they are next touched by the ray cast behind it); maps with a live pmap and
@@ -1537,7 +1540,7 @@ int slam_particles_dev(slam_ctx *c, const float *ranges2, const double *cos_t, c
             a.ppt = 0;
             a.B = pc; a.n_tar = n; a.n_src = n; a.max_iter = max_iter; a.tol = tol;
             a.T_out = T_out + 9 * (size_t)p0; a.iters_out = iters_out ? iters_out + p0 : nullptr; a.err_out = nullptr;
-            a.status = c->status; a.team_mode = c->icp_team; a.one_wave = c->icp_one_wave;
+            a.status = c->status; a.team_mode = c->icp_team; a.one_wave = c->icp_one_wave; a.f32_filter = c->icp_f32_filter;
             // (queries per lane by the size of the BATCH: its chunks share the chip with one another's ray casts)
             a.qpt_pref = c->icp_qpt > 0 ? c->icp_qpt : (P >= 2500 ? 3 : 0);
             Timed t(c, SLAM_K_ICP, nullptr, k == 0);
@@ -2067,7 +2070,7 @@ int slam_node_replay_dev(slam_ctx *c, const float *ranges, const double *cos_t, 
         a.ppt = n_scan - 1;
         a.B = (int)pairs; a.n_tar = n; a.n_src = n; a.max_iter = max_iter; a.tol = tol;
         a.T_out = T; a.iters_out = iters_out; a.err_out = nullptr;
-        a.status = c->status; a.qpt_pref = c->icp_qpt; a.team_mode = c->icp_team; a.one_wave = c->icp_one_wave;
+        a.status = c->status; a.qpt_pref = c->icp_qpt; a.team_mode = c->icp_team; a.one_wave = c->icp_one_wave; a.f32_filter = c->icp_f32_filter;
         a.batch_invariant = 1;      // a trajectory's result does not depend on how many run beside it
         Timed t(c, SLAM_K_ICP);
         HIPCHK(launch_icp(a, dtype, c->stream));
@@ -2155,7 +2158,7 @@ int slam_loc_replay_dev(slam_ctx *c, const float *ranges, int S, int n_scan, int
     IcpArgs icp;
     icp.prior = nullptr; icp.ranges = nullptr; icp.cos_t = icp.sin_t = nullptr; icp.tar_scan_stride = icp.src_scan_stride = 0;
     icp.ppt = 0; icp.n_tar = n; icp.n_src = n; icp.max_iter = max_iter; icp.tol = tol; icp.err_out = nullptr;
-    icp.status = c->status; icp.qpt_pref = c->icp_qpt; icp.team_mode = c->icp_team; icp.one_wave = c->icp_one_wave;
+    icp.status = c->status; icp.qpt_pref = c->icp_qpt; icp.team_mode = c->icp_team; icp.one_wave = c->icp_one_wave; icp.f32_filter = c->icp_f32_filter;
     icp.batch_invariant = 1;        // a trajectory's result does not depend on how many run beside it
     {   // the solves that depend on the stream alone, once per stream: every T2 (:100) and T1 of the steps after the first (:78)
         HIPCHK(launch_loc_stream_pairs(ranges, cos_t, sin_t, S, n_scan, n, pair_pts, c->stream));

@@ -61,11 +61,19 @@ constexpr int kStampRecords = 32768;
 // [13] lifetimes on the 100 MHz clock, [14] 2^62 - earliest start, [15] latest end (100 MHz clock).
 // Lane efficiency of the beam-window search (nn_polar::scan), -DSLAM_STAMPS_ICP only: candidates inside the lanes' own
 // windows against the candidate slots the waves ran (64 lanes x trips x candidates per trip), for the first iteration
-// ([0], [1]) and the later ones ([2], [3]); slam_debug_lanes (slam_abi.hip) reads and clears them.
+// ([0], [1]) and the later ones ([2], [3]); [4] wave-slots that scanned in float32 first (F32Image), [5] those of them that
+// fell back to the float64 scan; slam_debug_lanes (slam_abi.hip) reads and clears all six.
 // (-DSLAM_STAMPS_ICP=3: the phase timers alone - the lane counters' atomics, four addresses for every wave of the launch,
 // stretch a pair's lifetime tenfold and with it every phase)
 #if defined(SLAM_STAMPS_ICP) && SLAM_STAMPS_ICP != 3
-extern __device__ unsigned long long g_polar_lanes[4];
+extern __device__ unsigned long long g_polar_lanes[6];
+#define ISTAMP_F32(fell_back)                                                                            \
+    do {                                                                                                 \
+        if ((threadIdx.x & 63) == 0) {                                                                   \
+            atomicAdd(&g_polar_lanes[4], 1ull);                                                          \
+            if (fell_back) atomicAdd(&g_polar_lanes[5], 1ull);                                           \
+        }                                                                                                \
+    } while (0)
 #define ISTAMP_SCAN(first, own, trips, per_trip)                                                          \
     do {                                                                                                 \
         unsigned o_ = (unsigned)(own);                                                                   \
@@ -77,6 +85,7 @@ extern __device__ unsigned long long g_polar_lanes[4];
     } while (0)
 #else
 #define ISTAMP_SCAN(first, own, trips, per_trip)
+#define ISTAMP_F32(fell_back)
 #endif
 
 #ifdef SLAM_STAMPS_ICP
