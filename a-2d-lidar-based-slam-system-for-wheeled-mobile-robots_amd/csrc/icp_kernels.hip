@@ -1853,7 +1853,7 @@ static hipError_t launch_icp_t(const IcpArgs &a_in, hipStream_t s)
     const int block = icp_block(a.n_src, qpt);
     const size_t lds_base = nn_lds_bytes(a.n_tar) + icp_red_bytes(block / kWave) + kIcpExtraLds + kLdsGuard;
     // second, unpadded copy of the target for the beam-window search: only for scans, and only while both copies fit
-    // (up to 4 544 beams; larger scans, up to the documented 8 192, and point clouds go by the box search alone)
+    // (up to 4 557 beams; larger scans, up to the documented 8 192, and point clouds go by the box search alone)
     a.polar_copy = (a.ranges && lds_base + icp_polar_bytes(a.n_tar) <= 160 * 1024) ? 1 : 0;
     size_t lds = lds_base + (a.polar_copy ? icp_polar_bytes(a.n_tar) : 0);
     // the list of first-iteration queries without a usable window (nn_listed): room for half of the queries - on the

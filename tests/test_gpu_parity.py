@@ -9,6 +9,7 @@ import zlib
 import numpy as np
 import pytest
 
+import icp_shapes
 from conftest import pkg
 from oracle import c_oracle as co
 from oracle import oracle_np as on
@@ -232,11 +233,16 @@ def test_icp_batch_sizes_vs_oracle(slam, n, m):
     assert np.max(np.abs(T - oT)) < FTOL and np.max(np.abs(err - oerr)) < FTOL
 
 
-@pytest.mark.parametrize("beams", [4544, 4545, 8192])
+COPY_DROPPED = icp_shapes.edges(True)["dropped"]      # first scan size without the unpadded copy: 4 558
+
+
+@pytest.mark.parametrize("beams", [4544, 4545, COPY_DROPPED - 1, COPY_DROPPED, 8192])
 def test_replay_largest_scans_vs_oracle(slam, syn, beams):
-    """Scans of up to 8 192 beams through the fused replay: up to 4 544 beams the scan matcher keeps a second, unpadded
+    """Scans of up to 8 192 beams through the fused replay: up to 4 557 beams the scan matcher keeps a second, unpadded
     copy of the target in LDS for its beam-window search, beyond that both copies no longer fit and it goes by the box
-    search alone - same answers either way (iteration counts exact, poses to 1e-9)."""
+    search alone - same answers either way (iteration counts exact, poses to 1e-9).  (The size comes from
+    tests/icp_shapes.py; 4 544 is the last with a first-iteration list, of 32 slots, 4 545 the first without one.)"""
+    assert icp_shapes.launch(2, COPY_DROPPED - 1, COPY_DROPPED - 1, True).polar_copy and not icp_shapes.launch(2, COPY_DROPPED, COPY_DROPPED, True).polar_copy
     rep = syn.make_replay(3, beams, seed=21, stride=5)
     ctx = slam.Context(0)
     poses, T, it = slam.replay_host(rep.ranges, AMIN, AMAX, context=ctx)
