@@ -5,7 +5,8 @@ Drop-in replacements, on hand-written gfx950 HIP kernels behind a C ABI
 zjwzcx/A-2D-LiDAR-based-SLAM-System-for-Wheeled-Mobile-Robots:
 
     ICP        process / findNearest / getTransform / laserToNumpy / laserCallback / publishResult
-    Mapping    update -> pmap
+    Mapping    update -> pmap; raycast / score_scan read the map along rays (batched: DeviceGrid.raycast /
+               .score, grid_raycast_host / grid_score_host)
     bresenham  (start, end).path
     SLAM_EKF   laserCallback glue (scan matching + map building); landmarks=True: the whole W12
                node with Extraction and the landmark EKF on the host; batched on the device
@@ -23,6 +24,7 @@ libslamhip.so or the GPU is missing (there is no CPU implementation in the produ
 """
 from . import _abi, dist, param, synthetic
 from ._abi import Context, LibraryMissing, SlamError, default_context
+from ._abi import RAY_BAD, RAY_BLOCKED, RAY_CLASSES, RAY_EMPTY, RAY_FREE, RAY_HIT, RAY_NAMES, RAY_OUT, RAY_UNKNOWN
 from . import dwa
 from .bresenham import bresenham, rasterize
 from .dwa import DeviceDWA, dwa_batch_host, dwa_control
@@ -36,7 +38,7 @@ from .localization import Localization
 from .loc_replay import DeviceLocalizationReplay, loc_replay_host
 from .mapping import Mapping
 from .node_replay import DeviceNodeReplay, ekf_lm_host, landmarks_host, node_replay_host
-from .replay import DeviceGrid, DeviceReplay, icp_batch_host, particles_host, prior_matrices, replay_host
+from .replay import DeviceGrid, DeviceReplay, grid_raycast_host, grid_score_host, icp_batch_host, particles_host, prior_matrices, replay_host
 from .slam_ekf import SLAM_EKF
 from .synthetic import LaserScan
 
@@ -45,4 +47,5 @@ __all__ = ["ICP", "Mapping", "Localization", "EKF", "Extraction", "LandMarkSet",
            "LibraryMissing", "param", "synthetic", "dwa", "dwa_control", "DeviceDWA", "dwa_batch_host", "LocalPlanner",
            "global_planner", "find_path", "GlobalPlanner", "DeviceAStar", "astar_host", "inflate_host",
            "DeviceNodeReplay", "node_replay_host", "landmarks_host", "ekf_lm_host",
-           "DeviceLocalizationReplay", "loc_replay_host"]
+           "DeviceLocalizationReplay", "loc_replay_host", "grid_raycast_host", "grid_score_host",
+           "RAY_EMPTY", "RAY_HIT", "RAY_BLOCKED", "RAY_FREE", "RAY_UNKNOWN", "RAY_OUT", "RAY_BAD", "RAY_CLASSES", "RAY_NAMES"]

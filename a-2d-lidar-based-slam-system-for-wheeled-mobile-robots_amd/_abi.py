@@ -71,6 +71,10 @@ _SIGS = {
     "slam_grid_finalize_dev": ([_vp, _vp, _vp], _i),
     "slam_grid_occupancy_data": ([_vp, _vp, _i, _vp], _i),
     "slam_grid_visits": ([_vp, _vp, C.POINTER(C.c_uint64)], _i),
+    "slam_grid_raycast": ([_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, C.c_float, _i, _vp, _vp], _i),
+    "slam_grid_raycast_dev": ([_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, C.c_float, _i, _vp, _vp], _i),
+    "slam_grid_scan_score": ([_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp], _i),
+    "slam_grid_scan_score_dev": ([_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp], _i),
     "slam_bresenham_batch": ([_vp, _vp, _vp, _i, _vp, _vp, _vp, C.c_int64], _i),
     "slam_replay": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp], _i),
     "slam_particles": ([_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _d, _vp, _vp, _vp, _vp], _i),
@@ -113,6 +117,10 @@ _SIGS = {
 NODE_OK, NODE_REF_RAISES, NODE_LM_CAP, NODE_OBS_CAP = 0, 1, 2, 3
 LOC_OK, LOC_NONFINITE, LOC_BAD_ROUTE = 0, 1, 2
 EKF_MAX_LM = 32
+# classes of slam_grid_scan_score (SLAM_RAY_*)
+RAY_EMPTY, RAY_HIT, RAY_BLOCKED, RAY_FREE, RAY_UNKNOWN, RAY_OUT, RAY_BAD = range(7)
+RAY_CLASSES = 7
+RAY_NAMES = ("empty", "hit", "blocked", "free", "unknown", "out", "bad")
 
 
 def header_symbols(path=HEADER_PATH):

@@ -101,6 +101,7 @@ struct slam_ctx {
     int replay_reset = 0; // 1: slam_replay_dev clears its map's counters itself (inside the scan-matching launch)
     int icp_f32_filter = -1; // float32 pre-filter of the one-wave shape's beam windows: -1 = the library's choice (on), 0 = off, 1 = on; changes no result
     int icp_one_wave = -1; // scan matching with one wave per pair: -1 = where a full-chip launch allows it, 0 = never, 1 = wherever a pair fits
+    int raycast_lds = -1; // rays traced through a map: -1 = automatic, 0 = mask words from global memory, 1 = from LDS wherever the mask fits
     int icp_team = 0;     // first-iteration queries without a beam window: 0 = listed and searched apart from their lanes (nn_listed), 1 = box search
     // "pipeline" option: the map stage of slam_replay_dev (reset -> ray cast -> finalize) runs on
     // a second stream, so the map stage of one replay overlaps the scan matching of the next.
@@ -704,6 +705,7 @@ static const OptionRange kOptionRanges[] = {
     {"particle_chunks", [](double v) { return v >= 0 && v <= 64 && v == (int)v; }, "particle_chunks in [0, 64]"},
     {"icp_qpt", [](double v) { return v >= 0 && v <= 3; }, "icp_qpt in [0, 3]"},
     {"pipeline", [](double v) { return v == 0 || v == 1; }, "pipeline is 0 or 1"},
+    {"raycast_lds", [](double v) { return v == -1 || v == 0 || v == 1; }, "raycast_lds is -1, 0 or 1"},
 };
 
 int slam_set_option(slam_ctx *c, const char *name, double value)
@@ -724,6 +726,7 @@ int slam_set_option(slam_ctx *c, const char *name, double value)
     else if (!strcmp(name, "icp_f32_filter")) c->icp_f32_filter = (int)value;
     else if (!strcmp(name, "particle_chunks")) { TRY(join_particles(c)); c->particle_chunks = (int)value; }
     else if (!strcmp(name, "icp_qpt")) c->icp_qpt = (int)value;
+    else if (!strcmp(name, "raycast_lds")) c->raycast_lds = (int)value;
     else if (!strcmp(name, "pipeline")) {
         TRY(join_from_grid(c));
         if (value == 1 && !c->gstream) {
@@ -1313,6 +1316,111 @@ int slam_grid_visits(slam_ctx *c, slam_grid *g, uint64_t *visits_out)
     for (int k = 0; k < kVisitSlots; ++k) v += slots[(size_t)k * kVisitStride];
     *visits_out = v;
     return SLAM_OK;
+}
+
+// ---- rays traced through a map (raycast_kernels.hip) ------------------------------------------------------------
+static int check_raycast(const char *fn, const slam_grid *g, const double *poses, int B, const double *cos_t,
+                         const double *sin_t, int n, int skip, const void *out)
+{
+    REQUIRE_IN(fn, g && poses && cos_t && sin_t && out, "null pointer");
+    REQUIRE_IN(fn, n >= 1 && n <= 4096, "n outside [1, 4096]");
+    REQUIRE_IN(fn, B >= 1 && (long)B * n < (1L << 31), "B < 1 or B * n >= 2^31");
+    REQUIRE_IN(fn, skip >= 0 && skip <= kMaxRayCells, "skip outside [0, 2^20]");
+    return SLAM_OK;
+}
+
+static int check_grid_of_batch(const char *fn, const slam_grid *g, const int32_t *grid_of_batch, int B)
+{
+    if (grid_of_batch)
+        for (int b = 0; b < B; ++b)
+            if (grid_of_batch[b] < 0 || grid_of_batch[b] >= g->d.G)
+                return fail(SLAM_ERR_INVALID, "%s: grid_of_batch[%d] = %d outside [0, G = %d)", fn, b, grid_of_batch[b], g->d.G);
+    return SLAM_OK;
+}
+
+// pack the occupied bits of every map as the counters stand on the stream now (what k_grid_finalize would call 100),
+// then trace.  The counters are only read: a live pmap stays as current or as stale as it was.
+static int run_raycast(slam_ctx *c, slam_grid *g, RaycastArgs &a)
+{
+    TRY(grid_on_main(c));
+    const size_t words = raycast_mask_words(g->d);
+    TRY(arena_reserve(c, c->scratch, align_up(words * 4) + 1024));
+    uint32_t *mask = carve<uint32_t>(c->scratch, words);
+    REQUIRE_IN(a.counts_out ? "slam_grid_scan_score" : "slam_grid_raycast", mask, "internal: workspace");
+    a.g = g->d;
+    a.mask = mask;
+    {
+        Timed t(c, SLAM_K_FINALIZE);      // the threshold rule over every cell, as a finalize pass is
+        HIPCHK(launch_raycast_pack(g->d, mask, c->stream));
+    }
+    Timed t(c, SLAM_K_GRID);
+    HIPCHK(launch_raycast(a, choose_raycast_path(g->d, c->raycast_lds, a.B, a.n), c->stream));
+    return SLAM_OK;
+}
+
+int slam_grid_raycast_dev(slam_ctx *c, slam_grid *g, const double *poses, int B, const int32_t *grid_of_batch,
+                          const double *cos_t, const double *sin_t, int n, float max_range, int skip, float *ranges_out,
+                          int32_t *cells_out)
+{
+    TRY(use(c));
+    TRY(check_raycast(__func__, g, poses, B, cos_t, sin_t, n, skip, ranges_out));
+    REQUIRE(std::isfinite(max_range) && max_range > 0, "max_range must be finite and > 0");
+    RaycastArgs a;
+    a.poses = poses; a.maps = grid_of_batch; a.cos_t = cos_t; a.sin_t = sin_t;
+    a.B = B; a.n = n; a.skip = skip; a.max_range = max_range;
+    a.ranges_out = ranges_out; a.cells_out = cells_out;
+    return run_raycast(c, g, a);
+}
+
+int slam_grid_raycast(slam_ctx *c, slam_grid *g, const double *poses, int B, const int32_t *grid_of_batch, const double *cos_t,
+                      const double *sin_t, int n, float max_range, int skip, float *ranges_out, int32_t *cells_out)
+{
+    TRY(use(c));
+    TRY(check_raycast(__func__, g, poses, B, cos_t, sin_t, n, skip, ranges_out));
+    REQUIRE(std::isfinite(max_range) && max_range > 0, "max_range must be finite and > 0");
+    TRY(check_grid_of_batch(__func__, g, grid_of_batch, B));
+    const size_t rays = (size_t)B * n;
+    double *d_p, *d_c, *d_s; int32_t *d_g, *d_cells; float *d_r;
+    Staging s(c);
+    s.in(d_p, poses, (size_t)B * 3).in(d_g, grid_of_batch, B).in(d_c, cos_t, n).in(d_s, sin_t, n)
+        .out(d_r, ranges_out, rays).out(d_cells, cells_out, 2 * rays);
+    TRY(s.upload());
+    TRY(slam_grid_raycast_dev(c, g, d_p, B, d_g, d_c, d_s, n, max_range, skip, d_r, d_cells));
+    return s.download();
+}
+
+int slam_grid_scan_score_dev(slam_ctx *c, slam_grid *g, const float *ranges, int shared, const double *poses, int B,
+                             const int32_t *grid_of_batch, const double *cos_t, const double *sin_t, int n, int skip,
+                             int32_t *counts_out, int8_t *class_out)
+{
+    TRY(use(c));
+    TRY(check_raycast(__func__, g, poses, B, cos_t, sin_t, n, skip, counts_out));
+    REQUIRE(ranges, "null pointer");
+    RaycastArgs a;
+    a.poses = poses; a.maps = grid_of_batch; a.cos_t = cos_t; a.sin_t = sin_t;
+    a.B = B; a.n = n; a.skip = skip;
+    a.ranges = ranges; a.range_stride = shared ? 0 : n;
+    a.counts_out = counts_out; a.class_out = class_out;
+    HIPCHK(hipMemsetAsync(counts_out, 0, (size_t)B * SLAM_RAY_CLASSES * sizeof(int32_t), c->stream));
+    return run_raycast(c, g, a);
+}
+
+int slam_grid_scan_score(slam_ctx *c, slam_grid *g, const float *ranges, int shared, const double *poses, int B,
+                         const int32_t *grid_of_batch, const double *cos_t, const double *sin_t, int n, int skip,
+                         int32_t *counts_out, int8_t *class_out)
+{
+    TRY(use(c));
+    TRY(check_raycast(__func__, g, poses, B, cos_t, sin_t, n, skip, counts_out));
+    REQUIRE(ranges, "null pointer");
+    TRY(check_grid_of_batch(__func__, g, grid_of_batch, B));
+    const size_t rays = (size_t)B * n;
+    float *d_r; double *d_p, *d_c, *d_s; int32_t *d_g, *d_cnt; int8_t *d_cls;
+    Staging s(c);
+    s.in(d_r, ranges, shared ? (size_t)n : rays).in(d_p, poses, (size_t)B * 3).in(d_g, grid_of_batch, B).in(d_c, cos_t, n)
+        .in(d_s, sin_t, n).out(d_cnt, counts_out, (size_t)B * SLAM_RAY_CLASSES).out(d_cls, class_out, rays);
+    TRY(s.upload());
+    TRY(slam_grid_scan_score_dev(c, g, d_r, shared, d_p, B, d_g, d_c, d_s, n, skip, d_cnt, d_cls));
+    return s.download();
 }
 
 int slam_bresenham_batch(slam_ctx *c, const int32_t *starts, const int32_t *ends, int B, const int64_t *offsets,

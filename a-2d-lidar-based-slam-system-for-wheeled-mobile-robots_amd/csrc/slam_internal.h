@@ -179,6 +179,30 @@ hipError_t launch_grid_transpose(const int8_t *pmap, int xw, int yw, int8_t *dat
 hipError_t launch_bresenham(const int32_t *starts, const int32_t *ends, int B, const int64_t *offsets,
                             int32_t *lens, int32_t *cells, hipStream_t s);
 
+// ---- rays traced through a map (raycast_kernels.hip) ----------------------------------
+struct RaycastArgs {
+    GridDev g;
+    const uint32_t *mask = nullptr;          // [G][xw][ceil(yw / 32)]: bit ly % 32 of word [lx][ly / 32] = pmap == 100 (launch_raycast_pack)
+    int wpr = 0;                             // set by launch_raycast: mask words per row
+    const double *poses = nullptr;           // [B][3]
+    const int32_t *maps = nullptr;           // nullable [B]: the map of every hypothesis (an entry outside [0, G): a NaN / BAD row)
+    const double *cos_t = nullptr, *sin_t = nullptr;
+    int B = 0, n = 0, skip = 0;
+    float max_range = 0.f;                   // ray cast: every beam's range
+    float *ranges_out = nullptr;             // ray cast: [B][n]
+    int32_t *cells_out = nullptr;            // ray cast: nullable [B][n][2]
+    const float *ranges = nullptr;           // score: [B][n], or one [n] with range_stride 0
+    long range_stride = 0;
+    int32_t *counts_out = nullptr;           // score (non-null selects it): [B][SLAM_RAY_CLASSES], zero on entry
+    int8_t *class_out = nullptr;             // score: nullable [B][n]
+    int hyps_per_block = 1;                  // set by launch_raycast (staged engine)
+};
+size_t raycast_mask_words(const GridDev &g);
+// true: the staged engine (mask in LDS); lds_mode is the context option "raycast_lds"
+bool choose_raycast_path(const GridDev &g, int lds_mode, long B, int n);
+hipError_t launch_raycast_pack(const GridDev &g, uint32_t *mask, hipStream_t s);
+hipError_t launch_raycast(RaycastArgs a, bool staged, hipStream_t s);
+
 // ---- scan-to-map observation ---------------------------------------
 hipError_t launch_map_obstacles(const int8_t *map, int width, int height, int wire, double resolution, double origin_x,
                                 double origin_y, double *ox, double *oy, int cap, int *count, hipStream_t s);

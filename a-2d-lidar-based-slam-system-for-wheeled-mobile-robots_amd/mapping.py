@@ -130,6 +130,31 @@ class Mapping:
             self._datamap_stale = True
         return self._fetch_pmap()
 
+    def raycast(self, pose, angle_min, angle_max, n, max_range=30.0, skip=1, return_cells=False):
+        """The scan this map would give from ``pose`` (x, y, theta): ``n`` beams of ``linspace(angle_min, angle_max,
+        n)`` cast to ``max_range`` along the lines ``update`` walks (``slam_grid_raycast``).  Returns ranges float32
+        [n] to the centre of the first occupied cell from path index ``skip`` on (1: not the robot's own cell) -
+        inf where the ray meets none, NaN for a pose the reference's ``int()`` would raise on - and with
+        ``return_cells`` also the cells int32 [n, 2], (-1, -1) where there is none."""
+        p = np.ascontiguousarray(np.asarray(pose, dtype=np.float64).reshape(3))
+        ct, st = _abi.trig_tables(angle_min, angle_max, int(n))
+        r = np.empty(int(n), dtype=np.float32)
+        cells = np.empty((int(n), 2), dtype=np.int32) if return_cells else None
+        _abi.check(_abi.lib().slam_grid_raycast(self._ctx.handle, self._grid, _abi.ptr(p), 1, None, _abi.ptr(ct), _abi.ptr(st),
+                                                int(n), float(max_range), int(skip), _abi.ptr(r), _abi.ptr(cells)))
+        return (r, cells) if return_cells else r
+
+    def score_scan(self, ranges, angle_min, angle_max, pose, skip=1):
+        """How a measured scan sits in this map seen from ``pose`` (``slam_grid_scan_score``): the seven counts
+        int32 [7], indexed by ``_abi.RAY_EMPTY .. RAY_BAD``, of beams formed as ``update_scans`` forms them."""
+        r = np.ascontiguousarray(np.asarray(ranges, dtype=np.float32).reshape(-1))
+        p = np.ascontiguousarray(np.asarray(pose, dtype=np.float64).reshape(3))
+        ct, st = _abi.trig_tables(angle_min, angle_max, r.shape[0])
+        counts = np.empty(_abi.RAY_CLASSES, dtype=np.int32)
+        _abi.check(_abi.lib().slam_grid_scan_score(self._ctx.handle, self._grid, _abi.ptr(r), 1, _abi.ptr(p), 1, None, _abi.ptr(ct),
+                                                   _abi.ptr(st), r.shape[0], int(skip), _abi.ptr(counts), None))
+        return counts
+
     def counters(self):
         """(pass, hit) uint32 [xw, yw]: the integer evidence behind ``datamap``."""
         p = np.empty((self.xw, self.yw), dtype=np.uint32)

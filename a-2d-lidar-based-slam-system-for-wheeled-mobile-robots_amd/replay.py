@@ -97,6 +97,52 @@ def particles_host(ranges_prev, ranges_cur, angle_min, angle_max, prior_mats, po
     return poses, T.reshape(P, 3, 3), it
 
 
+def _batch_args(poses, grid_of_batch):
+    p = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 3))
+    gob = None if grid_of_batch is None else np.ascontiguousarray(np.asarray(grid_of_batch, dtype=np.int32).reshape(p.shape[0]))
+    return p, gob
+
+
+def _tables(cos_t, sin_t):
+    ct = np.ascontiguousarray(np.asarray(cos_t, dtype=np.float64).reshape(-1))
+    st = np.ascontiguousarray(np.asarray(sin_t, dtype=np.float64).reshape(ct.shape[0]))
+    return ct, st
+
+
+def grid_raycast_host(grid, poses, cos_t, sin_t, max_range=30.0, skip=1, grid_of_batch=None, return_cells=False):
+    """The scan the map would give (``slam_grid_raycast``): every beam of every pose [B, 3] cast to ``max_range``
+    through its map of ``grid`` (a :class:`DeviceGrid`) along the line ``Mapping.update`` would walk.  ``cos_t``,
+    ``sin_t`` [n]: the beam tables (``_abi.trig_tables``).  Returns ranges float32 [B, n] to the centre of the first
+    occupied cell from path index ``skip`` on - inf: none, NaN: a pose or cell index the reference would raise on -
+    and with ``return_cells`` also those cells int32 [B, n, 2], (-1, -1) where there is none."""
+    p, gob = _batch_args(poses, grid_of_batch)
+    ct, st = _tables(cos_t, sin_t)
+    B, n = p.shape[0], ct.shape[0]
+    r = np.empty((B, n), dtype=np.float32)
+    cells = np.empty((B, n, 2), dtype=np.int32) if return_cells else None
+    _abi.check(_abi.lib().slam_grid_raycast(grid._ctx.handle, grid._h, _abi.ptr(p), B, _abi.ptr(gob), _abi.ptr(ct), _abi.ptr(st),
+                                            n, float(max_range), int(skip), _abi.ptr(r), _abi.ptr(cells)))
+    return (r, cells) if return_cells else r
+
+
+def grid_score_host(grid, ranges, poses, cos_t, sin_t, skip=1, grid_of_batch=None, return_classes=False):
+    """How measured scans sit in the map (``slam_grid_scan_score``): ranges float32 [B, n], or one [n] shared by
+    every pose; each beam is formed as ``update_scans`` forms it and traced to its own end cell.  Returns counts
+    int32 [B, 7] per class (``_abi.RAY_*``) and with ``return_classes`` also the classes int8 [B, n]."""
+    p, gob = _batch_args(poses, grid_of_batch)
+    ct, st = _tables(cos_t, sin_t)
+    B, n = p.shape[0], ct.shape[0]
+    r = np.ascontiguousarray(np.asarray(ranges, dtype=np.float32))
+    shared = r.ndim == 1
+    if r.shape != ((n,) if shared else (B, n)):
+        raise ValueError("ranges must be [n] or [B, n]")
+    counts = np.empty((B, _abi.RAY_CLASSES), dtype=np.int32)
+    cls = np.empty((B, n), dtype=np.int8) if return_classes else None
+    _abi.check(_abi.lib().slam_grid_scan_score(grid._ctx.handle, grid._h, _abi.ptr(r), int(shared), _abi.ptr(p), B, _abi.ptr(gob),
+                                               _abi.ptr(ct), _abi.ptr(st), n, int(skip), _abi.ptr(counts), _abi.ptr(cls)))
+    return (counts, cls) if return_classes else counts
+
+
 class DeviceGrid:
     """G occupancy maps resident on the device (``slam_grid_*``)."""
 
@@ -163,6 +209,37 @@ class DeviceGrid:
         gob = None if grid_of_batch is None else np.ascontiguousarray(np.asarray(grid_of_batch, dtype=np.int32))
         _abi.check(_abi.lib().slam_grid_update(self._ctx.handle, self._h, _abi.ptr(ox), _abi.ptr(oy), _abi.ptr(cx),
                                                _abi.ptr(cy), B, n, _abi.ptr(gob)))
+
+    def raycast(self, poses, cos_t, sin_t, max_range=30.0, skip=1, grid_of_batch=None, ranges_out=None, cells_out=None,
+                return_cells=False):
+        """``slam_grid_raycast_dev`` on torch device tensors: poses float64 [B, 3], cos_t / sin_t float64 [n],
+        grid_of_batch int32 [B] or None.  Writes ranges float32 [B, n] (and cells int32 [B, n, 2]) into the tensors
+        given or into fresh ones; enqueued on the context's stream, no synchronise."""
+        import torch
+        B, n = int(poses.shape[0]), int(cos_t.shape[0])
+        if ranges_out is None:
+            ranges_out = torch.empty((B, n), dtype=torch.float32, device=poses.device)
+        if cells_out is None and return_cells:
+            cells_out = torch.empty((B, n, 2), dtype=torch.int32, device=poses.device)
+        _abi.check(_abi.lib().slam_grid_raycast_dev(self._ctx.handle, self._h, _abi.ptr(poses), B, _abi.ptr(grid_of_batch),
+                                                    _abi.ptr(cos_t), _abi.ptr(sin_t), n, float(max_range), int(skip),
+                                                    _abi.ptr(ranges_out), _abi.ptr(cells_out)))
+        return ranges_out if cells_out is None else (ranges_out, cells_out)
+
+    def score(self, ranges, poses, cos_t, sin_t, skip=1, grid_of_batch=None, counts_out=None, class_out=None,
+              return_classes=False):
+        """``slam_grid_scan_score_dev`` on torch device tensors: ranges float32 [B, n] or a shared [n].  Writes counts
+        int32 [B, 7] (and classes int8 [B, n]) into the tensors given or into fresh ones; no synchronise."""
+        import torch
+        B, n = int(poses.shape[0]), int(cos_t.shape[0])
+        if counts_out is None:
+            counts_out = torch.empty((B, _abi.RAY_CLASSES), dtype=torch.int32, device=poses.device)
+        if class_out is None and return_classes:
+            class_out = torch.empty((B, n), dtype=torch.int8, device=poses.device)
+        _abi.check(_abi.lib().slam_grid_scan_score_dev(self._ctx.handle, self._h, _abi.ptr(ranges), int(ranges.dim() == 1),
+                                                       _abi.ptr(poses), B, _abi.ptr(grid_of_batch), _abi.ptr(cos_t),
+                                                       _abi.ptr(sin_t), n, int(skip), _abi.ptr(counts_out), _abi.ptr(class_out)))
+        return counts_out if class_out is None else (counts_out, class_out)
 
     def read(self, g=0, want=("pmap",)):
         out = {}

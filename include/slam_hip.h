@@ -127,7 +127,10 @@ int slam_check_status(slam_ctx *ctx);
  *   i + 1 on the context's stream beside the ray cast of chunk i on a second stream.  The call still returns with the
  *   context's stream ordered behind ALL of its work (the second stream is joined at the end), so buffers may be
  *   reused by later calls as with any *_dev entry point.  Measured slower than one piece on MI355X;
- *   0 / 1 = off (default). */
+ *   0 / 1 = off (default).
+ * "raycast_lds": where slam_grid_raycast / slam_grid_scan_score read the map's occupied bits from: 0 = global
+ *   memory, one lane per ray (any map size); 1 = a copy in LDS per workgroup wherever the map's bit mask fits
+ *   64 KiB (512 K cells), else as 0; -1 = automatic (default).  Same bits either way; an A/B switch. */
 int slam_set_option(slam_ctx *ctx, const char *name, double value);
 /* Per-kernel-family timing with HIP events on the context's stream (bench.py roofline).
  * on: 0 = off, 1 = every family, 2 * mask = only the families in mask (bit SLAM_K_*): events on a
@@ -252,6 +255,53 @@ int slam_grid_finalize_dev(slam_ctx *ctx, slam_grid *grid, int8_t *pmap_dev);
 int slam_grid_occupancy_data(slam_ctx *ctx, slam_grid *grid, int g, int8_t *data);
 /* Number of in-bounds cell visits accumulated since creation / reset (SURVEY.md 8d "C"). */
 int slam_grid_visits(slam_ctx *ctx, slam_grid *grid, uint64_t *visits_out);
+
+/* ---- rays traced through a map ------------------------------------------------------- */
+/* The read side of the grid; the reference has no counterpart (it only writes its map).  Both operators rest on
+ *   trace(map, start, end, skip): with path = bresenham(start, end).path (W12m/bresenham.py:2-58, the cells
+ *   Mapping.update visits, in its order), the smallest path index j >= skip whose cell is in bounds and has
+ *   pmap == 100 (pmap as slam_grid_finalize_dev gives it), or -1; and the path length Lp.
+ * The calls see every update enqueued before them on the context's stream and change nothing in the grid; the
+ * context's sticky status is left untouched.  poses [B][3]; grid_of_batch [B] names the map of every hypothesis
+ * (NULL: all read map 0; the host forms reject an entry outside [0, G), the device forms give that hypothesis
+ * NaN / SLAM_RAY_BAD rows); cos_t, sin_t [n] as for slam_scan_to_points.  1 <= n <= 4096, B >= 1, B * n < 2^31,
+ * 0 <= skip <= 2^20 (skip = 1 leaves the ray's own cell out).  Under slam_timing_* the pass that packs the
+ * occupied bits counts as SLAM_K_FINALIZE, the trace as SLAM_K_GRID.
+ *
+ * slam_grid_raycast: the scan the map would give.  Beam i of hypothesis b ends where slam_grid_update_scans would
+ * put a beam of range max_range (finite, > 0) cast from poses[b]: obs = u2T(pose).dot(pc), the ray origin is the
+ * pose, both cells by int(scale * (v + off)) (W12m/slam_ekf.py:88-90, :115-123; mapping.py:33-36).
+ * ranges_out [B][n] float32: the distance sqrt(dx*dx + dy*dy), in float64 and rounded once, from (x, y) of the
+ * pose to the centre ((cx + 0.5) / scale - off_x, (cy + 0.5) / scale - off_y) of the cell found; +inf when the
+ * ray meets no occupied cell; NaN for a non-finite pose or a cell index beyond 2^20.  cells_out (nullable)
+ * [B][n][2] int32: the cell found, (-1, -1) otherwise. */
+int slam_grid_raycast(slam_ctx *ctx, slam_grid *grid, const double *poses, int B, const int32_t *grid_of_batch,
+                      const double *cos_t, const double *sin_t, int n, float max_range, int skip, float *ranges_out,
+                      int32_t *cells_out);
+int slam_grid_raycast_dev(slam_ctx *ctx, slam_grid *grid, const double *poses, int B, const int32_t *grid_of_batch,
+                          const double *cos_t, const double *sin_t, int n, float max_range, int skip, float *ranges_out,
+                          int32_t *cells_out);
+/* slam_grid_scan_score: how a measured scan sits in the map.  ranges float32 [B][n], or one [n] for every
+ * hypothesis when shared != 0.  Every beam is formed exactly as slam_grid_update_scans forms it (inf -> 30 m,
+ * slam_ekf.py:119), traced to its own end cell, and put into one class: */
+enum {
+    SLAM_RAY_EMPTY = 0,     /* Lp == 0: the beam ends in the cell it starts in                         */
+    SLAM_RAY_HIT = 1,       /* j == Lp - 1: the first occupied cell is the beam's end cell             */
+    SLAM_RAY_BLOCKED = 2,   /* 0 <= j < Lp - 1: an occupied cell in front of the end cell              */
+    SLAM_RAY_FREE = 3,      /* j == -1, the end cell is in bounds and its pmap is not 50               */
+    SLAM_RAY_UNKNOWN = 4,   /* j == -1, the end cell is in bounds and its pmap is 50                   */
+    SLAM_RAY_OUT = 5,       /* j == -1, the end cell is out of bounds                                  */
+    SLAM_RAY_BAD = 6,       /* NaN / cell index beyond 2^20 (what raises in mapping.py:33-36), bad map */
+    SLAM_RAY_CLASSES = 7
+};
+/* counts_out [B][SLAM_RAY_CLASSES] int32: beams per class (integer tallies: a hypothesis gets the same counts
+ * alone, in any batch and in any order); class_out (nullable) [B][n] int8. */
+int slam_grid_scan_score(slam_ctx *ctx, slam_grid *grid, const float *ranges, int shared, const double *poses, int B,
+                         const int32_t *grid_of_batch, const double *cos_t, const double *sin_t, int n, int skip,
+                         int32_t *counts_out, int8_t *class_out);
+int slam_grid_scan_score_dev(slam_ctx *ctx, slam_grid *grid, const float *ranges, int shared, const double *poses, int B,
+                             const int32_t *grid_of_batch, const double *cos_t, const double *sin_t, int n, int skip,
+                             int32_t *counts_out, int8_t *class_out);
 
 /* Replaces bresenham(start, end).path (W12m/bresenham.py:2-58), B lines at once.
  * starts, ends [B][2] int32.  lens_out [B] receives each path length; cells_out (may be
