@@ -1998,7 +1998,10 @@ __global__ void __launch_bounds__(1024) k_tile_cast(GridDev g, TileScratch ts, i
     for (int rr = wave; rr < W; rr += nwaves) {
         const int row = rr + rot < W ? rr + rot : rr + rot - W;
         size_t gbase = (size_t)(tx0 + row) * g.yw + ty0;
-        if ((gbase & 1) == 0) {                             // pairs of counters are aligned 8-byte words (see the window kernel)
+        // pairs of counters are aligned 8-byte words (see the window kernel).  gbase counts from g.pass itself: the tiles are
+        // never given a map offset (plan_cast sends grid_of_traj to the wedges or the window), so its parity is the address's.
+        // A cast into map gi would have to test (gi * xw * yw + gbase) & 1, as k_wedge_cast does.
+        if ((gbase & 1) == 0) {
             for (int d = lane; d < Hp2; d += kWave) {
                 unsigned v = win[row * Hs + d];
                 if (v) atomicAdd(reinterpret_cast<unsigned long long *>(&pass[gbase + 2 * d]),
@@ -2331,7 +2334,8 @@ __global__ void __launch_bounds__(kWedgeThreads, 2 * kWedgeThreads / 256) k_wedg
     if (lo >= hi) return;
     const bool steep = (cls / kWedgeSlopes) >= 2;
     const int M = wedge_shear(cls);
-    uint32_t *pass = g.pass + (size_t)(ws.got ? ws.got[l] : 0) * g.xw * g.yw;
+    const size_t map_off = (size_t)(ws.got ? ws.got[l] : 0) * g.xw * g.yw;   // the trajectory's map, in cells of g.pass
+    uint32_t *pass = g.pass + map_off;
     const unsigned wbase = lds_addr(win);
 
     for (int c0 = lo; c0 < hi; c0 += kWedgeThreads * kWedgeSlots) {     // (one pass unless a class holds more than 2 048 rays)
@@ -2473,7 +2477,13 @@ __global__ void __launch_bounds__(kWedgeThreads, 2 * kWedgeThreads / 256) k_wedg
                 if ((unsigned)mx >= (unsigned)g.xw) continue;            // (rows beyond the rays' reach hold nothing)
                 const int my0 = steep ? a_lo : v_lo + M * mx;            // map y of column 0
                 const size_t gbase = (size_t)mx * g.yw + my0;
-                const bool pair = ((gbase & 1) == 0);
+                // The 64-bit add needs an 8-byte address: the parity that counts is the cell's in g.pass (an 8-byte
+                // aligned allocation), not in the map - a map of an odd number of cells puts every odd-numbered map at
+                // 4 mod 8 (the window kernels: pair64).  With rows of an odd length every other row goes cell by cell.
+                // A pair's second cell may lie one past its row's end (C and Hw are even, yw need not be): its count is
+                // zero, it is the next row's or the next map's first cell, and past the last map it is the padding
+                // that an odd number of cells leaves in front of hit[] (slam_grid_create rounds pass[] up).
+                const bool pair = (((map_off + gbase) & 1) == 0);
                 for (int d = lane; d < (C >> 1); d += kWave) {
                     unsigned v;
                     if (!diag) v = win[p * (C >> 1) + d];
