@@ -30,6 +30,8 @@
 #include <utility>
 #include <vector>
 #include <climits>
+#include <cstdio>
+#include <cstdlib>
 #include <type_traits>
 
 #include "slam_internal.h"
@@ -111,7 +113,9 @@ __device__ __forceinline__ void finish_wave(const GridDev &g, uint32_t *pass, in
 // Window cells are 16-bit pass counters, two per dword, updated with ds_add_u32 of
 // 1 << 16*(cell & 1): a ray visits a cell at most once, so a count never exceeds the
 // group's ray count (<= 65,535 by construction) and never carries into its neighbour.
-// 36,864 cells = 72 KiB, so two workgroups share a CU's 160 KiB.  Hits (one per ray) go
+// 36,864 cells = 72 KiB; with the sorted order and the scan constants of 8 to 16 scans a workgroup
+// asks for 82 - 89 KB, which is ONE per CU of 160 KiB (the runtime's occupancy answer; two only with
+// the smaller window of win_cells_for's two_per_cu).  Hits (one per ray) go
 // straight to the global counters.  The window is the bounding box of the group's ray
 // origins and endpoints (clamped to the map) when that fits, else a sub-rectangle of it
 // around the first origin; cells of a ray outside the window fall back to direct global
@@ -475,13 +479,27 @@ __host__ __device__ inline size_t win_lds_bytes(int group, int sort_cap, int win
 // Window capacity (16-bit cells) of a launch: kWinCells, or, for small groups, whatever still lets two
 // workgroups share a CU's 160 KiB (a single 360-beam scan: 40 288 cells instead of 36 864 - the
 // bounding box of a scan of the 10 m x 8 m benchmark room, padded to 16-cell pieces, is 35-37 k cells)
-inline int win_cells_for(int group, int sort_cap)
+// two_per_cu (launch_win: a shared-map launch of sorted rays with more workgroups than the chip has CUs): the same carving even
+// where it comes out BELOW kWinCells, so that two workgroups are resident on a CU - one walks while the other sorts, zeroes or
+// flushes.  A group of 16 scans of 360 beams gets 33 216 cells (measured, profiles/win_two_per_cu.txt: one workgroup resident
+// per CU before, two now; the 32-trajectory launch 0.736 -> 0.705 ms).
+// The floor: a smaller window costs phases (more groups whose halves no longer fit), and below some size that must cost more
+// than the second resident gains.  Measured at the largest sorted groups of 360 beams, 20 and 22 scans (31 680 and 30 912 cells;
+// 24 x 360 is 8 640 rays, not sorted, and keeps its window anyway): 0.776 -> 0.688 and 0.723 -> 0.668 ms, MORE than group 16
+// gains, and with one resident a window of 30 720 cells cost 1 %, of 24 576 cells 8 %.  Nothing measured argues for a floor
+// above the smallest window the carving can ask for at all - 8 192 sorted rays in 64 scans: 29 632 cells -, so that is the floor;
+// it is also what keeps the window large enough for the 16-bit keys pass 1 parks in it.
+constexpr int kWinHalfSlack = 512;                                   // a little room for allocation granules
+constexpr int kWinTwoFloor = 29632;
+inline int win_cells_for(int group, int sort_cap, bool two_per_cu = false, long lds_per_cu = 160 * 1024)
 {
-    const long half = 80 * 1024 - 512;                               // (a little room for allocation granules)
+    const long half = lds_per_cu / 2 - kWinHalfSlack;
     long other = (long)win_lds_bytes(group, sort_cap, 0);
     long cells = ((half - other) / 2) & ~15L;
-    return cells > kWinCells ? (int)cells : kWinCells;
+    if (cells > kWinCells) return (int)cells;
+    return two_per_cu && cells >= kWinTwoFloor ? (int)cells : kWinCells;
 }
+static_assert(kWinTwoFloor >= kMaxSortRays && kWinTwoFloor % 16 == 0, "pass 1 parks a 16-bit key per sorted ray in the window");
 
 // The LDS regions of a window workgroup, carved for the launch's group size (win_lds_bytes): a small group leaves room
 // for a second workgroup on the CU.
@@ -691,8 +709,13 @@ __device__ __forceinline__ void finish_workgroup(const GridDev &g, unsigned long
 }
 
 // Shared-map form: groups of scans of a replay cast into a map that other workgroups write too.
+// __launch_bounds__(1024, 8): eight waves per SIMD, i.e. TWO 1024-thread workgroups on a CU, are part of the contract.  Without
+// the second figure the compiler used 93 scalar registers; a wave is given 16 more for the trap handler, 112 with the granule,
+// and a SIMD's 800 then hold seven waves, 28 a CU: the second workgroup's 16 waves never fit, whatever the LDS request and
+// whatever hipOccupancyMaxActiveBlocksPerMultiprocessor answered (stamps with the CU's id: one resident at a time).  With it
+// the kernel stays at 78 (16 scalars live in lanes of a vector register; no scratch).
 template <class Src>
-__global__ void __launch_bounds__(1024) k_grid_update_win(GridDev g, Src src, int group_size, const int32_t *__restrict__ got,
+__global__ void __launch_bounds__(1024, 8) k_grid_update_win(GridDev g, Src src, int group_size, const int32_t *__restrict__ got,
                                                           int sort_cap, int win_cells, int split)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -772,9 +795,17 @@ __global__ void __launch_bounds__(1024) k_grid_update_win(GridDev g, Src src, in
             else if (fits(mine)) part[0] = mine;
             else { part[0] = mine & 0x3u; part[1] = mine & 0xCu; nph = 2; }
         } else {
+            // One workgroup: the same cuts, decided per direction half - a half that fits is one phase, one that does not is cut
+            // at the origins' row: two, three or four phases (a window carved for two workgroups per CU is a tenth smaller, and
+            // it is mostly ONE half of a group's box that then no longer fits).
             if (!sorted || fits(0xFu)) part[0] = 0xFu;               // (the quadrants together: the box of everything)
-            else if (fits(0x5u) && fits(0xAu)) { part[0] = 0x5u; part[1] = 0xAu; nph = 2; }
-            else { part[0] = 1u; part[1] = 2u; part[2] = 4u; part[3] = 8u; nph = 4; }
+            else {
+                const bool left = fits(0x5u), right = fits(0xAu);
+                if (left && right) { part[0] = 0x5u; part[1] = 0xAu; nph = 2; }
+                else if (left) { part[0] = 0x5u; part[1] = 2u; part[2] = 8u; nph = 3; }
+                else if (right) { part[0] = 1u; part[1] = 4u; part[2] = 0xAu; nph = 3; }
+                else { part[0] = 1u; part[1] = 2u; part[2] = 4u; part[3] = 8u; nph = 4; }
+            }
         }
         for (int q = 0; q < 4; ++q) ctl->phq[q] = -1;
         for (int ph = 0; ph < nph; ++ph) {
@@ -1632,6 +1663,19 @@ static ChipShape chip_shape()
     return c;
 }
 
+// SLAM_WIN_RESIDENCY=1 in the environment: what the runtime says about how many workgroups of a k_grid_update_win launch a CU
+// holds, to stderr, for every such launch while the switch is set (the figures of DESIGN.md "K4a" round 6 come from here)
+static void report_win_residency(const void *kernel, int threads, size_t lds, int win_cells, long wgs)
+{
+    const char *on = getenv("SLAM_WIN_RESIDENCY");
+    if (!on || !*on || *on == '0') return;
+    int per_cu = -1;
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, lds);
+    if (e != hipSuccess) (void)hipGetLastError();
+    fprintf(stderr, "k_grid_update_win: %d threads, %zu bytes of LDS (window %d cells), %ld workgroups: %d resident per CU%s\n",
+            threads, lds, win_cells, wgs, per_cu, e == hipSuccess ? "" : " (the query failed)");
+}
+
 template <class Src>
 static hipError_t launch_win(const GridDev &g, const Src &src, int L, int scans, int n, int group, const int32_t *got,
                              hipStream_t s, int split_pref = -1)
@@ -1656,10 +1700,11 @@ static hipError_t launch_win(const GridDev &g, const Src &src, int L, int scans,
     constexpr int kWinMinThreads = 512;
     if (threads < kWinMinThreads) threads = kWinMinThreads;
     const int sort_cap = win_sort_cap((long)group * n);
-    const int win_cells = win_cells_for(group, sort_cap);
+    const int own_cells = win_cells_for(group, sort_cap);            // every launch but the chip-filling shared-map one below
     // one scan per map, cast by the map's only writer, live pmap, the reference's one-hit-occupies rule
     if (exclusive && group == 1 && scans == 1 && g.hit_levels == 1 && (g.yw & 15) == 0 && (((size_t)g.xw * g.yw) & 3) == 0 &&
-        g.yw <= win_cells && n <= kOwnerMaxRays * kOwnerThreads) {
+        g.yw <= own_cells && n <= kOwnerMaxRays * kOwnerThreads) {
+        const int win_cells = own_cells;
         for (const void *f : {reinterpret_cast<const void *>(&k_grid_update_owner<Src, 1>), reinterpret_cast<const void *>(&k_grid_update_owner<Src, 2>),
                               reinterpret_cast<const void *>(&k_grid_update_owner_redo<Src, 1>)}) {
             hipError_t e = allow_dynamic_lds(f, (int)lds_max);
@@ -1689,8 +1734,13 @@ static hipError_t launch_win(const GridDev &g, const Src &src, int L, int scans,
     // A launch of at most one workgroup per CU asks for more than half a CU's LDS, so that no CU gets two of its workgroups
     // while others stay empty: the dispatcher does not spread a small grid by itself (stamps, round 4: of 250 workgroups on
     // 256 CUs the slowest took 1.8 x the mean with the same number of cells to walk - it shared its CU with another one).
-    size_t lds = win_lds_bytes(group, sort_cap, win_cells);
     const long wgs = (long)(split ? 2 * groups : groups) * L;
+    // A launch of more workgroups than the chip has CUs, on the other hand, wants TWO of them on every CU: one workgroup's phases
+    // run one after the other behind barriers, and only a second one can fill the CU while the first sorts, zeroes or flushes.
+    // At kWinCells a group of 8 to 16 scans of 360 beams asks for 82 - 89 KB, which is one per CU; such a launch gets the smaller
+    // window that leaves room for two (win_cells_for).  Sorted rays only: the unsorted form cannot cut a box that no longer fits.
+    const int win_cells = (!exclusive && sort_cap > 0 && wgs > chip.cus) ? win_cells_for(group, sort_cap, true, chip.lds_per_cu) : own_cells;
+    size_t lds = win_lds_bytes(group, sort_cap, win_cells);
     // (only where a CU's LDS really is more than twice a workgroup's need, and the larger request is one the device grants)
     const size_t half_cu = (size_t)(chip.lds_per_cu / 2);
     if (split && wgs <= chip.cus && lds <= half_cu && half_cu + 512 <= (size_t)chip.lds_per_cu) lds = half_cu + 512;
@@ -1699,6 +1749,7 @@ static hipError_t launch_win(const GridDev &g, const Src &src, int L, int scans,
         hipError_t e = allow_dynamic_lds(f, (int)lds);
         if (e != hipSuccess) return e;
     }
+    if (!exclusive) report_win_residency(reinterpret_cast<const void *>(&k_grid_update_win<Src>), threads, lds, win_cells, wgs);
     // the map's only writer (then there is one group, and no `got`) finishes its cells itself, pmap included
     if (exclusive) SLAM_LAUNCH((k_grid_update_own<Src>), dim3(groups, L), dim3(threads), lds, s, g, src, group, sort_cap, win_cells);
     else SLAM_LAUNCH((k_grid_update_win<Src>), dim3(split ? 2 * groups : groups, L), dim3(threads), lds, s, g, src, group, got,
