@@ -115,8 +115,11 @@ __device__ __forceinline__ void finish_wave(const GridDev &g, uint32_t *pass, in
 // group's ray count (<= 65,535 by construction) and never carries into its neighbour.
 // 36,864 cells = 72 KiB; with the sorted order and the scan constants of 8 to 16 scans a workgroup
 // asks for 82 - 89 KB, which is ONE per CU of 160 KiB (the runtime's occupancy answer; two only with
-// the smaller window of win_cells_for's two_per_cu).  Hits (one per ray) go
-// straight to the global counters.  The window is the bounding box of the group's ray
+// the smaller window of win_cells_for's two_per_cu).  Hits (one per ray) went
+// straight to the global counters, 80 % of a replay launch's memory-side atomics; the shared-map kernel now counts the hits
+// of sorted rays per end cell in the window, once the pass counts have left it, and sends ONE add per distinct end cell
+// (flush_hits; context option "win_lds_hits", by default in launches of more workgroups than the chip has CUs: launch_win).
+// Every other form still adds its hits directly.  The window is the bounding box of the group's ray
 // origins and endpoints (clamped to the map) when that fits, else a sub-rectangle of it
 // around the first origin; cells of a ray outside the window fall back to direct global
 // atomics, so the result is exact for any window.
@@ -139,6 +142,7 @@ constexpr int kWinCells = 36864;     // 16-bit cells: 72 KiB of LDS
 constexpr int kWinMaxGroup = 64;     // scans per workgroup
 constexpr int kSortBins = 128;        // ray-length histogram (4 cells per bin)
 constexpr int kMaxSortRays = 8192;    // rays per workgroup that can be length-sorted (u16 ids in LDS)
+static_assert(kMaxSortRays <= 0xffff, "flush_hits counts a sorted phase's hits in 16-bit window cells: one count per ray at most");
 constexpr int kRaysPerLane = 4;     // lanes per workgroup = rays / kRaysPerLane (rays are dealt to waves dynamically)
 
 struct ScanConst {
@@ -351,15 +355,22 @@ __device__ __forceinline__ void lds_walk(unsigned a, int da_k, int da_y, int rem
 
 // Rays are handed to waves 64 at a time from an LDS counter, in `order` when the group was sorted.  False: none
 // are left for this wave; else r is the lane's ray, or -1 for a lane beyond the last one.
-__device__ __forceinline__ bool next_rays(int *next_ray, int nrays, const unsigned short *order, int &r)
+// slot: the lane's place in the order (dead once r has been read from it: cast_rays parks the ray's hit there).
+__device__ __forceinline__ bool next_rays(int *next_ray, int nrays, const unsigned short *order, int &r, int &slot)
 {
     const int lane = threadIdx.x & 63;
     int base = 0;
     if (lane == 0) base = atomicAdd(next_ray, kWave);
     base = __builtin_amdgcn_readfirstlane(base);
     if (base >= nrays) return false;
-    r = base + lane >= nrays ? -1 : order ? (int)order[base + lane] : base + lane;   // longest rays first when sorted
+    slot = base + lane;
+    r = slot >= nrays ? -1 : order ? (int)order[slot] : slot;        // longest rays first when sorted
     return true;
+}
+__device__ __forceinline__ bool next_rays(int *next_ray, int nrays, const unsigned short *order, int &r)
+{
+    int slot;
+    return next_rays(next_ray, nrays, order, r, slot);
 }
 
 // Pass 2 of the window kernel: walk a workgroup's rays.  Rays are handed to waves 64 at a
@@ -370,15 +381,20 @@ __device__ __forceinline__ bool next_rays(int *next_ray, int nrays, const unsign
 // (lx, ly) and advanced incrementally, and the path's last cell (the hit, mapping.py:45) is
 // remembered and written once after the loop.  It is the reference's loop
 // (bresenham.py:45-55) step for step.
+// park (nullable; the sorted order itself, writable): a ray of the unchecked walk sends no hit; it leaves the window index of
+// its end cell (< 0xffff) in the slot of the order it was fetched from, and every other fetched slot is set to kNoHit, for
+// flush_hits behind the pass flush.  Rays of a wave that walks the checked way add their hits directly, as without park.
+constexpr unsigned kNoHit = 0xffffu;
 template <bool COVERS, class Src>
 __device__ __forceinline__ unsigned cast_rays(const GridDev &g, const Src &src, const ScanConst *sc, int l, int s0, int n,
                                               int nrays, int *next_ray, const unsigned short *order, unsigned *win, int wx0,
                                               int wy0, int W, int H, int Hp2, uint32_t *__restrict__ pass,
-                                              uint32_t *__restrict__ hit, const int *first_bad)
+                                              uint32_t *__restrict__ hit, const int *first_bad, unsigned short *park = nullptr)
 {
     unsigned nvis = 0;
-    for (int r; next_rays(next_ray, nrays, order, r);) {
+    for (int r, slot; next_rays(next_ray, nrays, order, r, slot);) {
         if (r < 0) continue;
+        if (park) park[slot] = (unsigned short)kNoHit;
         int s = r / n, i = r - s * n, pox, poy, b2 = 0;
         Ray ry;
         if (i >= first_bad[s]) continue;                             // beams from the scan's first bad one on are not cast
@@ -399,7 +415,8 @@ __device__ __forceinline__ unsigned cast_rays(const GridDev &g, const Src &src, 
             nvis += (unsigned)ry.dx + 1u;                             // every cell of the path is in the map
             // pass cells: all but the path's last
             lds_walk(a2, 2 * w.stride_k(Hs), 2 * w.stride_y(Hs), ry.dx, w.derr, w.error, ry.flag);
-            atomicAdd(&hit[(size_t)pox * g.yw + poy], 1u);            // mapping.py:45
+            if (park) park[slot] = (unsigned short)((pox - wx0) * Hs + (poy - wy0));
+            else atomicAdd(&hit[(size_t)pox * g.yw + poy], 1u);       // mapping.py:45
             continue;
         }
         for (int k = 0; k <= ry.dx; ++k, w.next()) {                  // bresenham.py:45
@@ -613,7 +630,9 @@ __device__ __forceinline__ void fit_window(const GridDev &g, bool any, const int
 
 // Flush of a window: one wave per window row, lanes along y (contiguous in the [x][y] map), two cells per lane.  Every workgroup
 // flushes the same part of the map: each one starts at a different row so that concurrent flushes do not queue on the same addresses.
-__device__ __forceinline__ void flush_window(const unsigned *win, uint32_t *pass, int yw, int wx0, int wy0, int W, int Hp2, bool pair64)
+// zero: every dword is cleared once it has been read (flush_hits counts in the window next).
+__device__ __forceinline__ void flush_window(unsigned *win, uint32_t *pass, int yw, int wx0, int wy0, int W, int Hp2, bool pair64,
+                                             bool zero = false)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
     const int rot = W > 0 ? (int)((blockIdx.x * 37u + blockIdx.y * 11u) % (unsigned)W) : 0;
@@ -626,6 +645,7 @@ __device__ __forceinline__ void flush_window(const unsigned *win, uint32_t *pass
         if (pair64 && (wy0 & 1) == 0) {
             for (int d = lane; d < Hp2; d += kWave) {
                 unsigned v = win[row * Hp2 + d];
+                if (zero) win[row * Hp2 + d] = 0u;
                 if (v) atomicAdd(reinterpret_cast<unsigned long long *>(&pass[gbase + 2 * d]),
                                  (unsigned long long)(v & 0xffffu) | ((unsigned long long)(v >> 16) << 32));
             }
@@ -633,10 +653,37 @@ __device__ __forceinline__ void flush_window(const unsigned *win, uint32_t *pass
         }
         for (int d = lane; d < Hp2; d += kWave) {
             unsigned v = win[row * Hp2 + d];
+            if (zero) win[row * Hp2 + d] = 0u;
             unsigned p0 = v & 0xffffu, p1 = v >> 16;
             if (p0) atomicAdd(&pass[gbase + 2 * d], p0);
             if (p1) atomicAdd(&pass[gbase + 2 * d + 1], p1);          // p1 != 0 implies 2d+1 < H
         }
+    }
+}
+
+// The hits of a phase whose rays parked them (cast_rays), behind a flush_window that has cleared the window (rows of Hs = 2 Hp2
+// cells): every parked ray adds 1 to its end cell's 16-bit counter - a phase holds at most kMaxSortRays rays, so a count neither
+// overflows nor carries into its neighbour -, the ONE lane that found the cell at zero then reads the cell's total and sends it
+// to the global counter: one memory-side atomic per distinct end cell instead of one per ray.  Two barriers; the window is
+// left dirty, as the flush of the pass counts leaves it.
+__device__ __forceinline__ void flush_hits(unsigned *win, unsigned short *park, int nrays, uint32_t *hit, int yw, int wx0, int wy0,
+                                           int Hs)
+{
+    __syncthreads();                                                 // the flush has read and cleared every dword
+    for (int k = threadIdx.x; k < nrays; k += blockDim.x) {
+        const unsigned c = park[k];
+        if (c == kNoHit) continue;
+        const unsigned sh = (c & 1u) * 16u;
+        const unsigned old = atomicAdd(&win[c >> 1], 1u << sh);
+        if ((old >> sh) & 0xffffu) park[k] = (unsigned short)kNoHit;   // an earlier lane carries this cell
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < nrays; k += blockDim.x) {
+        const unsigned c = park[k];
+        if (c == kNoHit) continue;
+        const unsigned tot = (win[c >> 1] >> ((c & 1u) * 16u)) & 0xffffu;
+        const unsigned wx = c / (unsigned)Hs, wy = c - wx * (unsigned)Hs;
+        atomicAdd(&hit[(size_t)(wx0 + (int)wx) * yw + (wy0 + (int)wy)], tot);   // mapping.py:45, for every ray that ends here
     }
 }
 
@@ -716,7 +763,7 @@ __device__ __forceinline__ void finish_workgroup(const GridDev &g, unsigned long
 // the kernel stays at 78 (16 scalars live in lanes of a vector register; no scratch).
 template <class Src>
 __global__ void __launch_bounds__(1024, 8) k_grid_update_win(GridDev g, Src src, int group_size, const int32_t *__restrict__ got,
-                                                          int sort_cap, int win_cells, int split)
+                                                          int sort_cap, int win_cells, int split, int lds_hits)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const WinLds lds(smem, group_size, sort_cap, win_cells);
@@ -852,11 +899,14 @@ __global__ void __launch_bounds__(1024, 8) k_grid_update_win(GridDev g, Src src,
         STAMP(2);                                   // sort + zero
         // pass 2: walk the rays (the reference's float-error Bresenham, bresenham.py:45-55)
         const unsigned short *ord = sorted ? lds.order + seg0 : nullptr;
-        if (covers) nvis += cast_rays<true>(g, src, sc, l, s0, n, seg1 - seg0, &ctl->next_ray, ord, win, wx0, wy0, W, H, Hp2, pass, hit, ctl->first_bad);
-        else        nvis += cast_rays<false>(g, src, sc, l, s0, n, seg1 - seg0, &ctl->next_ray, ord, win, wx0, wy0, W, H, Hp2, pass, hit, ctl->first_bad);
+        // sorted rays leave their hits in the order's dead slots; they are counted in the window behind the flush (flush_hits)
+        unsigned short *park = sorted && lds_hits ? lds.order + seg0 : nullptr;
+        if (covers) nvis += cast_rays<true>(g, src, sc, l, s0, n, seg1 - seg0, &ctl->next_ray, ord, win, wx0, wy0, W, H, Hp2, pass, hit, ctl->first_bad, park);
+        else        nvis += cast_rays<false>(g, src, sc, l, s0, n, seg1 - seg0, &ctl->next_ray, ord, win, wx0, wy0, W, H, Hp2, pass, hit, ctl->first_bad, park);
         __syncthreads();
         STAMP(3);                                   // walk
-        flush_window(win, pass, g.yw, wx0, wy0, W, Hp2, pair64);
+        flush_window(win, pass, g.yw, wx0, wy0, W, Hp2, pair64, park != nullptr);
+        if (park) flush_hits(win, park, seg1 - seg0, hit, g.yw, wx0, wy0, 2 * Hp2);
     }
     finish_workgroup(g, &ctl->visits, nvis, tid);
     STAMP(4);                                   // flush
@@ -1678,7 +1728,7 @@ static void report_win_residency(const void *kernel, int threads, size_t lds, in
 
 template <class Src>
 static hipError_t launch_win(const GridDev &g, const Src &src, int L, int scans, int n, int group, const int32_t *got,
-                             hipStream_t s, int split_pref = -1)
+                             hipStream_t s, int split_pref = -1, int hits_pref = -1)
 {
     const size_t lds_max = win_lds_bytes(kWinMaxGroup, kMaxSortRays, kWinCells);
     for (const void *f : {reinterpret_cast<const void *>(&k_grid_update_win<Src>), reinterpret_cast<const void *>(&k_grid_update_own<Src>)}) {
@@ -1749,11 +1799,17 @@ static hipError_t launch_win(const GridDev &g, const Src &src, int L, int scans,
         hipError_t e = allow_dynamic_lds(f, (int)lds);
         if (e != hipSuccess) return e;
     }
+    // Hits of sorted rays counted in the window, one global add per distinct end cell (flush_hits; a window index must fit 16
+    // bits).  Left to the library: in launches of more workgroups than the chip has CUs, like the smaller window - there the
+    // launch lasts as long as its memory-side atomics take and the second resident hides flush_hits' two barriers (one-lane
+    // benchmark launch 0.705 -> 0.601 ms); a lone replay of 250 workgroups sends a thirtieth of the atomics, has its CU to
+    // itself, and was 5 % LONGER with the hits counted (profiles/win_lds_hits.txt).
+    const int lds_hits = sort_cap > 0 && win_cells < (int)kNoHit && (hits_pref > 0 || (hits_pref < 0 && wgs > chip.cus)) ? 1 : 0;
     if (!exclusive) report_win_residency(reinterpret_cast<const void *>(&k_grid_update_win<Src>), threads, lds, win_cells, wgs);
     // the map's only writer (then there is one group, and no `got`) finishes its cells itself, pmap included
     if (exclusive) SLAM_LAUNCH((k_grid_update_own<Src>), dim3(groups, L), dim3(threads), lds, s, g, src, group, sort_cap, win_cells);
     else SLAM_LAUNCH((k_grid_update_win<Src>), dim3(split ? 2 * groups : groups, L), dim3(threads), lds, s, g, src, group, got,
-                     sort_cap, win_cells, split);
+                     sort_cap, win_cells, split, lds_hits);
     return hipGetLastError();
 }
 
@@ -2656,7 +2712,7 @@ static hipError_t launch_cast(const GridDev &g, CastPath p, const Src &src, cons
     case CastPath::Wedges: return launch_wedges(g, src, r.L, r.scans, r.n, r.group, scratch, s, r.maps);
     case CastPath::Tiles: return launch_tiles(g, src, r.L, r.scans, r.n, r.group, scratch, s);
     case CastPath::Window:
-        return launch_win(g, src, r.L, r.scans, r.n, pick_group(r.group, (long)r.L * r.scans, r.scans, r.n), r.maps, s, r.split);
+        return launch_win(g, src, r.L, r.scans, r.n, pick_group(r.group, (long)r.L * r.scans, r.scans, r.n), r.maps, s, r.split, r.lds_hits);
     case CastPath::Direct: break;
     }
     if (g.pmap_live && g.live_dirty) *g.live_dirty = true;

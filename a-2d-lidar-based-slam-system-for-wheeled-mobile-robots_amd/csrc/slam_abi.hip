@@ -100,6 +100,7 @@ struct slam_ctx {
     int icp_qpt = 0;      // queries per lane of batched scan matching (0: by batch size)
     int replay_reset = 0; // 1: slam_replay_dev clears its map's counters itself (inside the scan-matching launch)
     int icp_f32_filter = -1; // float32 pre-filter of the one-wave shape's beam windows: -1 = the library's choice (on), 0 = off, 1 = on; changes no result
+    int win_lds_hits = -1; // shared-map window ray cast: hits of sorted rays counted in the LDS window, one global add per end cell: -1 = the library's choice (chip-filling launches), 0 = off, 1 = on; changes no result
     int icp_one_wave = -1; // scan matching with one wave per pair: -1 = where a full-chip launch allows it, 0 = never, 1 = wherever a pair fits
     int raycast_lds = -1; // rays traced through a map: -1 = automatic, 0 = mask words from global memory, 1 = from LDS wherever the mask fits
     int icp_team = 0;     // first-iteration queries without a beam window: 0 = listed and searched apart from their lanes (nn_listed), 1 = box search
@@ -702,6 +703,7 @@ static const OptionRange kOptionRanges[] = {
     {"icp_team", [](double v) { return v == 0 || v == 1; }, "icp_team is 0 or 1"},
     {"icp_one_wave", [](double v) { return v == -1 || v == 0 || v == 1; }, "icp_one_wave is -1, 0 or 1"},
     {"icp_f32_filter", [](double v) { return v == -1 || v == 0 || v == 1; }, "icp_f32_filter is -1, 0 or 1"},
+    {"win_lds_hits", [](double v) { return v == -1 || v == 0 || v == 1; }, "win_lds_hits is -1, 0 or 1"},
     {"particle_chunks", [](double v) { return v >= 0 && v <= 64 && v == (int)v; }, "particle_chunks in [0, 64]"},
     {"icp_qpt", [](double v) { return v >= 0 && v <= 3; }, "icp_qpt in [0, 3]"},
     {"pipeline", [](double v) { return v == 0 || v == 1; }, "pipeline is 0 or 1"},
@@ -724,6 +726,7 @@ int slam_set_option(slam_ctx *c, const char *name, double value)
     else if (!strcmp(name, "icp_team")) c->icp_team = (int)value;
     else if (!strcmp(name, "icp_one_wave")) c->icp_one_wave = (int)value;
     else if (!strcmp(name, "icp_f32_filter")) c->icp_f32_filter = (int)value;
+    else if (!strcmp(name, "win_lds_hits")) c->win_lds_hits = (int)value;
     else if (!strcmp(name, "particle_chunks")) { TRY(join_particles(c)); c->particle_chunks = (int)value; }
     else if (!strcmp(name, "icp_qpt")) c->icp_qpt = (int)value;
     else if (!strcmp(name, "raycast_lds")) c->raycast_lds = (int)value;
@@ -1108,7 +1111,7 @@ int slam_grid_update_dev(slam_ctx *c, slam_grid *g, const double *ox, const doub
     Timed t(c, SLAM_K_GRID);
     CastRequest r;
     r.ox = ox; r.oy = oy; r.cx = cx; r.cy = cy; r.scans = B; r.n = n; r.maps = grid_of_batch;
-    r.group = c->grid_group; r.split = c->grid_split;
+    r.group = c->grid_group; r.split = c->grid_split; r.lds_hits = c->win_lds_hits;
     const CastPath path = plan_cast(g->d, c->grid_mode, r);
     const size_t need = cast_scratch_bytes(path, r);
     if (need > c->tiles.cap) TRY(arena_reserve(c, c->tiles, need));
@@ -1142,7 +1145,7 @@ static int cast_replay(slam_ctx *c, slam_grid *g, const float *ranges, const dou
     CastRequest r;
     r.ranges = ranges; r.cos_t = cos_t; r.sin_t = sin_t; r.poses = poses; r.centres = centres;
     r.L = L; r.scans = n_scan - 1; r.n = n; r.maps = got;
-    r.group = c->grid_group; r.split = c->grid_split;
+    r.group = c->grid_group; r.split = c->grid_split; r.lds_hits = c->win_lds_hits;
     const CastPath path = plan_cast(g->d, c->grid_mode, r);
     REQUIRE(path != CastPath::Direct || !centres, "grid_mode 0 has no separate ray origins");
     const size_t need = cast_scratch_bytes(path, r);
@@ -1673,7 +1676,7 @@ int slam_particles_dev(slam_ctx *c, const float *ranges2, const double *cos_t, c
             CastRequest r;                                             // one scan per hypothesis into its own map (no scratch)
             r.ranges = ranges2; r.cos_t = cos_t; r.sin_t = sin_t; r.poses = poses_out + 3 * (size_t)p0;
             r.heading_cs = heading_cs + 2 * (size_t)p0;
-            r.L = pc; r.scans = 1; r.n = n; r.particles = true; r.group = 1;
+            r.L = pc; r.scans = 1; r.n = n; r.particles = true; r.group = 1; r.lds_hits = c->win_lds_hits;
             Timed t(c, SLAM_K_GRID, nullptr, k == 0);
             HIPCHK(launch_cast(d, plan_cast(d, c->grid_mode, r), r, nullptr, st));
             if (chunks > 1) HIPCHK(hipEventRecord(c->pev_cast[k], c->pstream));

@@ -169,6 +169,7 @@ struct CastRequest {
     const int32_t *maps = nullptr;         // nullable: the map of every scan (explicit) or trajectory (replay)
     bool particles = false;                // every trajectory reads the same two scans and casts into map l of its own
     int group = 0, split = -1;             // scans per workgroup (0: automatic); window split in two (-1: automatic, 0, 1)
+    int lds_hits = -1;                     // context option "win_lds_hits": hits of sorted window rays counted in LDS, one add per end cell: -1 = in chip-filling launches, 0 = off, 1 = on
 };
 CastPath plan_cast(const GridDev &g, int grid_mode, const CastRequest &r);
 size_t cast_scratch_bytes(CastPath p, const CastRequest &r);

@@ -110,6 +110,11 @@ int slam_check_status(slam_ctx *ctx);
  *   nearest target (it beats the runner-up by more than float32 can be wrong); any other wave runs the
  *   float64 scan as before.  -1 = the library's choice (default: on), 0 = off, 1 = on.  No result depends
  *   on it - bit-identical transforms, poses and iteration counts; an A/B switch.
+ * "win_lds_hits": the shared-map LDS-window ray cast (groups of scans of a replay, up to 8 192 rays a group)
+ *   counts the hits of its rays per end cell in the window, behind the flush of the pass counts, and sends
+ *   one global add per distinct end cell instead of one per ray.  -1 = the library's choice (default: in
+ *   launches of more workgroups than the chip has compute units, where the launch waits for its memory-side
+ *   atomics), 0 = off, 1 = wherever the rays are sorted.  No result depends on it - the counters are integers; an A/B switch.
  * "replay_reset": 1 = slam_replay_dev starts its map from zero (as slam_grid_reset before it would),
  *   clearing the counters inside its scan-matching launch: one dispatch less per replay.  0
  *   (default): the map accumulates across replays until slam_grid_reset.
