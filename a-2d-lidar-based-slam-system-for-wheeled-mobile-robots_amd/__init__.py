@@ -6,7 +6,9 @@ zjwzcx/A-2D-LiDAR-based-SLAM-System-for-Wheeled-Mobile-Robots:
 
     ICP        process / findNearest / getTransform / laserToNumpy / laserCallback / publishResult
     Mapping    update -> pmap; raycast / score_scan read the map along rays (batched: DeviceGrid.raycast /
-               .score, grid_raycast_host / grid_score_host)
+               .score, grid_raycast_host / grid_score_host); distance_field / match_scan: where a scan fits
+               the map best (batched: DeviceGrid.distance_field / .match, grid_distance_field_host /
+               grid_match_host, match_pose)
     bresenham  (start, end).path
     SLAM_EKF   laserCallback glue (scan matching + map building); landmarks=True: the whole W12
                node with Extraction and the landmark EKF on the host; batched on the device
@@ -39,6 +41,7 @@ from .loc_replay import DeviceLocalizationReplay, loc_replay_host
 from .mapping import Mapping
 from .node_replay import DeviceNodeReplay, ekf_lm_host, landmarks_host, node_replay_host
 from .replay import DeviceGrid, DeviceReplay, grid_raycast_host, grid_score_host, icp_batch_host, particles_host, prior_matrices, replay_host
+from .replay import grid_distance_field_host, grid_match_host, match_pose, match_rotations
 from .slam_ekf import SLAM_EKF
 from .synthetic import LaserScan
 
@@ -48,4 +51,5 @@ __all__ = ["ICP", "Mapping", "Localization", "EKF", "Extraction", "LandMarkSet",
            "global_planner", "find_path", "GlobalPlanner", "DeviceAStar", "astar_host", "inflate_host",
            "DeviceNodeReplay", "node_replay_host", "landmarks_host", "ekf_lm_host",
            "DeviceLocalizationReplay", "loc_replay_host", "grid_raycast_host", "grid_score_host",
+           "grid_distance_field_host", "grid_match_host", "match_pose", "match_rotations",
            "RAY_EMPTY", "RAY_HIT", "RAY_BLOCKED", "RAY_FREE", "RAY_UNKNOWN", "RAY_OUT", "RAY_BAD", "RAY_CLASSES", "RAY_NAMES"]

@@ -75,6 +75,10 @@ _SIGS = {
     "slam_grid_raycast_dev": ([_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, C.c_float, _i, _vp, _vp], _i),
     "slam_grid_scan_score": ([_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp], _i),
     "slam_grid_scan_score_dev": ([_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp], _i),
+    "slam_grid_distance_field": ([_vp, _vp, _i, _vp], _i),
+    "slam_grid_distance_field_dev": ([_vp, _vp, _i, _vp], _i),
+    "slam_grid_match": ([_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _d, C.c_float, _i, _vp, _vp, _vp, _vp], _i),
+    "slam_grid_match_dev": ([_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _d, C.c_float, _i, _vp, _vp, _vp, _vp], _i),
     "slam_bresenham_batch": ([_vp, _vp, _vp, _i, _vp, _vp, _vp, C.c_int64], _i),
     "slam_replay": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp], _i),
     "slam_particles": ([_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _d, _vp, _vp, _vp, _vp], _i),

@@ -1426,6 +1426,114 @@ int slam_grid_scan_score(slam_ctx *c, slam_grid *g, const float *ranges, int sha
     return s.download();
 }
 
+// ---- distance field and window matcher (match_kernels.hip) --------------------------------------------------------
+// The occupied bits packed as the counters stand on the stream now, then the field of all G maps: the mask and the
+// row distances in arena scratch, carved first; `field` null: carved behind them (the matcher's own copy).
+static int build_field(slam_ctx *c, slam_grid *g, const char *fn, int cap, size_t extra_bytes, int16_t *&field)
+{
+    TRY(grid_on_main(c));
+    const size_t words = raycast_mask_words(g->d), cells = (size_t)g->d.G * g->d.xw * g->d.yw;
+    TRY(arena_reserve(c, c->scratch, align_up(words * 4) + align_up(field_rowd_bytes(g->d)) + (field ? 0 : align_up(cells * 2)) +
+                                         align_up(extra_bytes) + 1024));
+    uint32_t *mask = carve<uint32_t>(c->scratch, words);
+    uint8_t *rowd = carve<uint8_t>(c->scratch, field_rowd_bytes(g->d));
+    if (!field) field = carve<int16_t>(c->scratch, cells);
+    REQUIRE_IN(fn, mask && rowd && field, "internal: workspace");
+    Timed t(c, SLAM_K_FINALIZE);          // the threshold rule over every cell, as a finalize pass is
+    HIPCHK(launch_raycast_pack(g->d, mask, c->stream));
+    HIPCHK(launch_distance_field(g->d, mask, cap, rowd, field, c->stream));
+    return SLAM_OK;
+}
+
+static int check_field(const char *fn, const slam_grid *g, int cap, const void *out)
+{
+    REQUIRE_IN(fn, g && out, "null pointer");
+    REQUIRE_IN(fn, cap >= 1 && cap <= 32767, "cap outside [1, 32767]");
+    return SLAM_OK;
+}
+
+int slam_grid_distance_field_dev(slam_ctx *c, slam_grid *g, int cap, int16_t *field_out)
+{
+    TRY(use(c));
+    TRY(check_field(__func__, g, cap, field_out));
+    return build_field(c, g, __func__, cap, 0, field_out);
+}
+
+int slam_grid_distance_field(slam_ctx *c, slam_grid *g, int cap, int16_t *field_out)
+{
+    TRY(use(c));
+    TRY(check_field(__func__, g, cap, field_out));
+    int16_t *d_f;
+    Staging s(c);
+    s.out(d_f, field_out, (size_t)g->d.G * g->d.xw * g->d.yw);
+    TRY(s.upload());
+    TRY(slam_grid_distance_field_dev(c, g, cap, d_f));
+    return s.download();
+}
+
+static int check_match(const char *fn, const slam_grid *g, const float *ranges, const double *centres, int B, const double *cos_t,
+                       const double *sin_t, int n, const double *rot_cs, int K, int nx, int ny, double step, float max_range,
+                       int cap, const int32_t *best_out, const int32_t *best_cost_out)
+{
+    REQUIRE_IN(fn, g && ranges && centres && cos_t && sin_t && rot_cs && best_out && best_cost_out, "null pointer");
+    REQUIRE_IN(fn, cap >= 1 && cap <= 32767, "cap outside [1, 32767]");
+    REQUIRE_IN(fn, n >= 1 && (long)n * cap < (1L << 31), "n < 1 or n * cap >= 2^31");
+    REQUIRE_IN(fn, n <= 4096, "n outside [1, 4096]");
+    REQUIRE_IN(fn, B >= 1 && (long)B * n < (1L << 31), "B < 1 or B * n >= 2^31");
+    REQUIRE_IN(fn, K >= 1 && nx >= 0 && ny >= 0, "K < 1, nx < 0 or ny < 0");
+    const long lim = 1L << 24;
+    REQUIRE_IN(fn, K <= lim && nx < lim && ny < lim && (2L * nx + 1) * (2L * ny + 1) <= lim &&
+                       (long)K * ((2L * nx + 1) * (2L * ny + 1)) <= lim, "K * (2 nx + 1) * (2 ny + 1) > 2^24");
+    REQUIRE_IN(fn, (long)B * K < (1L << 31), "B * K >= 2^31");
+    REQUIRE_IN(fn, std::isfinite(step) && step > 0, "step must be finite and > 0");
+    REQUIRE_IN(fn, max_range > 0, "max_range must be > 0");
+    return SLAM_OK;
+}
+
+int slam_grid_match_dev(slam_ctx *c, slam_grid *g, const float *ranges, int shared, const double *centres, int B,
+                        const int32_t *grid_of_batch, const double *cos_t, const double *sin_t, int n, const double *rot_cs,
+                        int K, int nx, int ny, double step, float max_range, int cap, int32_t *best_out,
+                        int32_t *best_cost_out, int32_t *used_out, int32_t *cost_out)
+{
+    TRY(use(c));
+    TRY(check_match(__func__, g, ranges, centres, B, cos_t, sin_t, n, rot_cs, K, nx, ny, step, max_range, cap, best_out,
+                    best_cost_out));
+    int16_t *field = nullptr;
+    TRY(build_field(c, g, __func__, cap, (size_t)B * 8, field));
+    MatchArgs a;
+    a.keys = carve<unsigned long long>(c->scratch, B);
+    REQUIRE(a.keys, "internal: workspace");
+    a.g = g->d; a.field = field;
+    a.ranges = ranges; a.range_stride = shared ? 0 : n;
+    a.centres = centres; a.maps = grid_of_batch; a.cos_t = cos_t; a.sin_t = sin_t; a.rot_cs = rot_cs;
+    a.B = B; a.n = n; a.K = K; a.nx = nx; a.ny = ny; a.step = step; a.max_range = max_range; a.cap = cap;
+    a.best_out = best_out; a.best_cost_out = best_cost_out; a.used_out = used_out; a.cost_out = cost_out;
+    HIPCHK(hipMemsetAsync(a.keys, 0xff, (size_t)B * 8, c->stream));
+    Timed t(c, SLAM_K_GRID);
+    HIPCHK(launch_match(a, c->stream));
+    return SLAM_OK;
+}
+
+int slam_grid_match(slam_ctx *c, slam_grid *g, const float *ranges, int shared, const double *centres, int B,
+                    const int32_t *grid_of_batch, const double *cos_t, const double *sin_t, int n, const double *rot_cs, int K,
+                    int nx, int ny, double step, float max_range, int cap, int32_t *best_out, int32_t *best_cost_out,
+                    int32_t *used_out, int32_t *cost_out)
+{
+    TRY(use(c));
+    TRY(check_match(__func__, g, ranges, centres, B, cos_t, sin_t, n, rot_cs, K, nx, ny, step, max_range, cap, best_out,
+                    best_cost_out));
+    const size_t cands = (size_t)K * (2 * (size_t)nx + 1) * (2 * (size_t)ny + 1);
+    float *d_r; double *d_ctr, *d_c, *d_s, *d_rot; int32_t *d_g, *d_best, *d_cost, *d_used, *d_vol;
+    Staging s(c);
+    s.in(d_r, ranges, shared ? (size_t)n : (size_t)B * n).in(d_ctr, centres, (size_t)B * 2).in(d_g, grid_of_batch, B)
+        .in(d_c, cos_t, n).in(d_s, sin_t, n).in(d_rot, rot_cs, (size_t)B * K * 2)
+        .out(d_best, best_out, B).out(d_cost, best_cost_out, B).out(d_used, used_out, B).out(d_vol, cost_out, (size_t)B * cands);
+    TRY(s.upload());
+    TRY(slam_grid_match_dev(c, g, d_r, shared, d_ctr, B, d_g, d_c, d_s, n, d_rot, K, nx, ny, step, max_range, cap, d_best,
+                            d_cost, d_used, d_vol));
+    return s.download();
+}
+
 int slam_bresenham_batch(slam_ctx *c, const int32_t *starts, const int32_t *ends, int B, const int64_t *offsets,
                          int32_t *lens_out, int32_t *cells_out, int64_t total_cells)
 {

@@ -204,6 +204,31 @@ bool choose_raycast_path(const GridDev &g, int lds_mode, long B, int n);
 hipError_t launch_raycast_pack(const GridDev &g, uint32_t *mask, hipStream_t s);
 hipError_t launch_raycast(RaycastArgs a, bool staged, hipStream_t s);
 
+// ---- distance field of the grid and the window matcher on it (match_kernels.hip) ---------
+struct MatchArgs {
+    GridDev g;
+    const int16_t *field = nullptr;          // [G][xw][yw] (launch_distance_field)
+    const float *ranges = nullptr;           // [B][n], or one [n] with range_stride 0
+    long range_stride = 0;
+    const double *centres = nullptr;         // [B][2]
+    const int32_t *maps = nullptr;           // nullable [B]: the map of every hypothesis (an entry outside [0, G): all outputs -1)
+    const double *cos_t = nullptr, *sin_t = nullptr;
+    const double *rot_cs = nullptr;          // [B][K][2] cos / sin of every rotation
+    int B = 0, n = 0, K = 0, nx = 0, ny = 0;
+    double step = 0.0;
+    float max_range = 0.f;
+    int cap = 0;
+    unsigned long long *keys = nullptr;      // workspace [B], every byte 0xff on entry: min of (cost << 32 | flat index)
+    int32_t *best_out = nullptr, *best_cost_out = nullptr;   // [B]
+    int32_t *used_out = nullptr;             // nullable [B]
+    int32_t *cost_out = nullptr;             // nullable [B][K][2 nx + 1][2 ny + 1]
+    int kc = 1, chunks = 1;                  // set by launch_match: rotations per workgroup, workgroups per hypothesis
+};
+size_t field_rowd_bytes(const GridDev &g);   // workspace of launch_distance_field
+// mask: launch_raycast_pack's words; rowd: field_rowd_bytes(g) bytes of workspace; field [G][xw][yw]; 1 <= cap <= 32767
+hipError_t launch_distance_field(const GridDev &g, const uint32_t *mask, int cap, uint8_t *rowd, int16_t *field, hipStream_t s);
+hipError_t launch_match(MatchArgs a, hipStream_t s);
+
 // ---- scan-to-map observation ---------------------------------------
 hipError_t launch_map_obstacles(const int8_t *map, int width, int height, int wire, double resolution, double origin_x,
                                 double origin_y, double *ox, double *oy, int cap, int *count, hipStream_t s);

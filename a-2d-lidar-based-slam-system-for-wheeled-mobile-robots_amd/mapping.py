@@ -155,6 +155,38 @@ class Mapping:
                                                    _abi.ptr(st), r.shape[0], int(skip), _abi.ptr(counts), None))
         return counts
 
+    def distance_field(self, cap=64):
+        """The distance field of this map (``slam_grid_distance_field``): int16 [xw, yw], the squared cell distance
+        to the nearest occupied cell, capped at ``cap`` (1 .. 32767); ``cap`` everywhere while nothing is occupied.
+        Rebuilt from the live counters on every call."""
+        out = np.empty((self.xw, self.yw), dtype=np.int16)
+        _abi.check(_abi.lib().slam_grid_distance_field(self._ctx.handle, self._grid, int(cap), _abi.ptr(out)))
+        return out
+
+    def match_scan(self, ranges, angle_min, angle_max, pose, window=(4, 4), step=None, n_rot=11, rot_step=0.01,
+                   max_range=30.0, cap=64, return_costs=False):
+        """Where a measured scan fits this map best near ``pose`` (x, y, theta) (``slam_grid_match``): every pose of
+        the window - ``n_rot`` rotations theta + (k - n_rot // 2) * rot_step, (2 window[0] + 1) x (2 window[1] + 1)
+        translations of ``step`` (default: one cell, 1 / index_scale) - costs the sum over the beams shorter than
+        ``max_range`` of the distance-field value at the beam's end cell (``cap`` off the map).  Returns (pose [3],
+        cost, used beams) of the cheapest candidate, ties to the lowest (rotation, x, y) index, and with
+        ``return_costs`` also the cost volume int32 [n_rot, 2 window[0] + 1, 2 window[1] + 1]."""
+        from .replay import _window_ok, match_pose, match_rotations
+        r = np.ascontiguousarray(np.asarray(ranges, dtype=np.float32).reshape(-1))
+        p = np.asarray(pose, dtype=np.float64).reshape(3)
+        n, nx, ny = r.shape[0], int(window[0]), int(window[1])
+        step = 1.0 / self.index_scale if step is None else float(step)
+        ct, st = _abi.trig_tables(angle_min, angle_max, n)
+        ctr = np.ascontiguousarray(p[None, :2])
+        th, rot = match_rotations(p[2:3], n_rot, rot_step)
+        best, cost, used = (np.empty(1, dtype=np.int32) for _ in range(3))
+        vol = np.empty((int(n_rot), 2 * nx + 1, 2 * ny + 1), dtype=np.int32) if return_costs and _window_ok(int(n_rot), nx, ny) else None
+        _abi.check(_abi.lib().slam_grid_match(self._ctx.handle, self._grid, _abi.ptr(r), 1, _abi.ptr(ctr), 1, None, _abi.ptr(ct),
+                                              _abi.ptr(st), n, _abi.ptr(rot), int(n_rot), nx, ny, step, float(max_range),
+                                              int(cap), _abi.ptr(best), _abi.ptr(cost), _abi.ptr(used), _abi.ptr(vol)))
+        out = (match_pose(ctr, th, best, nx, ny, step)[0], int(cost[0]), int(used[0]))
+        return out + (vol,) if return_costs else out
+
     def counters(self):
         """(pass, hit) uint32 [xw, yw]: the integer evidence behind ``datamap``."""
         p = np.empty((self.xw, self.yw), dtype=np.uint32)

@@ -143,6 +143,72 @@ def grid_score_host(grid, ranges, poses, cos_t, sin_t, skip=1, grid_of_batch=Non
     return (counts, cls) if return_classes else counts
 
 
+def _window_ok(K, nx, ny):
+    """The window sizes ``slam_grid_match`` takes (a cost volume is only allocated for those; the library rejects the rest)."""
+    return K >= 1 and nx >= 0 and ny >= 0 and K * (2 * int(nx) + 1) * (2 * int(ny) + 1) <= 1 << 24
+
+
+def grid_distance_field_host(grid, cap=64):
+    """The distance field of every map of ``grid`` (``slam_grid_distance_field``): int16 [G, xw, yw], the squared
+    cell distance to the nearest occupied cell (pmap == 100 as the counters stand now), capped at ``cap``
+    (1 .. 32767).  Rebuilt on every call."""
+    out = np.empty((grid.G, grid.xw, grid.yw), dtype=np.int16)
+    _abi.check(_abi.lib().slam_grid_distance_field(grid._ctx.handle, grid._h, int(cap), _abi.ptr(out)))
+    return out
+
+
+def grid_match_host(grid, ranges, centres, cos_t, sin_t, rot_cs, nx, ny, step, max_range=30.0, cap=64, grid_of_batch=None,
+                    return_costs=False):
+    """The window matcher on the distance field (``slam_grid_match``): ranges float32 [B, n] or one shared [n],
+    centres [B, 2], rot_cs [B, K, 2] the cos / sin of every rotation; the window is (2 nx + 1) x (2 ny + 1)
+    translations of ``step`` around each centre.  Returns (best int32 [B] flat candidate index, cost int32 [B],
+    used int32 [B]) and with ``return_costs`` also the cost volume int32 [B, K, 2 nx + 1, 2 ny + 1];
+    :func:`match_pose` turns ``best`` into poses.  The field is rebuilt on every call."""
+    ctr = np.ascontiguousarray(np.asarray(centres, dtype=np.float64).reshape(-1, 2))
+    B = ctr.shape[0]
+    gob = None if grid_of_batch is None else np.ascontiguousarray(np.asarray(grid_of_batch, dtype=np.int32).reshape(B))
+    ct, st = _tables(cos_t, sin_t)
+    n = ct.shape[0]
+    rot = np.ascontiguousarray(np.asarray(rot_cs, dtype=np.float64))
+    if rot.ndim != 3 or rot.shape[0] != B or rot.shape[2] != 2:
+        raise ValueError("rot_cs must be [B, K, 2]")
+    K = rot.shape[1]
+    r = np.ascontiguousarray(np.asarray(ranges, dtype=np.float32))
+    shared = r.ndim == 1
+    if r.shape != ((n,) if shared else (B, n)):
+        raise ValueError("ranges must be [n] or [B, n]")
+    best, cost, used = (np.empty(B, dtype=np.int32) for _ in range(3))
+    vol = np.empty((B, K, 2 * int(nx) + 1, 2 * int(ny) + 1), dtype=np.int32) if return_costs and _window_ok(K, nx, ny) else None
+    _abi.check(_abi.lib().slam_grid_match(grid._ctx.handle, grid._h, _abi.ptr(r), int(shared), _abi.ptr(ctr), B, _abi.ptr(gob),
+                                          _abi.ptr(ct), _abi.ptr(st), n, _abi.ptr(rot), K, int(nx), int(ny), float(step),
+                                          float(max_range), int(cap), _abi.ptr(best), _abi.ptr(cost), _abi.ptr(used),
+                                          _abi.ptr(vol)))
+    return (best, cost, used, vol) if return_costs else (best, cost, used)
+
+
+def match_rotations(thetas, n_rot=11, rot_step=0.01):
+    """(angles [B, K], rot_cs [B, K, 2]) of the matcher's rotations: theta + (k - n_rot // 2) * rot_step, cosine
+    and sine by NumPy."""
+    th = np.asarray(thetas, dtype=np.float64).reshape(-1, 1) + (np.arange(int(n_rot)) - int(n_rot) // 2) * float(rot_step)
+    return th, np.ascontiguousarray(np.stack([np.cos(th), np.sin(th)], axis=-1))
+
+
+def match_pose(centres, thetas, best, nx, ny, step):
+    """Poses [B, 3] of the flat candidate indices ``best`` [B] of a window match: ``thetas`` [B, K] the angles the
+    rotation tables were made from, x = cx + (i - nx) * step, y = cy + (j - ny) * step; NaN rows where best is -1."""
+    ctr = np.asarray(centres, dtype=np.float64).reshape(-1, 2)
+    th = np.asarray(thetas, dtype=np.float64).reshape(ctr.shape[0], -1)
+    best = np.asarray(best).reshape(-1).astype(np.int64)
+    wx, wy = 2 * int(nx) + 1, 2 * int(ny) + 1
+    ok = best >= 0
+    idx = np.where(ok, best, 0)
+    k, i, j = idx // (wx * wy), idx // wy % wx, idx % wy
+    out = np.stack([ctr[:, 0] + (i - int(nx)).astype(np.float64) * float(step),
+                    ctr[:, 1] + (j - int(ny)).astype(np.float64) * float(step), th[np.arange(len(idx)), k]], axis=1)
+    out[~ok] = np.nan
+    return out
+
+
 class DeviceGrid:
     """G occupancy maps resident on the device (``slam_grid_*``)."""
 
@@ -240,6 +306,36 @@ class DeviceGrid:
                                                        _abi.ptr(poses), B, _abi.ptr(grid_of_batch), _abi.ptr(cos_t),
                                                        _abi.ptr(sin_t), n, int(skip), _abi.ptr(counts_out), _abi.ptr(class_out)))
         return counts_out if class_out is None else (counts_out, class_out)
+
+    def distance_field(self, cap=64, out=None):
+        """``slam_grid_distance_field_dev``: the capped squared cell distance to the nearest occupied cell of every
+        map, into the torch int16 tensor [G, xw, yw] given or a fresh one on the context's device; rebuilt on every
+        call, enqueued on the context's stream, no synchronise."""
+        import torch
+        if out is None:
+            out = torch.empty((self.G, self.xw, self.yw), dtype=torch.int16, device=torch.device("cuda", self._ctx.device))
+        _abi.check(_abi.lib().slam_grid_distance_field_dev(self._ctx.handle, self._h, int(cap), _abi.ptr(out)))
+        return out
+
+    def match(self, ranges, centres, cos_t, sin_t, rot_cs, nx, ny, step, max_range=30.0, cap=64, grid_of_batch=None,
+              best_out=None, cost_out=None, used_out=None, costs_out=None, return_costs=False):
+        """``slam_grid_match_dev`` on torch device tensors: ranges float32 [B, n] or a shared [n], centres float64
+        [B, 2], cos_t / sin_t float64 [n], rot_cs float64 [B, K, 2].  Writes best / cost / used int32 [B] (and the
+        cost volume int32 [B, K, 2 nx + 1, 2 ny + 1]) into the tensors given or into fresh ones; no synchronise."""
+        import torch
+        B, n, K = int(centres.shape[0]), int(cos_t.shape[0]), int(rot_cs.shape[1])
+        new = lambda *shape: torch.empty(shape, dtype=torch.int32, device=centres.device)
+        best_out = new(B) if best_out is None else best_out
+        cost_out = new(B) if cost_out is None else cost_out
+        used_out = new(B) if used_out is None else used_out
+        if costs_out is None and return_costs:
+            costs_out = new(B, K, 2 * int(nx) + 1, 2 * int(ny) + 1)
+        _abi.check(_abi.lib().slam_grid_match_dev(self._ctx.handle, self._h, _abi.ptr(ranges), int(ranges.dim() == 1),
+                                                  _abi.ptr(centres), B, _abi.ptr(grid_of_batch), _abi.ptr(cos_t), _abi.ptr(sin_t),
+                                                  n, _abi.ptr(rot_cs), K, int(nx), int(ny), float(step), float(max_range),
+                                                  int(cap), _abi.ptr(best_out), _abi.ptr(cost_out), _abi.ptr(used_out),
+                                                  _abi.ptr(costs_out)))
+        return (best_out, cost_out, used_out) if costs_out is None else (best_out, cost_out, used_out, costs_out)
 
     def read(self, g=0, want=("pmap",)):
         out = {}

@@ -308,6 +308,50 @@ int slam_grid_scan_score_dev(slam_ctx *ctx, slam_grid *grid, const float *ranges
                              const int32_t *grid_of_batch, const double *cos_t, const double *sin_t, int n, int skip,
                              int32_t *counts_out, int8_t *class_out);
 
+/* ---- distance field of the map and the window scan-to-map matcher --------------------------- */
+/* Where a scan fits a map best; the reference has no counterpart.  Both calls see every update enqueued before
+ * them on the context's stream, change nothing in the grid and leave the context's sticky status untouched.
+ * "Occupied" is what the ray cast reads: pmap == 100 as slam_grid_finalize_dev would give it NOW.  The occupied
+ * bits and the field of all G maps are REBUILT at the start of every call (slam_grid_match builds a field of its
+ * own in the context's workspace); nothing is kept between calls.  Under slam_timing_* building the field counts
+ * as SLAM_K_FINALIZE, the match as SLAM_K_GRID.
+ *
+ * slam_grid_distance_field: field_out [G][xw][yw] int16, in pmap's cell order,
+ *   field[g][x][y] = min(cap, min over cells (u, v) of map g with pmap == 100 of (x-u)^2 + (y-v)^2),
+ * the squared cell distance to the nearest occupied cell, exact for every 1 <= cap <= 32767; cap everywhere on a
+ * map with no occupied cell. */
+int slam_grid_distance_field(slam_ctx *ctx, slam_grid *grid, int cap, int16_t *field_out);
+int slam_grid_distance_field_dev(slam_ctx *ctx, slam_grid *grid, int cap, int16_t *field_out);
+/* slam_grid_match: every pose of a window around a start pose, scored on the field.  Hypothesis b reads map
+ * gi = grid_of_batch[b] (NULL: map 0) around centre (cx, cy) = centres[b]; ranges float32 [B][n], or one [n] for
+ * every hypothesis when shared != 0; cos_t, sin_t [n] as for slam_scan_to_points; rot_cs [B][K][2] the cosine and
+ * sine of every rotation (made by the caller, as the beam tables are).  Candidate (k, i, j), 0 <= k < K,
+ * 0 <= i <= 2*nx, 0 <= j <= 2*ny, has flat index (k*(2*nx+1) + i)*(2*ny+1) + j and
+ *   px = cx + (double)(i - nx) * step,  py = cy + (double)(j - ny) * step,  c = rot_cs[b][k][0],  s = rot_cs[b][k][1];
+ *   per beam t:  rr = (double)ranges[t];  used iff isfinite(rr) && ranges[t] < max_range (compared as float32);
+ *                lx = cos_t[t]*rr;  ly = sin_t[t]*rr;
+ *                x = c*lx + (-s)*ly + px*1.0;  y = s*lx + c*ly + py*1.0     (u2T(pose).dot(pc), W12m/slam_ekf.py:88-90,
+ *                                                                             no fused multiply-add)
+ *                cell = (int(scale*(x + off_x)), int(scale*(y + off_y)))     (mapping.py:33-36)
+ *                cost += field[gi][cell] if the cell is in bounds, else cap  (also for NaN / a cell index beyond 2^20)
+ * Costs are int32 sums over the used beams.  best_out [B]: the flat index of the smallest cost, ties to the LOWEST
+ * flat index; best_cost_out [B] its cost; used_out (nullable) [B] the number of used beams; cost_out (nullable)
+ * [B][K][2*nx+1][2*ny+1] every candidate's cost.  A scan with no used beam: cost 0 everywhere, best 0, used 0.
+ * A hypothesis whose centre is not finite or whose centre cell index is beyond 2^20, or whose grid_of_batch entry
+ * is outside [0, G) (host and device form alike), gets best -1, cost -1, used 0 and costs of -1; the others of
+ * the batch are unaffected, and every hypothesis gets the same outputs alone, in any batch and in any order.
+ * 1 <= cap <= 32767, 1 <= n <= 4096, n * cap < 2^31, B >= 1, B * n < 2^31, K >= 1, nx, ny >= 0,
+ * K*(2*nx+1)*(2*ny+1) <= 2^24, B * K < 2^31, step finite and > 0, max_range > 0 (+inf: every finite range is used);
+ * anything else is SLAM_ERR_INVALID and leaves the context as it was. */
+int slam_grid_match(slam_ctx *ctx, slam_grid *grid, const float *ranges, int shared, const double *centres, int B,
+                    const int32_t *grid_of_batch, const double *cos_t, const double *sin_t, int n, const double *rot_cs, int K,
+                    int nx, int ny, double step, float max_range, int cap, int32_t *best_out, int32_t *best_cost_out,
+                    int32_t *used_out, int32_t *cost_out);
+int slam_grid_match_dev(slam_ctx *ctx, slam_grid *grid, const float *ranges, int shared, const double *centres, int B,
+                        const int32_t *grid_of_batch, const double *cos_t, const double *sin_t, int n, const double *rot_cs,
+                        int K, int nx, int ny, double step, float max_range, int cap, int32_t *best_out,
+                        int32_t *best_cost_out, int32_t *used_out, int32_t *cost_out);
+
 /* Replaces bresenham(start, end).path (W12m/bresenham.py:2-58), B lines at once.
  * starts, ends [B][2] int32.  lens_out [B] receives each path length; cells_out (may be
  * NULL) receives the paths, line b at cells_out + 2*offsets[b] (x, y interleaved), with
