@@ -15,6 +15,8 @@ zjwzcx/A-2D-LiDAR-based-SLAM-System-for-Wheeled-Mobile-Robots:
                as DeviceNodeReplay / node_replay_host, landmarks_host, ekf_lm_host
     Localization  updateMap / laserEstimation / calc_map_observation (scan-to-map, W9); the whole
                W9 node batched on the device as DeviceLocalizationReplay / loc_replay_host
+    MCL        Monte Carlo localisation on the map's distance field: one filter on a Mapping; batched and
+               device-resident as DeviceMCL, on NumPy arrays as mcl_weigh_host / mcl_resample_host
     dwa        dwa_control / Config / RobotType (course_agv_nav DWA local planner), batched as
                DeviceDWA / dwa_batch_host; LocalPlanner: the local planner node without ROS
     global_planner  find_path(...).start_find() / GlobalPlanner (course_agv_nav A*), batched as
@@ -39,6 +41,7 @@ from .local_planner import LocalPlanner
 from .localization import Localization
 from .loc_replay import DeviceLocalizationReplay, loc_replay_host
 from .mapping import Mapping
+from .mcl import MCL, MCL_DEAD, DeviceMCL, mcl_resample_host, mcl_weigh_host, mcl_weight_table
 from .node_replay import DeviceNodeReplay, ekf_lm_host, landmarks_host, node_replay_host
 from .replay import DeviceGrid, DeviceReplay, grid_raycast_host, grid_score_host, icp_batch_host, particles_host, prior_matrices, replay_host
 from .replay import grid_distance_field_host, grid_match_host, match_pose, match_rotations
@@ -52,4 +55,5 @@ __all__ = ["ICP", "Mapping", "Localization", "EKF", "Extraction", "LandMarkSet",
            "DeviceNodeReplay", "node_replay_host", "landmarks_host", "ekf_lm_host",
            "DeviceLocalizationReplay", "loc_replay_host", "grid_raycast_host", "grid_score_host",
            "grid_distance_field_host", "grid_match_host", "match_pose", "match_rotations",
+           "MCL", "DeviceMCL", "MCL_DEAD", "mcl_weight_table", "mcl_weigh_host", "mcl_resample_host",
            "RAY_EMPTY", "RAY_HIT", "RAY_BLOCKED", "RAY_FREE", "RAY_UNKNOWN", "RAY_OUT", "RAY_BAD", "RAY_CLASSES", "RAY_NAMES"]

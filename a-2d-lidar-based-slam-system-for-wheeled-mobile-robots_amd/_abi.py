@@ -79,6 +79,10 @@ _SIGS = {
     "slam_grid_distance_field_dev": ([_vp, _vp, _i, _vp], _i),
     "slam_grid_match": ([_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _d, C.c_float, _i, _vp, _vp, _vp, _vp], _i),
     "slam_grid_match_dev": ([_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _d, C.c_float, _i, _vp, _vp, _vp, _vp], _i),
+    "slam_mcl_weigh": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, C.c_float, _i, _vp, _vp, _vp, _vp], _i),
+    "slam_mcl_weigh_dev": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, C.c_float, _i, _vp, _vp, _vp, _vp], _i),
+    "slam_mcl_resample": ([_vp, _vp, _vp, _vp, _i, _i, _vp, _d, _i, _i, _vp, _vp, _vp, _vp], _i),
+    "slam_mcl_resample_dev": ([_vp, _vp, _vp, _vp, _i, _i, _vp, _d, _i, _i, _vp, _vp, _vp, _vp], _i),
     "slam_bresenham_batch": ([_vp, _vp, _vp, _i, _vp, _vp, _vp, C.c_int64], _i),
     "slam_replay": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp], _i),
     "slam_particles": ([_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _d, _vp, _vp, _vp, _vp], _i),
@@ -124,6 +128,7 @@ EKF_MAX_LM = 32
 # classes of slam_grid_scan_score (SLAM_RAY_*)
 RAY_EMPTY, RAY_HIT, RAY_BLOCKED, RAY_FREE, RAY_UNKNOWN, RAY_OUT, RAY_BAD = range(7)
 RAY_CLASSES = 7
+MCL_DEAD = 2 ** 31 - 1             # SLAM_MCL_DEAD: a dead particle's accumulated cost
 RAY_NAMES = ("empty", "hit", "blocked", "free", "unknown", "out", "bad")
 
 

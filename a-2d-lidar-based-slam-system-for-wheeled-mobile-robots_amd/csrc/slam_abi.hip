@@ -103,6 +103,7 @@ struct slam_ctx {
     int win_lds_hits = -1; // shared-map window ray cast: hits of sorted rays counted in the LDS window, one global add per end cell: -1 = the library's choice (chip-filling launches), 0 = off, 1 = on; changes no result
     int icp_one_wave = -1; // scan matching with one wave per pair: -1 = where a full-chip launch allows it, 0 = never, 1 = wherever a pair fits
     int raycast_lds = -1; // rays traced through a map: -1 = automatic, 0 = mask words from global memory, 1 = from LDS wherever the mask fits
+    int mcl_shape = -1;   // slam_mcl_weigh: -1 = the library's choice by beam count, 0 = lanes over particles, 1 = a wave per particle, lanes over beams; changes no result
     int icp_team = 0;     // first-iteration queries without a beam window: 0 = listed and searched apart from their lanes (nn_listed), 1 = box search
     // "pipeline" option: the map stage of slam_replay_dev (reset -> ray cast -> finalize) runs on
     // a second stream, so the map stage of one replay overlaps the scan matching of the next.
@@ -306,6 +307,8 @@ public:
     explicit Staging(slam_ctx *c) : c_(c) {}
     // an input copied from `host`; absent (null device pointer) when `host` is null
     template <typename T> Staging &in(T *&dev, const T *host, size_t n) { return add(dev, n, host, nullptr, !host); }
+    // copied from `host` and back to it; absent when `host` is null
+    template <typename T> Staging &inout(T *&dev, T *host, size_t n) { return add(dev, n, host, host, !host); }
     // an output copied back to `host`; absent when `host` is null
     template <typename T> Staging &out(T *&dev, T *host, size_t n) { return add(dev, n, nullptr, host, !host); }
     // an output the device form always needs: copied back only when `host` is non-null
@@ -708,6 +711,7 @@ static const OptionRange kOptionRanges[] = {
     {"icp_qpt", [](double v) { return v >= 0 && v <= 3; }, "icp_qpt in [0, 3]"},
     {"pipeline", [](double v) { return v == 0 || v == 1; }, "pipeline is 0 or 1"},
     {"raycast_lds", [](double v) { return v == -1 || v == 0 || v == 1; }, "raycast_lds is -1, 0 or 1"},
+    {"mcl_shape", [](double v) { return v == -1 || v == 0 || v == 1; }, "mcl_shape is -1, 0 or 1"},
 };
 
 int slam_set_option(slam_ctx *c, const char *name, double value)
@@ -730,6 +734,7 @@ int slam_set_option(slam_ctx *c, const char *name, double value)
     else if (!strcmp(name, "particle_chunks")) { TRY(join_particles(c)); c->particle_chunks = (int)value; }
     else if (!strcmp(name, "icp_qpt")) c->icp_qpt = (int)value;
     else if (!strcmp(name, "raycast_lds")) c->raycast_lds = (int)value;
+    else if (!strcmp(name, "mcl_shape")) c->mcl_shape = (int)value;
     else if (!strcmp(name, "pipeline")) {
         TRY(join_from_grid(c));
         if (value == 1 && !c->gstream) {
@@ -1531,6 +1536,122 @@ int slam_grid_match(slam_ctx *c, slam_grid *g, const float *ranges, int shared, 
     TRY(s.upload());
     TRY(slam_grid_match_dev(c, g, d_r, shared, d_ctr, B, d_g, d_c, d_s, n, d_rot, K, nx, ny, step, max_range, cap, d_best,
                             d_cost, d_used, d_vol));
+    return s.download();
+}
+
+// ---- Monte Carlo localisation on the distance field (mcl_kernels.hip) ----------------------------------------------
+static int check_mcl_shape(const char *fn, int F, int P)
+{
+    REQUIRE_IN(fn, F >= 1, "F < 1");
+    REQUIRE_IN(fn, P >= 1 && P <= (1 << 20), "P outside [1, 2^20]");
+    REQUIRE_IN(fn, (long)F * P < (1L << 31), "F * P >= 2^31");
+    return SLAM_OK;
+}
+
+static int check_mcl_weigh(const char *fn, const slam_grid *g, const double *poses, const double *motion, const double *noise,
+                           const float *ranges, const double *cos_t, const double *sin_t, int F, int P, int n, float max_range,
+                           int cap)
+{
+    REQUIRE_IN(fn, g && poses && ranges && cos_t && sin_t, "null pointer");
+    TRY(check_mcl_shape(fn, F, P));
+    REQUIRE_IN(fn, n >= 1 && n <= 4096, "n outside [1, 4096]");
+    REQUIRE_IN(fn, (long)F * n < (1L << 31), "F * n >= 2^31");
+    REQUIRE_IN(fn, cap >= 1 && cap <= 32767, "cap outside [1, 32767]");
+    REQUIRE_IN(fn, max_range > 0, "max_range must be > 0");
+    REQUIRE_IN(fn, motion || !noise, "noise without motion");
+    return SLAM_OK;
+}
+
+int slam_mcl_weigh_dev(slam_ctx *c, slam_grid *g, double *poses, const double *motion, const double *noise, const float *ranges,
+                       const double *cos_t, const double *sin_t, const int32_t *grid_of_filter, int F, int P, int n,
+                       float max_range, int cap, const int16_t *field, int32_t *acc, int32_t *cost_out, int32_t *used_out)
+{
+    TRY(use(c));
+    TRY(check_mcl_weigh(__func__, g, poses, motion, noise, ranges, cos_t, sin_t, F, P, n, max_range, cap));
+    int16_t *built = nullptr;
+    if (!field) TRY(build_field(c, g, __func__, cap, 0, built));
+    else TRY(grid_on_main(c));
+    MclWeighArgs a;
+    a.g = g->d; a.field = field ? field : built;
+    a.poses = poses; a.motion = motion; a.noise = noise; a.ranges = ranges; a.cos_t = cos_t; a.sin_t = sin_t;
+    a.maps = grid_of_filter; a.F = F; a.P = P; a.n = n; a.max_range = max_range; a.cap = cap;
+    a.acc = acc; a.cost_out = cost_out; a.used_out = used_out;
+    Timed t(c, SLAM_K_GRID);
+    HIPCHK(launch_mcl_weigh(a, c->mcl_shape, c->stream));
+    return SLAM_OK;
+}
+
+int slam_mcl_weigh(slam_ctx *c, slam_grid *g, double *poses, const double *motion, const double *noise, const float *ranges,
+                   const double *cos_t, const double *sin_t, const int32_t *grid_of_filter, int F, int P, int n, float max_range,
+                   int cap, const int16_t *field, int32_t *acc, int32_t *cost_out, int32_t *used_out)
+{
+    TRY(use(c));
+    TRY(check_mcl_weigh(__func__, g, poses, motion, noise, ranges, cos_t, sin_t, F, P, n, max_range, cap));
+    const size_t FP = (size_t)F * P;
+    double *d_p, *d_m, *d_n, *d_c, *d_s; float *d_r; int32_t *d_g, *d_acc, *d_cost, *d_used; int16_t *d_f;
+    Staging s(c);
+    s.inout(d_p, poses, FP * 3).in(d_m, motion, (size_t)F * 3).in(d_n, noise, FP * 3).in(d_r, ranges, (size_t)F * n).in(d_c, cos_t, n)
+        .in(d_s, sin_t, n).in(d_g, grid_of_filter, F).in(d_f, field, (size_t)g->d.G * g->d.xw * g->d.yw).inout(d_acc, acc, FP)
+        .out(d_cost, cost_out, FP).out(d_used, used_out, F);
+    TRY(s.upload());
+    TRY(slam_mcl_weigh_dev(c, g, d_p, d_m, d_n, d_r, d_c, d_s, d_g, F, P, n, max_range, cap, d_f, d_acc, d_cost, d_used));
+    return s.download();
+}
+
+static int check_mcl_resample(const char *fn, const double *poses, const int32_t *acc, const uint32_t *table, int T, int shift,
+                              const double *u0, double ess_frac, int F, int P, const double *poses_out, const double *est_out,
+                              const int32_t *info_out)
+{
+    REQUIRE_IN(fn, poses && acc && table && u0 && poses_out && est_out && info_out, "null pointer");
+    TRY(check_mcl_shape(fn, F, P));
+    REQUIRE_IN(fn, T >= 1 && T <= 65536, "T outside [1, 65536]");
+    REQUIRE_IN(fn, shift >= 0 && shift <= 30, "shift outside [0, 30]");
+    REQUIRE_IN(fn, ess_frac >= 0, "ess_frac must be >= 0 and not NaN");
+    REQUIRE_IN(fn, poses_out != poses, "poses_out must not be poses");
+    return SLAM_OK;
+}
+
+int slam_mcl_resample_dev(slam_ctx *c, const double *poses, int32_t *acc, const uint32_t *table, int T, int shift, const double *u0,
+                          double ess_frac, int F, int P, double *poses_out, int32_t *ancestors_out, double *est_out,
+                          int32_t *info_out)
+{
+    TRY(use(c));
+    TRY(check_mcl_resample(__func__, poses, acc, table, T, shift, u0, ess_frac, F, P, poses_out, est_out, info_out));
+    const size_t FP = (size_t)F * P, FB = (size_t)F * mcl_scan_blocks(P);
+    TRY(arena_reserve(c, c->scratch, align_up((size_t)F * 8) + align_up((size_t)F * 4) + align_up(FP * 8) + 2 * align_up(FB * 8) +
+                                         align_up(FB * 32) + align_up((size_t)F * 16) + 1024));
+    MclResampleArgs a;
+    a.keys = carve<unsigned long long>(c->scratch, F);
+    a.live = carve<int32_t>(c->scratch, F);
+    a.cum = carve<unsigned long long>(c->scratch, FP);
+    a.bsum = carve<unsigned long long>(c->scratch, FB);
+    a.bq = carve<unsigned long long>(c->scratch, FB);
+    a.bpart = carve<double>(c->scratch, FB * 4);
+    a.fpar = carve<unsigned long long>(c->scratch, (size_t)F * 2);
+    REQUIRE(a.keys && a.live && a.cum && a.bsum && a.bq && a.bpart && a.fpar, "internal: workspace");
+    a.poses = poses; a.acc = acc; a.table = table; a.T = T; a.shift = shift; a.u0 = u0; a.ess_frac = ess_frac; a.F = F; a.P = P;
+    a.poses_out = poses_out; a.ancestors_out = ancestors_out; a.est_out = est_out; a.info_out = info_out;
+    HIPCHK(hipMemsetAsync(a.keys, 0xff, (size_t)F * 8, c->stream));
+    HIPCHK(hipMemsetAsync(a.live, 0, (size_t)F * 4, c->stream));
+    Timed t(c, SLAM_K_GRID);
+    HIPCHK(launch_mcl_resample(a, c->stream));
+    return SLAM_OK;
+}
+
+int slam_mcl_resample(slam_ctx *c, const double *poses, int32_t *acc, const uint32_t *table, int T, int shift, const double *u0,
+                      double ess_frac, int F, int P, double *poses_out, int32_t *ancestors_out, double *est_out, int32_t *info_out)
+{
+    TRY(use(c));
+    TRY(check_mcl_resample(__func__, poses, acc, table, T, shift, u0, ess_frac, F, P, poses_out, est_out, info_out));
+    for (int f = 0; f < F; ++f) REQUIRE(u0[f] >= 0.0 && u0[f] < 1.0, "u0 outside [0, 1)");
+    for (int k = 0; k < T; ++k) REQUIRE(table[k] <= (1u << 20), "table entry above 2^20");
+    const size_t FP = (size_t)F * P;
+    double *d_p, *d_u, *d_po, *d_est; int32_t *d_acc, *d_anc, *d_info; uint32_t *d_t;
+    Staging s(c);
+    s.in(d_p, poses, FP * 3).inout(d_acc, acc, FP).in(d_t, table, T).in(d_u, u0, F).out(d_po, poses_out, FP * 3)
+        .out(d_anc, ancestors_out, FP).out(d_est, est_out, (size_t)F * 4).out(d_info, info_out, (size_t)F * 4);
+    TRY(s.upload());
+    TRY(slam_mcl_resample_dev(c, d_p, d_acc, d_t, T, shift, d_u, ess_frac, F, P, d_po, d_anc, d_est, d_info));
     return s.download();
 }
 

@@ -229,6 +229,52 @@ size_t field_rowd_bytes(const GridDev &g);   // workspace of launch_distance_fie
 hipError_t launch_distance_field(const GridDev &g, const uint32_t *mask, int cap, uint8_t *rowd, int16_t *field, hipStream_t s);
 hipError_t launch_match(MatchArgs a, hipStream_t s);
 
+// ---- Monte Carlo localisation on the distance field (mcl_kernels.hip) ---------------------
+constexpr int kMclScanBlock = 1024;          // particles per workgroup of the prefix sum: fixed, so a filter's sums do not depend on the batch
+inline int mcl_scan_blocks(int P) { return (P + kMclScanBlock - 1) / kMclScanBlock; }
+struct MclWeighArgs {
+    GridDev g;
+    const int16_t *field = nullptr;          // [G][xw][yw] (launch_distance_field)
+    double *poses = nullptr;                 // [F][P][3], moved in place when motion is given
+    const double *motion = nullptr;          // nullable [F][3]
+    const double *noise = nullptr;           // nullable [F][P][3]
+    const float *ranges = nullptr;           // [F][n]
+    const double *cos_t = nullptr, *sin_t = nullptr;
+    const int32_t *maps = nullptr;           // nullable [F]: the map of every filter (an entry outside [0, G): every particle dead)
+    int F = 0, P = 0, n = 0;
+    float max_range = 0.f;
+    int cap = 0;
+    int32_t *acc = nullptr;                  // nullable [F][P]
+    int32_t *cost_out = nullptr;             // nullable [F][P]
+    int32_t *used_out = nullptr;             // nullable [F]
+    int chunks = 1;                          // set by launch_mcl_weigh: workgroups per filter
+};
+struct MclResampleArgs {
+    const double *poses = nullptr;           // [F][P][3]
+    int32_t *acc = nullptr;                  // [F][P]
+    const uint32_t *table = nullptr;         // [T]
+    int T = 0, shift = 0;
+    const double *u0 = nullptr;              // [F]
+    double ess_frac = 0.0;
+    int F = 0, P = 0;
+    double *poses_out = nullptr;             // [F][P][3]
+    int32_t *ancestors_out = nullptr;        // nullable [F][P]
+    double *est_out = nullptr;               // [F][4]
+    int32_t *info_out = nullptr;             // [F][4]
+    // workspace, nblk = mcl_scan_blocks(P):
+    unsigned long long *keys = nullptr;      // [F], every byte 0xff on entry: min of (acc, index) over the live particles
+    int32_t *live = nullptr;                 // [F], zero on entry
+    unsigned long long *cum = nullptr;       // [F][P] inclusive prefix sums of the weights within each scan block
+    unsigned long long *bsum = nullptr;      // [F][nblk] block sums, then their exclusive scan
+    unsigned long long *bq = nullptr;        // [F][nblk] block sums of squares
+    double *bpart = nullptr;                 // [F][nblk][4] block sums of w x, w y, w sin, w cos
+    unsigned long long *fpar = nullptr;      // [F][2]: S if the filter resamples else 0, and the offset o
+    int nblk = 1;                            // set by launch_mcl_resample
+};
+// shape: the context option "mcl_shape" (-1: by beam count, 0: lanes over particles, 1: a wave per particle)
+hipError_t launch_mcl_weigh(MclWeighArgs a, int shape, hipStream_t s);
+hipError_t launch_mcl_resample(MclResampleArgs a, hipStream_t s);
+
 // ---- scan-to-map observation ---------------------------------------
 hipError_t launch_map_obstacles(const int8_t *map, int width, int height, int wire, double resolution, double origin_x,
                                 double origin_y, double *ox, double *oy, int cap, int *count, hipStream_t s);

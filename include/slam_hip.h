@@ -135,7 +135,10 @@ int slam_check_status(slam_ctx *ctx);
  *   0 / 1 = off (default).
  * "raycast_lds": where slam_grid_raycast / slam_grid_scan_score read the map's occupied bits from: 0 = global
  *   memory, one lane per ray (any map size); 1 = a copy in LDS per workgroup wherever the map's bit mask fits
- *   64 KiB (512 K cells), else as 0; -1 = automatic (default).  Same bits either way; an A/B switch. */
+ *   64 KiB (512 K cells), else as 0; -1 = automatic (default).  Same bits either way; an A/B switch.
+ * "mcl_shape": launch shape of slam_mcl_weigh: 0 = a workgroup's lanes run over the particles, each lane looping over
+ *   the beams; 1 = a wave per particle, its lanes over the beams; -1 = the library's choice by beam count (default).
+ *   Same bits either way; an A/B switch. */
 int slam_set_option(slam_ctx *ctx, const char *name, double value);
 /* Per-kernel-family timing with HIP events on the context's stream (bench.py roofline).
  * on: 0 = off, 1 = every family, 2 * mask = only the families in mask (bit SLAM_K_*): events on a
@@ -351,6 +354,68 @@ int slam_grid_match_dev(slam_ctx *ctx, slam_grid *grid, const float *ranges, int
                         const int32_t *grid_of_batch, const double *cos_t, const double *sin_t, int n, const double *rot_cs,
                         int K, int nx, int ny, double step, float max_range, int cap, int32_t *best_out,
                         int32_t *best_cost_out, int32_t *used_out, int32_t *cost_out);
+
+/* ---- Monte Carlo localisation on the distance field ----------------------------------------- */
+/* F particle filters of P particles each, weighed against their filter's scan on the field above and resampled on
+ * the device; the reference has no counterpart.  State: poses float64 [F][P][3] (x, y, theta; theta is not
+ * wrapped) and acc int32 [F][P], a particle's accumulated cost since its filter last resampled (the integer
+ * log-weight, >= 0).  acc == SLAM_MCL_DEAD marks a dead particle; it stays dead until a resample replaces it.
+ * Filter f reads map grid_of_filter[f] (NULL: map 0).  Everything that decides an index is integer: a filter gets
+ * the same outputs alone, in any batch and in any order.  Both calls change nothing in the grid and leave the
+ * context's sticky status untouched.  Under slam_timing_* building the field counts as SLAM_K_FINALIZE, the weigh
+ * and the resampling as SLAM_K_GRID.
+ *
+ * slam_mcl_weigh: moves the particles, then scores the filter's scan from every particle.
+ *   motion (nullable) [F][3]; noise (nullable, only together with motion) [F][P][3], made by the caller (no random
+ *   numbers are drawn on the device):  d = motion[f] + noise[f][p] componentwise (absent noise: motion[f]), then
+ *     x' = (x + cos(th)*dx) - sin(th)*dy;  y' = (y + sin(th)*dx) + cos(th)*dy;  th' = th + dth     (icp.py:185-190)
+ *   is written back to poses and the cost is taken from the NEW pose (motion NULL: poses is not written).
+ *   Cost: c = cos(th), s = sin(th) on the device; per beam t of ranges [F][n] exactly slam_grid_match's expression
+ *   with px, py the particle's position: used iff isfinite(rr) && ranges[t] < max_range (as float32);
+ *   lx = cos_t[t]*rr; ly = sin_t[t]*rr; x = c*lx + (-s)*ly + px*1.0; y = s*lx + c*ly + py*1.0; both through
+ *   int(scale*(v + off)); cost += field[gi][cell] if the cell is in bounds, else cap.  No used beam: cost 0.
+ *   A particle is dead if a component of its (new) pose is not finite, if its own cell index is NaN or beyond 2^20,
+ *   if its filter's grid_of_filter entry is outside [0, G), or if it arrives with acc == SLAM_MCL_DEAD: its
+ *   cost_out is -1 and its acc SLAM_MCL_DEAD (its pose is still moved).  A live one: acc = min(acc + cost, 2^30).
+ *   acc (nullable: nothing is accumulated), cost_out (nullable) int32 [F][P]; used_out (nullable) [F] the number of
+ *   used beams of the filter's scan (whatever its map entry).
+ *   field (nullable) int16 [G][xw][yw]: a field made by slam_grid_distance_field_dev at the SAME cap; it is used
+ *   and nothing is built (a static map costs no rebuild per scan).  NULL: the field of all G maps is rebuilt in the
+ *   context's workspace at the start of the call, as slam_grid_match does.  In the host form `field` is a host array.
+ *
+ * slam_mcl_resample: weights, estimate, effective sample size and systematic resampling.
+ *   amin = the smallest acc among filter f's live particles; a live particle has
+ *     w[p] = min(table[min((acc[p] - amin) >> shift, T - 1)], 2^20),  a dead one 0;
+ *   S = sum w, Q = sum w^2 (uint64);  ESS = (double)S * (double)S / (double)Q, 0 when S == 0.
+ *   est_out [F][4] float64 = (sum w x / S, sum w y / S, atan2(sum w sin th, sum w cos th), ESS), taken BEFORE
+ *   resampling over the particles of non-zero weight (summation order: the library's, fixed for a given P); the
+ *   first three are NaN when S == 0.  info_out [F][4] int32 = (best, live, resampled, amin): best the live particle
+ *   of lowest acc, ties to the lowest index, -1 when none is alive; amin 0 when none is alive.
+ *   Filter f resamples iff S > 0 and ESS < ess_frac * P (+inf: always, 0: never - a pure estimate).  Then
+ *     o = min((uint64)(u0[f] * (double)S), S - 1);  slot j has threshold t_j = o + j*S;  cum = inclusive prefix sums
+ *     of w;  ancestor a_j = the smallest i with cum[i] * P > t_j;  poses_out[j] = poses[a_j];  acc[j] = 0.
+ *   A filter that does not resample copies its poses, keeps acc and gets the identity in ancestors_out (nullable
+ *   int32 [F][P]).  poses_out [F][P][3] must not be poses.  u0 [F] must lie in [0, 1): the host form rejects
+ *   anything else, in the device form that is the caller's duty (a value outside is clamped into the range, NaN
+ *   counts as 0).  table uint32 [T]: the host form rejects an entry above 2^20, the device form clamps it.
+ *
+ * F >= 1, 1 <= P <= 2^20, F * P < 2^31, 1 <= n <= 4096, F * n < 2^31, 1 <= cap <= 32767, max_range > 0, noise only
+ * with motion, 1 <= T <= 65536, 0 <= shift <= 30, ess_frac >= 0 and not NaN, required pointers non-null; anything
+ * else is SLAM_ERR_INVALID, enqueues nothing and leaves the context as it was. */
+#define SLAM_MCL_DEAD 2147483647
+int slam_mcl_weigh(slam_ctx *ctx, slam_grid *grid, double *poses, const double *motion, const double *noise,
+                   const float *ranges, const double *cos_t, const double *sin_t, const int32_t *grid_of_filter, int F, int P,
+                   int n, float max_range, int cap, const int16_t *field, int32_t *acc, int32_t *cost_out, int32_t *used_out);
+int slam_mcl_weigh_dev(slam_ctx *ctx, slam_grid *grid, double *poses, const double *motion, const double *noise,
+                       const float *ranges, const double *cos_t, const double *sin_t, const int32_t *grid_of_filter, int F,
+                       int P, int n, float max_range, int cap, const int16_t *field, int32_t *acc, int32_t *cost_out,
+                       int32_t *used_out);
+int slam_mcl_resample(slam_ctx *ctx, const double *poses, int32_t *acc, const uint32_t *table, int T, int shift,
+                      const double *u0, double ess_frac, int F, int P, double *poses_out, int32_t *ancestors_out,
+                      double *est_out, int32_t *info_out);
+int slam_mcl_resample_dev(slam_ctx *ctx, const double *poses, int32_t *acc, const uint32_t *table, int T, int shift,
+                          const double *u0, double ess_frac, int F, int P, double *poses_out, int32_t *ancestors_out,
+                          double *est_out, int32_t *info_out);
 
 /* Replaces bresenham(start, end).path (W12m/bresenham.py:2-58), B lines at once.
  * starts, ends [B][2] int32.  lens_out [B] receives each path length; cells_out (may be
