@@ -52,6 +52,10 @@ _SIGS = {
     "slam_set_option": ([_vp, C.c_char_p, _d], _i),
     "slam_timing_enable": ([_vp, _i], _i),
     "slam_timing_read": ([_vp, _vp, _vp], _i),
+    "slam_plan_win": ([_i] * 16 + [_vp], _i),
+    "slam_plan_icp": ([_i] * 10 + [_vp], _i),
+    "slam_plan_win_phases": ([_vp, _vp, _i, _i, _i, _i, _i, _i, _vp], _i),
+    "slam_plan_query": ([C.c_char_p, _i, _i, _i, _i, C.POINTER(C.c_int64)], _i),
     "slam_scan_to_points": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
     "slam_scan_to_points_dev": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
     "slam_nn": ([_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp], _i),

@@ -118,13 +118,13 @@ __device__ __forceinline__ void finish_wave(const GridDev &g, uint32_t *pass, in
 // the smaller window of win_cells_for's two_per_cu).  Hits (one per ray) went
 // straight to the global counters, 80 % of a replay launch's memory-side atomics; the shared-map kernel now counts the hits
 // of sorted rays per end cell in the window, once the pass counts have left it, and sends ONE add per distinct end cell
-// (flush_hits; context option "win_lds_hits", by default in launches of more workgroups than the chip has CUs: launch_win).
+// (flush_hits; context option "win_lds_hits", by default in launches of more workgroups than the chip has CUs: plan_win, launch_shapes.h).
 // Every other form still adds its hits directly.  The window is the bounding box of the group's ray
 // origins and endpoints (clamped to the map) when that fits, else a sub-rectangle of it
 // around the first origin; cells of a ray outside the window fall back to direct global
 // atomics, so the result is exact for any window.
 //
-// Which kernel casts a launch (launch_win; first match wins):
+// Which kernel casts a launch (plan_win in launch_shapes.h decides, launch_win launches; first match wins):
 //   the map's only writer (live pmap, one group, one stream or a map per stream), one scan, one hit occupies, rows of a
 //   multiple of 16 cells of which one fits the window, and
 //       at most 384 beams, a re-do list      k_grid_update_owner8, then k_grid_update_owner_redo for what it left
@@ -138,17 +138,13 @@ __device__ __forceinline__ void finish_wave(const GridDev &g, uint32_t *pass, in
 // can exist), so nothing has to be written back or invalidated: a device-wide __threadfence()
 // here made every owner write the XCD's whole L2 back.
 __device__ __forceinline__ void owner_fence() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-constexpr int kWinCells = 36864;     // 16-bit cells: 72 KiB of LDS
-constexpr int kWinMaxGroup = 64;     // scans per workgroup
-constexpr int kSortBins = 128;        // ray-length histogram (4 cells per bin)
-constexpr int kMaxSortRays = 8192;    // rays per workgroup that can be length-sorted (u16 ids in LDS)
-static_assert(kMaxSortRays <= 0xffff, "flush_hits counts a sorted phase's hits in 16-bit window cells: one count per ray at most");
-constexpr int kRaysPerLane = 4;     // lanes per workgroup = rays / kRaysPerLane (rays are dealt to waves dynamically)
+// (the window's constants, LDS sizes and launch decision: launch_shapes.h)
 
 struct ScanConst {
     double px, py, c, s;   // ray origin (world) and heading cos / sin (replay source only)
     int pcx, pcy, cbad, pad;
 };
+static_assert(sizeof(ScanConst) == kScanConstBytes, "win_sc_bytes (launch_shapes.h) sizes the scan constants by kScanConstBytes");
 
 // Source of rays: scans of a replay (ranges + poses) ...
 struct ReplaySource {
@@ -384,7 +380,6 @@ __device__ __forceinline__ bool next_rays(int *next_ray, int nrays, const unsign
 // park (nullable; the sorted order itself, writable): a ray of the unchecked walk sends no hit; it leaves the window index of
 // its end cell (< 0xffff) in the slot of the order it was fetched from, and every other fetched slot is set to kNoHit, for
 // flush_hits behind the pass flush.  Rays of a wave that walks the checked way add their hits directly, as without park.
-constexpr unsigned kNoHit = 0xffffu;
 template <bool COVERS, class Src>
 __device__ __forceinline__ unsigned cast_rays(const GridDev &g, const Src &src, const ScanConst *sc, int l, int s0, int n,
                                               int nrays, int *next_ray, const unsigned short *order, unsigned *win, int wx0,
@@ -485,38 +480,7 @@ struct WinCtl {
     int phq[4];                      // phase of a quadrant's rays (-1: not this workgroup's)
     int seg[5];                      // boundaries of the phases in the sorted order
 };
-constexpr int kWinBoxInts = 160;     // ints of LDS set aside for the control block
 static_assert(sizeof(WinCtl) <= kWinBoxInts * 4 && alignof(WinCtl) <= 16, "the control block outgrew its LDS region");
-__host__ __device__ inline size_t win_sc_bytes(int group) { return ((size_t)group * sizeof(ScanConst) + 15) & ~(size_t)15; }
-__host__ __device__ inline int win_sort_cap(long rays) { return rays <= kMaxSortRays ? (int)((rays + 7) & ~7L) : 0; }   // 16-byte multiple
-__host__ __device__ inline size_t win_lds_bytes(int group, int sort_cap, int win_cells)
-{
-    return win_sc_bytes(group) + kWinBoxInts * 4 + 4 * kSortBins * 4 + (size_t)sort_cap * 2 + (size_t)win_cells * 2 + kLdsGuard;
-}
-// Window capacity (16-bit cells) of a launch: kWinCells, or, for small groups, whatever still lets two
-// workgroups share a CU's 160 KiB (a single 360-beam scan: 40 288 cells instead of 36 864 - the
-// bounding box of a scan of the 10 m x 8 m benchmark room, padded to 16-cell pieces, is 35-37 k cells)
-// two_per_cu (launch_win: a shared-map launch of sorted rays with more workgroups than the chip has CUs): the same carving even
-// where it comes out BELOW kWinCells, so that two workgroups are resident on a CU - one walks while the other sorts, zeroes or
-// flushes.  A group of 16 scans of 360 beams gets 33 216 cells (measured, profiles/win_two_per_cu.txt: one workgroup resident
-// per CU before, two now; the 32-trajectory launch 0.736 -> 0.705 ms).
-// The floor: a smaller window costs phases (more groups whose halves no longer fit), and below some size that must cost more
-// than the second resident gains.  Measured at the largest sorted groups of 360 beams, 20 and 22 scans (31 680 and 30 912 cells;
-// 24 x 360 is 8 640 rays, not sorted, and keeps its window anyway): 0.776 -> 0.688 and 0.723 -> 0.668 ms, MORE than group 16
-// gains, and with one resident a window of 30 720 cells cost 1 %, of 24 576 cells 8 %.  Nothing measured argues for a floor
-// above the smallest window the carving can ask for at all - 8 192 sorted rays in 64 scans: 29 632 cells -, so that is the floor;
-// it is also what keeps the window large enough for the 16-bit keys pass 1 parks in it.
-constexpr int kWinHalfSlack = 512;                                   // a little room for allocation granules
-constexpr int kWinTwoFloor = 29632;
-inline int win_cells_for(int group, int sort_cap, bool two_per_cu = false, long lds_per_cu = 160 * 1024)
-{
-    const long half = lds_per_cu / 2 - kWinHalfSlack;
-    long other = (long)win_lds_bytes(group, sort_cap, 0);
-    long cells = ((half - other) / 2) & ~15L;
-    if (cells > kWinCells) return (int)cells;
-    return two_per_cu && cells >= kWinTwoFloor ? (int)cells : kWinCells;
-}
-static_assert(kWinTwoFloor >= kMaxSortRays && kWinTwoFloor % 16 == 0, "pass 1 parks a 16-bit key per sorted ray in the window");
 
 // The LDS regions of a window workgroup, carved for the launch's group size (win_lds_bytes): a small group leaves room
 // for a second workgroup on the CU.
@@ -596,19 +560,7 @@ __device__ __forceinline__ void counting_sort(int *hist, const unsigned short *b
     __syncthreads();
 }
 
-// o[4] (x0, y0, x1, y1) clamped to the map, its first row moved down to a multiple of ymask + 1 cells (1: the window's
-// dwords line up with 8-byte pairs of counters, 3: with the quads of the fused sweep).  False: nothing of it is in the map.
-__device__ __forceinline__ bool clamp_box(const GridDev &g, int *o, int ymask)
-{
-    o[0] = max(o[0], 0); o[1] = max(o[1], 0); o[2] = min(o[2], g.xw - 1); o[3] = min(o[3], g.yw - 1);
-    o[1] &= ~ymask;
-    return o[0] <= o[2] && o[1] <= o[3];
-}
-__device__ __forceinline__ bool box_fits(const int *o, int win_cells)   // (rows are stored padded to an even height)
-{
-    return (long)(o[2] - o[0] + 1) * ((o[3] - o[1] + 2) & ~1) <= win_cells;
-}
-
+// (clamp_box, box_fits and the phase rule of k_grid_update_win: launch_shapes.h)
 // The window for the rays of a clamped box o (clamp_box, same ymask; any: its result), into w[5] (x0, y0, W, H, covers):
 // the box itself when it fits win_cells, else a sub-rectangle of it next to the first origin (the rays start there; clamped
 // into the box, i.e. in its corner for a quadrant) - the rest goes by direct atomics.  Nothing in the map: no window.
@@ -809,57 +761,23 @@ __global__ void __launch_bounds__(1024, 8) k_grid_update_win(GridDev g, Src src,
         bins[r] = casts ? (unsigned short)(lbin | (quad << 7) | ((i & 1) << 9)) : (unsigned short)0xffffu;
     });
     if (tid == 0) {
-        // A quadrant's rays lie between the group's origins and the edges of its bounding box on the quadrant's side (every ray
-        // lies in the box of its two ends): the box of quadrant q from the box of everything and the extremes of the origins
+        // the quadrants' boxes, and the parts (sets of quadrants) this workgroup casts, one phase each: launch_shapes.h
         const int *bb = ctl->bbox;
         if (bb[0] <= bb[2]) {
             int ox0 = INT_MAX, oy0 = INT_MAX, ox1 = INT_MIN, oy1 = INT_MIN;
             for (int k = 0; k < cnt; ++k) { ox0 = min(ox0, sc[k].pcx); ox1 = max(ox1, sc[k].pcx); oy0 = min(oy0, sc[k].pcy); oy1 = max(oy1, sc[k].pcy); }
-            for (int q = 0; q < 4; ++q) {
-                ctl->qbox[q][0] = (q & 1) ? max(ox0, bb[0]) : bb[0]; ctl->qbox[q][2] = (q & 1) ? bb[2] : min(ox1, bb[2]);
-                ctl->qbox[q][1] = (q & 2) ? max(oy0, bb[1]) : bb[1]; ctl->qbox[q][3] = (q & 2) ? bb[3] : min(oy1, bb[3]);
-            }
+            quadrant_boxes(bb, ox0, oy0, ox1, oy1, ctl->qbox);
         }
-        // union of the quadrants in mask -> clamped box; false: empty
-        auto box_of = [&](unsigned mask, int *o) -> bool {
-            o[0] = o[1] = INT_MAX; o[2] = o[3] = INT_MIN;
-            for (int q = 0; q < 4; ++q) {
-                const int *b = ctl->qbox[q];
-                if ((mask >> q & 1u) && b[0] <= b[2]) { o[0] = min(o[0], b[0]); o[1] = min(o[1], b[1]); o[2] = max(o[2], b[2]); o[3] = max(o[3], b[3]); }
-            }
-            return clamp_box(g, o, ymask);
-        };
-        auto fits = [&](unsigned mask) -> bool { int o[4]; return !box_of(mask, o) || box_fits(o, win_cells); };
-        // the parts (sets of quadrants) this workgroup casts, one phase each
+        auto fits = [&](unsigned mask) -> bool { int o[4]; return !box_of(ctl->qbox, mask, g.xw, g.yw, ymask, o) || box_fits(o, win_cells); };
         unsigned part[4] = {0u, 0u, 0u, 0u};
         int nph = 1, parity = 0;
-        if (split) {
-            // Two workgroups per group.  When the group's whole box fits one window, both take that window and share the rays evenly,
-            // by beam parity (neighbouring beams are about equally long; the direction halves of a scan taken off-centre differ up to
-            // 3 : 1 in cells to walk).  Else a workgroup per direction half, cut again at the origins' row if the half does not fit.
-            const unsigned mine = my_half ? 0xAu : 0x5u;             // quadrants right / left of the origins' column
-            if (fits(0xFu)) { part[0] = 0xFu; parity = 1; }
-            else if (fits(mine)) part[0] = mine;
-            else { part[0] = mine & 0x3u; part[1] = mine & 0xCu; nph = 2; }
-        } else {
-            // One workgroup: the same cuts, decided per direction half - a half that fits is one phase, one that does not is cut
-            // at the origins' row: two, three or four phases (a window carved for two workgroups per CU is a tenth smaller, and
-            // it is mostly ONE half of a group's box that then no longer fits).
-            if (!sorted || fits(0xFu)) part[0] = 0xFu;               // (the quadrants together: the box of everything)
-            else {
-                const bool left = fits(0x5u), right = fits(0xAu);
-                if (left && right) { part[0] = 0x5u; part[1] = 0xAu; nph = 2; }
-                else if (left) { part[0] = 0x5u; part[1] = 2u; part[2] = 8u; nph = 3; }
-                else if (right) { part[0] = 1u; part[1] = 4u; part[2] = 0xAu; nph = 3; }
-                else { part[0] = 1u; part[1] = 2u; part[2] = 4u; part[3] = 8u; nph = 4; }
-            }
-        }
+        pick_parts(split != 0, my_half, sorted, fits, part, nph, parity);
         for (int q = 0; q < 4; ++q) ctl->phq[q] = -1;
         for (int ph = 0; ph < nph; ++ph) {
             for (int q = 0; q < 4; ++q)
                 if (part[ph] >> q & 1u) ctl->phq[q] = ph;
             int o[4];
-            const bool any = box_of(part[ph], o);
+            const bool any = box_of(ctl->qbox, part[ph], g.xw, g.yw, ymask, o);
             fit_window(g, any, o, ymask, sc[0], win_cells, ctl->phw[ph]);
         }
         ctl->phases = nph; ctl->parity = parity;
@@ -959,7 +877,7 @@ __global__ void __launch_bounds__(1024) k_grid_update_own(GridDev g, Src src, in
     if (tid == 0) {
         int o[4] = {ctl->bbox[0], ctl->bbox[1], ctl->bbox[2], ctl->bbox[3]};
         int *w = ctl->phw[0];
-        const bool any = clamp_box(g, o, 0);
+        const bool any = clamp_box(g.xw, g.yw, o, 0);
         // Single-scan strip form (below): one scan, one hit occupies, and the window, widened to whole 64-byte pieces of the
         // counter rows (16 cells) and cut into S strips of at most Ws rows, holds every cell.
         if (any && fused && cnt == 1 && nrays < 32768 && g.hit_levels == 1 && (g.yw & 15) == 0) {
@@ -1099,8 +1017,7 @@ __global__ void __launch_bounds__(1024) k_grid_update_own(GridDev g, Src src, in
 // Rays that leave the map (mapping.py:41 drops their outside cells) are rare and take a plain
 // bounds-checked walk per strip.
 // ---------------------------------------------------------------------------------
-constexpr int kOwnerThreads = 512;   // 8 waves: two workgroups per CU at up to 128 VGPRs
-constexpr int kOwnerMaxRays = 2;                    // rays per lane (template parameter: 1 up to 512 beams)
+// (kOwnerThreads, kOwnerMaxRays: launch_shapes.h)
 
 struct OwnRay {
     int lx, h;            // current cell: map x, halfword index in the strip's window
@@ -1412,20 +1329,14 @@ __global__ void __launch_bounds__(kOwnerThreads) k_grid_update_owner_redo(GridDe
 //     pieces read and written back in place, scattered over 14 GB of maps - at 3.8 TB/s with the default cache
 //     policy and 4.75 TB/s non-temporal; a plain streaming copy reaches 4.5 TB/s (reads alone 6.3, writes alone 4.4).
 // ---------------------------------------------------------------------------------
-constexpr int kOwn8Bins = 128;
-constexpr int kOwn8BoxInts = 16;
+// (kOwn8Bins, kOwn8BoxInts, kOwn8Threads, kOwn8LdsBytes - half a CU's LDS - and own8_fixed_bytes: launch_shapes.h)
 constexpr int kOwn8MaxLen = 2048;
-constexpr int kOwn8Threads = 384;       // >= kOwn8Bins, a multiple of 64: six waves, one ray per lane up to 384 beams
 constexpr int kOwn8Batch = 8;           // window rows a wave keeps in flight in the sweep (4: 15 % slower, 12: 10 % slower; 512 threads: equal)
-// LDS of a workgroup: half a CU's 160 KiB.  (Three workgroups per CU with 52.5 KiB each - the benchmark scan's box just fit -
-// were measured no faster: the kernel goes at the pace of the memory system, not of the workgroups in flight.)
-constexpr int kOwn8LdsBytes = 81920;
 // cache policy of the sweep's counter and pmap traffic (buffer aux bits: 1 sc0, 2 nt, 16 sc1): every byte is read and
 // written once per launch, and non-temporal loads AND stores run the in-place read-modify-write 24 % faster than the
 // default policy (tools/ubench_rmw.hip: 4.75 against 3.83 TB/s on this access pattern; nt on the stores alone: no gain)
 constexpr int kOwn8Aux = 2;
 constexpr int kOwn8PerCU = 163840 / kOwn8LdsBytes;      // workgroups per CU the register budget is set for
-__host__ __device__ inline size_t own8_fixed_bytes(int threads) { return (size_t)(kOwn8BoxInts + kOwn8Bins) * 4 + (size_t)threads * 4; }
 
 typedef unsigned short u16x2_t __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
@@ -1699,7 +1610,7 @@ static ChipShape chip_shape()
     static std::mutex mu;
     static std::vector<std::pair<int, ChipShape>> seen;
     int dev = 0;
-    ChipShape c{256, 160 * 1024};                                    // MI355X, should a query fail
+    ChipShape c{kChipCus, (long)kLdsPerCu};                          // MI355X, should a query fail
     if (hipGetDevice(&dev) != hipSuccess) return c;
     std::lock_guard<std::mutex> lock(mu);
     for (const auto &e : seen)
@@ -1730,102 +1641,38 @@ template <class Src>
 static hipError_t launch_win(const GridDev &g, const Src &src, int L, int scans, int n, int group, const int32_t *got,
                              hipStream_t s, int split_pref = -1, int hits_pref = -1)
 {
-    const size_t lds_max = win_lds_bytes(kWinMaxGroup, kMaxSortRays, kWinCells);
-    for (const void *f : {reinterpret_cast<const void *>(&k_grid_update_win<Src>), reinterpret_cast<const void *>(&k_grid_update_own<Src>)}) {
-        hipError_t e = allow_dynamic_lds(f, (int)lds_max);
-        if (e != hipSuccess) return e;
-    }
-    int groups = (scans + group - 1) / group;
-    long rays = (long)group * n;
-    long want = (rays + kRaysPerLane - 1) / kRaysPerLane;
-    int threads = want >= kMaxWaves * kWave ? kMaxWaves * kWave : (int)(((want + kWave - 1) / kWave) * kWave);
-    if (threads < 128) threads = 128;
-    // one workgroup per map and no other writer: single stream (L == 1) or one map per stream
-    const int exclusive = g.pmap_live && groups == 1 && !got && (L == 1 || src.maps_are_private());
-    if (g.pmap_live && !exclusive && g.live_dirty) *g.live_dirty = true;
-    // the window takes most of a CU's LDS, so a CU runs one or two workgroups: the flush / the
-    // exclusive sweep (a streaming pass over the touched rectangle) need lanes for memory
-    // operations in flight even when there are few rays (measured on 10 000 single-scan groups:
-    // 2.88 ms with 128 threads, 2.05 ms with 512)
-    constexpr int kWinMinThreads = 512;
-    if (threads < kWinMinThreads) threads = kWinMinThreads;
-    const int sort_cap = win_sort_cap((long)group * n);
-    const int own_cells = win_cells_for(group, sort_cap);            // every launch but the chip-filling shared-map one below
-    // one scan per map, cast by the map's only writer, live pmap, the reference's one-hit-occupies rule
-    if (exclusive && group == 1 && scans == 1 && g.hit_levels == 1 && (g.yw & 15) == 0 && (((size_t)g.xw * g.yw) & 3) == 0 &&
-        g.yw <= own_cells && n <= kOwnerMaxRays * kOwnerThreads) {
-        const int win_cells = own_cells;
-        for (const void *f : {reinterpret_cast<const void *>(&k_grid_update_owner<Src, 1>), reinterpret_cast<const void *>(&k_grid_update_owner<Src, 2>),
-                              reinterpret_cast<const void *>(&k_grid_update_owner_redo<Src, 1>)}) {
-            hipError_t e = allow_dynamic_lds(f, (int)lds_max);
-            if (e != hipSuccess) return e;
-        }
-        const size_t lds = win_lds_bytes(1, sort_cap, win_cells);
-        // the plain case (all of a closed room's scans) goes through the byte-window kernel, three workgroups per CU;
-        // whatever it leaves on the re-do list is cast by the general kernel behind it
-        if (g.redo && n <= kOwn8Threads && n <= kOwnerThreads && g.xw <= 65535 && g.yw <= 65535 && (long)g.xw * g.yw < (1L << 29)) {
-            const int own8_lds = kOwn8LdsBytes + kLdsGuard, own8_win = (int)(kOwn8LdsBytes - own8_fixed_bytes(kOwn8Threads));
-            SLAM_LAUNCH((k_grid_update_owner8<Src, kOwn8Threads, kOwn8Batch>), dim3(1, L), dim3(kOwn8Threads), own8_lds, s,
-                        g, src, own8_win, g.redo);
-            SLAM_LAUNCH((k_grid_update_owner_redo<Src, 1>), dim3(std::min(L, 256)), dim3(kOwnerThreads), lds, s, g, src, sort_cap, win_cells, g.redo);
-            return hipGetLastError();
-        }
-        if (n <= kOwnerThreads) SLAM_LAUNCH((k_grid_update_owner<Src, 1>), dim3(1, L), dim3(kOwnerThreads), lds, s, g, src, sort_cap, win_cells);
-        else                    SLAM_LAUNCH((k_grid_update_owner<Src, 2>), dim3(1, L), dim3(kOwnerThreads), lds, s, g, src, sort_cap, win_cells);
-        return hipGetLastError();
-    }
-    // Two workgroups per group where the rays are sorted and the map is not the workgroup's own - a group whose box fits one
-    // window is shared by beam parity, else one workgroup takes the rays right of the origins' column and one those left of it
-    // (k_grid_update_win): a launch that cannot fill the chip on its own (a 1 000-scan replay is 125 groups on 256 CUs) runs
-    // 11 % shorter that way (0.088 -> 0.078 ms); when launches of several contexts share the chip the duplicated first pass
-    // costs 4 % of the throughput, so callers that overlap replays switch it off (context option "grid_split")
+    // the shape is plan_win's (launch_shapes.h); here: the attributes it asks for, and the kernel of its form
     const ChipShape chip = chip_shape();
-    const int split = (!exclusive && sort_cap > 0 && (split_pref > 0 || (split_pref < 0 && (long)groups * L <= (3L * chip.cus) / 4))) ? 1 : 0;
-    // A launch of at most one workgroup per CU asks for more than half a CU's LDS, so that no CU gets two of its workgroups
-    // while others stay empty: the dispatcher does not spread a small grid by itself (stamps, round 4: of 250 workgroups on
-    // 256 CUs the slowest took 1.8 x the mean with the same number of cells to walk - it shared its CU with another one).
-    const long wgs = (long)(split ? 2 * groups : groups) * L;
-    // A launch of more workgroups than the chip has CUs, on the other hand, wants TWO of them on every CU: one workgroup's phases
-    // run one after the other behind barriers, and only a second one can fill the CU while the first sorts, zeroes or flushes.
-    // At kWinCells a group of 8 to 16 scans of 360 beams asks for 82 - 89 KB, which is one per CU; such a launch gets the smaller
-    // window that leaves room for two (win_cells_for).  Sorted rays only: the unsorted form cannot cut a box that no longer fits.
-    const int win_cells = (!exclusive && sort_cap > 0 && wgs > chip.cus) ? win_cells_for(group, sort_cap, true, chip.lds_per_cu) : own_cells;
-    size_t lds = win_lds_bytes(group, sort_cap, win_cells);
-    // (only where a CU's LDS really is more than twice a workgroup's need, and the larger request is one the device grants)
-    const size_t half_cu = (size_t)(chip.lds_per_cu / 2);
-    if (split && wgs <= chip.cus && lds <= half_cu && half_cu + 512 <= (size_t)chip.lds_per_cu) lds = half_cu + 512;
-    if (lds > lds_max) {
-        const void *f = exclusive ? reinterpret_cast<const void *>(&k_grid_update_own<Src>) : reinterpret_cast<const void *>(&k_grid_update_win<Src>);
-        hipError_t e = allow_dynamic_lds(f, (int)lds);
+    WinRequest req{L, scans, n, group, got != nullptr, g.pmap_live != 0, src.maps_are_private(), g.hit_levels, g.xw, g.yw,
+                   g.redo != nullptr, split_pref, hits_pref, chip.cus, chip.lds_per_cu, kLdsGuard};
+    const WinShape p = plan_win(req);
+    const bool owner = p.form != kWinFormWin && p.form != kWinFormOwn;
+    const void *const standing[] = {reinterpret_cast<const void *>(&k_grid_update_win<Src>), reinterpret_cast<const void *>(&k_grid_update_own<Src>),
+                                    reinterpret_cast<const void *>(&k_grid_update_owner<Src, 1>), reinterpret_cast<const void *>(&k_grid_update_owner<Src, 2>),
+                                    reinterpret_cast<const void *>(&k_grid_update_owner_redo<Src, 1>)};
+    for (int k = 0; k < (owner ? 5 : 2); ++k) {
+        hipError_t e = allow_dynamic_lds(standing[k], (int)win_lds_max());
         if (e != hipSuccess) return e;
     }
-    // Hits of sorted rays counted in the window, one global add per distinct end cell (flush_hits; a window index must fit 16
-    // bits).  Left to the library: in launches of more workgroups than the chip has CUs, like the smaller window - there the
-    // launch lasts as long as its memory-side atomics take and the second resident hides flush_hits' two barriers (one-lane
-    // benchmark launch 0.705 -> 0.601 ms); a lone replay of 250 workgroups sends a thirtieth of the atomics, has its CU to
-    // itself, and was 5 % LONGER with the hits counted (profiles/win_lds_hits.txt).
-    const int lds_hits = sort_cap > 0 && win_cells < (int)kNoHit && (hits_pref > 0 || (hits_pref < 0 && wgs > chip.cus)) ? 1 : 0;
-    if (!exclusive) report_win_residency(reinterpret_cast<const void *>(&k_grid_update_win<Src>), threads, lds, win_cells, wgs);
-    // the map's only writer (then there is one group, and no `got`) finishes its cells itself, pmap included
-    if (exclusive) SLAM_LAUNCH((k_grid_update_own<Src>), dim3(groups, L), dim3(threads), lds, s, g, src, group, sort_cap, win_cells);
-    else SLAM_LAUNCH((k_grid_update_win<Src>), dim3(split ? 2 * groups : groups, L), dim3(threads), lds, s, g, src, group, got,
-                     sort_cap, win_cells, split, lds_hits);
-    return hipGetLastError();
-}
-
-// group == 0: automatic.  Measured on the 1k-scan replay (profiles/r01_*): the kernel is
-// fastest with about one workgroup per two CUs (8 scans each); more, smaller groups re-flush
-// the same map region more often, fewer leave CUs idle.
-static int pick_group(int group, long total_scans, int scans_per_traj, int n)
-{
-    int gmax = std::min(kWinMaxGroup, 65535 / std::max(n, 1));
-    if (gmax < 1) return 0;                                          // n too large for the packed counters
-    if (group <= 0) {
-        long want = (total_scans + 127) / 128;
-        group = (int)std::min<long>(std::max<long>(want, 1), 12);   // (5 000-scan replays, four overlapping: 12 -> 9.3, 16 -> 8.9 M scans/s)
+    if (p.live_dirty && g.live_dirty) *g.live_dirty = true;
+    if (p.lds_attr) {
+        hipError_t e = allow_dynamic_lds(standing[p.form == kWinFormOwn ? 1 : 0], (int)p.lds_attr);
+        if (e != hipSuccess) return e;
     }
-    group = std::min(std::min(group, gmax), std::max(scans_per_traj, 1));
-    return group;
+    const dim3 grid(p.grid_x, p.grid_y), block(p.threads);
+    switch (p.form) {
+    case kWinFormOwner8ThenRedo:
+        SLAM_LAUNCH((k_grid_update_owner8<Src, kOwn8Threads, kOwn8Batch>), grid, dim3(kOwn8Threads), p.own8_lds, s, g, src, p.own8_win, g.redo);
+        SLAM_LAUNCH((k_grid_update_owner_redo<Src, 1>), dim3(p.redo_grid), block, p.lds, s, g, src, p.sort_cap, p.win_cells, g.redo);
+        break;
+    case kWinFormOwner1: SLAM_LAUNCH((k_grid_update_owner<Src, 1>), grid, block, p.lds, s, g, src, p.sort_cap, p.win_cells); break;
+    case kWinFormOwner2: SLAM_LAUNCH((k_grid_update_owner<Src, 2>), grid, block, p.lds, s, g, src, p.sort_cap, p.win_cells); break;
+    case kWinFormOwn: SLAM_LAUNCH((k_grid_update_own<Src>), grid, block, p.lds, s, g, src, group, p.sort_cap, p.win_cells); break;
+    default:
+        report_win_residency(standing[0], p.threads, p.lds, p.win_cells, p.wgs);
+        SLAM_LAUNCH((k_grid_update_win<Src>), grid, block, p.lds, s, g, src, group, got, p.sort_cap, p.win_cells, p.split, p.lds_hits);
+    }
+    return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------------

@@ -279,11 +279,12 @@ __device__ __forceinline__ Rigid2 kabsch_from_sums_wave(double cax, double cay, 
 // farther than U >= the final minimum, marked blocks are scanned in index order with strict
 // '<', and the result (index and distance) is bit-identical to the exhaustive scan, ties
 // included.
-constexpr int kNNBlock = 16;
-constexpr int kNNStride = kNNBlock + 1;   // LDS slots per block: the pad spreads the blocks over the banks
+// (kNNBlock, kNNStride and the sizes of the LDS image: launch_shapes.h)
 static_assert(kNNBlock == 16, "tslot() assumes 16-point blocks");
 
 struct Box { double x0, x1, y0, y1; };
+static_assert(sizeof(Box) == kBoxBytes && sizeof(double2) == kDouble2Bytes && sizeof(float2) == kFloat2Bytes,
+              "launch_shapes.h sizes the LDS regions by these");
 
 __device__ __forceinline__ int tslot(int j) { return j + (j >> 4); }   // LDS slot of target point j
 
@@ -443,7 +444,6 @@ constexpr int kPolarMaxFirst = 16;            // ... and in a first iteration wh
 constexpr int kPolarMaxListed = 48;           // where a window may be this wide after the re-guess
 constexpr int kPolarProbe = 8;                // beams either side of a useless guess that are tried for a better one
 constexpr bool kOnePass = true;               // iterations after the first: centroids and centred products in one reduction (k_icp)
-constexpr int kPolarTail = 4;                 // NaN points behind the beam-window search's copy of the target
 
 template <typename T> struct StoreSlack { static constexpr float ang = 2e-7f; };              // float64 points
 template <> struct StoreSlack<float> { static constexpr float ang = 1e-6f; };                // 2 x 2^-24 sqrt(2), doubled
@@ -782,16 +782,7 @@ __device__ __forceinline__ void nn_listed(const double2 *__restrict__ tarP, int 
     }
 }
 
-// LDS image of the target: float64 (x, y) pairs padded with NaN points to a whole number
-// of blocks (NaN never wins a comparison), then one bounding box per block.
-__host__ __device__ inline int nn_blocks(int n_tar) { return (n_tar + kNNBlock - 1) / kNNBlock; }
-__host__ __device__ inline int nn_boxes_padded(int n_tar) { return (nn_blocks(n_tar) + 3) / 4 * 4; }   // multiple of 4
-__host__ __device__ inline int nn_boxes4(int n_tar) { return nn_boxes_padded(n_tar) / 4; }
-__host__ __device__ inline size_t nn_lds_bytes(int n_tar)
-{
-    return (size_t)nn_blocks(n_tar) * kNNStride * sizeof(double2) +
-           (size_t)(nn_boxes_padded(n_tar) + nn_boxes4(n_tar)) * sizeof(Box);
-}
+// (the LDS image of the target - nn_blocks, nn_boxes_padded, nn_boxes4, nn_lds_bytes: launch_shapes.h)
 
 // A cloud read either from a point buffer or straight from a raw scan (laserToNumpy fused:
 // slam_ekf.py:115-123, x = cos(angle_i) * r with inf -> 30 m, rounded to the buffer type T).
@@ -1258,13 +1249,7 @@ __device__ __forceinline__ void store_result(const IcpArgs &a, int b, const Rigi
 // ---------------------------------------------------------------------------------
 // k_icp: ICP.process (icp.py:38-88), one workgroup per pair, QPT queries per lane.
 // ---------------------------------------------------------------------------------
-constexpr int kIcpExtraLds = 32;               // flag words: source set collapsed, count of listed queries, re-do
-__host__ __device__ inline size_t icp_polar_bytes(int n_tar) { return (size_t)(n_tar + kPolarTail) * sizeof(double2); }
-// cross-wave stage of the reductions ([2][nwaves][8] doubles: seven values in the one-pass iteration; 128 B a wave, so
-// what follows stays 16-byte aligned) and of the collapsed-set test ([2][nwaves][4]: matched point of the wave's first
-// query, "this wave saw another"), two alternating buffers each
-constexpr int kRedStride = 8;
-__host__ __device__ inline size_t icp_red_bytes(int nwaves) { return (size_t)2 * nwaves * (kRedStride + 4) * sizeof(double) + 8 * sizeof(double); }   // + what a pair's first wave hands the others (kLead)
+// (the regions of its LDS - kIcpExtraLds, icp_polar_bytes, kRedStride, icp_red_bytes - and its launch shape: launch_shapes.h)
 
 // EXACT: the second pass over a pair in which the first saw a best undercut its predecessor by less than a class of
 // equal distances (see "Best"): the same solve with the reference's own nearest-neighbour loop (nn_exact).
@@ -1281,7 +1266,7 @@ __device__ __forceinline__ bool icp_pair(const IcpArgs &a, const int b, char *sm
     Box *boxes = reinterpret_cast<Box *>(smem + (size_t)nblocks * kNNStride * sizeof(double2));  // [padded to x4]
     Box *boxes4 = boxes + nn_boxes_padded(a.n_tar);                                              // one per 4 blocks
     // the target again, not padded, for the beam-window search (nn_polar): carved when the target is a scan and
-    // both copies fit the CU's LDS (launch_icp_t); without it the padded copy serves every purpose
+    // both copies fit the CU's LDS (plan_icp, launch_shapes.h); without it the padded copy serves every purpose
     const bool has_p = a.polar_copy != 0;
     const size_t p_bytes = has_p ? icp_polar_bytes(a.n_tar) : 0;
     double2 *tarP = has_p ? reinterpret_cast<double2 *>(smem + nn_lds_bytes(a.n_tar)) : nullptr;   // [n_tar + kPolarTail]
@@ -1527,22 +1512,7 @@ __device__ __forceinline__ bool icp_pair(const IcpArgs &a, const int b, char *sm
 // resident on a CU.  The box search (1.3 % of the queries) reads the unpadded image.  Sums are added in another order than
 // in the workgroup shape; everything else is the shared pieces above.
 // ---------------------------------------------------------------------------------
-constexpr int kWaveQpt = 6;
-constexpr int kWaveRound = 4 * 1024;          // pairs resident at once in this shape: 4 per SIMD, 1 024 SIMDs
-__host__ __device__ inline int icp_wave_points(int n_tar)
-{
-    const int whole = nn_blocks(n_tar) * kNNBlock, tail = n_tar + kPolarTail;
-    return whole > tail ? whole : tail;
-}
-// (f32: the float32 image of the later iterations lies over the first iteration's list, which is dead by then - 360 beams:
-// 8 768 B with a list of 96, 9 792 B with the image of 368 points over it, 16 pairs a CU either way; side by side they
-// would be 11 712 B and 13)
-__host__ __device__ inline size_t icp_wave_lds_bytes(int n_tar, int cap, bool f32)
-{
-    const size_t list = (size_t)cap * (sizeof(double2) + sizeof(int)), image = f32 ? (size_t)icp_wave_points(n_tar) * sizeof(float2) : 0;
-    return (size_t)icp_wave_points(n_tar) * sizeof(double2) + (size_t)(nn_boxes_padded(n_tar) + nn_boxes4(n_tar)) * sizeof(Box) +
-           (list > image ? list : image);
-}
+// (kWaveQpt, kWaveRound, icp_wave_points, icp_wave_lds_bytes: launch_shapes.h)
 
 // The distance of a match in this shape (match_distance for the lanes that are active here): a float64 square root
 // without the range scaling.  What the compiler makes of sqrt(double) is
@@ -1797,97 +1767,39 @@ __global__ void __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(4)))
     }
 }
 
-static inline int icp_block(int n_src, int qpt)
+// one workgroup per pair, as plan_icp (launch_shapes.h) shaped it
+template <typename T, int Q, int U>
+static hipError_t launch_icp_workgroup(const IcpArgs &a, const IcpShape &p, hipStream_t s)
 {
-    int per = (n_src + qpt - 1) / qpt;
-    int blk = ((per + kWave - 1) / kWave) * kWave;
-    return blk < kWave ? kWave : blk;
+    if (p.raise_attr) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_icp<T, Q, U>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+        if (e != hipSuccess) return e;
+    }
+    SLAM_LAUNCH((k_icp<T, Q, U>), dim3(a.B), dim3(p.block), p.lds, s, a);
+    return hipGetLastError();
 }
 
 template <typename T>
 static hipError_t launch_icp_t(const IcpArgs &a_in, hipStream_t s)
 {
     IcpArgs a = a_in;
-    int qpt = (a.n_src + 1023) / 1024;
-    // Queries per lane for batches (a handful of pairs cannot fill the chip anyway: one query per lane
-    // gives the lowest latency, 0.13 instead of 0.15 ms for the drop-in ICP.process call).  Fewer waves per
-    // pair repeat the per-iteration fixed work less often: three queries per lane are fastest when
-    // the chip is full (10 000 pairs: 0.510 against 0.536 ms; four overlapping 999-pair replays: 6.2
-    // against 6.0 M scans/s); a launch that cannot fill the chip on its own runs shorter with two
-    // (999 pairs alone: 0.121 against 0.140 ms).  a.qpt_pref: 0 = by batch size, else 1..3.  "Full" goes by the waves the
-    // batch would have at two queries per lane: from 7 500 on - 2 500 pairs of 360 beams, 834 pairs of 1 080 (999 such pairs
-    // alone: 0.338 ms with three queries per lane against 0.364 with two) - the chip holds them in more than one round.
-    const long waves_at_two = (long)a.B * ((a.n_src + 127) / 128);
-    // a.batch_invariant (slam_node_replay_dev): the shape must not follow the batch size, so that a trajectory's transforms
-    // are the same bits whether it runs alone or among thousands - two queries per lane for every B, never the automatic
-    // one-wave shape; an explicit "icp_qpt" / "icp_one_wave" = 1 still holds, for every B alike.
-    int pref = a.qpt_pref > 0 ? a.qpt_pref : (a.batch_invariant ? 2 : waves_at_two >= 7500 ? 3 : 2);
-    if ((a.B > 64 || a.batch_invariant) && qpt < pref && a.n_src > 64 * pref) qpt = pref;
-    if (qpt > 4) qpt = 8;                     // the shapes that exist: 1, 2, 3, 4, 8 queries per lane
-    // One wave per pair with six queries per lane (k_icp<T>): no barriers, the per-iteration fixed work paid once per
-    // pair.  For launches that fill the chip several times over on their own, where instructions are time: the preference
-    // resolves to the full-chip shape (given or automatic) and the batch is at least FOUR rounds of this shape's own
-    // workgroups - 4 resident per SIMD on 1 024 SIMDs, 16 384 pairs.  A launch of a round or two ends on its longest pairs,
-    // and a pair is slower alone in this shape (six queries in sequence: 0.28 against 0.20 ms for 999 pairs when it was
-    // first tried, in the era of lone launches), so every smaller launch - the particle batches of 10 000 and their chunks
-    // among them, which were not measured in this shape - keeps the shape it had.  Measured on the benchmark's launches of
-    // 31 968 pairs (7.8 rounds), two contexts: 17.46 against 15.50 M scans/s, a step of 1.831 instead of 2.062 ms
-    // (profiles/icp_one_wave.txt).  Automatic only for scans (the box search of a point cloud would read the unpadded image
-    // throughout) and while 16 pairs fit a CU's LDS.  a.one_wave: -1 = by this rule, 0 = never, 1 = wherever a pair fits
-    // (context option "icp_one_wave").
-    {
-        const int cap = (a.ranges && a.team_mode == 0) ? ((a.n_src + 3) / 4 + 15) / 16 * 16 : 0;   // the list: a quarter of the queries (a fifth is listed on the benchmark scans)
-        // a.f32_filter: -1 / 1 = the float32 pre-filter of the later iterations' beam windows (scans only: a point cloud has no
-        // windows), 0 = the float64 scan alone (context option "icp_f32_filter"; no result depends on it)
-        const bool f32 = a.f32_filter != 0 && a.ranges;
-        const size_t lds = icp_wave_lds_bytes(a.n_tar, cap, f32) + kLdsGuard;
-        const bool fits = a.n_src <= kWave * kWaveQpt && lds <= 64 * 1024;
-        const bool full = !a.batch_invariant && pref == 3 && a.B >= 4 * kWaveRound && a.n_src > kWave * 3 && a.ranges && lds - kLdsGuard <= 10 * 1024;   // (the shipped layout's size: the debug build's guard does not choose the shape)
-        if (fits && (a.one_wave == 1 || (a.one_wave < 0 && full))) {
-            a.team_cap = cap;
-            if (f32) SLAM_LAUNCH((k_icp<T, true>), dim3(a.B), dim3(kWave), lds, s, a);
-            else SLAM_LAUNCH((k_icp<T, false>), dim3(a.B), dim3(kWave), lds, s, a);
-            return hipGetLastError();
+    IcpRequest req{a.B, a.n_src, a.n_tar, a.ranges != nullptr, a.qpt_pref, a.batch_invariant, a.one_wave, a.f32_filter, a.team_mode, kLdsGuard};
+    const IcpShape p = plan_icp(req);
+    a.polar_copy = p.polar_copy;
+    a.team_cap = p.team_cap;
+    switch (p.form) {
+    case kIcpFormWaveF32: SLAM_LAUNCH((k_icp<T, true>), dim3(a.B), dim3(p.block), p.lds, s, a); return hipGetLastError();
+    case kIcpFormWaveF64: SLAM_LAUNCH((k_icp<T, false>), dim3(a.B), dim3(p.block), p.lds, s, a); return hipGetLastError();
+    case kIcpFormWorkgroup:
+        switch (p.qpt) {                      // the instances that exist (plan_icp gives no other)
+        case 1: return launch_icp_workgroup<T, 1, 4>(a, p, s);
+        case 2: return launch_icp_workgroup<T, 2, 4>(a, p, s);
+        case 3: return launch_icp_workgroup<T, 3, 4>(a, p, s);
+        case 4: return launch_icp_workgroup<T, 4, 2>(a, p, s);
+        case 8: return launch_icp_workgroup<T, 8, 2>(a, p, s);
         }
     }
-    const int block = icp_block(a.n_src, qpt);
-    const size_t lds_base = nn_lds_bytes(a.n_tar) + icp_red_bytes(block / kWave) + kIcpExtraLds + kLdsGuard;
-    // second, unpadded copy of the target for the beam-window search: only for scans, and only while both copies fit
-    // (up to 4 557 beams; larger scans, up to the documented 8 192, and point clouds go by the box search alone)
-    a.polar_copy = (a.ranges && lds_base + icp_polar_bytes(a.n_tar) <= 160 * 1024) ? 1 : 0;
-    size_t lds = lds_base + (a.polar_copy ? icp_polar_bytes(a.n_tar) : 0);
-    // the list of first-iteration queries without a usable window (nn_listed): room for half of the queries - on the
-    // benchmark scans a fifth of them is listed - as far as the CU's LDS goes; a full list leaves the rest to the box search
-    a.team_cap = 0;
-    if (a.polar_copy && a.team_mode == 0) {
-        long cap = ((a.n_src + 1) / 2 + 15) / 16 * 16;
-        const long room = ((long)160 * 1024 - (long)lds) / (long)(sizeof(double2) + sizeof(int));
-        cap = cap < room ? cap : room / 16 * 16;
-        a.team_cap = cap > 0 ? (int)cap : 0;
-    }
-    lds += (size_t)a.team_cap * (sizeof(double2) + sizeof(int));
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    dim3 grid(a.B);
-#define SLAM_ICP_CASE(Q, U)                                                                                     \
-    {                                                                                                           \
-        if (lds > 64 * 1024) {                                                                                  \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_icp<T, Q, U>),                         \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);          \
-            if (e != hipSuccess) return e;                                                                      \
-        }                                                                                                       \
-        SLAM_LAUNCH((k_icp<T, Q, U>), grid, dim3(block), lds, s, a);                                            \
-    }
-    // (candidates per trip of the beam-window search: see nn_polar.  Four
-    // per trip are as fast as two when the chip is full and faster when it is not - four overlapping 999-pair
-    // replays 8.5 -> 8.9 M scans/s - since the candidates come from the unpadded copy.)
-    if (qpt <= 1) SLAM_ICP_CASE(1, 4)
-    else if (qpt <= 2) SLAM_ICP_CASE(2, 4)
-    else if (qpt <= 3) SLAM_ICP_CASE(3, 4)
-    else if (qpt <= 4) SLAM_ICP_CASE(4, 2)
-    else if (qpt <= 8) SLAM_ICP_CASE(8, 2)
-    else return hipErrorInvalidValue;   // n_src > 8192
-#undef SLAM_ICP_CASE
-    return hipGetLastError();
+    return hipErrorInvalidValue;
 }
 
 hipError_t launch_icp(const IcpArgs &a, int dtype, hipStream_t s)
@@ -1933,8 +1845,8 @@ static hipError_t launch_nn_t(const void *src, const void *tar, int B, int n_src
                               int32_t *idx, hipStream_t s)
 {
     size_t lds = nn_lds_bytes(n_tar);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    if (lds > 64 * 1024) {
+    if (lds > kLdsPerCu) return hipErrorInvalidValue;
+    if (lds > kLdsDefault) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_nn<T>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;

@@ -788,6 +788,85 @@ int slam_timing_read(slam_ctx *c, double ms_out[SLAM_K_COUNT], int64_t launches_
     return SLAM_OK;
 }
 
+/* ---- introspection of the launch decisions (launch_shapes.h): no context, no device call ---- */
+
+static int sat_int(long v) { return v > INT_MAX ? INT_MAX : (int)v; }
+
+int slam_plan_win(int L, int scans, int n, int group, int has_got, int pmap_live, int maps_are_private, int hit_levels, int xw,
+                  int yw, int has_redo, int split_pref, int hits_pref, int cus, int lds_per_cu, int guard, slam_win_plan *out)
+{
+    if (!out) return fail(SLAM_ERR_INVALID, "slam_plan_win: out is null");
+    if (L < 1 || scans < 1 || n < 1 || group < 1 || xw < 1 || yw < 1 || cus < 1 || lds_per_cu < 1)
+        return fail(SLAM_ERR_INVALID, "slam_plan_win: L, scans, n, group, xw, yw, cus and lds_per_cu must be positive");
+    WinRequest r{L, scans, n, group, has_got != 0, pmap_live != 0, maps_are_private != 0, hit_levels, xw, yw, has_redo != 0,
+                 split_pref, hits_pref, cus, (long)lds_per_cu, guard < 0 ? kLdsGuard : guard};
+    const WinShape p = plan_win(r);
+    *out = slam_win_plan{p.form, p.grid_x, p.grid_y, p.threads, (int)p.lds, (int)p.lds_attr, p.exclusive, p.sort_cap, p.win_cells,
+                         p.split, p.lds_hits, p.two_per_cu, sat_int(p.wgs), p.own8_lds, p.own8_win, p.redo_grid, p.live_dirty ? 1 : 0};
+    return SLAM_OK;
+}
+
+int slam_plan_icp(int B, int n_src, int n_tar, int is_scan, int qpt_pref, int batch_invariant, int one_wave, int f32_filter,
+                  int team_mode, int guard, slam_icp_plan *out)
+{
+    if (!out) return fail(SLAM_ERR_INVALID, "slam_plan_icp: out is null");
+    if (B < 1 || n_src < 1 || n_tar < 1) return fail(SLAM_ERR_INVALID, "slam_plan_icp: B, n_src and n_tar must be positive");
+    IcpRequest r{B, n_src, n_tar, is_scan != 0, qpt_pref, batch_invariant, one_wave, f32_filter, team_mode, guard < 0 ? kLdsGuard : guard};
+    const IcpShape p = plan_icp(r);
+    *out = slam_icp_plan{p.form, p.pref, p.preferred, p.qpt, p.unroll, p.block, sat_int((long)p.lds), p.polar_copy, p.team_cap,
+                         p.cap_wanted, p.raise_attr ? 1 : 0, sat_int((long)p.nn_bytes)};
+    return SLAM_OK;
+}
+
+int slam_plan_win_phases(const int32_t bbox[4], const int32_t origins[4], int xw, int yw, int ymask, int win_cells, int sorted,
+                         int half, slam_win_phases *out)
+{
+    if (!bbox || !origins || !out) return fail(SLAM_ERR_INVALID, "slam_plan_win_phases: null pointer");
+    if (xw < 1 || yw < 1 || half < -1 || half > 1) return fail(SLAM_ERR_INVALID, "slam_plan_win_phases: xw, yw must be positive, half -1, 0 or 1");
+    int qbox[4][4];
+    for (auto &q : qbox) { q[0] = q[1] = INT_MAX; q[2] = q[3] = INT_MIN; }
+    if (bbox[0] <= bbox[2]) quadrant_boxes(bbox, origins[0], origins[1], origins[2], origins[3], qbox);
+    auto fits = [&](unsigned mask) -> bool { int o[4]; return !box_of(qbox, mask, xw, yw, ymask, o) || box_fits(o, win_cells); };
+    unsigned part[4] = {0u, 0u, 0u, 0u};
+    slam_win_phases p{};
+    p.nph = 1;
+    pick_parts(half >= 0, half, sorted != 0, fits, part, p.nph, p.parity);
+    for (int ph = 0; ph < p.nph; ++ph) {
+        p.part[ph] = (int)part[ph];
+        p.any[ph] = box_of(qbox, part[ph], xw, yw, ymask, p.box[ph]) ? 1 : 0;
+        p.fits[ph] = fits(part[ph]) ? 1 : 0;
+    }
+    *out = p;
+    return SLAM_OK;
+}
+
+int slam_plan_query(const char *name, int a, int b, int c, int guard, int64_t *out)
+{
+    if (!name || !out) return fail(SLAM_ERR_INVALID, "slam_plan_query: null pointer");
+    const int g = guard < 0 ? kLdsGuard : guard;
+    struct Entry { const char *name; int64_t value; };
+    const Entry table[] = {
+        {"kLdsGuard", kLdsGuard}, {"kLdsPerCu", (int64_t)kLdsPerCu}, {"kLdsDefault", (int64_t)kLdsDefault}, {"kChipCus", kChipCus},
+        {"kWave", kWave}, {"kMaxWaves", kMaxWaves}, {"kScanConstBytes", (int64_t)kScanConstBytes}, {"kDouble2Bytes", (int64_t)kDouble2Bytes},
+        {"kBoxBytes", (int64_t)kBoxBytes}, {"kListSlotBytes", (int64_t)kListSlotBytes},
+        {"kWinCells", kWinCells}, {"kWinMaxGroup", kWinMaxGroup}, {"kSortBins", kSortBins}, {"kMaxSortRays", kMaxSortRays},
+        {"kRaysPerLane", kRaysPerLane}, {"kWinBoxInts", kWinBoxInts}, {"kWinHalfSlack", kWinHalfSlack}, {"kWinTwoFloor", kWinTwoFloor},
+        {"kWinMinThreads", kWinMinThreads}, {"kOwnerThreads", kOwnerThreads}, {"kOwnerMaxRays", kOwnerMaxRays}, {"kOwn8Threads", kOwn8Threads},
+        {"kOwn8LdsBytes", kOwn8LdsBytes},
+        {"kNNBlock", kNNBlock}, {"kNNStride", kNNStride}, {"kPolarTail", kPolarTail}, {"kRedStride", kRedStride},
+        {"kIcpExtraLds", kIcpExtraLds}, {"kWaveQpt", kWaveQpt}, {"kWaveRound", kWaveRound}, {"kIcpFullChipWaves", kIcpFullChipWaves},
+        {"win_sc_bytes", (int64_t)win_sc_bytes(a)}, {"win_sort_cap", win_sort_cap(a)}, {"win_lds_bytes", (int64_t)win_lds_bytes(a, b, c, g)},
+        {"win_cells_for", win_cells_for(a, b, c != 0, (long)kLdsPerCu, g)}, {"win_lds_max", (int64_t)win_lds_max(g)},
+        {"own8_fixed_bytes", (int64_t)own8_fixed_bytes(a)},
+        {"nn_blocks", nn_blocks(a)}, {"nn_boxes_padded", nn_boxes_padded(a)}, {"nn_boxes4", nn_boxes4(a)}, {"nn_lds_bytes", (int64_t)nn_lds_bytes(a)},
+        {"icp_polar_bytes", (int64_t)icp_polar_bytes(a)}, {"icp_red_bytes", (int64_t)icp_red_bytes(a)},
+        {"icp_wave_lds_bytes", (int64_t)icp_wave_lds_bytes(a, b, c != 0)}, {"icp_block", b > 0 ? icp_block(a, b) : 0},
+    };
+    for (const Entry &e : table)
+        if (!strcmp(e.name, name)) { *out = e.value; return SLAM_OK; }
+    return fail(SLAM_ERR_INVALID, "slam_plan_query: unknown name");
+}
+
 #if defined(SLAM_STAMPS) || defined(SLAM_STAMPS_ICP)
 /* diagnostic builds only: the 256-byte status block (word 0: status bits; from word 8: phase counters) */
 int slam_debug_read(slam_ctx *c, void *out256, int clear)

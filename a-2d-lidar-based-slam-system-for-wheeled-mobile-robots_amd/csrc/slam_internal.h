@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include "slam_hip.h"
+#include "launch_shapes.h"
 
 #include <hip/hip_ext.h>
 
@@ -43,22 +44,11 @@ inline bool launch_events(hipEvent_t *e0, hipEvent_t *e1)
 // needs more LDS than any before it raises it.
 hipError_t allow_dynamic_lds(const void *kernel, int bytes);
 
-constexpr int kWave = 64;
-constexpr int kMaxWaves = 16;            // 1024-thread workgroups
+// (kWave, kMaxWaves and kLdsGuard, the guard bytes of the LDS-guard debug build: launch_shapes.h)
 constexpr int kMaxRayCells = 1 << 20;    // longest ray the grid kernels will walk (cells)
 
 enum : int { kStatusNaN = 1, kStatusOverflow = 2, kStatusGuard = 4 };
 
-// Debug build (-DSLAM_LDS_GUARD, `make guard`): every kernel with dynamic LDS gets kLdsGuard
-// extra bytes behind its last region, fills them with a pattern and checks them before it
-// exits; a changed word raises kStatusGuard (SLAM_ERR_HIP from slam_check_status).  GPU
-// AddressSanitizer is not available on the target pool; this catches the overrun class that
-// matters here (a region sized too small, e.g. a window row count rounded the wrong way).
-#ifdef SLAM_LDS_GUARD
-constexpr int kLdsGuard = 512;
-#else
-constexpr int kLdsGuard = 0;
-#endif
 #if defined(__HIPCC__)
 __device__ __forceinline__ void lds_guard_fill(char *p)
 {

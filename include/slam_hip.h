@@ -147,6 +147,69 @@ int slam_set_option(slam_ctx *ctx, const char *name, double value);
 int slam_timing_enable(slam_ctx *ctx, int on);
 int slam_timing_read(slam_ctx *ctx, double ms_out[SLAM_K_COUNT], int64_t launches_out[SLAM_K_COUNT]);
 
+/* Introspection of launch decisions: what the library WOULD launch for a request, decided by the same functions its
+ * launchers call.  No context and no device call: each works on a machine without a GPU.  Stable in meaning, not a
+ * promise that shapes stay: a later version may decide differently for the same request.  cus / lds_per_cu: the chip the
+ * launch is planned for (MI355X: 256 CUs, 163 840 bytes).  guard: guard bytes behind every dynamic LDS region, 0 in the
+ * shipped build, 512 in the LDS-guard debug build; negative = those of the build that was loaded.
+ *
+ * slam_plan_win: the LDS-window ray cast of L streams of `scans` scans of n beams in groups of `group` scans per workgroup
+ * into a map of xw x yw cells.  has_got: the caller names every stream's map; pmap_live, maps_are_private, hit_levels,
+ * has_redo: the grid's state (a live pmap, a map per stream, 1 or 3 hit levels, a re-do list); split_pref / hits_pref: the
+ * context options "grid_split" / "win_lds_hits" (-1: the library's choice). */
+enum { SLAM_WIN_FORM_WIN = 0, SLAM_WIN_FORM_OWN = 1, SLAM_WIN_FORM_OWNER1 = 2, SLAM_WIN_FORM_OWNER2 = 3,
+       SLAM_WIN_FORM_OWNER8_THEN_REDO = 4 };
+typedef struct slam_win_plan {
+    int form;                 /* SLAM_WIN_FORM_*: shared-map kernel, the map's only writer, its single-scan forms */
+    int grid_x, grid_y, threads;
+    int lds;                  /* dynamic LDS of the launch, bytes */
+    int lds_attr;             /* LDS size the launch must be allowed by attribute first; 0: the standing allowance does */
+    int exclusive, sort_cap, win_cells, split, lds_hits;   /* kernel arguments */
+    int two_per_cu;           /* the window was carved so that two workgroups fit a CU */
+    int wgs;                  /* workgroups (0 for the single-scan owner forms) */
+    int own8_lds, own8_win;   /* OWNER8_THEN_REDO: dynamic LDS and window bytes of the byte-window launch ... */
+    int redo_grid;            /* ... and workgroups of the re-do launch behind it (threads, lds, sort_cap, win_cells are its) */
+    int live_dirty;           /* the launch leaves the live pmap behind the counters */
+} slam_win_plan;
+int slam_plan_win(int L, int scans, int n, int group, int has_got, int pmap_live, int maps_are_private, int hit_levels, int xw,
+                  int yw, int has_redo, int split_pref, int hits_pref, int cus, int lds_per_cu, int guard, slam_win_plan *out);
+/* slam_plan_win_phases: how one workgroup of the shared-map kernel cuts its group's rays into phases, each with the window
+ * to itself.  bbox: x0, y0, x1, y1 (cells) of everything the group's rays can touch; origins: min x, min y, max x, max y of
+ * the scans' origin cells; ymask: 1 where the map's rows hold an even number of cells (the window's rows then start on an
+ * even cell), else 0; win_cells: the window's capacity (slam_win_plan.win_cells); sorted: the rays are sorted
+ * (slam_win_plan.sort_cap > 0); half: -1 = one workgroup per group, 0 / 1 = the workgroup of a split launch that takes the
+ * rays left / right of the origins' column.  Per phase: the quadrants it casts (bit q: end cell right of the origin for
+ * q & 1, above it for q & 2), their box clamped to the map (any = 0: nothing of it is in the map; the box is then
+ * meaningless), and whether the box fits the window (0: a sub-rectangle gets the window, the rest goes by global atomics). */
+typedef struct slam_win_phases {
+    int nph, parity;          /* phases; 1: two workgroups share one window's rays by beam parity */
+    int part[4];
+    int box[4][4];            /* x0, y0, x1, y1 */
+    int any[4], fits[4];
+} slam_win_phases;
+int slam_plan_win_phases(const int32_t bbox[4], const int32_t origins[4], int xw, int yw, int ymask, int win_cells, int sorted,
+                         int half, slam_win_phases *out);
+/* slam_plan_icp: the scan matcher for B pairs of n_src against n_tar points.  is_scan: the clouds are raw scans (the replay
+ * and particle entry points), not point buffers; qpt_pref, one_wave, f32_filter, team_mode: the context options "icp_qpt",
+ * "icp_one_wave", "icp_f32_filter", "icp_team"; batch_invariant: the node replay's shape that does not follow B. */
+enum { SLAM_ICP_FORM_INVALID = 0, SLAM_ICP_FORM_WAVE_F32 = 1, SLAM_ICP_FORM_WAVE_F64 = 2, SLAM_ICP_FORM_WORKGROUP = 3 };
+typedef struct slam_icp_plan {
+    int form;                 /* SLAM_ICP_FORM_*: no launch (more LDS than a CU has), one wave per pair, one workgroup per pair */
+    int pref, preferred;      /* preferred queries per lane; whether they replaced the size-derived ones */
+    int qpt, unroll, block;   /* queries per lane, candidates per trip of the beam-window search, threads */
+    int lds;                  /* dynamic LDS of the launch, bytes */
+    int polar_copy, team_cap, cap_wanted;   /* unpadded copy of the target in LDS; slots of the first-iteration list, and before the LDS cut it */
+    int raise_attr;           /* lds is more than a kernel gets by default */
+    int nn_bytes;             /* bytes of the padded target image and its boxes */
+} slam_icp_plan;
+int slam_plan_icp(int B, int n_src, int n_tar, int is_scan, int qpt_pref, int batch_invariant, int one_wave, int f32_filter,
+                  int team_mode, int guard, slam_icp_plan *out);
+/* slam_plan_query: a constant or an LDS size function of the two planners by its name in csrc/launch_shapes.h, e.g.
+ * "kWinCells", "win_lds_bytes" (a, b, c = group, sort_cap, win_cells), "win_cells_for" (group, sort_cap, two_per_cu),
+ * "win_sort_cap" (rays), "nn_lds_bytes" / "icp_polar_bytes" (n_tar), "icp_red_bytes" (waves), "icp_block" (n_src, qpt);
+ * arguments a function does not take are ignored.  SLAM_ERR_INVALID for a name it does not know. */
+int slam_plan_query(const char *name, int a, int b, int c, int guard, int64_t *out);
+
 /* ---- ICP ------------------------------------------------------------------------ */
 /* Replaces ICP.laserToNumpy (W7/icp.py:182-195) and SLAM_EKF.laserToNumpy
  * (W12m/slam_ekf.py:115-123; clip_inf != 0 applies its inf -> 30 m rule, :119).

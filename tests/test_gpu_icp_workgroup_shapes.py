@@ -3,8 +3,8 @@ at the edges of their launch decision, against the C oracle: iteration counts eq
 two device runs against each other within 1e-12 or bit for bit.  Every case sets icp_one_wave = 0.
 
 Every size at which the launch changes - another instance, more than 64 KiB of LDS, a shorter or no first-iteration list,
-no unpadded copy of the target - comes from tests/icp_shapes.py, which restates launch_icp_t and is checked against the
-source by tests/test_icp_launch_shapes_cpu.py."""
+no unpadded copy of the target - comes from tests/icp_shapes.py, which asks the library's own planner (slam_plan_icp); tests/test_icp_launch_shapes_cpu.py
+asserts the sizes."""
 import math
 
 import numpy as np

@@ -31,13 +31,12 @@ compared a NaN matches any NaN: sign and payload of an invalid operation's resul
 processor's choice."""
 import ctypes as C
 import math
-import os
-import re
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, PKG, pkg
+import icp_shapes
+from conftest import pkg
 from oracle import c_oracle as co
 from oracle import oracle_np as on
 
@@ -505,15 +504,6 @@ def test_kabsch_exact_rotations_and_reflections(slam):
 
 # ---- 4. nearest neighbour, the operator ------------------------------------------------------------
 
-def nn_lds_bytes(n_tar):
-    """nn_lds_bytes of icp_kernels.hip: blocks of kNNBlock = 16 points in kNNStride = 17 slots of a
-    double2 (16 bytes), a Box (4 doubles = 32 bytes) per block padded to a multiple of 4, and a Box
-    per 4 blocks."""
-    blocks = (n_tar + 15) // 16
-    padded = (blocks + 3) // 4 * 4
-    return blocks * 17 * 16 + (padded + padded // 4) * 32
-
-
 NN_SMALL, NN_RAISED = 3344, 3345
 
 
@@ -523,16 +513,14 @@ def test_nn_lds_threshold_arithmetic():
       n_tar = 3 344: 209 blocks -> 209 * 272 = 56 848, boxes padded to 212 -> (212 + 53) * 32 = 8 480: 65 328 <= 65 536;
       n_tar = 3 345: 210 blocks -> 210 * 272 = 57 120, boxes 212 -> 8 480: 65 600 > 65 536;
       n_tar = 8 192: 512 blocks -> 139 264 + (512 + 128) * 32 = 159 744 <= 160 KiB, the kernel's bound.
-    Passes without a GPU; the constants are read back from the source."""
+    Passes without a GPU; the sizes are the library's own (slam_plan_query)."""
+    nn_lds_bytes = icp_shapes.nn_lds_bytes
     assert nn_lds_bytes(NN_SMALL) == 56848 + 8480 == 65328 <= 64 * 1024
     assert nn_lds_bytes(NN_RAISED) == 57120 + 8480 == 65600 > 64 * 1024
     assert all(nn_lds_bytes(n) <= 64 * 1024 for n in range(1, NN_SMALL + 1))
     assert all(nn_lds_bytes(n) > 64 * 1024 for n in range(NN_RAISED, 8193))
     assert nn_lds_bytes(8191) == nn_lds_bytes(8192) == 159744 <= 160 * 1024
-    text = open(os.path.join(ROOT, PKG, "csrc", "icp_kernels.hip")).read()
-    assert re.search(r"constexpr int kNNBlock = 16;", text) and re.search(r"constexpr int kNNStride = kNNBlock \+ 1;", text)
-    assert re.search(r"nn_blocks\(n_tar\) \* kNNStride \* sizeof\(double2\) \+\s*\(size_t\)\(nn_boxes_padded\(n_tar\) \+ nn_boxes4\(n_tar\)\) \* sizeof\(Box\)", text)
-    assert "if (lds > 64 * 1024) {" in text and "if (lds > 160 * 1024) return hipErrorInvalidValue;" in text
+    assert icp_shapes.LDS_DEFAULT == 64 * 1024 and icp_shapes.LDS_LIMIT == 160 * 1024      # launch_nn_t's two limits
 
 
 def nn_clouds(rng, n_src, n_tar):

@@ -1,102 +1,7 @@
-"""The scan matcher's workgroup launch decision (launch_icp_t, csrc/icp_kernels.hip) without a GPU: tests/icp_shapes.py
-restates it; here its constants and deciding expressions are read back from the source text, so that an edit to the
-kernel fails these tests instead of silently moving the edges the GPU tests sit on, and every size at which a decision
-changes is asserted over n = 1..8192."""
-import os
-import re
-
-import pytest
-
+"""The scan matcher's launch decision (plan_icp, csrc/launch_shapes.h) without a GPU, as the library answers for it
+(tests/icp_shapes.py: slam_plan_icp, slam_plan_query): every size at which a decision of the workgroup shapes changes is
+asserted over n = 1..8192, and the rule that chooses the one-wave shape at its edges."""
 import icp_shapes as sh
-from conftest import PKG, ROOT
-
-CSRC = os.path.join(ROOT, PKG, "csrc")
-
-
-def source_text():
-    """The scan matcher's source and the header with the constants every kernel file shares (kWave)."""
-    return open(os.path.join(CSRC, "icp_kernels.hip")).read() + open(os.path.join(CSRC, "slam_internal.h")).read()
-
-
-def constants(text):
-    """name -> value of the integer constants the launch decision rests on, as the source spells them."""
-    def one(pattern):
-        m = re.findall(pattern, text)
-        assert len(m) == 1, (pattern, m)
-        return int(m[0])
-    return {"kNNBlock": one(r"constexpr int kNNBlock = (\d+);"),
-            "kNNStride - kNNBlock": one(r"constexpr int kNNStride = kNNBlock \+ (\d+);"),
-            "kRedStride": one(r"constexpr int kRedStride = (\d+);"),
-            "kPolarTail": one(r"constexpr int kPolarTail = (\d+);"),
-            "kIcpExtraLds": one(r"constexpr int kIcpExtraLds = (\d+);"),
-            "kWave": one(r"constexpr int kWave = (\d+);")}
-
-
-# the deciding expressions, each as the source writes it (whitespace free); sh.launch() is their restatement
-EXPRESSIONS = [
-    # sizes of the LDS regions
-    r"return \(size_t\)nn_blocks\(n_tar\) \* kNNStride \* sizeof\(double2\) \+\s*\(size_t\)\(nn_boxes_padded\(n_tar\) \+ nn_boxes4\(n_tar\)\) \* sizeof\(Box\);",
-    r"int nn_blocks\(int n_tar\) \{ return \(n_tar \+ kNNBlock - 1\) / kNNBlock; \}",
-    r"int nn_boxes_padded\(int n_tar\) \{ return \(nn_blocks\(n_tar\) \+ 3\) / 4 \* 4; \}",
-    r"int nn_boxes4\(int n_tar\) \{ return nn_boxes_padded\(n_tar\) / 4; \}",
-    r"size_t icp_polar_bytes\(int n_tar\) \{ return \(size_t\)\(n_tar \+ kPolarTail\) \* sizeof\(double2\); \}",
-    r"size_t icp_red_bytes\(int nwaves\) \{ return \(size_t\)2 \* nwaves \* \(kRedStride \+ 4\) \* sizeof\(double\) \+ 8 \* sizeof\(double\); \}",
-    # the block
-    r"static inline int icp_block\(int n_src, int qpt\)\s*\{\s*int per = \(n_src \+ qpt - 1\) / qpt;\s*int blk = \(\(per \+ kWave - 1\) / kWave\) \* kWave;\s*return blk < kWave \? kWave : blk;\s*\}",
-    # queries per lane: by size, the preference, the shapes that exist
-    r"int qpt = \(a\.n_src \+ 1023\) / 1024;",
-    r"const long waves_at_two = \(long\)a\.B \* \(\(a\.n_src \+ 127\) / 128\);",
-    r"int pref = a\.qpt_pref > 0 \? a\.qpt_pref : \(a\.batch_invariant \? 2 : waves_at_two >= 7500 \? 3 : 2\);",
-    r"if \(\(a\.B > 64 \|\| a\.batch_invariant\) && qpt < pref && a\.n_src > 64 \* pref\) qpt = pref;",
-    r"if \(qpt > 4\) qpt = 8;",
-    # LDS: the base, the copy, the list, the two limits
-    r"const int block = icp_block\(a\.n_src, qpt\);",
-    r"const size_t lds_base = nn_lds_bytes\(a\.n_tar\) \+ icp_red_bytes\(block / kWave\) \+ kIcpExtraLds \+ kLdsGuard;",
-    r"a\.polar_copy = \(a\.ranges && lds_base \+ icp_polar_bytes\(a\.n_tar\) <= 160 \* 1024\) \? 1 : 0;",
-    r"size_t lds = lds_base \+ \(a\.polar_copy \? icp_polar_bytes\(a\.n_tar\) : 0\);",
-    r"a\.team_cap = 0;\s*if \(a\.polar_copy && a\.team_mode == 0\) \{\s*long cap = \(\(a\.n_src \+ 1\) / 2 \+ 15\) / 16 \* 16;\s*"
-    r"const long room = \(\(long\)160 \* 1024 - \(long\)lds\) / \(long\)\(sizeof\(double2\) \+ sizeof\(int\)\);\s*"
-    r"cap = cap < room \? cap : room / 16 \* 16;\s*a\.team_cap = cap > 0 \? \(int\)cap : 0;\s*\}\s*"
-    r"lds \+= \(size_t\)a\.team_cap \* \(sizeof\(double2\) \+ sizeof\(int\)\);\s*"
-    r"if \(lds > 160 \* 1024\) return hipErrorInvalidValue;",
-    r"if \(lds > 64 \* 1024\) \{\s*\\\s*hipError_t e = hipFuncSetAttribute\(reinterpret_cast<const void \*>\(&k_icp<T, Q, U>\),",
-    # the five instances
-    r"if \(qpt <= 1\) SLAM_ICP_CASE\(1, 4\)\s*else if \(qpt <= 2\) SLAM_ICP_CASE\(2, 4\)\s*else if \(qpt <= 3\) SLAM_ICP_CASE\(3, 4\)\s*"
-    r"else if \(qpt <= 4\) SLAM_ICP_CASE\(4, 2\)\s*else if \(qpt <= 8\) SLAM_ICP_CASE\(8, 2\)",
-    # what the regions hold: a Box is four doubles, the flag words behind the hand-over are kIcpExtraLds bytes
-    r"struct Box \{\s*double x0, x1, y0, y1;\s*\};",
-    r"unsigned \*geo = reinterpret_cast<unsigned \*>\(lead \+ 8\);",
-    r"double2 \*qlist = reinterpret_cast<double2 \*>\(geo \+ 8\);",
-]
-
-
-def check_source(text):
-    """The restatement's constants are the source's, and every expression it restates is in the source once."""
-    got = constants(text)
-    want = {"kNNBlock": sh.NN_BLOCK, "kNNStride - kNNBlock": sh.NN_STRIDE - sh.NN_BLOCK, "kRedStride": sh.RED_STRIDE,
-            "kPolarTail": sh.POLAR_TAIL, "kIcpExtraLds": sh.EXTRA_LDS, "kWave": sh.WAVE}
-    assert got == want, (got, want)
-    for e in EXPRESSIONS:
-        assert len(re.findall(e, text)) == 1, e
-    assert sh.LDS_LIMIT == 160 * 1024 and sh.LDS_DEFAULT == 64 * 1024 and sh.FULL_CHIP_WAVES == 7500
-    assert sh.EXTRA_LDS == 8 * 4 and sh.BOX == 4 * 8 and sh.LIST_SLOT == 16 + 4
-
-
-def test_constants_and_expressions_are_those_of_the_source():
-    check_source(source_text())
-
-
-@pytest.mark.parametrize("edit", [("constexpr int kRedStride = 8;", "constexpr int kRedStride = 16;"),
-                                  ("constexpr int kPolarTail = 4;", "constexpr int kPolarTail = 8;"),
-                                  ("<= 160 * 1024) ? 1 : 0;", "<= 128 * 1024) ? 1 : 0;"),
-                                  ("if (qpt > 4) qpt = 8;", "if (qpt > 5) qpt = 8;"),
-                                  ("a.n_src > 64 * pref) qpt = pref;", "a.n_src >= 64 * pref) qpt = pref;")])
-def test_an_edit_to_the_source_is_noticed(edit):
-    """The check above on a copy of the source text with one constant or comparison changed: it must fail."""
-    text = source_text()
-    assert text.count(edit[0]) == 1
-    with pytest.raises(AssertionError):
-        check_source(text.replace(edit[0], edit[1]))
 
 
 def test_lds_regions_at_the_sizes_worked_out_by_hand():
@@ -182,3 +87,50 @@ def test_the_preference_rules_truth_table():
     assert sh.queries_per_lane(1, 360, batch_invariant=True) == sh.queries_per_lane(5000, 360, batch_invariant=True) == 2
     # the preference never lowers a size-derived shape
     assert all(sh.queries_per_lane(65, n, icp_qpt=q) >= sh.queries_per_lane(1, n) for n in range(1, 8193, 7) for q in (0, 1, 2, 3))
+
+
+def test_one_wave_where_a_pair_fits():
+    """icp_one_wave = 1: one wave per pair exactly while n_src <= 384 (six queries a lane) and the pair's LDS is at most the
+    64 KiB a kernel gets by default; else the workgroup shape, as with icp_one_wave = 0."""
+    for scans in (True, False):
+        at = {n: sh.plan_icp(2, 384, n, scans, one_wave=1) for n in range(1, sh.N_MAX + 1)}
+        last = sh.first(lambda n: not at[n].form.startswith("Wave")) - 1
+        assert 2000 < last < sh.N_MAX and at[last].lds <= sh.LDS_DEFAULT and (at[last].qpt, at[last].block) == (sh.WAVE_QPT, sh.WAVE)
+        assert sh.query("icp_wave_lds_bytes", last + 1, at[last].team_cap, scans) > sh.LDS_DEFAULT
+        assert at[last].lds == sh.query("icp_wave_lds_bytes", last, at[last].team_cap, scans)
+        for n_tar in (1, 360, last, last + 1):
+            wave = [sh.plan_icp(2, n_src, n_tar, scans, one_wave=1).form.startswith("Wave") for n_src in (1, 383, 384, 385, 1000)]
+            assert wave == [n_tar <= last] * 3 + [False, False], (scans, n_tar, wave)
+            off = sh.plan_icp(2, 385, n_tar, scans, one_wave=1)
+            assert off == sh.plan_icp(2, 385, n_tar, scans, one_wave=0) and off.form == "Workgroup"
+    assert sh.plan_icp(2, 360, 360, True, one_wave=1, guard=512).lds == sh.plan_icp(2, 360, 360, True, one_wave=1).lds + 512 == 9792 + 512
+
+
+def test_one_wave_by_itself_only_in_launches_that_fill_the_chip_four_times():
+    """icp_one_wave = -1: scans, B >= 16 384, n_src > 192, the preference three queries per lane, not batch-invariant, a
+    pair's LDS at most 10 KiB; the guard build's 512 bytes do not change the choice."""
+    auto = lambda B, n, scans=True, **kw: sh.plan_icp(B, n, n, scans, **kw).form
+    assert auto(4 * sh.WAVE_ROUND - 1, 360) == "Workgroup" and auto(4 * sh.WAVE_ROUND, 360) == "WaveF32"
+    assert 4 * sh.WAVE_ROUND == 16384
+    assert auto(16384, 192) == "Workgroup" and auto(16384, 193) == "WaveF32"
+    assert auto(16384, 360, icp_qpt=3) == "WaveF32" and auto(16384, 360, icp_qpt=2) == auto(16384, 360, icp_qpt=1) == "Workgroup"
+    assert auto(16384, 360, batch_invariant=True) == "Workgroup" and auto(16384, 360, batch_invariant=True, one_wave=1) == "WaveF32"
+    assert auto(16384, 360, scans=False) == "Workgroup" and auto(16384, 360, one_wave=0) == "Workgroup"
+    assert sh.plan_icp(16384, 384, 360, True).form == "WaveF32" and sh.plan_icp(16384, 385, 360, True).form == "Workgroup"
+    # 10 KiB: the shipped layout's size decides, with and without the guard
+    for guard in (0, 512):
+        forms = {n: sh.plan_icp(16384, 384, n, True, guard=guard).form for n in range(300, 500)}
+        last = sh.first(lambda n: forms[n] == "Workgroup", lo=300, hi=499) - 1
+        assert sh.plan_icp(16384, 384, last, True).lds <= 10 * 1024 < sh.plan_icp(16384, 384, last + 1, True, one_wave=1).lds
+        assert guard == 0 or forms == keep
+        keep = forms
+    assert all(sh.plan_icp(B, n, n, True, guard=512).form == sh.plan_icp(B, n, n, True).form
+               for B in (16383, 16384, 40000) for n in range(1, 500, 7))
+
+
+def test_the_float32_filter_is_for_scans():
+    """icp_f32_filter -1 / 1: the float32 form, for scans only; 0: the float64 form.  A point cloud has no beam windows."""
+    form = lambda scans, f: sh.plan_icp(2, 360, 360, scans, one_wave=1, f32_filter=f).form
+    assert [form(True, f) for f in (-1, 0, 1)] == ["WaveF32", "WaveF64", "WaveF32"]
+    assert [form(False, f) for f in (-1, 0, 1)] == ["WaveF64"] * 3
+    assert sh.plan_icp(2, 360, 360, True, one_wave=1, f32_filter=0).lds == 8768     # a list of 96; 9 792 with the image over it

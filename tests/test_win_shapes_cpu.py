@@ -1,7 +1,7 @@
-"""tests/win_shapes.py against the source text of csrc/grid_kernels.hip, the window's capacity over every group size,
-and the phases of the benchmark trajectory under the old and the new capacity.  No GPU."""
+"""The window ray cast's launch decision and phase rule as the library answers for them (tests/win_shapes.py: slam_plan_win,
+slam_plan_win_phases, slam_plan_query): the kernel form of a launch, the window's capacity over every group size, and
+the phases of the benchmark trajectory under the old and the new capacity.  No GPU."""
 import importlib
-import re
 from collections import Counter
 
 import pytest
@@ -11,37 +11,74 @@ import win_shapes as ws
 BEAMS = (90, 360, 720, 1080)
 
 
-@pytest.fixture(scope="module")
-def text():
-    with open(ws.SOURCE) as f:
-        return f.read()
+@pytest.mark.parametrize("yw", [400, 401])
+@pytest.mark.parametrize("redo", [False, True])
+def test_forms_of_the_maps_only_writer(yw, redo):
+    """One scan into a map that is the workgroup's own (live pmap, a map per stream, one hit occupies): the byte-window
+    kernel with its re-do launch up to 384 beams where the grid has a re-do list, one ray per lane up to 512 beams, two up
+    to 1 024, the general owner kernel beyond - and for rows that are no multiple of 16 cells (401)."""
+    want = {384: "Owner8ThenRedo" if redo else "Owner1", 385: "Owner1", 512: "Owner1", 513: "Owner2", 1024: "Owner2", 1025: "Own"}
+    for n, form in want.items():
+        p = ws.plan_win(1, n, 1, L=32, pmap_live=True, private=True, hit_levels=1, xw=400, yw=yw, redo=redo)
+        assert p.form == (form if yw == 400 else "Own"), (n, p)
+        assert p.exclusive and not p.live_dirty and not p.split and not p.lds_hits
+        if p.form == "Own":
+            assert (p.grid_x, p.grid_y, p.threads) == (1, 32, ws.MIN_THREADS)
+        else:
+            assert (p.grid_x, p.grid_y, p.threads) == (1, 32, ws.query("kOwnerThreads")) and p.lds_attr == 0
+            assert p.win_cells == ws.win_cells_for(1, p.sort_cap) >= yw and p.lds == ws.win_lds_bytes(1, p.sort_cap, p.win_cells)
+        if p.form == "Owner8ThenRedo":
+            assert p.redo_grid == 32 and p.own8_lds == ws.query("kOwn8LdsBytes") == ws.LDS_PER_CU // 2
+            assert p.own8_win == p.own8_lds - ws.query("own8_fixed_bytes", ws.query("kOwn8Threads"))
+            assert ws.plan_win(1, n, 1, L=1000, pmap_live=True, private=True, xw=400, yw=yw, redo=True).redo_grid == 256
+    # three hit levels, or several scans to the workgroup: the general owner kernel
+    assert ws.plan_win(1, 360, 1, pmap_live=True, hit_levels=3, redo=redo).form == "Own"
+    assert ws.plan_win(4, 360, 4, pmap_live=True, redo=redo).form == "Own"
 
 
-def test_constants_are_the_sources(text):
-    for name, value in ws.source_constants(text).items():
-        assert getattr(ws, name) == value, name
-    assert "double px, py, c, s;" in text and "int pcx, pcy, cbad, pad;" in text       # ScanConst: 48 bytes
+def test_launches_that_are_not_exclusive():
+    """Three hit levels alone do not make a launch shared; a map named by the caller, or several streams into one map, do:
+    the shared-map kernel, and the live pmap is left behind."""
+    own = dict(pmap_live=True, xw=400, yw=400)
+    assert ws.plan_win(1, 360, 1, L=8, private=True, hit_levels=2, **own).form == "Own"
+    for p in (ws.plan_win(1, 360, 1, L=8, private=True, hit_levels=2, got=True, **own), ws.plan_win(1, 360, 1, got=True, **own),
+              ws.plan_win(1, 360, 1, L=2, private=False, **own), ws.plan_win(2, 360, 1, **own)):
+        assert p.form == "Win" and not p.exclusive and p.live_dirty
+    assert ws.plan_win(1, 360, 1, L=2, private=True, **own).exclusive and ws.plan_win(1, 360, 1, L=1, **own).exclusive
+    assert not ws.plan_win(1, 360, 1, L=2).live_dirty                  # (no live pmap: nothing to leave behind)
 
 
-def test_rules_are_the_sources(text):
-    """The lines the restatement stands for, as they are written."""
-    flat = re.sub(r"\s+", " ", text)
-    for line in (
-        "return win_sc_bytes(group) + kWinBoxInts * 4 + 4 * kSortBins * 4 + (size_t)sort_cap * 2 + (size_t)win_cells * 2 + kLdsGuard;",
-        "return rays <= kMaxSortRays ? (int)((rays + 7) & ~7L) : 0;",
-        "const long half = lds_per_cu / 2 - kWinHalfSlack;",
-        "long cells = ((half - other) / 2) & ~15L;",
-        "if (cells > kWinCells) return (int)cells;",
-        "return two_per_cu && cells >= kWinTwoFloor ? (int)cells : kWinCells;",
-        "(!exclusive && sort_cap > 0 && wgs > chip.cus) ? win_cells_for(group, sort_cap, true, chip.lds_per_cu) : own_cells;",
-        "const long wgs = (long)(split ? 2 * groups : groups) * L;",
-        "if (left && right) { part[0] = 0x5u; part[1] = 0xAu; nph = 2; }",
-        "else if (left) { part[0] = 0x5u; part[1] = 2u; part[2] = 8u; nph = 3; }",
-        "else if (right) { part[0] = 1u; part[1] = 4u; part[2] = 0xAu; nph = 3; }",
-        "else { part[0] = 1u; part[1] = 2u; part[2] = 4u; part[3] = 8u; nph = 4; }",
-        "return (long)(o[2] - o[0] + 1) * ((o[3] - o[1] + 2) & ~1) <= win_cells;",
-    ):
-        assert line in flat, line
+def test_threads_hits_and_the_spreading_request():
+    """Threads: a lane per four rays in whole waves, 512 at least (one scan of 90 beams), 1 024 at most (from 4 096 rays).
+    Hits in the window: by default exactly in sorted launches of more workgroups than CUs; "win_lds_hits" 1 in every
+    sorted launch, 0 in none.  The spreading request, half a CU's LDS and 512 bytes, exactly in split launches of at most
+    a workgroup per CU whose own need is at most half a CU's."""
+    assert ws.plan_win(1, 90, 1).threads == ws.plan_win(8, 256, 8).threads == 512 and ws.plan_win(9, 228, 9).threads == 576
+    assert ws.plan_win(16, 256, 16).threads == ws.plan_win(64, 1000, 64).threads == 1024
+    half = ws.LDS_PER_CU // 2
+    seen = Counter()
+    for n in BEAMS:
+        for group in (1, 2, 7, 8, 16, 22, 24, 64):
+            if group * n > 65535:
+                continue
+            for scans, L in ((group, 1), (40 * group, 1), (192 * group, 1), (193 * group, 1), (256 * group, 1), (257 * group, 1), (999, 32)):
+                for split_pref in (-1, 0, 1):
+                    p = ws.plan_win(scans, n, group, L=L, split_pref=split_pref)
+                    groups = -(-scans // group)
+                    assert p.split == int(p.sort_cap > 0 and (split_pref > 0 or (split_pref < 0 and groups * L <= 3 * ws.CUS // 4)))
+                    assert p.wgs == (2 if p.split else 1) * groups * L == p.grid_x * p.grid_y
+                    assert p.lds_hits == int(p.sort_cap > 0 and p.wgs > ws.CUS)
+                    for pref in (0, 1):
+                        q = ws.plan_win(scans, n, group, L=L, split_pref=split_pref, hits_pref=pref)
+                        assert q.lds_hits == int(pref and p.sort_cap > 0) and q._replace(lds_hits=p.lds_hits) == p
+                    need = ws.win_lds_bytes(group, p.sort_cap, p.win_cells)
+                    spread = bool(p.split) and p.wgs <= ws.CUS and need <= half
+                    assert p.lds == (half + 512 if spread else need) and p.lds_attr == (p.lds if p.lds > ws.query("win_lds_max") else 0)
+                    seen[spread, bool(p.lds_hits), bool(p.lds_attr)] += 1
+    assert all(seen[k] for k in ((True, False, False), (False, True, False), (False, False, False))) and len(seen) == 3, seen
+    # on this chip no launch needs more than the standing allowance; the spreading request of a chip with more LDS does
+    big = ws.plan_win(40 * 8, 360, 8, lds_per_cu=256 * 1024)
+    assert big.split and big.lds == big.lds_attr == 128 * 1024 + 512 > ws.query("win_lds_max")
 
 
 def test_benchmark_shape():

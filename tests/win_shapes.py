@@ -1,74 +1,77 @@
-"""Plain-Python restatement of how the LDS-window ray cast (launch_win / k_grid_update_win in csrc/grid_kernels.hip)
-sizes its window and cuts a group's rays into phases.  Test infrastructure only: tests/test_win_shapes_cpu.py checks
-it against the source text and sweeps it, tests/test_gpu_window_two_per_cu.py takes its box sizes from it.
+"""How the LDS-window ray cast sizes its window and shapes a shared-map launch, asked of the library itself (plan_win and
+the size functions of csrc/launch_shapes.h, through slam_plan_win / slam_plan_query of the C ABI: no GPU needed), and
+how k_grid_update_win cuts a group's rays into phases.  Test infrastructure only: tests/test_win_shapes_cpu.py sweeps it,
+tests/test_gpu_window_two_per_cu.py takes its box sizes from it.
 
-What is restated:
   win_lds_bytes    dynamic LDS of a window workgroup: scan constants, control block, histogram, sorted order, window
   win_cells_for    the window's capacity in 16-bit cells: kWinCells; more for small groups (two workgroups still share
                    a CU); and, for a launch that wants two per CU (two_per_cu), the same carving even where it comes
                    out below kWinCells, down to kWinTwoFloor
-  launch           which of the two a shared-map launch gets: two per CU only for sorted rays (sort_cap > 0) in a
-                   launch of more workgroups than the chip has CUs
+  launch           the shape of a shared-map launch: two per CU only for sorted rays (sort_cap > 0) in a launch of more
+                   workgroups than the chip has CUs
+  plan_win         every field of slam_plan_win's answer, for any request
   plan             the phases of one workgroup: the box of everything if it fits, else per direction half (left /
                    right of the origins' column) one phase if the half fits and two (cut at the origins' row) if not
 """
 from __future__ import annotations
 
-import os
-import re
+import ctypes as C
+import importlib
 from collections import namedtuple
 
 import numpy as np
 
-SOURCE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
-                      "a-2d-lidar-based-slam-system-for-wheeled-mobile-robots_amd", "csrc", "grid_kernels.hip")
-
-WIN_CELLS = 36864              # kWinCells
-WIN_MAX_GROUP = 64             # kWinMaxGroup
-SORT_BINS = 128                # kSortBins
-MAX_SORT_RAYS = 8192           # kMaxSortRays
-WIN_BOX_INTS = 160             # kWinBoxInts
-HALF_SLACK = 512               # kWinHalfSlack
-TWO_FLOOR = 29632              # kWinTwoFloor
-SCAN_CONST = 4 * 8 + 4 * 4     # sizeof(ScanConst): four doubles, four ints
-LDS_PER_CU = 160 * 1024
-CUS = 256
-
-NAMES = {"kWinCells": "WIN_CELLS", "kWinMaxGroup": "WIN_MAX_GROUP", "kSortBins": "SORT_BINS", "kMaxSortRays": "MAX_SORT_RAYS",
-         "kWinBoxInts": "WIN_BOX_INTS", "kWinHalfSlack": "HALF_SLACK", "kWinTwoFloor": "TWO_FLOOR"}
+PKG = "a-2d-lidar-based-slam-system-for-wheeled-mobile-robots_amd"
 
 
-def source_constants(text=None):
-    """The constants above as csrc/grid_kernels.hip states them: {Python name: value}."""
-    if text is None:
-        with open(SOURCE) as f:
-            text = f.read()
-    out = {}
-    for c_name, py_name in NAMES.items():
-        m = re.findall(r"constexpr int %s = (\d+);" % c_name, text)
-        assert len(m) == 1, c_name
-        out[py_name] = int(m[0])
-    return out
+def query(name, a=0, b=0, c=0, guard=0):
+    """slam_plan_query: a constant or a size function of csrc/launch_shapes.h by its name there."""
+    abi = importlib.import_module(PKG + "._abi")
+    out = C.c_int64()
+    abi.check(abi.lib().slam_plan_query(name.encode(), int(a), int(b), int(c), int(guard), C.byref(out)))
+    return out.value
 
 
-def win_sc_bytes(group):
-    return (group * SCAN_CONST + 15) & ~15
+WIN_CELLS = query("kWinCells")
+WIN_MAX_GROUP = query("kWinMaxGroup")
+SORT_BINS = query("kSortBins")
+MAX_SORT_RAYS = query("kMaxSortRays")
+WIN_BOX_INTS = query("kWinBoxInts")
+HALF_SLACK = query("kWinHalfSlack")
+TWO_FLOOR = query("kWinTwoFloor")
+MIN_THREADS = query("kWinMinThreads")
+SCAN_CONST = query("kScanConstBytes")
+LDS_PER_CU = query("kLdsPerCu")
+CUS = query("kChipCus")
+FORMS = ("Win", "Own", "Owner1", "Owner2", "Owner8ThenRedo")        # SLAM_WIN_FORM_*
 
 
 def win_sort_cap(rays):
-    return (rays + 7) & ~7 if rays <= MAX_SORT_RAYS else 0
+    return query("win_sort_cap", rays)
 
 
 def win_lds_bytes(group, sort_cap, win_cells, guard=0):
-    return win_sc_bytes(group) + WIN_BOX_INTS * 4 + 4 * SORT_BINS * 4 + sort_cap * 2 + win_cells * 2 + guard
+    return query("win_lds_bytes", group, sort_cap, win_cells, guard)
 
 
-def win_cells_for(group, sort_cap, two_per_cu=False, lds_per_cu=LDS_PER_CU, guard=0):
-    half = lds_per_cu // 2 - HALF_SLACK
-    cells = ((half - win_lds_bytes(group, sort_cap, 0, guard)) // 2) & ~15
-    if cells > WIN_CELLS:
-        return cells
-    return cells if two_per_cu and cells >= TWO_FLOOR else WIN_CELLS
+def win_cells_for(group, sort_cap, two_per_cu=False, guard=0):
+    """(for a CU of LDS_PER_CU bytes; launch() takes another chip's)"""
+    return query("win_cells_for", group, sort_cap, two_per_cu, guard)
+
+
+WinPlan = namedtuple("WinPlan", "form grid_x grid_y threads lds lds_attr exclusive sort_cap win_cells split lds_hits two_per_cu wgs "
+                                "own8_lds own8_win redo_grid live_dirty")
+
+
+def plan_win(scans, n, group, L=1, got=False, pmap_live=False, private=False, hit_levels=1, xw=400, yw=400, redo=False,
+             split_pref=-1, hits_pref=-1, cus=CUS, lds_per_cu=LDS_PER_CU, guard=0):
+    """slam_plan_win's answer for a launch of L streams of `scans` scans of n beams in groups of `group`; form by name."""
+    abi = importlib.import_module(PKG + "._abi")
+    out = (C.c_int * len(WinPlan._fields))()
+    abi.check(abi.lib().slam_plan_win(L, scans, n, group, int(got), int(pmap_live), int(private), hit_levels, xw, yw, int(redo),
+                                      split_pref, hits_pref, cus, lds_per_cu, guard, out))
+    p = WinPlan(*out)
+    return p._replace(form=FORMS[p.form])
 
 
 Launch = namedtuple("Launch", "group sort_cap split wgs two_per_cu win_cells lds")
@@ -76,27 +79,12 @@ Launch = namedtuple("Launch", "group sort_cap split wgs two_per_cu win_cells lds
 
 def launch(scans, n, group, L=1, split_pref=-1, cus=CUS, lds_per_cu=LDS_PER_CU, guard=0):
     """A shared-map launch (k_grid_update_win) of L streams of `scans` scans of n beams in groups of `group`."""
-    groups = (scans + group - 1) // group
-    sort_cap = win_sort_cap(group * n)
-    split = int(sort_cap > 0 and (split_pref > 0 or (split_pref < 0 and groups * L <= 3 * cus // 4)))
-    wgs = (2 * groups if split else groups) * L
-    two = sort_cap > 0 and wgs > cus
-    cells = win_cells_for(group, sort_cap, two, lds_per_cu, guard)
-    lds = win_lds_bytes(group, sort_cap, cells, guard)
-    half_cu = lds_per_cu // 2
-    if split and wgs <= cus and lds <= half_cu and half_cu + 512 <= lds_per_cu:
-        lds = half_cu + 512                                          # the spreading request of a lone launch
-    return Launch(group, sort_cap, split, wgs, two, cells, lds)
+    p = plan_win(scans, n, group, L=L, split_pref=split_pref, cus=cus, lds_per_cu=lds_per_cu, guard=guard)
+    assert p.form == "Win"
+    return Launch(group, p.sort_cap, p.split, p.wgs, bool(p.two_per_cu), p.win_cells, p.lds)
 
 
 # ---- phases -------------------------------------------------------------------------------------------------------
-
-def _clamp(box, xw, yw, ymask):
-    """clamp_box: None where nothing of the box is in the map."""
-    x0, y0, x1, y1 = max(box[0], 0), max(box[1], 0), min(box[2], xw - 1), min(box[3], yw - 1)
-    y0 &= ~ymask
-    return (x0, y0, x1, y1) if x0 <= x1 and y0 <= y1 else None
-
 
 def box_cells(box):
     """Window cells a clamped box takes: rows are stored padded to an even height."""
@@ -106,51 +94,37 @@ def box_cells(box):
 Plan = namedtuple("Plan", "parts boxes fits")      # per phase: quadrant mask, clamped box (None: empty), whether it fits
 
 
+class _Phases(C.Structure):                         # slam_win_phases
+    _fields_ = [("nph", C.c_int), ("parity", C.c_int), ("part", C.c_int * 4), ("box", (C.c_int * 4) * 4), ("any", C.c_int * 4),
+                ("fits", C.c_int * 4)]
+
+
 def plan(orgs, ends, xw, yw, win_cells, half=None, sorted_rays=True, even_rows=None, per_half=True):
-    """Phases of a workgroup for scans with origin cells orgs [S, 2] and end cells ends [R, 2] (all of the group's valid
-    rays).  half: None for one workgroup per group, 0 / 1 for the two of grid_split.  per_half False: the earlier rule
-    of the unsplit form (both halves fit, or four quadrants)."""
+    """Phases of a workgroup (slam_plan_win_phases) for scans with origin cells orgs [S, 2] and end cells ends [R, 2] (all
+    of the group's valid rays).  half: None for one workgroup per group, 0 / 1 for the two of grid_split.  per_half False:
+    the earlier rule of the unsplit form (both halves fit, or four quadrants), which the library no longer has."""
     orgs, ends = np.asarray(orgs), np.asarray(ends)
     ymask = 1 if (yw % 2 == 0 if even_rows is None else even_rows) else 0
-    bb = (min(orgs[:, 0].min(), ends[:, 0].min()), min(orgs[:, 1].min(), ends[:, 1].min()),
-          max(orgs[:, 0].max(), ends[:, 0].max()), max(orgs[:, 1].max(), ends[:, 1].max()))
-    ox0, oy0, ox1, oy1 = orgs[:, 0].min(), orgs[:, 1].min(), orgs[:, 0].max(), orgs[:, 1].max()
-    qbox = []
-    for q in range(4):
-        qbox.append((max(ox0, bb[0]) if q & 1 else bb[0], max(oy0, bb[1]) if q & 2 else bb[1],
-                     bb[2] if q & 1 else min(ox1, bb[2]), bb[3] if q & 2 else min(oy1, bb[3])))
+    bb = (C.c_int * 4)(min(orgs[:, 0].min(), ends[:, 0].min()), min(orgs[:, 1].min(), ends[:, 1].min()),
+                       max(orgs[:, 0].max(), ends[:, 0].max()), max(orgs[:, 1].max(), ends[:, 1].max()))
+    org = (C.c_int * 4)(orgs[:, 0].min(), orgs[:, 1].min(), orgs[:, 0].max(), orgs[:, 1].max())
+    abi = importlib.import_module(PKG + "._abi")
 
-    def box_of(mask):
-        bs = [qbox[q] for q in range(4) if mask >> q & 1 and qbox[q][0] <= qbox[q][2]]
-        if not bs:
-            return None
-        return _clamp((min(b[0] for b in bs), min(b[1] for b in bs), max(b[2] for b in bs), max(b[3] for b in bs)), xw, yw, ymask)
+    def ask(cells, half):
+        p = _Phases()
+        abi.check(abi.lib().slam_plan_win_phases(bb, org, xw, yw, ymask, min(cells, 2 ** 31 - 1), int(sorted_rays),
+                                                 -1 if half is None else half, C.byref(p)))
+        return Plan(list(p.part[:p.nph]), [tuple(p.box[k]) if p.any[k] else None for k in range(p.nph)],
+                    [bool(p.fits[k]) for k in range(p.nph)])
 
-    def fits(mask):
-        b = box_of(mask)
-        return b is None or box_cells(b) <= win_cells
-
-    if half is not None:
-        mine = 0xA if half else 0x5
-        if fits(0xF):
-            parts = [0xF]
-        elif fits(mine):
-            parts = [mine]
-        else:
-            parts = [mine & 0x3, mine & 0xC]
-    elif not sorted_rays or fits(0xF):
-        parts = [0xF]
-    else:
-        left, right = fits(0x5), fits(0xA)
-        if left and right:
-            parts = [0x5, 0xA]
-        elif left and per_half:
-            parts = [0x5, 0x2, 0x8]
-        elif right and per_half:
-            parts = [0x1, 0x4, 0xA]
-        else:
-            parts = [0x1, 0x2, 0x4, 0x8]
-    return Plan(parts, [box_of(p) for p in parts], [fits(p) for p in parts])
+    got = ask(win_cells, half)
+    if per_half or half is not None or len(got.parts) != 3:
+        return got
+    # one half fits, the other does not: the earlier rule cut both.  The quadrants' boxes are what the two workgroups of a
+    # split launch get when nothing fits (a half that is empty altogether stays one part, with no box)
+    left, right = ([q.boxes[0], q.boxes[1]] if len(q.parts) == 2 else [None, None] for q in (ask(0, 0), ask(0, 1)))
+    boxes = [left[0], right[0], left[1], right[1]]
+    return Plan([0x1, 0x2, 0x4, 0x8], boxes, [b is None or box_cells(b) <= win_cells for b in boxes])
 
 
 def plan_two_then_four(orgs, ends, xw, yw, win_cells):

@@ -5,8 +5,8 @@ distinct aligned pairs of end cells (what a sweep with 64-bit pair adds would se
 
     python tools/win_hit_cells.py [traj=32] [group=16] [scans=1000] [seed=1]
 
-The scans are cast from the oracle's own replay poses (the device's agree to 1e-9), with the phase rule as
-tests/win_shapes.py restates it and the window a chip-filling launch of that shape gets."""
+The scans are cast from the oracle's own replay poses (the device's agree to 1e-9), with the phase rule and
+the launch shape as the library answers for them (tests/win_shapes.py) and the window a chip-filling launch of that shape gets."""
 import importlib
 import os
 import sys
