@@ -17,6 +17,10 @@ zjwzcx/A-2D-LiDAR-based-SLAM-System-for-Wheeled-Mobile-Robots:
                W9 node batched on the device as DeviceLocalizationReplay / loc_replay_host
     MCL        Monte Carlo localisation on the map's distance field: one filter on a Mapping; batched and
                device-resident as DeviceMCL, on NumPy arrays as mcl_weigh_host / mcl_resample_host
+    GridSLAM   grid FastSLAM: a particle filter whose every particle builds its own map, and the maps follow the
+               resampling (in place; only the maps of particles that died are copied); batched and device-resident
+               as DeviceGridSLAM, on NumPy arrays as mcl_weigh_host(own_maps=True) / mcl_settle_host /
+               grid_copy_maps_host / grid_update_particles_host (DeviceGrid.copy_maps / .update_particles)
     dwa        dwa_control / Config / RobotType (course_agv_nav DWA local planner), batched as
                DeviceDWA / dwa_batch_host; LocalPlanner: the local planner node without ROS
     global_planner  find_path(...).start_find() / GlobalPlanner (course_agv_nav A*), batched as
@@ -41,10 +45,12 @@ from .local_planner import LocalPlanner
 from .localization import Localization
 from .loc_replay import DeviceLocalizationReplay, loc_replay_host
 from .mapping import Mapping
-from .mcl import MCL, MCL_DEAD, DeviceMCL, mcl_resample_host, mcl_weigh_host, mcl_weight_table
+from .mcl import MCL, MCL_DEAD, DeviceMCL, mcl_resample_host, mcl_settle_host, mcl_weigh_host, mcl_weight_table
 from .node_replay import DeviceNodeReplay, ekf_lm_host, landmarks_host, node_replay_host
 from .replay import DeviceGrid, DeviceReplay, grid_raycast_host, grid_score_host, icp_batch_host, particles_host, prior_matrices, replay_host
 from .replay import grid_distance_field_host, grid_match_host, match_pose, match_rotations
+from .replay import grid_copy_maps_host, grid_update_particles_host
+from .grid_slam import DeviceGridSLAM, GridSLAM
 from .slam_ekf import SLAM_EKF
 from .synthetic import LaserScan
 
@@ -56,4 +62,5 @@ __all__ = ["ICP", "Mapping", "Localization", "EKF", "Extraction", "LandMarkSet",
            "DeviceLocalizationReplay", "loc_replay_host", "grid_raycast_host", "grid_score_host",
            "grid_distance_field_host", "grid_match_host", "match_pose", "match_rotations",
            "MCL", "DeviceMCL", "MCL_DEAD", "mcl_weight_table", "mcl_weigh_host", "mcl_resample_host",
+           "GridSLAM", "DeviceGridSLAM", "mcl_settle_host", "grid_copy_maps_host", "grid_update_particles_host",
            "RAY_EMPTY", "RAY_HIT", "RAY_BLOCKED", "RAY_FREE", "RAY_UNKNOWN", "RAY_OUT", "RAY_BAD", "RAY_CLASSES", "RAY_NAMES"]

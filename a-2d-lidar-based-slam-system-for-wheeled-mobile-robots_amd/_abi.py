@@ -87,6 +87,14 @@ _SIGS = {
     "slam_mcl_weigh_dev": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, C.c_float, _i, _vp, _vp, _vp, _vp], _i),
     "slam_mcl_resample": ([_vp, _vp, _vp, _vp, _i, _i, _vp, _d, _i, _i, _vp, _vp, _vp, _vp], _i),
     "slam_mcl_resample_dev": ([_vp, _vp, _vp, _vp, _i, _i, _vp, _d, _i, _i, _vp, _vp, _vp, _vp], _i),
+    "slam_mcl_weigh_maps": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, C.c_float, _i, _vp, _vp, _vp, _vp], _i),
+    "slam_mcl_weigh_maps_dev": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, C.c_float, _i, _vp, _vp, _vp, _vp], _i),
+    "slam_mcl_settle": ([_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
+    "slam_mcl_settle_dev": ([_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
+    "slam_grid_copy_maps": ([_vp, _vp, _vp, _i, _i, _vp], _i),
+    "slam_grid_copy_maps_dev": ([_vp, _vp, _vp, _i, _i, _vp], _i),
+    "slam_grid_update_particles": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i], _i),
+    "slam_grid_update_particles_dev": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i], _i),
     "slam_bresenham_batch": ([_vp, _vp, _vp, _i, _vp, _vp, _vp, C.c_int64], _i),
     "slam_replay": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp], _i),
     "slam_particles": ([_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _d, _vp, _vp, _vp, _vp], _i),

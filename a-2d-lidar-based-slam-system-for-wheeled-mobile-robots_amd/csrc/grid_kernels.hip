@@ -224,6 +224,48 @@ struct ReplaySource {
     }
 };
 
+// ... or the particles of grid FastSLAM (slam_grid_update_particles): trajectory l is particle l0 + l of F filters of P; it
+// reads ITS FILTER's scan (l0 + l) / P and its own pose l, and casts into map l of its own.  Everything else - the beam's
+// arithmetic above all - is the replay source's.  A dead particle (acc == SLAM_MCL_DEAD) gets a harmless origin and
+// every beam skipped as mapping.py:30 skips one: nothing is cast and nothing is flagged.
+struct ParticleSource : ReplaySource {
+    const int32_t *acc;    // nullable [L]
+    int P;
+    long l0;               // particles before this launch's first (launches split at 65 535 particles)
+    ParticleSource(const float *ranges_, const double *cos_t_, const double *sin_t_, const double *poses_, const int32_t *acc_, int n_, int P_)
+        : ReplaySource{ranges_, cos_t_, sin_t_, poses_, 2, n_, 0L, 1, nullptr, nullptr}, acc(acc_), P(P_), l0(0) {}
+    ParticleSource trajectories_from(long k) const
+    {
+        ParticleSource r = *this;
+        r.poses += 3 * (size_t)k;
+        if (acc) r.acc += k;
+        r.l0 += k;
+        return r;
+    }
+    ParticleSource scans_from(int, int) const { return *this; }      // (one scan per particle)
+    __device__ void scan_const(int l, int k, const GridDev &g, ScanConst &sc) const
+    {
+        sc.pad = acc && acc[l] == SLAM_MCL_DEAD;
+        if (!sc.pad) {
+            ReplaySource::scan_const(l, k, g, sc);
+            return;
+        }
+        sc.px = 0.0; sc.py = 0.0; sc.c = 1.0; sc.s = 0.0;            // (a dead particle's pose may hold anything)
+        sc.cbad = 0;
+        sc.pcx = to_cell(0.0, g.scale, g.off_x, sc.cbad);
+        sc.pcy = to_cell(0.0, g.scale, g.off_y, sc.cbad);
+    }
+    __device__ Beam fetch(int l, int, int i) const { return Beam{ranges[(size_t)((l0 + l) / P) * n + i], cos_t[i], sin_t[i]}; }
+    __device__ bool ray(const Beam &b, const ScanConst &sc, const GridDev &g, int &pox, int &poy, int &bad) const
+    {
+        return !sc.pad && ReplaySource::ray(b, sc, g, pox, poy, bad);
+    }
+    __device__ bool ray(int l, int k, int i, const ScanConst &sc, const GridDev &g, int &pox, int &poy, int &bad) const
+    {
+        return ray(fetch(l, k, i), sc, g, pox, poy, bad);
+    }
+};
+
 // ... or explicit world-frame endpoints (Mapping.update's own arguments).
 struct ExplicitSource {
     const double *ox, *oy, *cx, *cy;
@@ -2571,6 +2613,11 @@ static hipError_t launch_cast(const GridDev &g, CastPath p, const Src &src, cons
 hipError_t launch_cast(const GridDev &g, CastPath p, const CastRequest &r, void *scratch, hipStream_t s)
 {
     if (r.ox) return launch_cast(g, p, ExplicitSource{r.ox, r.oy, r.cx, r.cy, r.scans, r.n}, r, scratch, s);
+    if (r.per_filter) {
+        ParticleSource src(r.ranges, r.cos_t, r.sin_t, r.poses, r.acc, r.n, r.per_filter);
+        src.l0 = r.first_particle;
+        return launch_cast(g, p, src, r, scratch, s);
+    }
     const ReplaySource src{r.ranges, r.cos_t, r.sin_t, r.poses, r.scans + 1, r.n, r.particles ? 0L : (long)(r.scans + 1) * r.n,
                            r.particles, r.centres, r.heading_cs};
     return launch_cast(g, p, src, r, scratch, s);
@@ -2673,6 +2720,73 @@ hipError_t launch_bresenham(const int32_t *starts, const int32_t *ends, int B, c
                             int32_t *cells, hipStream_t s)
 {
     SLAM_LAUNCH(k_bresenham, dim3((B + 255) / 256), dim3(256), 0, s, starts, ends, B, offsets, lens, cells);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------
+// Maps that follow their ancestors (slam_grid_copy_maps): bandwidth work.
+// ---------------------------------------------------------------------------------
+// n dwords by the whole workgroup: 16 bytes per lane where source and destination are equally aligned (a map's base is
+// g * xw * yw * 4 bytes and need not be 16-byte aligned), the head, the tail and unequal alignment dword by dword.
+__device__ __forceinline__ void copy_dwords(uint32_t *__restrict__ dst, const uint32_t *__restrict__ src, long n)
+{
+    const uintptr_t ad = reinterpret_cast<uintptr_t>(dst), as = reinterpret_cast<uintptr_t>(src);
+    if (((ad ^ as) & 15) != 0) {
+        for (long i = threadIdx.x; i < n; i += blockDim.x) dst[i] = src[i];
+        return;
+    }
+    const long head = std::min(n, (long)(((16 - (ad & 15)) & 15) / 4)), body = (n - head) / 4;
+    for (long i = threadIdx.x; i < head; i += blockDim.x) dst[i] = src[i];
+    const uint4 *s4 = reinterpret_cast<const uint4 *>(src + head);
+    uint4 *d4 = reinterpret_cast<uint4 *>(dst + head);
+    for (long i = threadIdx.x; i < body; i += blockDim.x) d4[i] = s4[i];
+    for (long i = head + 4 * body + threadIdx.x; i < n; i += blockDim.x) dst[i] = src[i];
+}
+
+// the same for the bytes of the live pmap: a dword per lane where both are equally aligned
+__device__ __forceinline__ void copy_bytes(int8_t *__restrict__ dst, const int8_t *__restrict__ src, long n)
+{
+    const uintptr_t ad = reinterpret_cast<uintptr_t>(dst), as = reinterpret_cast<uintptr_t>(src);
+    if (((ad ^ as) & 3) != 0) {
+        for (long i = threadIdx.x; i < n; i += blockDim.x) dst[i] = src[i];
+        return;
+    }
+    const long head = std::min(n, (long)((4 - (ad & 3)) & 3)), body = (n - head) / 4;
+    for (long i = threadIdx.x; i < head; i += blockDim.x) dst[i] = src[i];
+    const uint32_t *s4 = reinterpret_cast<const uint32_t *>(src + head);
+    uint32_t *d4 = reinterpret_cast<uint32_t *>(dst + head);
+    for (long i = threadIdx.x; i < body; i += blockDim.x) d4[i] = s4[i];
+    for (long i = head + 4 * body + threadIdx.x; i < n; i += blockDim.x) dst[i] = src[i];
+}
+
+// Group = (destination k, chunk ch of its cells), taken grid-stride.  Map first + k becomes a copy of map src[k]; kept
+// (copied 0) when that is itself or no map; left alone (copied -1) when the source is a destination of this call - the one
+// extra load - so that no map is read that the launch writes.
+__global__ void __launch_bounds__(kCopyThreads) k_grid_copy_maps(GridDev g, const int32_t *__restrict__ src, int first, int count,
+                                                                long chunks, int32_t *__restrict__ copied)
+{
+    const long cells = (long)g.xw * g.yw, groups = (long)count * chunks;
+    for (long grp = blockIdx.x; grp < groups; grp += gridDim.x) {
+        const int k = (int)(grp / chunks);
+        const long ch = grp % chunks;
+        const int d = first + k, s = src[k];
+        int what = 1;
+        if (s == d || (unsigned)s >= (unsigned)g.G) what = 0;
+        else if (s >= first && s - first < count && src[s - first] != s) what = -1;
+        if (ch == 0 && threadIdx.x == 0 && copied) copied[k] = what;
+        if (what != 1) continue;
+        const long c0 = ch * kCopyChunkCells, len = std::min((long)kCopyChunkCells, cells - c0);
+        const size_t so = (size_t)s * cells + c0, dof = (size_t)d * cells + c0;
+        copy_dwords(g.pass + dof, g.pass + so, len);
+        copy_dwords(g.hit + dof, g.hit + so, len);
+        if (g.pmap_live) copy_bytes(g.pmap_live + dof, g.pmap_live + so, len);
+    }
+}
+
+hipError_t launch_grid_copy_maps(const GridDev &g, const int32_t *src, int first, int count, int32_t *copied_out, hipStream_t s)
+{
+    const CopyShape p = plan_copy_maps((long)g.xw * g.yw, count);
+    SLAM_LAUNCH(k_grid_copy_maps, dim3((unsigned)p.grid), dim3(p.threads), 0, s, g, src, first, count, p.chunks, copied_out);
     return hipGetLastError();
 }
 

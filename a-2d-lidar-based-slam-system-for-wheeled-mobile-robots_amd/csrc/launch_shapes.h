@@ -439,4 +439,30 @@ inline IcpShape plan_icp(const IcpRequest &a)
     return p;
 }
 
+// ---------------------------------------------------------------------------------
+// In-place copy of maps (k_grid_copy_maps, slam_grid_copy_maps)
+// ---------------------------------------------------------------------------------
+// A workgroup takes (destination k, chunk of cells): kCopyChunkCells cells of both counter arrays (and of the live pmap),
+// 16 bytes per lane and trip where source and destination are equally aligned.  The chunk is a multiple of four cells, so
+// a chunk's start has its map's alignment.  More groups than kCopyMaxGroups are taken grid-stride.
+constexpr int kCopyThreads = 256;
+constexpr int kCopyChunkCells = 8192;        // 32 KiB of each counter array per workgroup: 8 trips of 16 bytes per lane
+constexpr long kCopyMaxGroups = 1L << 20;
+static_assert(kCopyChunkCells % 4 == 0, "a chunk's first cell keeps its map's 16-byte alignment");
+struct CopyShape {
+    long chunks = 0;       // workgroups per destination
+    long groups = 0;       // count * chunks
+    long grid = 0;         // workgroups launched
+    int threads = kCopyThreads;
+};
+inline CopyShape plan_copy_maps(long cells, long count)
+{
+    CopyShape p;
+    if (cells < 1 || count < 1) return p;
+    p.chunks = (cells + kCopyChunkCells - 1) / kCopyChunkCells;
+    p.groups = p.chunks * count;
+    p.grid = std::min(p.groups, kCopyMaxGroups);
+    return p;
+}
+
 }  // namespace slam

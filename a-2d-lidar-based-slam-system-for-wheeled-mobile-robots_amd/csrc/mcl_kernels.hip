@@ -112,6 +112,13 @@ __device__ __forceinline__ int mcl_beam(const MclWeighArgs &a, const int16_t *fi
     return in ? (int)field[(size_t)ex * g.yw + ey] : a.cap;
 }
 
+// The map of particle i = f * P + p: its filter's (slam_mcl_weigh), or its own (slam_mcl_weigh_maps).
+__device__ __forceinline__ int mcl_map_of(const MclWeighArgs &a, int f, size_t i)
+{
+    if (a.own_maps) return a.pmaps ? a.pmaps[i] : (int)i;
+    return a.maps ? a.maps[f] : 0;
+}
+
 __device__ __forceinline__ void mcl_store(const MclWeighArgs &a, size_t i, int before, int cost)
 {
     if (a.cost_out) a.cost_out[i] = cost;
@@ -130,12 +137,12 @@ __global__ void __launch_bounds__(256) k_mcl_weigh(MclWeighArgs a)
     const long groups = (long)a.F * a.chunks;
     for (long grp = blockIdx.x; grp < groups; grp += gridDim.x) {
         const int f = (int)(grp / a.chunks), ch = (int)(grp % a.chunks);
-        const int gi = a.maps ? a.maps[f] : 0;
-        const bool nomap = (unsigned)gi >= (unsigned)g.G;
         const int m = mcl_stage_beams(a, f, lds_mcl, &s_used);
         if (ch == 0 && threadIdx.x == 0 && a.used_out) a.used_out[f] = m;
         const int p = ch * (int)blockDim.x + (int)threadIdx.x;
         const size_t i = (size_t)f * a.P + p;
+        const int gi = p < a.P ? mcl_map_of(a, f, i) : 0;             // the lane's own particle's map
+        const bool nomap = (unsigned)gi >= (unsigned)g.G;
         double px, py, th;
         int before;
         if (p < a.P && mcl_move(a, f, i, nomap, true, px, py, th, before)) {   // (no lane leaves the loop body early: the barriers above)
@@ -178,13 +185,12 @@ __global__ void __launch_bounds__(256) k_mcl_weigh_wave(MclWeighArgs a)
     const long groups = (long)a.F * a.chunks;
     for (long grp = blockIdx.x; grp < groups; grp += gridDim.x) {
         const int f = (int)(grp / a.chunks), ch = (int)(grp % a.chunks);
-        const int gi = a.maps ? a.maps[f] : 0;
-        const bool nomap = (unsigned)gi >= (unsigned)g.G;
         const int m = mcl_stage_beams(a, f, lds_mcl, &s_used);
         if (ch == 0 && threadIdx.x == 0 && a.used_out) a.used_out[f] = m;
-        const int16_t *field = a.field + (size_t)(nomap ? 0 : gi) * g.xw * g.yw;
         const int p = ch * kMclWaveRun + wave * per + lane;
         const size_t i = (size_t)f * a.P + p;
+        const int gi = lane < per && p < a.P ? mcl_map_of(a, f, i) : 0;   // broadcast below with the particle's other values
+        const bool nomap = (unsigned)gi >= (unsigned)g.G;
         double px = 0.0, py = 0.0, th = 0.0, c = 0.0, s = 0.0;
         int before = 0, mine = 0;
         if (lane < per && p < a.P && mcl_move(a, f, i, nomap, true, px, py, th, before)) {
@@ -196,6 +202,7 @@ __global__ void __launch_bounds__(256) k_mcl_weigh_wave(MclWeighArgs a)
         for (int q = 0; q < per; ++q) {
             if (!__shfl(mine, q, kWave)) continue;                    // (wave-uniform) no such particle, or a dead one
             const double qx = shfl64(px, q), qy = shfl64(py, q), qc = shfl64(c, q), qs = shfl64(s, q);
+            const int16_t *field = a.field + (size_t)__shfl(gi, q, kWave) * g.xw * g.yw;   // (a live particle: its map exists)
             int part = 0;
             for (int t = lane; t < m; t += kWave) part += mcl_beam(a, field, qc, qs, qx, qy, lds_mcl[2 * t], lds_mcl[2 * t + 1]);
 #pragma unroll
@@ -422,6 +429,92 @@ __global__ void __launch_bounds__(256) k_mcl_select(MclResampleArgs a)
         dst[0] = src[0]; dst[1] = src[1]; dst[2] = src[2];
         if (a.ancestors_out) a.ancestors_out[idx] = anc;
     }
+}
+
+// slam_mcl_settle: the resampled set rearranged so that every surviving particle keeps its own slot.  One workgroup per
+// filter, taken grid-stride.  Dynamic LDS, three int arrays of P: cnt (how often each slot is an ancestor), the exclusive
+// rank of every slot among the free ones (cnt == 0) and the inclusive sum of the surplus max(cnt - 1, 0).  The free slot
+// of rank r takes the smallest i whose surplus sum exceeds r (a binary search): free slots and surplus copies are paired
+// in ascending order, and the two lists are equally long because the counts add up to P.
+constexpr int kMclSettleThreads = 256;
+__global__ void __launch_bounds__(kMclSettleThreads) k_mcl_settle(MclSettleArgs a)
+{
+    extern __shared__ int lds_settle[];
+    __shared__ int s_wave[2][kMclSettleThreads / kWave], s_moved;
+    const int P = a.P, lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    int *cnt = lds_settle, *frank = lds_settle + P, *sur = lds_settle + 2 * (size_t)P;
+    char *guard = reinterpret_cast<char *>(lds_settle + 3 * (size_t)P);
+    lds_guard_fill(guard);
+    const int per = (P + kMclSettleThreads - 1) / kMclSettleThreads;   // consecutive slots of one lane of the scans
+    for (long f = blockIdx.x; f < a.F; f += gridDim.x) {
+        const size_t base = (size_t)f * P;
+        __syncthreads();                                              // every lane is done with the filter before
+        for (int j = threadIdx.x; j < P; j += blockDim.x) cnt[j] = 0;
+        if (threadIdx.x == 0) s_moved = 0;
+        __syncthreads();
+        for (int j = threadIdx.x; j < P; j += blockDim.x) atomicAdd(&cnt[std::min(std::max(a.ancestors[base + j], 0), P - 1)], 1);
+        __syncthreads();
+        const int j0 = (int)threadIdx.x * per, j1 = std::min(P, j0 + per);
+        int nfree = 0, nsur = 0;
+        for (int j = j0; j < j1; ++j) {
+            nfree += cnt[j] == 0;
+            nsur += std::max(cnt[j] - 1, 0);
+        }
+        int ifree = nfree, isur = nsur;                               // inclusive over the lanes of the wave
+#pragma unroll
+        for (int off = 1; off < kWave; off <<= 1) {
+            const int of = __shfl_up(ifree, off, kWave), os = __shfl_up(isur, off, kWave);
+            if (lane >= off) { ifree += of; isur += os; }
+        }
+        if (lane == kWave - 1) { s_wave[0][wave] = ifree; s_wave[1][wave] = isur; }
+        __syncthreads();
+        int rfree = ifree - nfree, rsur = isur - nsur;                // exclusive within the workgroup
+        for (int v = 0; v < wave; ++v) { rfree += s_wave[0][v]; rsur += s_wave[1][v]; }
+        for (int j = j0; j < j1; ++j) {
+            frank[j] = rfree;
+            rfree += cnt[j] == 0;
+            rsur += std::max(cnt[j] - 1, 0);
+            sur[j] = rsur;
+        }
+        __syncthreads();
+        int moved = 0;
+        for (int j = threadIdx.x; j < P; j += blockDim.x) {
+            int from = j;
+            if (cnt[j] == 0) {
+                const int r = frank[j];
+                int lo = 0, hi = P - 1;                               // the answer lies in [lo, hi]: sur[P - 1] = the free slots > r
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    if (sur[mid] > r) hi = mid;
+                    else lo = mid + 1;
+                }
+                from = lo;
+                ++moved;
+            }
+            a.settled[base + j] = from;
+            if (a.map_src) a.map_src[base + j] = a.map0 + (int)base + from;
+            if (a.poses_out) {
+                const double *src = a.poses_src + 3 * (base + from);
+                double *dst = a.poses_out + 3 * (base + j);
+                dst[0] = src[0]; dst[1] = src[1]; dst[2] = src[2];
+            }
+        }
+        if (a.moved) {
+#pragma unroll
+            for (int off = kWave / 2; off; off >>= 1) moved += __shfl_xor(moved, off, kWave);
+            if (lane == 0 && moved) atomicAdd(&s_moved, moved);
+            __syncthreads();
+            if (threadIdx.x == 0) a.moved[f] = s_moved;
+        }
+    }
+    lds_guard_check(guard, a.status);
+}
+
+hipError_t launch_mcl_settle(const MclSettleArgs &a, hipStream_t s)
+{
+    const int lds = 3 * 4 * a.P + kLdsGuard;                          // P <= kMclSettleMaxP: 48 KiB, within what a kernel gets unasked
+    SLAM_LAUNCH(k_mcl_settle, dim3((unsigned)std::min((long)a.F, kMclMaxBlocks)), dim3(kMclSettleThreads), lds, s, a);
+    return hipGetLastError();
 }
 
 // Launch shape of the weigh (context option "mcl_shape"; DESIGN.md section 15 has the measurements).

@@ -861,6 +861,10 @@ int slam_plan_query(const char *name, int a, int b, int c, int guard, int64_t *o
         {"nn_blocks", nn_blocks(a)}, {"nn_boxes_padded", nn_boxes_padded(a)}, {"nn_boxes4", nn_boxes4(a)}, {"nn_lds_bytes", (int64_t)nn_lds_bytes(a)},
         {"icp_polar_bytes", (int64_t)icp_polar_bytes(a)}, {"icp_red_bytes", (int64_t)icp_red_bytes(a)},
         {"icp_wave_lds_bytes", (int64_t)icp_wave_lds_bytes(a, b, c != 0)}, {"icp_block", b > 0 ? icp_block(a, b) : 0},
+        // slam_grid_copy_maps: a = xw, b = yw, c = count
+        {"kCopyThreads", kCopyThreads}, {"kCopyChunkCells", kCopyChunkCells}, {"kCopyMaxGroups", (int64_t)kCopyMaxGroups},
+        {"copy_chunks", (int64_t)plan_copy_maps((long)a * b, c).chunks}, {"copy_groups", (int64_t)plan_copy_maps((long)a * b, c).groups},
+        {"copy_grid", (int64_t)plan_copy_maps((long)a * b, c).grid}, {"copy_threads", plan_copy_maps((long)a * b, c).threads},
     };
     for (const Entry &e : table)
         if (!strcmp(e.name, name)) { *out = e.value; return SLAM_OK; }
@@ -1732,6 +1736,177 @@ int slam_mcl_resample(slam_ctx *c, const double *poses, int32_t *acc, const uint
     TRY(s.upload());
     TRY(slam_mcl_resample_dev(c, d_p, d_acc, d_t, T, shift, d_u, ess_frac, F, P, d_po, d_anc, d_est, d_info));
     return s.download();
+}
+
+// ---- grid FastSLAM: a map per particle that follows resampling ------------------------------
+static int check_mcl_weigh_maps(const char *fn, const slam_grid *g, const int32_t *grid_of_particle, int F, int P)
+{
+    REQUIRE_IN(fn, grid_of_particle || (long)F * P <= g->d.G, "grid_of_particle is null and F * P > G");
+    return SLAM_OK;
+}
+
+int slam_mcl_weigh_maps_dev(slam_ctx *c, slam_grid *g, double *poses, const double *motion, const double *noise, const float *ranges,
+                            const double *cos_t, const double *sin_t, const int32_t *grid_of_particle, int F, int P, int n,
+                            float max_range, int cap, const int16_t *field, int32_t *acc, int32_t *cost_out, int32_t *used_out)
+{
+    TRY(use(c));
+    TRY(check_mcl_weigh(__func__, g, poses, motion, noise, ranges, cos_t, sin_t, F, P, n, max_range, cap));
+    TRY(check_mcl_weigh_maps(__func__, g, grid_of_particle, F, P));
+    int16_t *built = nullptr;
+    if (!field) TRY(build_field(c, g, __func__, cap, 0, built));
+    else TRY(grid_on_main(c));
+    MclWeighArgs a;
+    a.g = g->d; a.field = field ? field : built;
+    a.poses = poses; a.motion = motion; a.noise = noise; a.ranges = ranges; a.cos_t = cos_t; a.sin_t = sin_t;
+    a.own_maps = 1; a.pmaps = grid_of_particle; a.F = F; a.P = P; a.n = n; a.max_range = max_range; a.cap = cap;
+    a.acc = acc; a.cost_out = cost_out; a.used_out = used_out;
+    Timed t(c, SLAM_K_GRID);
+    HIPCHK(launch_mcl_weigh(a, c->mcl_shape, c->stream));
+    return SLAM_OK;
+}
+
+int slam_mcl_weigh_maps(slam_ctx *c, slam_grid *g, double *poses, const double *motion, const double *noise, const float *ranges,
+                        const double *cos_t, const double *sin_t, const int32_t *grid_of_particle, int F, int P, int n,
+                        float max_range, int cap, const int16_t *field, int32_t *acc, int32_t *cost_out, int32_t *used_out)
+{
+    TRY(use(c));
+    TRY(check_mcl_weigh(__func__, g, poses, motion, noise, ranges, cos_t, sin_t, F, P, n, max_range, cap));
+    TRY(check_mcl_weigh_maps(__func__, g, grid_of_particle, F, P));
+    const size_t FP = (size_t)F * P;
+    double *d_p, *d_m, *d_n, *d_c, *d_s; float *d_r; int32_t *d_g, *d_acc, *d_cost, *d_used; int16_t *d_f;
+    Staging s(c);
+    s.inout(d_p, poses, FP * 3).in(d_m, motion, (size_t)F * 3).in(d_n, noise, FP * 3).in(d_r, ranges, (size_t)F * n).in(d_c, cos_t, n)
+        .in(d_s, sin_t, n).in(d_g, grid_of_particle, FP).in(d_f, field, (size_t)g->d.G * g->d.xw * g->d.yw).inout(d_acc, acc, FP)
+        .out(d_cost, cost_out, FP).out(d_used, used_out, F);
+    TRY(s.upload());
+    TRY(slam_mcl_weigh_maps_dev(c, g, d_p, d_m, d_n, d_r, d_c, d_s, d_g, F, P, n, max_range, cap, d_f, d_acc, d_cost, d_used));
+    return s.download();
+}
+
+static int check_mcl_settle(const char *fn, const int32_t *ancestors, const double *poses_src, int F, int P, int map0,
+                            const int32_t *settled_out, const double *poses_out)
+{
+    REQUIRE_IN(fn, ancestors && settled_out, "null pointer");
+    REQUIRE_IN(fn, F >= 1, "F < 1");
+    REQUIRE_IN(fn, P >= 1 && P <= kMclSettleMaxP, "P outside [1, 4096]");
+    REQUIRE_IN(fn, (long)F * P < (1L << 31), "F * P >= 2^31");
+    REQUIRE_IN(fn, map0 >= 0 && (long)map0 + (long)F * P < (1L << 31), "map0 < 0 or map0 + F * P >= 2^31");
+    REQUIRE_IN(fn, !poses_out || poses_src, "poses_out without poses_src");
+    REQUIRE_IN(fn, !poses_out || poses_out != poses_src, "poses_out must not be poses_src");
+    return SLAM_OK;
+}
+
+int slam_mcl_settle_dev(slam_ctx *c, const int32_t *ancestors, const double *poses_src, int F, int P, int map0, int32_t *settled_out,
+                        double *poses_out, int32_t *map_src_out, int32_t *moved_out)
+{
+    TRY(use(c));
+    TRY(check_mcl_settle(__func__, ancestors, poses_src, F, P, map0, settled_out, poses_out));
+    MclSettleArgs a;
+    a.ancestors = ancestors; a.poses_src = poses_src; a.F = F; a.P = P; a.map0 = map0;
+    a.settled = settled_out; a.poses_out = poses_out; a.map_src = map_src_out; a.moved = moved_out; a.status = c->status;
+    Timed t(c, SLAM_K_GRID);
+    HIPCHK(launch_mcl_settle(a, c->stream));
+    return SLAM_OK;
+}
+
+int slam_mcl_settle(slam_ctx *c, const int32_t *ancestors, const double *poses_src, int F, int P, int map0, int32_t *settled_out,
+                    double *poses_out, int32_t *map_src_out, int32_t *moved_out)
+{
+    TRY(use(c));
+    TRY(check_mcl_settle(__func__, ancestors, poses_src, F, P, map0, settled_out, poses_out));
+    const size_t FP = (size_t)F * P;
+    for (size_t i = 0; i < FP; ++i) REQUIRE(ancestors[i] >= 0 && ancestors[i] < P, "ancestor outside [0, P)");
+    int32_t *d_a, *d_set, *d_map, *d_mov; double *d_p, *d_po;
+    Staging s(c);
+    s.in(d_a, ancestors, FP).in(d_p, poses_out ? poses_src : nullptr, FP * 3).out(d_set, settled_out, FP).out(d_po, poses_out, FP * 3)
+        .out(d_map, map_src_out, FP).out(d_mov, moved_out, F);
+    TRY(s.upload());
+    TRY(slam_mcl_settle_dev(c, d_a, d_p, F, P, map0, d_set, d_po, d_map, d_mov));
+    return s.download();
+}
+
+static int check_copy_maps(const char *fn, const slam_grid *g, const int32_t *src, int first, int count)
+{
+    REQUIRE_IN(fn, g && src, "null pointer");
+    REQUIRE_IN(fn, first >= 0 && count >= 1 && (long)first + count <= g->d.G, "first < 0, count < 1 or first + count > G");
+    return SLAM_OK;
+}
+
+int slam_grid_copy_maps_dev(slam_ctx *c, slam_grid *g, const int32_t *src, int first, int count, int32_t *copied_out)
+{
+    TRY(use(c));
+    TRY(check_copy_maps(__func__, g, src, first, count));
+    TRY(grid_on_main(c));
+    // a live pmap is copied with its counters: one that was current stays current, a stale one stays marked stale
+    Timed t(c, SLAM_K_GRID);
+    HIPCHK(launch_grid_copy_maps(g->d, src, first, count, copied_out, c->stream));
+    return SLAM_OK;
+}
+
+int slam_grid_copy_maps(slam_ctx *c, slam_grid *g, const int32_t *src, int first, int count, int32_t *copied_out)
+{
+    TRY(use(c));
+    TRY(check_copy_maps(__func__, g, src, first, count));
+    for (int k = 0; k < count; ++k) {
+        const int s = src[k];
+        const bool kept = s == first + k || s < 0 || s >= g->d.G;
+        REQUIRE(kept || s < first || s - first >= count || src[s - first] == s, "a source is itself a destination of this call");
+    }
+    int32_t *d_src, *d_out;
+    Staging s(c);
+    s.in(d_src, src, count).out(d_out, copied_out, count);
+    TRY(s.upload());
+    TRY(slam_grid_copy_maps_dev(c, g, d_src, first, count, d_out));
+    return s.download();
+}
+
+static int check_update_particles(const char *fn, const slam_grid *g, const float *ranges, const double *cos_t, const double *sin_t,
+                                  const double *poses, int F, int P, int n, int map0)
+{
+    REQUIRE_IN(fn, g && ranges && cos_t && sin_t && poses, "null pointer");
+    REQUIRE_IN(fn, F >= 1 && P >= 1 && n >= 1 && n <= 65535, "F < 1, P < 1 or n outside [1, 65535]");
+    REQUIRE_IN(fn, map0 >= 0 && (long)map0 + (long)F * P <= g->d.G, "map0 < 0 or map0 + F * P > G");
+    return SLAM_OK;
+}
+
+int slam_grid_update_particles_dev(slam_ctx *c, slam_grid *g, const float *ranges, const double *cos_t, const double *sin_t,
+                                   const double *poses, const int32_t *acc, int F, int P, int n, int map0)
+{
+    TRY(use(c));
+    TRY(check_update_particles(__func__, g, ranges, cos_t, sin_t, poses, F, P, n, map0));
+    TRY(grid_on_main(c));
+    // One scan per particle into its own map, through the window path as slam_particles_dev casts its hypotheses: a live
+    // pmap stays current.  A launch takes at most 65 535 particles (one workgroup row each).
+    g->pristine = false;
+    const long L = (long)F * P, span = 65535;
+    Timed t(c, SLAM_K_GRID);
+    for (long l0 = 0; l0 < L; l0 += span) {
+        const int cnt = (int)std::min(span, L - l0);
+        GridDev d = g->d;                                              // the chunk's maps
+        const size_t off = ((size_t)map0 + (size_t)l0) * d.xw * d.yw;
+        d.G = cnt; d.pass += off; d.hit += off;
+        if (d.pmap_live) d.pmap_live += off;
+        CastRequest r;
+        r.ranges = ranges; r.cos_t = cos_t; r.sin_t = sin_t; r.poses = poses + 3 * (size_t)l0; r.acc = acc ? acc + l0 : nullptr;
+        r.L = cnt; r.scans = 1; r.n = n; r.particles = true; r.per_filter = P; r.first_particle = l0; r.group = 1;
+        r.lds_hits = c->win_lds_hits;
+        HIPCHK(launch_cast(d, plan_cast(d, c->grid_mode, r), r, nullptr, c->stream));
+    }
+    return SLAM_OK;
+}
+
+int slam_grid_update_particles(slam_ctx *c, slam_grid *g, const float *ranges, const double *cos_t, const double *sin_t,
+                               const double *poses, const int32_t *acc, int F, int P, int n, int map0)
+{
+    TRY(use(c));
+    TRY(check_update_particles(__func__, g, ranges, cos_t, sin_t, poses, F, P, n, map0));
+    const size_t FP = (size_t)F * P;
+    float *d_r; double *d_c, *d_s, *d_p; int32_t *d_a;
+    Staging s(c);
+    s.in(d_r, ranges, (size_t)F * n).in(d_c, cos_t, n).in(d_s, sin_t, n).in(d_p, poses, FP * 3).in(d_a, acc, FP);
+    TRY(s.upload());
+    TRY(slam_grid_update_particles_dev(c, g, d_r, d_c, d_s, d_p, d_a, F, P, n, map0));
+    return check_status_sync(c);
 }
 
 int slam_bresenham_batch(slam_ctx *c, const int32_t *starts, const int32_t *ends, int B, const int64_t *offsets,

@@ -158,6 +158,11 @@ struct CastRequest {
     int L = 1, scans = 0, n = 0;
     const int32_t *maps = nullptr;         // nullable: the map of every scan (explicit) or trajectory (replay)
     bool particles = false;                // every trajectory reads the same two scans and casts into map l of its own
+    // with `particles` (slam_grid_update_particles): per_filter = P > 0: trajectory l is particle first_particle + l of F filters
+    // of P; it reads scan (first_particle + l) / P of ranges [F][n] and poses[l], and casts nothing when acc[l] is SLAM_MCL_DEAD
+    int per_filter = 0;
+    long first_particle = 0;
+    const int32_t *acc = nullptr;          // nullable [L]
     int group = 0, split = -1;             // scans per workgroup (0: automatic); window split in two (-1: automatic, 0, 1)
     int lds_hits = -1;                     // context option "win_lds_hits": hits of sorted window rays counted in LDS, one add per end cell: -1 = in chip-filling launches, 0 = off, 1 = on
 };
@@ -165,6 +170,8 @@ CastPath plan_cast(const GridDev &g, int grid_mode, const CastRequest &r);
 size_t cast_scratch_bytes(CastPath p, const CastRequest &r);
 hipError_t launch_cast(const GridDev &g, CastPath p, const CastRequest &r, void *scratch, hipStream_t s);
 hipError_t launch_grid_finalize(const GridDev &g, int g0, int gcount, int8_t *pmap, hipStream_t s);
+// slam_grid_copy_maps: map first + k becomes a copy of map src[k], counters and (when kept) live pmap; copied_out nullable [count]
+hipError_t launch_grid_copy_maps(const GridDev &g, const int32_t *src, int first, int count, int32_t *copied_out, hipStream_t s);
 hipError_t launch_grid_datamap(const GridDev &g, int gi, double *datamap, hipStream_t s);
 hipError_t launch_grid_transpose(const int8_t *pmap, int xw, int yw, int8_t *data, hipStream_t s);
 hipError_t launch_bresenham(const int32_t *starts, const int32_t *ends, int B, const int64_t *offsets,
@@ -231,6 +238,8 @@ struct MclWeighArgs {
     const float *ranges = nullptr;           // [F][n]
     const double *cos_t = nullptr, *sin_t = nullptr;
     const int32_t *maps = nullptr;           // nullable [F]: the map of every filter (an entry outside [0, G): every particle dead)
+    int own_maps = 0;                        // 1 (slam_mcl_weigh_maps): a map per PARTICLE, pmaps[f][p] or, pmaps null, map f * P + p
+    const int32_t *pmaps = nullptr;          // nullable [F][P] (own_maps only; an entry outside [0, G): that particle dead)
     int F = 0, P = 0, n = 0;
     float max_range = 0.f;
     int cap = 0;
@@ -264,6 +273,19 @@ struct MclResampleArgs {
 // shape: the context option "mcl_shape" (-1: by beam count, 0: lanes over particles, 1: a wave per particle)
 hipError_t launch_mcl_weigh(MclWeighArgs a, int shape, hipStream_t s);
 hipError_t launch_mcl_resample(MclResampleArgs a, hipStream_t s);
+constexpr int kMclSettleMaxP = 4096;         // three int arrays of P in LDS: 48 KiB
+// slam_mcl_settle: every surviving particle keeps its slot; every output but settled is nullable
+struct MclSettleArgs {
+    const int32_t *ancestors = nullptr;      // [F][P]; an entry outside [0, P) is clamped into it
+    const double *poses_src = nullptr;       // nullable [F][P][3]
+    int F = 0, P = 0, map0 = 0;
+    int32_t *settled = nullptr;              // [F][P]
+    double *poses_out = nullptr;             // [F][P][3]
+    int32_t *map_src = nullptr;              // [F][P]
+    int32_t *moved = nullptr;                // [F]
+    int *status = nullptr;
+};
+hipError_t launch_mcl_settle(const MclSettleArgs &a, hipStream_t s);
 
 // ---- scan-to-map observation ---------------------------------------
 hipError_t launch_map_obstacles(const int8_t *map, int width, int height, int wire, double resolution, double origin_x,

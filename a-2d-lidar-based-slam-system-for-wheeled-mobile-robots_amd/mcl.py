@@ -9,6 +9,7 @@ batch it runs in.
 
     mcl_weight_table     the table: rint(2^20 exp(-(k << shift) / (2 sigma^2)))
     mcl_weigh_host / mcl_resample_host    the two operators on NumPy arrays
+    mcl_settle_host      ``slam_mcl_settle``: the resampled set rearranged so that every survivor keeps its slot
     DeviceMCL            device-resident filters on a DeviceGrid, steps enqueued without a synchronise
     MCL                  one filter on a ``Mapping``, NumPy in and out
 """
@@ -40,12 +41,16 @@ def _opt(a, dtype, shape):
 
 
 def mcl_weigh_host(grid, poses, ranges, cos_t, sin_t, motion=None, noise=None, max_range=30.0, cap=64, grid_of_filter=None,
-                   field=None, acc=None):
+                   field=None, acc=None, grid_of_particle=None, own_maps=False):
     """``slam_mcl_weigh`` on NumPy arrays: poses [F, P, 3], ranges float32 [F, n], cos_t / sin_t [n], motion [F, 3],
     noise [F, P, 3] (only with motion), grid_of_filter int32 [F], field int16 [G, xw, yw] as ``grid_distance_field_host``
     gives it at the same ``cap`` (None: rebuilt), acc int32 [F, P] (None: nothing is accumulated).  Returns (poses
     after the motion, cost int32 [F, P] with -1 for dead particles, acc or None, used int32 [F]); the inputs are not
-    changed."""
+    changed.  ``grid_of_particle`` int32 [F, P] or ``own_maps=True`` (particle (f, p) on map f * P + p) take
+    ``slam_mcl_weigh_maps``: every particle is weighed on its own map."""
+    if grid_of_particle is not None or own_maps:
+        if grid_of_filter is not None:
+            raise ValueError("grid_of_filter and grid_of_particle / own_maps exclude each other")
     p = np.array(poses, dtype=np.float64, order="C")
     if p.ndim != 3 or p.shape[2] != 3:
         raise ValueError("poses must be [F, P, 3]")
@@ -58,11 +63,30 @@ def mcl_weigh_host(grid, poses, ranges, cos_t, sin_t, motion=None, noise=None, m
     f = None if field is None else np.ascontiguousarray(np.asarray(field, dtype=np.int16))
     cost, used = np.empty((F, P), dtype=np.int32), np.empty(F, dtype=np.int32)
     ch, gh = _handles(grid)
-    _abi.check(_abi.lib().slam_mcl_weigh(ch, gh, _abi.ptr(p), _abi.ptr(_opt(motion, np.float64, (F, 3))),
-                                         _abi.ptr(_opt(noise, np.float64, (F, P, 3))), _abi.ptr(r), _abi.ptr(ct), _abi.ptr(st),
-                                         _abi.ptr(_opt(grid_of_filter, np.int32, (F,))), F, P, n, float(max_range), int(cap),
-                                         _abi.ptr(f), _abi.ptr(a), _abi.ptr(cost), _abi.ptr(used)))
+    own = grid_of_particle is not None or own_maps
+    fn = _abi.lib().slam_mcl_weigh_maps if own else _abi.lib().slam_mcl_weigh
+    maps = _opt(grid_of_particle, np.int32, (F, P)) if own else _opt(grid_of_filter, np.int32, (F,))
+    _abi.check(fn(ch, gh, _abi.ptr(p), _abi.ptr(_opt(motion, np.float64, (F, 3))), _abi.ptr(_opt(noise, np.float64, (F, P, 3))),
+                  _abi.ptr(r), _abi.ptr(ct), _abi.ptr(st), _abi.ptr(maps), F, P, n, float(max_range), int(cap), _abi.ptr(f), _abi.ptr(a),
+                  _abi.ptr(cost), _abi.ptr(used)))
     return p, cost, a, used
+
+
+def mcl_settle_host(context, ancestors, poses_src=None, map0=0):
+    """``slam_mcl_settle`` on NumPy arrays: ancestors int32 [F, P] as ``mcl_resample_host`` gives them, poses_src
+    [F, P, 3] the particles BEFORE that resampling (or None).  Every surviving particle keeps its slot; the slots of
+    particles that died take the surplus copies in ascending order.  Returns (settled int32 [F, P], poses [F, P, 3] =
+    poses_src[settled] or None, map_src int32 [F, P] = map0 + f * P + settled, moved int32 [F])."""
+    anc = np.ascontiguousarray(np.asarray(ancestors, dtype=np.int32))
+    if anc.ndim != 2:
+        raise ValueError("ancestors must be [F, P]")
+    F, P = anc.shape
+    src = _opt(poses_src, np.float64, (F, P, 3))
+    settled, map_src, moved = np.empty((F, P), dtype=np.int32), np.empty((F, P), dtype=np.int32), np.empty(F, dtype=np.int32)
+    out = None if src is None else np.empty((F, P, 3), dtype=np.float64)
+    _abi.check(_abi.lib().slam_mcl_settle(context.handle, _abi.ptr(anc), _abi.ptr(src), F, P, int(map0), _abi.ptr(settled),
+                                          _abi.ptr(out), _abi.ptr(map_src), _abi.ptr(moved)))
+    return settled, out, map_src, moved
 
 
 def mcl_resample_host(context, poses, acc, table, u0, shift=0, ess_frac=0.5):

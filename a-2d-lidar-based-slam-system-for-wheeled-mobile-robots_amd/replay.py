@@ -186,6 +186,26 @@ def grid_match_host(grid, ranges, centres, cos_t, sin_t, rot_cs, nx, ny, step, m
     return (best, cost, used, vol) if return_costs else (best, cost, used)
 
 
+def grid_copy_maps_host(grid, src, first=0):
+    """``slam_grid_copy_maps`` on a NumPy array: map ``first + k`` of ``grid`` becomes a copy of map ``src[k]``.  Returns
+    int32 [count]: 1 copied, 0 kept (its own map, or no map).  A source that is itself a destination raises."""
+    s = np.ascontiguousarray(np.asarray(src, dtype=np.int32).reshape(-1))
+    out = np.empty(s.shape[0], dtype=np.int32)
+    _abi.check(_abi.lib().slam_grid_copy_maps(grid._ctx.handle, grid._h, _abi.ptr(s), int(first), s.shape[0], _abi.ptr(out)))
+    return out
+
+
+def grid_update_particles_host(grid, ranges, cos_t, sin_t, poses, acc=None, map0=0):
+    """``slam_grid_update_particles`` on NumPy arrays: ranges [F, n], poses [F, P, 3], acc int32 [F, P] or None."""
+    p = np.ascontiguousarray(np.asarray(poses, dtype=np.float64))
+    F, P = p.shape[:2]
+    ct, st = _tables(cos_t, sin_t)
+    r = np.ascontiguousarray(np.asarray(ranges, dtype=np.float32).reshape(F, ct.shape[0]))
+    a = None if acc is None else np.ascontiguousarray(np.asarray(acc, dtype=np.int32).reshape(F, P))
+    _abi.check(_abi.lib().slam_grid_update_particles(grid._ctx.handle, grid._h, _abi.ptr(r), _abi.ptr(ct), _abi.ptr(st), _abi.ptr(p),
+                                                     _abi.ptr(a), F, P, ct.shape[0], int(map0)))
+
+
 def match_rotations(thetas, n_rot=11, rot_step=0.01):
     """(angles [B, K], rot_cs [B, K, 2]) of the matcher's rotations: theta + (k - n_rot // 2) * rot_step, cosine
     and sine by NumPy."""
@@ -336,6 +356,26 @@ class DeviceGrid:
                                                   int(cap), _abi.ptr(best_out), _abi.ptr(cost_out), _abi.ptr(used_out),
                                                   _abi.ptr(costs_out)))
         return (best_out, cost_out, used_out) if costs_out is None else (best_out, cost_out, used_out, costs_out)
+
+    def copy_maps(self, src, first=0, out=None):
+        """``slam_grid_copy_maps_dev``: map ``first + k`` becomes a copy of map ``src[k]`` (torch int32 device tensor
+        [count]), counters and live pmap, in place.  An entry that names its own map or no map keeps it (0 in the
+        result); a source that is itself a destination of the call leaves that destination alone (-1); otherwise 1.
+        Writes int32 [count] into ``out`` or a fresh tensor; no synchronise."""
+        import torch
+        count = int(src.shape[0])
+        if out is None:
+            out = torch.empty((count,), dtype=torch.int32, device=src.device)
+        _abi.check(_abi.lib().slam_grid_copy_maps_dev(self._ctx.handle, self._h, _abi.ptr(src), int(first), count, _abi.ptr(out)))
+        return out
+
+    def update_particles(self, ranges, cos_t, sin_t, poses, acc=None, map0=0):
+        """``slam_grid_update_particles_dev`` on torch device tensors: ranges float32 [F, n], poses float64 [F, P, 3],
+        acc int32 [F, P] or None.  Scan f is integrated from every pose of filter f into map ``map0 + f * P + p`` as
+        ``slam_grid_update_scans`` would; a particle whose acc is ``MCL_DEAD`` casts nothing.  No synchronise."""
+        F, P, n = int(poses.shape[0]), int(poses.shape[1]), int(cos_t.shape[0])
+        _abi.check(_abi.lib().slam_grid_update_particles_dev(self._ctx.handle, self._h, _abi.ptr(ranges), _abi.ptr(cos_t),
+                                                             _abi.ptr(sin_t), _abi.ptr(poses), _abi.ptr(acc), F, P, n, int(map0)))
 
     def read(self, g=0, want=("pmap",)):
         out = {}

@@ -480,6 +480,58 @@ int slam_mcl_resample_dev(slam_ctx *ctx, const double *poses, int32_t *acc, cons
                           const double *u0, double ess_frac, int F, int P, double *poses_out, int32_t *ancestors_out,
                           double *est_out, int32_t *info_out);
 
+/* ---- grid FastSLAM: a map per particle that follows resampling --------------------------------- */
+/* Particle (f, p) of F filters of P particles owns map map0 + f*P + p of the grid.  A step of the filter is five calls:
+ * slam_mcl_weigh_maps (every particle on ITS OWN map), slam_mcl_resample, slam_mcl_settle (every survivor keeps its
+ * slot), slam_grid_copy_maps (only the maps of slots whose particle died are copied, in place, from a survivor's map
+ * that nobody overwrites) and slam_grid_update_particles (the scan integrated from every particle).  The reference has
+ * no counterpart.  Everything that decides an index is integer.  The new kernels count as SLAM_K_GRID, the field build
+ * as SLAM_K_FINALIZE.  A failed up-front check is SLAM_ERR_INVALID, enqueues nothing and leaves the context as it was.
+ *
+ * slam_mcl_weigh_maps: slam_mcl_weigh with grid_of_particle int32 [F][P] where grid_of_filter stands; NULL: particle
+ *   (f, p) reads map f*P + p, which needs F*P <= G.  Every other argument and rule is slam_mcl_weigh's, with the
+ *   PARTICLE's map entry outside [0, G) in place of the filter's among the "dead" rules.
+ *
+ * slam_mcl_settle: per filter, cnt[i] = the number of slots j with ancestors[j] == i.  A slot with cnt[i] >= 1 gets
+ *   settled[i] = i; the free slots (cnt == 0), in ascending order, receive in ascending order the surplus list: every i
+ *   repeated cnt[i] - 1 times (the two lists are equally long).  The identity gives the identity; the ancestors need
+ *   not be monotone.  No slot that is a source (settled[j] for some j != itself) is a destination.
+ *   poses_out[j] = poses_src[settled[j]] (poses_src: the particles BEFORE slam_mcl_resample gathered them; must not be
+ *   poses_out); map_src_out[f][p] = map0 + f*P + settled[f][p]; moved_out[f] = the slots with settled[j] != j.
+ *   ancestors, settled_out int32 [F][P]; poses_src, poses_out, map_src_out, moved_out nullable.  F >= 1,
+ *   1 <= P <= 4096, F*P < 2^31, map0 >= 0, map0 + F*P < 2^31.  The host form rejects an ancestor outside [0, P), the
+ *   device form clamps it into the range.
+ *
+ * slam_grid_copy_maps: for k < count, map d = first + k becomes a copy of map s = src[k]: pass, hit and, when the grid
+ *   keeps one, the live pmap (one that was current stays current).  s == d or s outside [0, G): the map is kept and
+ *   copied_out[k] (nullable int32 [count]) is 0.  A source that is itself a destination of this call (first <= s <
+ *   first + count and src[s - first] != s) is SLAM_ERR_INVALID in the host form; in the device form that destination is
+ *   left unchanged and copied_out[k] is -1.  Otherwise copied_out[k] is 1.  first >= 0, count >= 1, first + count <= G.
+ *   The visit counters of slam_grid_visits are not touched.
+ *
+ * slam_grid_update_particles: for every (f, p) exactly what slam_grid_update_scans does for the one scan ranges[f]
+ *   (float32 [F][n]) at pose poses[f][p] (float64 [F][P][3]; centres NULL, inf -> 30 m), into map map0 + f*P + p.  A
+ *   particle with acc[f][p] == SLAM_MCL_DEAD (acc nullable int32 [F][P]) casts nothing and raises no sticky status.
+ *   n <= 65535, map0 >= 0, map0 + F*P <= G.  The host form ends with the status check of slam_grid_update_scans. */
+int slam_mcl_weigh_maps(slam_ctx *ctx, slam_grid *grid, double *poses, const double *motion, const double *noise,
+                        const float *ranges, const double *cos_t, const double *sin_t, const int32_t *grid_of_particle, int F,
+                        int P, int n, float max_range, int cap, const int16_t *field, int32_t *acc, int32_t *cost_out,
+                        int32_t *used_out);
+int slam_mcl_weigh_maps_dev(slam_ctx *ctx, slam_grid *grid, double *poses, const double *motion, const double *noise,
+                            const float *ranges, const double *cos_t, const double *sin_t, const int32_t *grid_of_particle,
+                            int F, int P, int n, float max_range, int cap, const int16_t *field, int32_t *acc,
+                            int32_t *cost_out, int32_t *used_out);
+int slam_mcl_settle(slam_ctx *ctx, const int32_t *ancestors, const double *poses_src, int F, int P, int map0,
+                    int32_t *settled_out, double *poses_out, int32_t *map_src_out, int32_t *moved_out);
+int slam_mcl_settle_dev(slam_ctx *ctx, const int32_t *ancestors, const double *poses_src, int F, int P, int map0,
+                        int32_t *settled_out, double *poses_out, int32_t *map_src_out, int32_t *moved_out);
+int slam_grid_copy_maps(slam_ctx *ctx, slam_grid *grid, const int32_t *src, int first, int count, int32_t *copied_out);
+int slam_grid_copy_maps_dev(slam_ctx *ctx, slam_grid *grid, const int32_t *src, int first, int count, int32_t *copied_out);
+int slam_grid_update_particles(slam_ctx *ctx, slam_grid *grid, const float *ranges, const double *cos_t, const double *sin_t,
+                               const double *poses, const int32_t *acc, int F, int P, int n, int map0);
+int slam_grid_update_particles_dev(slam_ctx *ctx, slam_grid *grid, const float *ranges, const double *cos_t,
+                                   const double *sin_t, const double *poses, const int32_t *acc, int F, int P, int n, int map0);
+
 /* Replaces bresenham(start, end).path (W12m/bresenham.py:2-58), B lines at once.
  * starts, ends [B][2] int32.  lens_out [B] receives each path length; cells_out (may be
  * NULL) receives the paths, line b at cells_out + 2*offsets[b] (x, y interleaved), with
