@@ -8,7 +8,8 @@ zjwzcx/A-2D-LiDAR-based-SLAM-System-for-Wheeled-Mobile-Robots:
     Mapping    update -> pmap; raycast / score_scan read the map along rays (batched: DeviceGrid.raycast /
                .score, grid_raycast_host / grid_score_host); distance_field / match_scan: where a scan fits
                the map best (batched: DeviceGrid.distance_field / .match, grid_distance_field_host /
-               grid_match_host, match_pose)
+               grid_match_host, match_pose); locate_scan: where in the whole map a scan was taken (batched:
+               DeviceGrid.locate, grid_locate_host, locate_rotations, locate_pose; MCL.init_global starts from it)
     bresenham  (start, end).path
     SLAM_EKF   laserCallback glue (scan matching + map building); landmarks=True: the whole W12
                node with Extraction and the landmark EKF on the host; batched on the device
@@ -50,6 +51,7 @@ from .node_replay import DeviceNodeReplay, ekf_lm_host, landmarks_host, node_rep
 from .replay import DeviceGrid, DeviceReplay, grid_raycast_host, grid_score_host, icp_batch_host, particles_host, prior_matrices, replay_host
 from .replay import grid_distance_field_host, grid_match_host, match_pose, match_rotations
 from .replay import grid_copy_maps_host, grid_update_particles_host
+from .replay import grid_locate_host, locate_pose, locate_rotations
 from .grid_slam import DeviceGridSLAM, GridSLAM
 from .slam_ekf import SLAM_EKF
 from .synthetic import LaserScan
@@ -61,6 +63,7 @@ __all__ = ["ICP", "Mapping", "Localization", "EKF", "Extraction", "LandMarkSet",
            "DeviceNodeReplay", "node_replay_host", "landmarks_host", "ekf_lm_host",
            "DeviceLocalizationReplay", "loc_replay_host", "grid_raycast_host", "grid_score_host",
            "grid_distance_field_host", "grid_match_host", "match_pose", "match_rotations",
+           "grid_locate_host", "locate_pose", "locate_rotations",
            "MCL", "DeviceMCL", "MCL_DEAD", "mcl_weight_table", "mcl_weigh_host", "mcl_resample_host",
            "GridSLAM", "DeviceGridSLAM", "mcl_settle_host", "grid_copy_maps_host", "grid_update_particles_host",
            "RAY_EMPTY", "RAY_HIT", "RAY_BLOCKED", "RAY_FREE", "RAY_UNKNOWN", "RAY_OUT", "RAY_BAD", "RAY_CLASSES", "RAY_NAMES"]

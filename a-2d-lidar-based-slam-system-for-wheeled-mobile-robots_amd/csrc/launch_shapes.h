@@ -465,4 +465,83 @@ inline CopyShape plan_copy_maps(long cells, long count)
     return p;
 }
 
+// ---------------------------------------------------------------------------------
+// Global scan localisation (locate_kernels.hip, slam_grid_locate)
+// ---------------------------------------------------------------------------------
+// Two shapes, by what the node counts of a search say:
+//   dense   the top level, every node of every rotation: a workgroup takes (pair = hypothesis x rotation, tile of nodes),
+//           stages the rotation's cell offsets in LDS once and runs its lanes over the tile's nodes, each lane looping
+//           over the beams - as k_match does.  A tile is kLocateTileRounds rounds of the workgroup, so that the staging
+//           (a few float64 products per beam) is paid once per 4 096 nodes and a brute-force rotation of a large map
+//           still spreads over many workgroups.
+//   sparse  the survivors' children: a lane per child, looping over its pair's row of a table of packed offsets that the
+//           dense pass of the chunk left in global memory; grid-stride over a list whose length is read on the device;
+//           the launch is sized by the chip, not the list.  (A wave per node with its lanes over the beams - what lists
+//           of tens to thousands of nodes suggest - was built first and measured: the offsets formed in float64 per
+//           node and one atomic per survivor made 64 scans slower than brute force)
+// The node lists and the table live in a budget (context option "locate_ws_mb"): level h of one pair holds at most every
+// node of that level (an empty map: everything ties and survives), kLocateNodeBytes each; pairs are taken in chunks that fit.
+constexpr int kLocateMaxLevels = 8;
+constexpr int kLocateMaxBeams = 4096;
+constexpr int kLocateThreads = 256;
+constexpr int kLocateTileRounds = 16;
+constexpr size_t kLocateOffsetBytes = 8;     // an (ax, ay) pair of int32 in LDS
+constexpr size_t kLocateNodeBytes = 8;       // a list entry: pair, I * nJ + J
+constexpr long kLocateMaxBlocks = 1L << 20;  // workgroups of a dense launch; more groups are taken grid-stride
+constexpr int kLocateSweepBlocks = 2048;     // workgroups of a sparse launch: eight per CU of 256
+
+SLAM_HD inline long locate_level_nodes(int ni, int nj, int h)
+{
+    const long s = 1L << h;
+    return ((ni + s - 1) / s) * ((nj + s - 1) / s);
+}
+// worst-case bytes of one pair's lists: the survivors of levels H .. 1
+SLAM_HD inline long locate_pair_bytes(int ni, int nj, int H)
+{
+    long nodes = 0;
+    for (int h = 1; h <= H; ++h) nodes += locate_level_nodes(ni, nj, h);
+    return nodes * (long)kLocateNodeBytes;
+}
+// a pair's row of the sweep's offset table and its two counts (H = 0 keeps neither lists nor table)
+SLAM_HD inline long locate_table_bytes(int n) { return (long)n * (long)kLocateOffsetBytes + 8; }
+SLAM_HD inline size_t locate_dense_lds(int n, int guard = kLdsGuard) { return (size_t)n * kLocateOffsetBytes + guard; }
+SLAM_HD inline int locate_dense_threads(long nodes)
+{
+    return (int)std::min((long)kLocateThreads, (nodes + kWave - 1) / kWave * kWave);
+}
+
+struct LocateRequest {
+    long pairs = 0;              // B * K
+    int n = 0, ni = 0, nj = 0;   // beams; the largest region of the batch
+    int H = 0;
+    long ws_bytes = 0;           // the list budget
+    int guard = kLdsGuard;
+};
+struct LocateShape {
+    bool ok = false;             // false: one pair's worst-case lists do not fit the budget
+    int dense_threads = 0, dense_lds = 0;
+    long tile = 0, tiles = 0;    // top-level nodes per workgroup, workgroups per pair
+    long pair_bytes = 0;         // lists and table row of one pair
+    long chunk_pairs = 0, chunks = 0;
+    long level_nodes[kLocateMaxLevels + 1] = {0};   // worst-case nodes of level h of one pair
+    int sweep_threads = kLocateThreads;
+};
+inline LocateShape plan_locate(const LocateRequest &r)
+{
+    LocateShape p;
+    if (r.pairs < 1 || r.n < 1 || r.ni < 1 || r.nj < 1 || r.H < 0 || r.H > kLocateMaxLevels) return p;
+    for (int h = 0; h <= r.H; ++h) p.level_nodes[h] = locate_level_nodes(r.ni, r.nj, h);
+    const long top = p.level_nodes[r.H];
+    p.dense_threads = locate_dense_threads(top);
+    p.dense_lds = (int)locate_dense_lds(r.n, r.guard);
+    p.tile = (long)p.dense_threads * kLocateTileRounds;
+    p.tiles = (top + p.tile - 1) / p.tile;
+    p.pair_bytes = locate_pair_bytes(r.ni, r.nj, r.H) + (r.H ? locate_table_bytes(r.n) : 0);
+    p.chunk_pairs = p.pair_bytes ? std::min(r.pairs, r.ws_bytes / p.pair_bytes) : r.pairs;   // H = 0 keeps no list
+    if (p.chunk_pairs < 1) return p;
+    p.chunks = (r.pairs + p.chunk_pairs - 1) / p.chunk_pairs;
+    p.ok = true;
+    return p;
+}
+
 }  // namespace slam

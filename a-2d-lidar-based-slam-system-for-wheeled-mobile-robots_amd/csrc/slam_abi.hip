@@ -104,6 +104,7 @@ struct slam_ctx {
     int icp_one_wave = -1; // scan matching with one wave per pair: -1 = where a full-chip launch allows it, 0 = never, 1 = wherever a pair fits
     int raycast_lds = -1; // rays traced through a map: -1 = automatic, 0 = mask words from global memory, 1 = from LDS wherever the mask fits
     int mcl_shape = -1;   // slam_mcl_weigh: -1 = the library's choice by beam count, 0 = lanes over particles, 1 = a wave per particle, lanes over beams; changes no result
+    long locate_ws_bytes = 64L << 20; // slam_grid_locate: bytes its node lists may take ("locate_ws_mb"); pairs are cut into chunks that fit; changes no result
     int icp_team = 0;     // first-iteration queries without a beam window: 0 = listed and searched apart from their lanes (nn_listed), 1 = box search
     // "pipeline" option: the map stage of slam_replay_dev (reset -> ray cast -> finalize) runs on
     // a second stream, so the map stage of one replay overlaps the scan matching of the next.
@@ -712,6 +713,7 @@ static const OptionRange kOptionRanges[] = {
     {"pipeline", [](double v) { return v == 0 || v == 1; }, "pipeline is 0 or 1"},
     {"raycast_lds", [](double v) { return v == -1 || v == 0 || v == 1; }, "raycast_lds is -1, 0 or 1"},
     {"mcl_shape", [](double v) { return v == -1 || v == 0 || v == 1; }, "mcl_shape is -1, 0 or 1"},
+    {"locate_ws_mb", [](double v) { return v > 0 && v <= 1048576; }, "locate_ws_mb in (0, 1048576]"},
 };
 
 int slam_set_option(slam_ctx *c, const char *name, double value)
@@ -735,6 +737,7 @@ int slam_set_option(slam_ctx *c, const char *name, double value)
     else if (!strcmp(name, "icp_qpt")) c->icp_qpt = (int)value;
     else if (!strcmp(name, "raycast_lds")) c->raycast_lds = (int)value;
     else if (!strcmp(name, "mcl_shape")) c->mcl_shape = (int)value;
+    else if (!strcmp(name, "locate_ws_mb")) c->locate_ws_bytes = (long)(value * 1048576.0);
     else if (!strcmp(name, "pipeline")) {
         TRY(join_from_grid(c));
         if (value == 1 && !c->gstream) {
@@ -840,6 +843,20 @@ int slam_plan_win_phases(const int32_t bbox[4], const int32_t origins[4], int xw
     return SLAM_OK;
 }
 
+static LocateShape locate_plan_for(int ni, int nj, int H, long pairs, long ws_bytes, int guard)
+{
+    LocateRequest r;
+    r.pairs = pairs; r.n = 1; r.ni = ni; r.nj = nj; r.H = H; r.ws_bytes = ws_bytes; r.guard = guard;
+    return plan_locate(r);
+}
+
+// pairs per chunk for a budget and a pair's worst-case bytes, as plan_locate cuts them (0: one pair does not fit)
+static int64_t locate_plan_chunk(long ws_bytes, long pair_bytes, long pairs)
+{
+    if (pairs < 1 || pair_bytes < 0) return 0;
+    return pair_bytes ? std::min(pairs, ws_bytes / pair_bytes) : pairs;
+}
+
 int slam_plan_query(const char *name, int a, int b, int c, int guard, int64_t *out)
 {
     if (!name || !out) return fail(SLAM_ERR_INVALID, "slam_plan_query: null pointer");
@@ -865,6 +882,16 @@ int slam_plan_query(const char *name, int a, int b, int c, int guard, int64_t *o
         {"kCopyThreads", kCopyThreads}, {"kCopyChunkCells", kCopyChunkCells}, {"kCopyMaxGroups", (int64_t)kCopyMaxGroups},
         {"copy_chunks", (int64_t)plan_copy_maps((long)a * b, c).chunks}, {"copy_groups", (int64_t)plan_copy_maps((long)a * b, c).groups},
         {"copy_grid", (int64_t)plan_copy_maps((long)a * b, c).grid}, {"copy_threads", plan_copy_maps((long)a * b, c).threads},
+        // slam_grid_locate: a = ni, b = nj, c = level (locate_level_nodes) or levels (locate_pair_bytes, locate_tile*: the top level's
+        // nodes per workgroup and workgroups per pair); locate_dense_lds: a = n; locate_dense_threads: a = nodes;
+        // locate_table_bytes: a = n; locate_chunk_pairs: a = the budget in KiB, b = locate_pair_bytes + locate_table_bytes, c = pairs
+        {"kLocateMaxLevels", kLocateMaxLevels}, {"kLocateMaxBeams", kLocateMaxBeams}, {"kLocateThreads", kLocateThreads},
+        {"kLocateTileRounds", kLocateTileRounds}, {"kLocateNodeBytes", (int64_t)kLocateNodeBytes}, {"kLocateSweepBlocks", kLocateSweepBlocks},
+        {"locate_level_nodes", (c >= 0 && c <= kLocateMaxLevels) ? locate_level_nodes(a, b, c) : 0},
+        {"locate_pair_bytes", (c >= 0 && c <= kLocateMaxLevels) ? locate_pair_bytes(a, b, c) : 0},
+        {"locate_table_bytes", locate_table_bytes(a)}, {"locate_dense_lds", (int64_t)locate_dense_lds(a, g)}, {"locate_dense_threads", locate_dense_threads(a)},
+        {"locate_tile", locate_plan_for(a, b, c, 1, 1L << 40, g).tile}, {"locate_tiles", locate_plan_for(a, b, c, 1, 1L << 40, g).tiles},
+        {"locate_chunk_pairs", locate_plan_chunk((long)a * 1024, b, c)},
     };
     for (const Entry &e : table)
         if (!strcmp(e.name, name)) { *out = e.value; return SLAM_OK; }
@@ -1619,6 +1646,123 @@ int slam_grid_match(slam_ctx *c, slam_grid *g, const float *ranges, int shared, 
     TRY(s.upload());
     TRY(slam_grid_match_dev(c, g, d_r, shared, d_ctr, B, d_g, d_c, d_s, n, d_rot, K, nx, ny, step, max_range, cap, d_best,
                             d_cost, d_used, d_vol));
+    return s.download();
+}
+
+// ---- global scan localisation (locate_kernels.hip) ------------------------------------------------------------------
+// Everything the host can check, and the plan.  max_ni, max_nj: the largest region of the batch where the host knows the
+// regions (the host form), else the map (the device form: a region the device finds outside the map costs its hypothesis
+// its answer, as a map entry outside [0, G) does).
+static int check_locate(const char *fn, const slam_ctx *c, const slam_grid *g, const float *ranges, int B, const double *cos_t,
+                        const double *sin_t, int n, const double *rot_cs, int K, int max_ni, int max_nj, int levels,
+                        float max_range, int cap, const int32_t *best_out, const int32_t *best_cost_out, LocateShape &plan)
+{
+    REQUIRE_IN(fn, g && ranges && cos_t && sin_t && rot_cs && best_out && best_cost_out, "null pointer");
+    REQUIRE_IN(fn, cap >= 1 && cap <= 32767, "cap outside [1, 32767]");
+    REQUIRE_IN(fn, n >= 1 && n <= kLocateMaxBeams, "n outside [1, 4096]");
+    REQUIRE_IN(fn, (long)n * cap < (1L << 31), "n * cap >= 2^31");
+    REQUIRE_IN(fn, B >= 1 && K >= 1, "B < 1 or K < 1");
+    REQUIRE_IN(fn, (long)B * K < (1L << 31), "B * K >= 2^31");
+    REQUIRE_IN(fn, levels >= 0 && levels <= kLocateMaxLevels, "levels outside [0, 8]");
+    REQUIRE_IN(fn, max_range > 0, "max_range must be > 0");
+    REQUIRE_IN(fn, (long)K * ((long)max_ni * max_nj) < (1L << 31), "K * ni * nj >= 2^31");
+    LocateRequest r;
+    r.pairs = (long)B * K; r.n = n; r.ni = max_ni; r.nj = max_nj; r.H = levels; r.ws_bytes = c->locate_ws_bytes;
+    plan = plan_locate(r);
+    if (!plan.ok)
+        return fail(SLAM_ERR_INVALID, "%s: the node lists and offsets of one rotation (%ld bytes at worst) do not fit the context option "
+                    "locate_ws_mb (%ld bytes)", fn, plan.pair_bytes, c->locate_ws_bytes);
+    return SLAM_OK;
+}
+
+static int locate_dev(const char *fn, slam_ctx *c, slam_grid *g, const float *ranges, int shared, int B,
+                      const int32_t *grid_of_batch, const double *cos_t, const double *sin_t, int n, const double *rot_cs, int K,
+                      const int32_t *region, int max_ni, int max_nj, int levels, float max_range, int cap, int32_t *best_out,
+                      int32_t *best_cost_out, int32_t *used_out, int64_t *stats_out)
+{
+    LocateShape plan;
+    TRY(check_locate(fn, c, g, ranges, B, cos_t, sin_t, n, rot_cs, K, max_ni, max_nj, levels, max_range, cap, best_out,
+                     best_cost_out, plan));
+    const int H = levels;
+    const size_t pyr_cells = locate_pyramid_cells(g->d, H), keys = 2 * (size_t)B, evals = (size_t)B * (H + 1);
+    size_t extra = align_up(pyr_cells * 2) + align_up((keys + evals) * 8) + 2 * align_up((size_t)B * 4) + align_up(64);
+    for (int h = 1; h <= H; ++h) extra += align_up((size_t)plan.chunk_pairs * plan.level_nodes[h] * kLocateNodeBytes);
+    const size_t rows = H ? (size_t)plan.chunk_pairs : 0;
+    extra += align_up(rows * n * kLocateOffsetBytes) + align_up(rows * 8);
+    int16_t *field = nullptr;
+    TRY(build_field(c, g, fn, cap, extra, field));
+    LocateArgs a;
+    int16_t *pyr = carve<int16_t>(c->scratch, pyr_cells);
+    unsigned long long *words = carve<unsigned long long>(c->scratch, keys + evals);
+    a.bound = carve<int32_t>(c->scratch, B);
+    a.used = carve<int32_t>(c->scratch, B);
+    a.list_len = carve<unsigned>(c->scratch, kLocateMaxLevels + 1);
+    bool carved = pyr && words && a.bound && a.used && a.list_len;
+    for (int h = 1; h <= H; ++h) {
+        a.list_cap[h] = plan.chunk_pairs * plan.level_nodes[h];
+        a.list[h] = carve<int32_t>(c->scratch, (size_t)a.list_cap[h] * 2);
+        carved = carved && a.list[h];
+    }
+    a.table = carve<int32_t>(c->scratch, rows * n * 2);
+    a.table_cnt = carve<int32_t>(c->scratch, rows * 2);
+    REQUIRE_IN(fn, carved && a.table && a.table_cnt, "internal: workspace");
+    a.key_top = words; a.key_leaf = words + B; a.evaluated = words + keys;
+    a.g = g->d;
+    a.ranges = ranges; a.range_stride = shared ? 0 : n;
+    a.maps = grid_of_batch; a.cos_t = cos_t; a.sin_t = sin_t; a.rot_cs = rot_cs; a.region = region;
+    a.B = B; a.n = n; a.K = K; a.H = H; a.max_ni = max_ni; a.max_nj = max_nj; a.max_range = max_range; a.cap = cap;
+    a.best_out = best_out; a.best_cost_out = best_cost_out; a.used_out = used_out; a.stats_out = stats_out;
+    HIPCHK(hipMemsetAsync(words, 0xff, keys * 8, c->stream));
+    HIPCHK(hipMemsetAsync(words + keys, 0, evals * 8, c->stream));
+    {
+        Timed t(c, SLAM_K_FINALIZE);      // the pyramid is part of the field: a pass over every cell of every map
+        HIPCHK(launch_locate_pyramid(a, field, pyr, c->stream));
+    }
+    Timed t(c, SLAM_K_GRID);
+    HIPCHK(launch_locate(a, plan, c->stream));
+    return SLAM_OK;
+}
+
+int slam_grid_locate_dev(slam_ctx *c, slam_grid *g, const float *ranges, int shared, int B, const int32_t *grid_of_batch,
+                         const double *cos_t, const double *sin_t, int n, const double *rot_cs, int K, const int32_t *region,
+                         int levels, float max_range, int cap, int32_t *best_out, int32_t *best_cost_out, int32_t *used_out,
+                         int64_t *stats_out)
+{
+    TRY(use(c));
+    REQUIRE(g, "null pointer");
+    return locate_dev(__func__, c, g, ranges, shared, B, grid_of_batch, cos_t, sin_t, n, rot_cs, K, region, g->d.xw, g->d.yw, levels,
+                      max_range, cap, best_out, best_cost_out, used_out, stats_out);
+}
+
+int slam_grid_locate(slam_ctx *c, slam_grid *g, const float *ranges, int shared, int B, const int32_t *grid_of_batch,
+                     const double *cos_t, const double *sin_t, int n, const double *rot_cs, int K, const int32_t *region, int levels,
+                     float max_range, int cap, int32_t *best_out, int32_t *best_cost_out, int32_t *used_out, int64_t *stats_out)
+{
+    TRY(use(c));
+    REQUIRE(g && B >= 1, "null pointer or B < 1");
+    int max_ni = g->d.xw, max_nj = g->d.yw;
+    if (region) {
+        max_ni = max_nj = 1;
+        for (int b = 0; b < B; ++b) {
+            const int32_t *r = region + 4 * (size_t)b;
+            if (r[0] < 0 || r[1] < 0 || r[2] < 1 || r[3] < 1 || (long)r[0] + r[2] > g->d.xw || (long)r[1] + r[3] > g->d.yw)
+                return fail(SLAM_ERR_INVALID, "%s: region[%d] = (%d, %d, %d, %d) is empty or not inside the map of %d x %d cells",
+                            __func__, b, r[0], r[1], r[2], r[3], g->d.xw, g->d.yw);
+            max_ni = std::max(max_ni, r[2]);
+            max_nj = std::max(max_nj, r[3]);
+        }
+    }
+    LocateShape plan;
+    TRY(check_locate(__func__, c, g, ranges, B, cos_t, sin_t, n, rot_cs, K, max_ni, max_nj, levels, max_range, cap, best_out,
+                     best_cost_out, plan));
+    float *d_r; double *d_c, *d_s, *d_rot; int32_t *d_g, *d_reg, *d_best, *d_cost, *d_used; int64_t *d_st;
+    Staging s(c);
+    s.in(d_r, ranges, shared ? (size_t)n : (size_t)B * n).in(d_g, grid_of_batch, B).in(d_c, cos_t, n).in(d_s, sin_t, n)
+        .in(d_rot, rot_cs, (size_t)K * 2).in(d_reg, region, (size_t)B * 4).out(d_best, best_out, (size_t)B * 3)
+        .out(d_cost, best_cost_out, B).out(d_used, used_out, B).out(d_st, stats_out, (size_t)B * (levels + 2));
+    TRY(s.upload());
+    TRY(locate_dev(__func__, c, g, d_r, shared, B, d_g, d_c, d_s, n, d_rot, K, d_reg, max_ni, max_nj, levels, max_range, cap, d_best,
+                   d_cost, d_used, d_st));
     return s.download();
 }
 

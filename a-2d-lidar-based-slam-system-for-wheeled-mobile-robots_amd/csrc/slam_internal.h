@@ -226,6 +226,47 @@ size_t field_rowd_bytes(const GridDev &g);   // workspace of launch_distance_fie
 hipError_t launch_distance_field(const GridDev &g, const uint32_t *mask, int cap, uint8_t *rowd, int16_t *field, hipStream_t s);
 hipError_t launch_match(MatchArgs a, hipStream_t s);
 
+// ---- global scan localisation on a pyramid of the field (locate_kernels.hip) --------------
+// Level h of the pyramid: P_h[x][y] for -pad <= x < xw, -pad <= y < yw (pad = 2^h - 1) at base[(gi * X + x + pad) * Y + y + pad];
+// cap everywhere else.  Level 0 is the field itself.
+struct LocateLevel {
+    const int16_t *base = nullptr;
+    int pad = 0, X = 0, Y = 0;
+};
+struct LocateArgs {
+    GridDev g;
+    LocateLevel lvl[kLocateMaxLevels + 1];
+    const float *ranges = nullptr;           // [B][n], or one [n] with range_stride 0
+    long range_stride = 0;
+    const int32_t *maps = nullptr;           // nullable [B]
+    const double *cos_t = nullptr, *sin_t = nullptr;
+    const double *rot_cs = nullptr;          // [K][2]
+    const int32_t *region = nullptr;         // nullable [B][4]
+    int B = 0, n = 0, K = 0, H = 0;
+    int max_ni = 0, max_nj = 0;              // what the lists were sized for: a larger region makes its hypothesis invalid
+    float max_range = 0.f;
+    int cap = 0;
+    // workspace, per hypothesis
+    unsigned long long *key_top = nullptr;   // [B] 0xff on entry: min of (LB << 32 | node index) over the level-H nodes
+    unsigned long long *key_leaf = nullptr;  // [B] 0xff on entry: min of (cost << 32 | flat) over the sweep's level-0 survivors
+    int32_t *bound = nullptr;                // [B] U, written by the descent
+    int32_t *used = nullptr;                 // [B] used beams, -1: the hypothesis names no map / no region
+    unsigned long long *evaluated = nullptr; // [B][H + 1] zero on entry: nodes evaluated per level below H
+    // workspace, per chunk of pairs
+    int32_t *list[kLocateMaxLevels + 1] = {nullptr};   // [h]: [list_cap[h]][2] survivors of level h: pair, I * nJ_h + J
+    long list_cap[kLocateMaxLevels + 1] = {0};
+    unsigned *list_len = nullptr;            // [kLocateMaxLevels + 1] zero at the start of a chunk
+    int32_t *table = nullptr;                // [chunk pairs][n][2] (ax, ay) of a pair's used beams that are on, packed to the front
+    int32_t *table_cnt = nullptr;            // [chunk pairs][2] how many of them, and how many used beams are off
+    int32_t *best_out = nullptr, *best_cost_out = nullptr, *used_out = nullptr;   // [B][3], [B], nullable [B]
+    int64_t *stats_out = nullptr;            // nullable [B][H + 2]
+};
+size_t locate_pyramid_cells(const GridDev &g, int H);   // int16 cells of levels 1 .. H of all G maps
+// pyr: locate_pyramid_cells(g, H) int16; fills a.lvl[0 .. H] and builds levels 1 .. H from `field`
+hipError_t launch_locate_pyramid(LocateArgs &a, const int16_t *field, int16_t *pyr, hipStream_t s);
+// the whole search on a built pyramid: top level, descent, sweep in chunks of pairs, finish
+hipError_t launch_locate(const LocateArgs &a, const LocateShape &p, hipStream_t s);
+
 // ---- Monte Carlo localisation on the distance field (mcl_kernels.hip) ---------------------
 constexpr int kMclScanBlock = 1024;          // particles per workgroup of the prefix sum: fixed, so a filter's sums do not depend on the batch
 inline int mcl_scan_blocks(int P) { return (P + kMclScanBlock - 1) / kMclScanBlock; }

@@ -187,6 +187,24 @@ class Mapping:
         out = (match_pose(ctr, th, best, nx, ny, step)[0], int(cost[0]), int(used[0]))
         return out + (vol,) if return_costs else out
 
+    def locate_scan(self, ranges, angle_min, angle_max, n_rot=256, levels=5, region=None, max_range=30.0, cap=64):
+        """Where in this map a measured scan was taken (``slam_grid_locate``): the cheapest of ``n_rot`` rotations over the
+        full circle x every cell of the map - or of ``region`` = (i0, j0, ni, nj) - as the robot's cell, found exactly by
+        branch and bound on a ``levels``-deep pyramid of the distance field.  Returns (pose [3] at the cell's centre,
+        cost, used beams)."""
+        from .replay import locate_pose, locate_rotations
+        r = np.ascontiguousarray(np.asarray(ranges, dtype=np.float32).reshape(-1))
+        ct, st = _abi.trig_tables(angle_min, angle_max, r.shape[0])
+        _, rot = locate_rotations(n_rot)
+        reg = None if region is None else np.ascontiguousarray(np.asarray(region, dtype=np.int32).reshape(1, 4))
+        best = np.empty((1, 3), dtype=np.int32)
+        cost, used = (np.empty(1, dtype=np.int32) for _ in range(2))
+        _abi.check(_abi.lib().slam_grid_locate(self._ctx.handle, self._grid, _abi.ptr(r), 1, 1, None, _abi.ptr(ct), _abi.ptr(st),
+                                               r.shape[0], _abi.ptr(rot), rot.shape[0], _abi.ptr(reg), int(levels),
+                                               float(max_range), int(cap), _abi.ptr(best), _abi.ptr(cost), _abi.ptr(used), None))
+        pose = locate_pose(best, self.index_scale, self.index_offset_x, self.index_offset_y, rot)[0]
+        return pose, int(cost[0]), int(used[0])
+
     def counters(self):
         """(pass, hit) uint32 [xw, yw]: the integer evidence behind ``datamap``."""
         p = np.empty((self.xw, self.yw), dtype=np.uint32)

@@ -296,6 +296,15 @@ class MCL:
         self.acc = np.zeros(self.P, dtype=np.int32)
         return self.particles
 
+    def init_global(self, ranges, angle_min, angle_max, spread, **locate_kw):
+        """Start without a pose: locate the scan in the map (``Mapping.locate_scan``, which takes ``locate_kw``), then
+        :meth:`init` around the answer.  Returns (pose [3], cost, used beams) of the localisation."""
+        locate_kw.setdefault("max_range", self.max_range)
+        locate_kw.setdefault("cap", self.cap)
+        pose, cost, used = self.mapping.locate_scan(ranges, angle_min, angle_max, **locate_kw)
+        self.init(pose, spread)
+        return pose, cost, used
+
     def update(self, ranges, angle_min, angle_max, u=None):
         """One scan: ``u`` the odometry step (dx, dy, dtheta) in the robot frame since the last scan, or None.
         Returns (pose [3], ess): the weighted estimate taken before resampling."""

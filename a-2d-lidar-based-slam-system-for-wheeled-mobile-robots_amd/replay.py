@@ -186,6 +186,59 @@ def grid_match_host(grid, ranges, centres, cos_t, sin_t, rot_cs, nx, ny, step, m
     return (best, cost, used, vol) if return_costs else (best, cost, used)
 
 
+def grid_locate_host(grid, ranges, cos_t, sin_t, rot_cs, levels=5, region=None, max_range=30.0, cap=64, grid_of_batch=None,
+                     B=None, return_stats=False):
+    """Global scan localisation (``slam_grid_locate``): the best pose of every scan over its whole map, or over
+    ``region`` int32 [B, 4] = (i0, j0, ni, nj) robot cells, and the rotations ``rot_cs`` [K, 2]
+    (:func:`locate_rotations`), exact, by branch and bound on a ``levels``-deep pyramid of the distance field.  ranges
+    float32 [B, n], or one shared [n] (then ``B`` comes from ``grid_of_batch`` / ``region`` / ``B``, default 1).
+    Returns (best int32 [B, 3] = (k, i, j), cost int32 [B], used int32 [B]) and with ``return_stats`` also stats int64
+    [B, levels + 2]: the nodes evaluated per level and the incumbent U.  :func:`locate_pose` turns ``best`` into poses."""
+    ct, st = _tables(cos_t, sin_t)
+    n = ct.shape[0]
+    r = np.ascontiguousarray(np.asarray(ranges, dtype=np.float32))
+    shared = r.ndim == 1
+    gob = None if grid_of_batch is None else np.ascontiguousarray(np.asarray(grid_of_batch, dtype=np.int32).reshape(-1))
+    reg = None if region is None else np.ascontiguousarray(np.asarray(region, dtype=np.int32).reshape(-1, 4))
+    if B is None:
+        B = r.shape[0] if not shared else gob.shape[0] if gob is not None else reg.shape[0] if reg is not None else 1
+    B = int(B)
+    if r.shape != ((n,) if shared else (B, n)) or (gob is not None and gob.shape[0] != B) or (reg is not None and reg.shape[0] != B):
+        raise ValueError("ranges must be [n] or [B, n], grid_of_batch [B], region [B, 4]")
+    rot = np.ascontiguousarray(np.asarray(rot_cs, dtype=np.float64))
+    if rot.ndim != 2 or rot.shape[1] != 2:
+        raise ValueError("rot_cs must be [K, 2]")
+    H = int(levels)
+    best = np.empty((max(B, 0), 3), dtype=np.int32)
+    cost, used = (np.empty(max(B, 0), dtype=np.int32) for _ in range(2))
+    stats = np.empty((max(B, 0), max(H, 0) + 2), dtype=np.int64) if return_stats else None
+    _abi.check(_abi.lib().slam_grid_locate(grid._ctx.handle, grid._h, _abi.ptr(r), int(shared), B, _abi.ptr(gob), _abi.ptr(ct),
+                                           _abi.ptr(st), n, _abi.ptr(rot), rot.shape[0], _abi.ptr(reg), H, float(max_range),
+                                           int(cap), _abi.ptr(best), _abi.ptr(cost), _abi.ptr(used), _abi.ptr(stats)))
+    return (best, cost, used, stats) if return_stats else (best, cost, used)
+
+
+def locate_rotations(n_rot):
+    """(angles [K], rot_cs [K, 2]) of a full circle of ``n_rot`` rotations: theta_k = -pi + k * 2 pi / n_rot, cosine and
+    sine by NumPy."""
+    th = -np.pi + np.arange(int(n_rot)) * (2.0 * np.pi / int(n_rot))
+    return th, np.ascontiguousarray(np.stack([np.cos(th), np.sin(th)], axis=-1))
+
+
+def locate_pose(best, scale, off_x, off_y, rot_cs):
+    """Poses [B, 3] of the answers ``best`` [B, 3] = (k, i, j) of a global localisation on a grid of index rule
+    (scale, off_x, off_y): the CENTRE of cell (i, j), x = (i + 0.5) / scale - off_x, y alike, theta = atan2(sin_k, cos_k);
+    NaN rows where best is -1."""
+    best = np.asarray(best).reshape(-1, 3).astype(np.int64)
+    rot = np.asarray(rot_cs, dtype=np.float64).reshape(-1, 2)
+    ok = best[:, 0] >= 0
+    k = np.where(ok, best[:, 0], 0)
+    out = np.stack([(best[:, 1].astype(np.float64) + 0.5) / float(scale) - float(off_x),
+                    (best[:, 2].astype(np.float64) + 0.5) / float(scale) - float(off_y), np.arctan2(rot[k, 1], rot[k, 0])], axis=1)
+    out[~ok] = np.nan
+    return out
+
+
 def grid_copy_maps_host(grid, src, first=0):
     """``slam_grid_copy_maps`` on a NumPy array: map ``first + k`` of ``grid`` becomes a copy of map ``src[k]``.  Returns
     int32 [count]: 1 copied, 0 kept (its own map, or no map).  A source that is itself a destination raises."""
@@ -235,6 +288,7 @@ class DeviceGrid:
     def __init__(self, G, xw, yw, scale, off_x, off_y, free_inc=0.01, hit_inc=20.0, thresh=10.0, context=None):
         self._ctx = context or _abi.default_context()
         self.G, self.xw, self.yw = int(G), int(xw), int(yw)
+        self.scale, self.off_x, self.off_y = float(scale), float(off_x), float(off_y)
         h = C.c_void_p()
         _abi.check(_abi.lib().slam_grid_create(self._ctx.handle, self.G, self.xw, self.yw, float(scale), float(off_x),
                                                float(off_y), float(free_inc), float(hit_inc), float(thresh), C.byref(h)))
@@ -356,6 +410,30 @@ class DeviceGrid:
                                                   int(cap), _abi.ptr(best_out), _abi.ptr(cost_out), _abi.ptr(used_out),
                                                   _abi.ptr(costs_out)))
         return (best_out, cost_out, used_out) if costs_out is None else (best_out, cost_out, used_out, costs_out)
+
+    def locate(self, ranges, cos_t, sin_t, rot_cs, levels=5, region=None, max_range=30.0, cap=64, grid_of_batch=None, B=None,
+               best_out=None, cost_out=None, used_out=None, stats_out=None, return_stats=False):
+        """``slam_grid_locate_dev`` on torch device tensors: ranges float32 [B, n] or a shared [n] (then ``B`` comes from
+        ``grid_of_batch`` / ``region`` / ``B``, default 1), cos_t / sin_t float64 [n], rot_cs float64 [K, 2], region int32
+        [B, 4] or None, grid_of_batch int32 [B] or None.  Writes best int32 [B, 3] = (k, i, j), cost / used int32 [B]
+        (and stats int64 [B, levels + 2]) into the tensors given or into fresh ones; no synchronise."""
+        import torch
+        n, K, H = int(cos_t.shape[0]), int(rot_cs.shape[0]), int(levels)
+        if B is None:
+            B = (ranges.shape[0] if ranges.dim() == 2 else grid_of_batch.shape[0] if grid_of_batch is not None
+                 else region.shape[0] if region is not None else 1)
+        B = int(B)
+        new = lambda dtype, *shape: torch.empty(shape, dtype=dtype, device=cos_t.device)
+        best_out = new(torch.int32, B, 3) if best_out is None else best_out
+        cost_out = new(torch.int32, B) if cost_out is None else cost_out
+        used_out = new(torch.int32, B) if used_out is None else used_out
+        if stats_out is None and return_stats:
+            stats_out = new(torch.int64, B, max(H, 0) + 2)
+        _abi.check(_abi.lib().slam_grid_locate_dev(self._ctx.handle, self._h, _abi.ptr(ranges), int(ranges.dim() == 1), B,
+                                                   _abi.ptr(grid_of_batch), _abi.ptr(cos_t), _abi.ptr(sin_t), n, _abi.ptr(rot_cs), K,
+                                                   _abi.ptr(region), H, float(max_range), int(cap), _abi.ptr(best_out),
+                                                   _abi.ptr(cost_out), _abi.ptr(used_out), _abi.ptr(stats_out)))
+        return (best_out, cost_out, used_out) if stats_out is None else (best_out, cost_out, used_out, stats_out)
 
     def copy_maps(self, src, first=0, out=None):
         """``slam_grid_copy_maps_dev``: map ``first + k`` becomes a copy of map ``src[k]`` (torch int32 device tensor

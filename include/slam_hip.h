@@ -138,7 +138,10 @@ int slam_check_status(slam_ctx *ctx);
  *   64 KiB (512 K cells), else as 0; -1 = automatic (default).  Same bits either way; an A/B switch.
  * "mcl_shape": launch shape of slam_mcl_weigh: 0 = a workgroup's lanes run over the particles, each lane looping over
  *   the beams; 1 = a wave per particle, its lanes over the beams; -1 = the library's choice by beam count (default).
- *   Same bits either way; an A/B switch. */
+ *   Same bits either way; an A/B switch.
+ * "locate_ws_mb": MiB that the node lists of slam_grid_locate may take in the context's workspace, in (0, 2^20],
+ *   fractions allowed; default 64.  The (hypothesis, rotation) pairs of a call are cut into chunks whose worst-case
+ *   lists fit; a call whose single pair does not fit is SLAM_ERR_INVALID.  No result depends on it. */
 int slam_set_option(slam_ctx *ctx, const char *name, double value);
 /* Per-kernel-family timing with HIP events on the context's stream (bench.py roofline).
  * on: 0 = off, 1 = every family, 2 * mask = only the families in mask (bit SLAM_K_*): events on a
@@ -207,6 +210,8 @@ int slam_plan_icp(int B, int n_src, int n_tar, int is_scan, int qpt_pref, int ba
 /* slam_plan_query: a constant or an LDS size function of the two planners by its name in csrc/launch_shapes.h, e.g.
  * "kWinCells", "win_lds_bytes" (a, b, c = group, sort_cap, win_cells), "win_cells_for" (group, sort_cap, two_per_cu),
  * "win_sort_cap" (rays), "nn_lds_bytes" / "icp_polar_bytes" (n_tar), "icp_red_bytes" (waves), "icp_block" (n_src, qpt);
+ * "locate_level_nodes" (ni, nj, level), "locate_pair_bytes" / "locate_tile" / "locate_tiles" (ni, nj, levels),
+ * "locate_dense_lds" (n), "locate_dense_threads" (nodes), "locate_chunk_pairs" (budget in KiB, a pair's bytes, pairs);
  * arguments a function does not take are ignored.  SLAM_ERR_INVALID for a name it does not know. */
 int slam_plan_query(const char *name, int a, int b, int c, int guard, int64_t *out);
 
@@ -417,6 +422,77 @@ int slam_grid_match_dev(slam_ctx *ctx, slam_grid *grid, const float *ranges, int
                         const int32_t *grid_of_batch, const double *cos_t, const double *sin_t, int n, const double *rot_cs,
                         int K, int nx, int ny, double step, float max_range, int cap, int32_t *best_out,
                         int32_t *best_cost_out, int32_t *used_out, int32_t *cost_out);
+
+/* ---- global scan localisation: exact branch and bound on a pyramid of the field ------------- */
+/* slam_grid_locate: the best pose of a scan over a whole map (or a rectangle of it) and a table of rotations -
+ * "where in this map was this scan taken?" - exact, integer end to end, batched over (scan, map) pairs.  The
+ * reference has no counterpart.  It changes nothing in the grid, leaves the context's sticky status untouched and
+ * sees every update enqueued before it on the context's stream.
+ *
+ * Inputs.  ranges float32 [B][n], or one [n] for every hypothesis when shared != 0; grid_of_batch [B] (NULL: map 0);
+ * cos_t, sin_t [n] as for slam_scan_to_points; rot_cs [K][2] the cosine and sine of every rotation, made by the
+ * caller and shared by all hypotheses; region int32 [B][4] = (i0, j0, ni, nj), the robot cells searched (NULL: the
+ * whole map); levels = H, 0 <= H <= 8; max_range, cap as for slam_grid_match.
+ *
+ * Field.  The field slam_grid_distance_field gives NOW at this cap, rebuilt at the start of the call for all G maps;
+ * on it a pyramid P_1 .. P_H (below) for all G maps, in the context's workspace: a grid of many maps pays for all of
+ * them, 2 bytes per cell of the field plus about 2 * H bytes per cell of the pyramid.  Nothing is kept between calls.
+ * Under slam_timing_* field and pyramid count as SLAM_K_FINALIZE, the search as SLAM_K_GRID.
+ *
+ * Scan discretisation, once per rotation k with c = rot_cs[k][0], s = rot_cs[k][1].  Beam t is used iff
+ * isfinite(rr) && ranges[t] < max_range (compared as float32), rr = (double)ranges[t].  For a used beam
+ *   lx = cos_t[t]*rr;  ly = sin_t[t]*rr;  rx = c*lx + (-s)*ly;  ry = s*lx + c*ly     (no fused multiply-add)
+ *   ax = (int)floor(scale*rx + 0.5);  ay = (int)floor(scale*ry + 0.5)
+ * A used beam whose scale*rx or scale*ry is not finite, or is 2^20 or more in magnitude, is "off": it adds cap to
+ * every candidate.
+ *
+ * Candidates.  (k, i, j), 0 <= k < K, i0 <= i < i0 + ni, j0 <= j < j0 + nj, is the robot at the CENTRE of cell (i, j)
+ * with rotation k:
+ *   cost = sum over the used beams of E(i + ax, j + ay),  E(x, y) = field[gi][x][y] inside the map, cap outside; int32.
+ * This is the DISCRETISED-SCAN cost, not slam_grid_match's expression: a shift of the robot by whole cells shifts every
+ * end cell by the same cells, by definition (slam_grid_match rounds every beam's end for every candidate anew).  That
+ * is what makes the bound below exact.  The pose of a candidate is x = ((double)i + 0.5) / scale - off_x,
+ * y = ((double)j + 0.5) / scale - off_y, theta = atan2(s, c).
+ *
+ * Answer.  The smallest (cost, flat), flat = (k*ni + (i - i0))*nj + (j - j0).  best_out [B][3] = (k, i, j);
+ * best_cost_out [B]; used_out (nullable) [B] the number of used beams; stats_out (nullable) int64 [B][H + 2], below.
+ * A hypothesis whose grid_of_batch entry is outside [0, G) gets best (-1, -1, -1), cost -1, used 0 and stats of 0; the
+ * others of the batch are unaffected.  A scan with no used beam answers (0, i0, j0), cost 0, used 0 and stats of 0;
+ * no search is run for it.
+ *
+ * The search is part of the contract (stats_out is tested).  P_h[x][y] = min over 0 <= a, b < 2^h of E(x + a, y + b)
+ * for every integer (x, y); P_0 = E.  Node (h, k, I, J), 0 <= I < nI_h = ceil(ni / 2^h), 0 <= J < nJ_h = ceil(nj / 2^h),
+ * covers the cells i0 + I*2^h .. i0 + (I+1)*2^h - 1 of the region and likewise in j; its bound is
+ *   LB = sum over the used beams of P_h[i0 + I*2^h + ax][j0 + J*2^h + ay]      (an off beam adds cap).
+ * A child's bound is never below its parent's; at level 0 the bound is the cost.  The children of (h, k, I, J) are
+ * (h - 1, k, 2I + a, 2J + b), a, b in {0, 1}, those inside the level's node counts (they intersect the region).
+ *   1. The incumbent.  Take the level-H node of smallest (LB, node index (k*nI_H + I)*nJ_H + J) and descend to level
+ *      0, at every level to the child of smallest (LB, I, J).  U is the cost of the leaf reached; it is fixed before
+ *      the sweep and never tightened during it.
+ *   2. The sweep.  Every level-H node is evaluated; a node survives iff LB <= U; every child of a survivor is
+ *      evaluated; at level 0 the survivors' keys cost << 32 | flat are minimised.
+ * stats_out[b][h], h = 0 .. H, is the number of nodes evaluated at level h in the sweep; stats_out[b][H + 1] is U.
+ * Because U is fixed first, every output, the statistics included, is the same alone, in any batch, in any order and
+ * for any chunking (below).  H = 0 is brute force through the same code.
+ *
+ * Workspace.  The survivors of a level are kept in lists, sized for the worst case (an empty map: everything ties
+ * and survives): 8 bytes per node of levels 1 .. H of every (hypothesis, rotation) pair.  The context option
+ * "locate_ws_mb" bounds them; the pairs are taken in chunks whose lists fit, and no result depends on the cut.
+ *
+ * 1 <= cap <= 32767, 1 <= n <= 4096, n * cap < 2^31, B >= 1, K >= 1, B * K < 2^31, 0 <= H <= 8, max_range > 0 (+inf:
+ * every finite range is used), every region inside the map with ni, nj >= 1, K * ni * nj < 2^31 for the largest
+ * region, and the lists of ONE pair within "locate_ws_mb"; anything else is SLAM_ERR_INVALID, enqueues nothing and
+ * leaves the context as it was.  In the device form `region` is device memory the host cannot check: K * xw * yw
+ * < 2^31 is required whenever it is given, the lists are sized for the whole map, and a hypothesis whose region is
+ * empty or not inside the map is answered like one whose map entry is outside [0, G). */
+int slam_grid_locate(slam_ctx *ctx, slam_grid *grid, const float *ranges, int shared, int B, const int32_t *grid_of_batch,
+                     const double *cos_t, const double *sin_t, int n, const double *rot_cs, int K, const int32_t *region,
+                     int levels, float max_range, int cap, int32_t *best_out, int32_t *best_cost_out, int32_t *used_out,
+                     int64_t *stats_out);
+int slam_grid_locate_dev(slam_ctx *ctx, slam_grid *grid, const float *ranges, int shared, int B, const int32_t *grid_of_batch,
+                         const double *cos_t, const double *sin_t, int n, const double *rot_cs, int K, const int32_t *region,
+                         int levels, float max_range, int cap, int32_t *best_out, int32_t *best_cost_out, int32_t *used_out,
+                         int64_t *stats_out);
 
 /* ---- Monte Carlo localisation on the distance field ----------------------------------------- */
 /* F particle filters of P particles each, weighed against their filter's scan on the field above and resampled on
