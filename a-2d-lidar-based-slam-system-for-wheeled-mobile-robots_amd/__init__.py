@@ -9,7 +9,10 @@ zjwzcx/A-2D-LiDAR-based-SLAM-System-for-Wheeled-Mobile-Robots:
                .score, grid_raycast_host / grid_score_host); distance_field / match_scan: where a scan fits
                the map best (batched: DeviceGrid.distance_field / .match, grid_distance_field_host /
                grid_match_host, match_pose); locate_scan: where in the whole map a scan was taken (batched:
-               DeviceGrid.locate, grid_locate_host, locate_rotations, locate_pose; MCL.init_global starts from it)
+               DeviceGrid.locate, grid_locate_host, locate_rotations, locate_pose; MCL.init_global starts from it);
+               frontiers / next_goal: where to go next to see more of the map - clustered frontier cells, one goal per
+               cluster (batched: DeviceGrid.frontiers, grid_frontiers_host, frontier_points; GridSLAM / DeviceGridSLAM
+               .frontiers on the best particle's map)
     bresenham  (start, end).path
     SLAM_EKF   laserCallback glue (scan matching + map building); landmarks=True: the whole W12
                node with Extraction and the landmark EKF on the host; batched on the device
@@ -52,6 +55,7 @@ from .replay import DeviceGrid, DeviceReplay, grid_raycast_host, grid_score_host
 from .replay import grid_distance_field_host, grid_match_host, match_pose, match_rotations
 from .replay import grid_copy_maps_host, grid_update_particles_host
 from .replay import grid_locate_host, locate_pose, locate_rotations
+from .replay import frontier_points, grid_frontiers_host
 from .grid_slam import DeviceGridSLAM, GridSLAM
 from .slam_ekf import SLAM_EKF
 from .synthetic import LaserScan
@@ -63,7 +67,7 @@ __all__ = ["ICP", "Mapping", "Localization", "EKF", "Extraction", "LandMarkSet",
            "DeviceNodeReplay", "node_replay_host", "landmarks_host", "ekf_lm_host",
            "DeviceLocalizationReplay", "loc_replay_host", "grid_raycast_host", "grid_score_host",
            "grid_distance_field_host", "grid_match_host", "match_pose", "match_rotations",
-           "grid_locate_host", "locate_pose", "locate_rotations",
+           "grid_locate_host", "locate_pose", "locate_rotations", "grid_frontiers_host", "frontier_points",
            "MCL", "DeviceMCL", "MCL_DEAD", "mcl_weight_table", "mcl_weigh_host", "mcl_resample_host",
            "GridSLAM", "DeviceGridSLAM", "mcl_settle_host", "grid_copy_maps_host", "grid_update_particles_host",
            "RAY_EMPTY", "RAY_HIT", "RAY_BLOCKED", "RAY_FREE", "RAY_UNKNOWN", "RAY_OUT", "RAY_BAD", "RAY_CLASSES", "RAY_NAMES"]

@@ -85,6 +85,8 @@ _SIGS = {
     "slam_grid_match_dev": ([_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _d, C.c_float, _i, _vp, _vp, _vp, _vp], _i),
     "slam_grid_locate": ([_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, C.c_float, _i, _vp, _vp, _vp, _vp], _i),
     "slam_grid_locate_dev": ([_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, C.c_float, _i, _vp, _vp, _vp, _vp], _i),
+    "slam_grid_frontiers": ([_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
+    "slam_grid_frontiers_dev": ([_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
     "slam_mcl_weigh": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, C.c_float, _i, _vp, _vp, _vp, _vp], _i),
     "slam_mcl_weigh_dev": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, C.c_float, _i, _vp, _vp, _vp, _vp], _i),
     "slam_mcl_resample": ([_vp, _vp, _vp, _vp, _i, _i, _vp, _d, _i, _i, _vp, _vp, _vp, _vp], _i),

@@ -544,4 +544,70 @@ inline LocateShape plan_locate(const LocateRequest &r)
     return p;
 }
 
+// ---------------------------------------------------------------------------------
+// Map frontiers (frontier_kernels.hip, slam_grid_frontiers)
+// ---------------------------------------------------------------------------------
+// One query = one map.  Its cells are cut into tiles of kFrontierTileX x kFrontierTileY (lanes along y, the fast axis); a
+// workgroup forms the frontier bits of a tile from the counters (with a halo of max(radius, 1) cells in LDS), labels the
+// tile in LDS and writes one int32 label per cell.  The unions across tile borders are one work item per border cell
+// (the rows x = k * TileX and the columns y = k * TileY), through global atomics.  Every later phase is a pass over the
+// query's cells in segments of kFrontierSeg cells; the ordered table comes from per-segment counts of kept roots.
+// Workspace of a query (context option "frontier_ws_mb"): 4 bytes per cell of labels and 8 bytes per segment of counts;
+// queries are taken in chunks that fit.
+constexpr int kFrontierTileX = 32;
+constexpr int kFrontierTileY = 64;
+constexpr int kFrontierThreads = 256;
+constexpr int kFrontierMaxRadius = 8;
+constexpr int kFrontierSeg = 1024;            // cells per segment of the passes behind the labelling: four per lane
+constexpr int kFrontierMaxClusters = 65536;
+constexpr long kFrontierMaxBlocks = 1L << 20; // workgroups of a launch; more groups are taken grid-stride
+
+SLAM_HD inline int frontier_halo(int radius) { return radius > 1 ? radius : 1; }
+// dynamic LDS of the tile kernel: labels int32 [TileX * TileY], cell codes uint8 [(TileX + 2h) * (TileY + 2h)], the
+// window's row sums uint8 [(TileX + 2h) * TileY], rounded up to 16 bytes, then the guard
+SLAM_HD inline size_t frontier_lds_bytes(int radius, int guard = kLdsGuard)
+{
+    const size_t h = (size_t)frontier_halo(radius);
+    const size_t b = (size_t)kFrontierTileX * kFrontierTileY * 4 + (kFrontierTileX + 2 * h) * (kFrontierTileY + 2 * h) +
+                     (kFrontierTileX + 2 * h) * kFrontierTileY;
+    return (b + 15) / 16 * 16 + (size_t)guard;
+}
+SLAM_HD inline long frontier_segs(long cells) { return (cells + kFrontierSeg - 1) / kFrontierSeg; }
+SLAM_HD inline long frontier_query_bytes(long cells) { return cells * 4 + frontier_segs(cells) * 8; }
+
+struct FrontierRequest {
+    long B = 0;
+    int xw = 0, yw = 0, radius = 0;
+    long ws_bytes = 0;
+    int guard = kLdsGuard;
+};
+struct FrontierShape {
+    bool ok = false;             // false: one query's workspace does not fit the budget
+    int tiles_x = 0, tiles_y = 0;
+    long tiles = 0;              // workgroups of the tile kernel per query
+    long border = 0;             // work items of the border unions per query
+    long segs = 0;               // segments per query
+    long query_bytes = 0;
+    long chunk_queries = 0, chunks = 0;
+    int lds = 0, threads = kFrontierThreads;
+};
+inline FrontierShape plan_frontiers(const FrontierRequest &r)
+{
+    FrontierShape p;
+    if (r.B < 1 || r.xw < 1 || r.yw < 1 || r.radius < 0 || r.radius > kFrontierMaxRadius) return p;
+    const long cells = (long)r.xw * r.yw;
+    p.tiles_x = (r.xw + kFrontierTileX - 1) / kFrontierTileX;
+    p.tiles_y = (r.yw + kFrontierTileY - 1) / kFrontierTileY;
+    p.tiles = (long)p.tiles_x * p.tiles_y;
+    p.border = (long)(p.tiles_x - 1) * r.yw + (long)(p.tiles_y - 1) * r.xw;
+    p.segs = frontier_segs(cells);
+    p.query_bytes = frontier_query_bytes(cells);
+    p.lds = (int)frontier_lds_bytes(r.radius, r.guard);
+    p.chunk_queries = std::min(r.B, r.ws_bytes / p.query_bytes);
+    if (p.chunk_queries < 1) return p;
+    p.chunks = (r.B + p.chunk_queries - 1) / p.chunk_queries;
+    p.ok = true;
+    return p;
+}
+
 }  // namespace slam

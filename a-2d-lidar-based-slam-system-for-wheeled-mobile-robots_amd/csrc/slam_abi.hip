@@ -105,6 +105,7 @@ struct slam_ctx {
     int raycast_lds = -1; // rays traced through a map: -1 = automatic, 0 = mask words from global memory, 1 = from LDS wherever the mask fits
     int mcl_shape = -1;   // slam_mcl_weigh: -1 = the library's choice by beam count, 0 = lanes over particles, 1 = a wave per particle, lanes over beams; changes no result
     long locate_ws_bytes = 64L << 20; // slam_grid_locate: bytes its node lists may take ("locate_ws_mb"); pairs are cut into chunks that fit; changes no result
+    long frontier_ws_bytes = 256L << 20; // slam_grid_frontiers: bytes its labels may take ("frontier_ws_mb"); queries are cut into chunks that fit; changes no result
     int icp_team = 0;     // first-iteration queries without a beam window: 0 = listed and searched apart from their lanes (nn_listed), 1 = box search
     // "pipeline" option: the map stage of slam_replay_dev (reset -> ray cast -> finalize) runs on
     // a second stream, so the map stage of one replay overlaps the scan matching of the next.
@@ -714,6 +715,7 @@ static const OptionRange kOptionRanges[] = {
     {"raycast_lds", [](double v) { return v == -1 || v == 0 || v == 1; }, "raycast_lds is -1, 0 or 1"},
     {"mcl_shape", [](double v) { return v == -1 || v == 0 || v == 1; }, "mcl_shape is -1, 0 or 1"},
     {"locate_ws_mb", [](double v) { return v > 0 && v <= 1048576; }, "locate_ws_mb in (0, 1048576]"},
+    {"frontier_ws_mb", [](double v) { return v > 0 && v <= 1048576; }, "frontier_ws_mb in (0, 1048576]"},
 };
 
 int slam_set_option(slam_ctx *c, const char *name, double value)
@@ -738,6 +740,7 @@ int slam_set_option(slam_ctx *c, const char *name, double value)
     else if (!strcmp(name, "raycast_lds")) c->raycast_lds = (int)value;
     else if (!strcmp(name, "mcl_shape")) c->mcl_shape = (int)value;
     else if (!strcmp(name, "locate_ws_mb")) c->locate_ws_bytes = (long)(value * 1048576.0);
+    else if (!strcmp(name, "frontier_ws_mb")) c->frontier_ws_bytes = (long)(value * 1048576.0);
     else if (!strcmp(name, "pipeline")) {
         TRY(join_from_grid(c));
         if (value == 1 && !c->gstream) {
@@ -857,6 +860,13 @@ static int64_t locate_plan_chunk(long ws_bytes, long pair_bytes, long pairs)
     return pair_bytes ? std::min(pairs, ws_bytes / pair_bytes) : pairs;
 }
 
+static FrontierShape frontier_plan_for(int xw, int yw, int radius, long B, long ws_bytes, int guard)
+{
+    FrontierRequest r;
+    r.B = B; r.xw = xw; r.yw = yw; r.radius = radius; r.ws_bytes = ws_bytes; r.guard = guard;
+    return plan_frontiers(r);
+}
+
 int slam_plan_query(const char *name, int a, int b, int c, int guard, int64_t *out)
 {
     if (!name || !out) return fail(SLAM_ERR_INVALID, "slam_plan_query: null pointer");
@@ -892,6 +902,15 @@ int slam_plan_query(const char *name, int a, int b, int c, int guard, int64_t *o
         {"locate_table_bytes", locate_table_bytes(a)}, {"locate_dense_lds", (int64_t)locate_dense_lds(a, g)}, {"locate_dense_threads", locate_dense_threads(a)},
         {"locate_tile", locate_plan_for(a, b, c, 1, 1L << 40, g).tile}, {"locate_tiles", locate_plan_for(a, b, c, 1, 1L << 40, g).tiles},
         {"locate_chunk_pairs", locate_plan_chunk((long)a * 1024, b, c)},
+        // slam_grid_frontiers: a = xw, b = yw (frontier_tiles*, frontier_border, frontier_segs, frontier_query_bytes); frontier_lds:
+        // a = radius; frontier_chunk_queries: a = the budget in KiB, b = frontier_query_bytes, c = B, as plan_frontiers cuts them
+        {"kFrontierTileX", kFrontierTileX}, {"kFrontierTileY", kFrontierTileY}, {"kFrontierThreads", kFrontierThreads},
+        {"kFrontierSeg", kFrontierSeg}, {"kFrontierMaxRadius", kFrontierMaxRadius}, {"kFrontierMaxClusters", kFrontierMaxClusters},
+        {"frontier_tiles_x", frontier_plan_for(a, b, 0, 1, 1L << 40, g).tiles_x}, {"frontier_tiles_y", frontier_plan_for(a, b, 0, 1, 1L << 40, g).tiles_y},
+        {"frontier_tiles", frontier_plan_for(a, b, 0, 1, 1L << 40, g).tiles}, {"frontier_border", frontier_plan_for(a, b, 0, 1, 1L << 40, g).border},
+        {"frontier_segs", frontier_plan_for(a, b, 0, 1, 1L << 40, g).segs}, {"frontier_query_bytes", frontier_plan_for(a, b, 0, 1, 1L << 40, g).query_bytes},
+        {"frontier_lds", (a >= 0 && a <= kFrontierMaxRadius) ? (int64_t)frontier_lds_bytes(a, g) : 0},
+        {"frontier_chunk_queries", (b > 0 && c >= 1) ? std::min((int64_t)c, (int64_t)a * 1024 / b) : 0},
     };
     for (const Entry &e : table)
         if (!strcmp(e.name, name)) { *out = e.value; return SLAM_OK; }
@@ -1763,6 +1782,92 @@ int slam_grid_locate(slam_ctx *c, slam_grid *g, const float *ranges, int shared,
     TRY(s.upload());
     TRY(locate_dev(__func__, c, g, d_r, shared, B, d_g, d_c, d_s, n, d_rot, K, d_reg, max_ni, max_nj, levels, max_range, cap, d_best,
                    d_cost, d_used, d_st));
+    return s.download();
+}
+
+// ---- map frontiers (frontier_kernels.hip) -----------------------------------------------------------------------------
+static int check_frontiers(const char *fn, const slam_ctx *c, const slam_grid *g, int B, const int32_t *grid_of_batch, int radius,
+                           int min_unknown, int min_clear2, int cap, int min_size, int max_clusters, const int32_t *count_out,
+                           const int32_t *clusters_out, const int64_t *sums_out, FrontierShape &plan)
+{
+    REQUIRE_IN(fn, g && count_out, "null pointer");
+    REQUIRE_IN(fn, B >= 1, "B < 1");
+    REQUIRE_IN(fn, grid_of_batch || B <= g->d.G, "B > G without grid_of_batch (query b reads map b)");
+    REQUIRE_IN(fn, radius >= 0 && radius <= kFrontierMaxRadius, "radius outside [0, 8]");
+    REQUIRE_IN(fn, min_unknown >= 0 && min_unknown <= (2 * radius + 1) * (2 * radius + 1), "min_unknown outside [0, (2 radius + 1)^2]");
+    REQUIRE_IN(fn, min_clear2 >= 0, "min_clear2 < 0");
+    if (min_clear2 > 0) {
+        REQUIRE_IN(fn, cap >= 1 && cap <= 32767, "cap outside [1, 32767]");
+        REQUIRE_IN(fn, min_clear2 <= cap, "min_clear2 > cap");
+    }
+    REQUIRE_IN(fn, min_size >= 1, "min_size < 1");
+    REQUIRE_IN(fn, max_clusters >= 0 && max_clusters <= kFrontierMaxClusters, "max_clusters outside [0, 65536]");
+    REQUIRE_IN(fn, (long)B * std::max(max_clusters, 1) < (1L << 31), "B * max(max_clusters, 1) >= 2^31");
+    REQUIRE_IN(fn, max_clusters == 0 || (clusters_out && sums_out), "null table with max_clusters > 0");
+    REQUIRE_IN(fn, g->d.xw <= 32768 && g->d.yw <= 32768, "a map of more than 32768 cells in an axis");
+    plan = frontier_plan_for(g->d.xw, g->d.yw, radius, B, c->frontier_ws_bytes, kLdsGuard);
+    if (!plan.ok)
+        return fail(SLAM_ERR_INVALID, "%s: the labels of one query (%ld bytes) do not fit the context option frontier_ws_mb (%ld bytes)",
+                    fn, plan.query_bytes, c->frontier_ws_bytes);
+    return SLAM_OK;
+}
+
+static int frontiers_dev(const char *fn, slam_ctx *c, slam_grid *g, int B, const int32_t *grid_of_batch, int radius, int min_unknown,
+                         int min_clear2, int cap, int min_size, int max_clusters, int32_t *count_out, int32_t *clusters_out,
+                         int64_t *sums_out, int32_t *labels_out)
+{
+    FrontierShape plan;
+    TRY(check_frontiers(fn, c, g, B, grid_of_batch, radius, min_unknown, min_clear2, cap, min_size, max_clusters, count_out,
+                        clusters_out, sums_out, plan));
+    const size_t cells = (size_t)g->d.xw * g->d.yw;
+    const size_t lab_words = (size_t)plan.chunk_queries * cells, seg_words = (size_t)plan.chunk_queries * plan.segs * 2;
+    const size_t ws = align_up(lab_words * 4) + align_up(seg_words * 4);
+    FrontierArgs a;
+    if (min_clear2 > 0) {       // the field of all G maps, as slam_grid_match builds it
+        int16_t *field = nullptr;
+        TRY(build_field(c, g, fn, cap, ws, field));
+        a.field = field;
+    } else {
+        TRY(grid_on_main(c));
+        TRY(arena_reserve(c, c->scratch, ws + 1024));
+    }
+    a.lab = carve<int32_t>(c->scratch, lab_words);
+    a.seg = carve<int32_t>(c->scratch, seg_words);
+    REQUIRE_IN(fn, a.lab && a.seg, "internal: workspace");
+    a.g = g->d;
+    a.maps = grid_of_batch;
+    a.B = B; a.radius = radius; a.min_unknown = min_unknown; a.min_clear2 = min_clear2; a.min_size = min_size; a.M = max_clusters;
+    a.count_out = count_out; a.clusters_out = clusters_out; a.sums_out = sums_out; a.labels_out = labels_out;
+    Timed t(c, SLAM_K_GRID);
+    for (long b0 = 0; b0 < B; b0 += plan.chunk_queries)
+        HIPCHK(launch_frontiers(a, plan, b0, std::min(plan.chunk_queries, (long)B - b0), c->stream));
+    return SLAM_OK;
+}
+
+int slam_grid_frontiers_dev(slam_ctx *c, slam_grid *g, int B, const int32_t *grid_of_batch, int radius, int min_unknown, int min_clear2,
+                            int cap, int min_size, int max_clusters, int32_t *count_out, int32_t *clusters_out, int64_t *sums_out,
+                            int32_t *labels_out)
+{
+    TRY(use(c));
+    return frontiers_dev(__func__, c, g, B, grid_of_batch, radius, min_unknown, min_clear2, cap, min_size, max_clusters, count_out,
+                         clusters_out, sums_out, labels_out);
+}
+
+int slam_grid_frontiers(slam_ctx *c, slam_grid *g, int B, const int32_t *grid_of_batch, int radius, int min_unknown, int min_clear2,
+                        int cap, int min_size, int max_clusters, int32_t *count_out, int32_t *clusters_out, int64_t *sums_out,
+                        int32_t *labels_out)
+{
+    TRY(use(c));
+    FrontierShape plan;
+    TRY(check_frontiers(__func__, c, g, B, grid_of_batch, radius, min_unknown, min_clear2, cap, min_size, max_clusters, count_out,
+                        clusters_out, sums_out, plan));
+    const size_t rows = (size_t)B * max_clusters;
+    int32_t *d_g, *d_cnt, *d_cl, *d_lab; int64_t *d_sums;
+    Staging s(c);
+    s.in(d_g, grid_of_batch, B).out(d_cnt, count_out, (size_t)B * 2).out(d_cl, clusters_out, rows * 8).out(d_sums, sums_out, rows * 2)
+        .out(d_lab, labels_out, (size_t)B * g->d.xw * g->d.yw);
+    TRY(s.upload());
+    TRY(frontiers_dev(__func__, c, g, B, d_g, radius, min_unknown, min_clear2, cap, min_size, max_clusters, d_cnt, d_cl, d_sums, d_lab));
     return s.download();
 }
 

@@ -267,6 +267,28 @@ hipError_t launch_locate_pyramid(LocateArgs &a, const int16_t *field, int16_t *p
 // the whole search on a built pyramid: top level, descent, sweep in chunks of pairs, finish
 hipError_t launch_locate(const LocateArgs &a, const LocateShape &p, hipStream_t s);
 
+// ---- map frontiers: clustered exploration goals (frontier_kernels.hip) --------------------
+// The label word of a cell (workspace, [chunk][xw][yw] int32) through the phases:
+//   -1            not a frontier cell
+//   v >= 0        a frontier cell whose parent (after k_frontier_flatten: whose root) is flat cell v of its query
+//   v <= -2       a root, from k_frontier_flatten on: -(size + 1) until k_frontier_rank, then -(row + 2) for a cluster
+//                 with a row in the table and kFrontierNoRow for one without (too small, or behind max_clusters)
+constexpr int32_t kFrontierNoRow = INT32_MIN;
+struct FrontierArgs {
+    GridDev g;
+    const int16_t *field = nullptr;          // [G][xw][yw] when min_clear2 > 0
+    const int32_t *maps = nullptr;           // nullable [B]: NULL = query b reads map b
+    int B = 0, radius = 0, min_unknown = 0, min_clear2 = 0, min_size = 0, M = 0;
+    int32_t *lab = nullptr;                  // workspace [chunk queries][xw * yw]
+    int32_t *seg = nullptr;                  // workspace [chunk queries][segs][2]: kept roots, frontier cells of a segment
+    int32_t *count_out = nullptr;            // [B][2]
+    int32_t *clusters_out = nullptr;         // [B][M][8], nullable when M == 0
+    int64_t *sums_out = nullptr;             // [B][M][2], nullable when M == 0
+    int32_t *labels_out = nullptr;           // nullable [B][xw][yw]
+};
+// every phase of queries b0 .. b0 + nb - 1 (nb <= p.chunk_queries), enqueued on s
+hipError_t launch_frontiers(const FrontierArgs &a, const FrontierShape &p, long b0, long nb, hipStream_t s);
+
 // ---- Monte Carlo localisation on the distance field (mcl_kernels.hip) ---------------------
 constexpr int kMclScanBlock = 1024;          // particles per workgroup of the prefix sum: fixed, so a filter's sums do not depend on the batch
 inline int mcl_scan_blocks(int P) { return (P + kMclScanBlock - 1) / kMclScanBlock; }

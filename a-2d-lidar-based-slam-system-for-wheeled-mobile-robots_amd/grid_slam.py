@@ -191,6 +191,26 @@ class DeviceGridSLAM:
             raise _abi.SlamError("filter %d has no live particle" % f)
         return self.grid.read(f * self.P + b, want=("pmap",))["pmap"]
 
+    def frontiers(self, radius=2, min_unknown=13, min_clear2=0, cap=64, min_size=5, max_clusters=256, labels=False):
+        """The frontiers (:meth:`DeviceGrid.frontiers`) of every filter's best particle's map, one query per filter on map
+        ``f * P + info[f, 0]``; the map index is formed on the device and a filter with no live particle (``info[f, 0]
+        < 0``) asks for no map: its counts are (-1, -1).  Returns the device tensors; no synchronise."""
+        torch = self.torch
+        self._begin()
+        best = self.info[:, 0]
+        maps = torch.where(best >= 0, torch.arange(self.F, dtype=torch.int32, device=self.dev) * self.P + best,
+                           torch.full_like(best, -1)).to(torch.int32).contiguous()
+        out = (torch.empty((self.F, 2), dtype=torch.int32, device=self.dev),
+               torch.empty((self.F, int(max_clusters), 8), dtype=torch.int32, device=self.dev),
+               torch.empty((self.F, int(max_clusters), 2), dtype=torch.int64, device=self.dev))
+        if labels:
+            out += (torch.empty((self.F, self.grid.xw, self.grid.yw), dtype=torch.int32, device=self.dev),)
+        self.ctx.stream_order(self._torch_stream(), 1)
+        self.grid.frontiers(maps, radius=radius, min_unknown=min_unknown, min_clear2=min_clear2, cap=cap, min_size=min_size,
+                            max_clusters=max_clusters, out=out)
+        self._held = (maps,) + out
+        return out
+
     @property
     def trajectory(self):
         """The per-step estimates [S, F, 3] of the last :meth:`run` (or [1, F, 3] of the last :meth:`step`); synchronises."""
@@ -247,6 +267,22 @@ class GridSLAM:
         self.pose, self.ess, self.best = est[0, :3].copy(), float(est[0, 3]), int(info[0, 0])
         self.trajectory.append(self.pose)
         return self.pose, self.ess
+
+    def frontiers(self, radius=2, min_unknown=13, clearance=0.0, min_size=5, max_clusters=256, cap=64):
+        """:meth:`Mapping.frontiers` on the best particle's map."""
+        import math
+        from .replay import frontier_dict, grid_frontiers_host
+        c2 = int(math.ceil((float(clearance) * self.grid.scale) ** 2)) if clearance > 0 else 0
+        if c2 > int(cap):
+            raise ValueError("clearance of %g m is %d squared cells, beyond cap = %d" % (clearance, c2, cap))
+        count, clusters, sums = grid_frontiers_host(self.grid, [max(self.best, 0)], radius=radius, min_unknown=min_unknown, min_clear2=c2,
+                                                    cap=cap, min_size=min_size, max_clusters=max_clusters)
+        return frontier_dict(count[0], clusters[0], sums[0], self.grid.scale, self.grid.off_x, self.grid.off_y)
+
+    def next_goal(self, **kw):
+        """The nearest-frontier rule from the best particle's pose on its map (:meth:`Mapping.next_goal`)."""
+        from .replay import nearest_goal
+        return nearest_goal(self.frontiers(**kw), self.best_pose)
 
     @property
     def best_pose(self):

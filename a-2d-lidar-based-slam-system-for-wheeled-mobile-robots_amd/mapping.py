@@ -205,6 +205,35 @@ class Mapping:
         pose = locate_pose(best, self.index_scale, self.index_offset_x, self.index_offset_y, rot)[0]
         return pose, int(cost[0]), int(used[0])
 
+    def frontiers(self, radius=2, min_unknown=13, clearance=0.0, min_size=5, max_clusters=256, cap=64):
+        """Where to go next to see more of this map (``slam_grid_frontiers``): the free cells that border unknown space
+        with at least ``min_unknown`` unknown cells in their (2 radius + 1)^2 window and at least ``clearance`` metres
+        from every occupied cell (``min_clear2 = ceil((clearance * scale)^2)``, an error when it exceeds ``cap``), in
+        8-connected clusters of at least ``min_size`` cells.  Returns a dict of arrays over the kept clusters, in label
+        order: ``label``, ``size``, ``cell`` [K, 2] (the representative, a member cell), ``point`` [K, 2] (its centre in
+        world coordinates), ``centroid`` [K, 2] (world, from the sums), ``bbox`` [K, 4]; and ``count`` (the true number
+        of kept clusters, also beyond ``max_clusters``) and ``n_frontier``.  The defaults (2, 13, 5) come from one
+        experiment on the synthetic room; they are not tuned."""
+        import math
+        from .replay import frontier_dict
+        c2 = int(math.ceil((float(clearance) * self.index_scale) ** 2)) if clearance > 0 else 0
+        if c2 > int(cap):
+            raise ValueError("clearance of %g m is %d squared cells, beyond cap = %d" % (clearance, c2, cap))
+        M = int(max_clusters)
+        count = np.empty((1, 2), dtype=np.int32)
+        clusters = np.empty((1, max(M, 0), 8), dtype=np.int32)
+        sums = np.empty((1, max(M, 0), 2), dtype=np.int64)
+        _abi.check(_abi.lib().slam_grid_frontiers(self._ctx.handle, self._grid, 1, None, int(radius), int(min_unknown), c2, int(cap),
+                                                  int(min_size), M, _abi.ptr(count), _abi.ptr(clusters) if M > 0 else None,
+                                                  _abi.ptr(sums) if M > 0 else None, None))
+        return frontier_dict(count[0], clusters[0], sums[0], self.index_scale, self.index_offset_x, self.index_offset_y)
+
+    def next_goal(self, pose, **kw):
+        """The nearest-frontier rule: the representative point [2] of the kept cluster (:meth:`frontiers`, ``**kw``) whose
+        point is nearest to the pose's (x, y); None when no cluster is kept - exploration is complete."""
+        from .replay import nearest_goal
+        return nearest_goal(self.frontiers(**kw), pose)
+
     def counters(self):
         """(pass, hit) uint32 [xw, yw]: the integer evidence behind ``datamap``."""
         p = np.empty((self.xw, self.yw), dtype=np.uint32)

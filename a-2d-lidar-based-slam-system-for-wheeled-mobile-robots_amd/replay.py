@@ -239,6 +239,55 @@ def locate_pose(best, scale, off_x, off_y, rot_cs):
     return out
 
 
+def grid_frontiers_host(grid, grid_of_batch=None, B=None, radius=2, min_unknown=13, min_clear2=0, cap=64, min_size=5,
+                        max_clusters=256, labels=False):
+    """Map frontiers (``slam_grid_frontiers``) on NumPy arrays: query b reads map ``grid_of_batch[b]`` (None: map b, B
+    defaults to G).  Returns (count int32 [B, 2] = (kept clusters, frontier cells), clusters int32 [B, M, 8] = (label,
+    size, rep_x, rep_y, x0, y0, x1, y1), sums int64 [B, M, 2] = (sx, sy)) and with ``labels`` also int32 [B, xw, yw].
+    The defaults (2, 13, 5) come from one experiment on the synthetic room; they are not tuned."""
+    gob = None if grid_of_batch is None else np.ascontiguousarray(np.asarray(grid_of_batch, dtype=np.int32).reshape(-1))
+    B = int((grid.G if gob is None else gob.shape[0]) if B is None else B)
+    if gob is not None and gob.shape[0] != B:
+        raise ValueError("grid_of_batch must be [B]")
+    M = int(max_clusters)
+    count = np.empty((max(B, 0), 2), dtype=np.int32)
+    clusters = np.empty((max(B, 0), max(M, 0), 8), dtype=np.int32)
+    sums = np.empty((max(B, 0), max(M, 0), 2), dtype=np.int64)
+    lab = np.empty((max(B, 0), grid.xw, grid.yw), dtype=np.int32) if labels else None
+    _abi.check(_abi.lib().slam_grid_frontiers(grid._ctx.handle, grid._h, B, _abi.ptr(gob), int(radius), int(min_unknown),
+                                              int(min_clear2), int(cap), int(min_size), M, _abi.ptr(count),
+                                              _abi.ptr(clusters) if M > 0 else None, _abi.ptr(sums) if M > 0 else None,
+                                              _abi.ptr(lab)))
+    return (count, clusters, sums, lab) if labels else (count, clusters, sums)
+
+
+def frontier_points(cells, scale, off_x, off_y):
+    """World coordinates [..., 2] of the CENTRES of cells [..., 2] on a grid of index rule (scale, off_x, off_y):
+    x = (i + 0.5) / scale - off_x, y alike, as :func:`locate_pose` places a cell."""
+    c = np.asarray(cells, dtype=np.float64)
+    return np.stack([(c[..., 0] + 0.5) / float(scale) - float(off_x), (c[..., 1] + 0.5) / float(scale) - float(off_y)], axis=-1)
+
+
+def frontier_dict(count, clusters, sums, scale, off_x, off_y):
+    """One query's outputs of ``slam_grid_frontiers`` as the dict :meth:`Mapping.frontiers` returns."""
+    K = max(0, min(int(count[0]), clusters.shape[0]))
+    cl, sm = clusters[:K], sums[:K].astype(np.float64)
+    size = cl[:, 1].astype(np.float64).reshape(-1, 1)
+    return dict(label=cl[:, 0].copy(), size=cl[:, 1].copy(), cell=cl[:, 2:4].copy(), point=frontier_points(cl[:, 2:4], scale, off_x, off_y),
+                centroid=frontier_points(sm / np.maximum(size, 1.0), scale, off_x, off_y), bbox=cl[:, 4:8].copy(),
+                count=int(count[0]), n_frontier=int(count[1]))
+
+
+def nearest_goal(fr, pose):
+    """The representative point of the kept cluster nearest to the pose's (x, y) - squared distance in float64, ties to
+    the lowest label (the rows are in label order) - or None when no cluster is kept."""
+    if fr["point"].shape[0] == 0:
+        return None
+    p = np.asarray(pose, dtype=np.float64).reshape(-1)
+    d = (fr["point"][:, 0] - p[0]) ** 2 + (fr["point"][:, 1] - p[1]) ** 2
+    return fr["point"][int(np.argmin(d))].copy()
+
+
 def grid_copy_maps_host(grid, src, first=0):
     """``slam_grid_copy_maps`` on a NumPy array: map ``first + k`` of ``grid`` becomes a copy of map ``src[k]``.  Returns
     int32 [count]: 1 copied, 0 kept (its own map, or no map).  A source that is itself a destination raises."""
@@ -434,6 +483,28 @@ class DeviceGrid:
                                                    _abi.ptr(region), H, float(max_range), int(cap), _abi.ptr(best_out),
                                                    _abi.ptr(cost_out), _abi.ptr(used_out), _abi.ptr(stats_out)))
         return (best_out, cost_out, used_out) if stats_out is None else (best_out, cost_out, used_out, stats_out)
+
+    def frontiers(self, grid_of_batch=None, B=None, radius=2, min_unknown=13, min_clear2=0, cap=64, min_size=5, max_clusters=256,
+                  labels=False, out=None):
+        """``slam_grid_frontiers_dev`` on torch device tensors: grid_of_batch int32 [B] or None (query b reads map b, B
+        defaults to G).  Writes count int32 [B, 2], clusters int32 [B, M, 8], sums int64 [B, M, 2] (and with ``labels``
+        int32 [B, xw, yw]) into the tensors of ``out`` (a tuple in that order) or into fresh ones and returns them; no
+        synchronise.  The defaults (2, 13, 5) come from one experiment on the synthetic room; they are not tuned."""
+        import torch
+        B = int((self.G if grid_of_batch is None else grid_of_batch.shape[0]) if B is None else B)
+        M = int(max_clusters)
+        if out is None:
+            dev = grid_of_batch.device if grid_of_batch is not None else torch.device("cuda", self._ctx.device)
+            new = lambda dtype, *shape: torch.empty(shape, dtype=dtype, device=dev)
+            out = (new(torch.int32, max(B, 0), 2), new(torch.int32, max(B, 0), max(M, 0), 8), new(torch.int64, max(B, 0), max(M, 0), 2))
+            if labels:
+                out += (new(torch.int32, max(B, 0), self.xw, self.yw),)
+        lab = out[3] if len(out) > 3 else None
+        _abi.check(_abi.lib().slam_grid_frontiers_dev(self._ctx.handle, self._h, B, _abi.ptr(grid_of_batch), int(radius),
+                                                      int(min_unknown), int(min_clear2), int(cap), int(min_size), M, _abi.ptr(out[0]),
+                                                      _abi.ptr(out[1]) if M > 0 else None, _abi.ptr(out[2]) if M > 0 else None,
+                                                      _abi.ptr(lab)))
+        return out
 
     def copy_maps(self, src, first=0, out=None):
         """``slam_grid_copy_maps_dev``: map ``first + k`` becomes a copy of map ``src[k]`` (torch int32 device tensor

@@ -141,7 +141,10 @@ int slam_check_status(slam_ctx *ctx);
  *   Same bits either way; an A/B switch.
  * "locate_ws_mb": MiB that the node lists of slam_grid_locate may take in the context's workspace, in (0, 2^20],
  *   fractions allowed; default 64.  The (hypothesis, rotation) pairs of a call are cut into chunks whose worst-case
- *   lists fit; a call whose single pair does not fit is SLAM_ERR_INVALID.  No result depends on it. */
+ *   lists fit; a call whose single pair does not fit is SLAM_ERR_INVALID.  No result depends on it.
+ * "frontier_ws_mb": MiB that the labels of slam_grid_frontiers may take in the context's workspace, in (0, 2^20],
+ *   fractions allowed; default 256.  The queries of a call are cut into chunks that fit; a call whose single query
+ *   does not fit is SLAM_ERR_INVALID.  No result depends on it. */
 int slam_set_option(slam_ctx *ctx, const char *name, double value);
 /* Per-kernel-family timing with HIP events on the context's stream (bench.py roofline).
  * on: 0 = off, 1 = every family, 2 * mask = only the families in mask (bit SLAM_K_*): events on a
@@ -212,6 +215,8 @@ int slam_plan_icp(int B, int n_src, int n_tar, int is_scan, int qpt_pref, int ba
  * "win_sort_cap" (rays), "nn_lds_bytes" / "icp_polar_bytes" (n_tar), "icp_red_bytes" (waves), "icp_block" (n_src, qpt);
  * "locate_level_nodes" (ni, nj, level), "locate_pair_bytes" / "locate_tile" / "locate_tiles" (ni, nj, levels),
  * "locate_dense_lds" (n), "locate_dense_threads" (nodes), "locate_chunk_pairs" (budget in KiB, a pair's bytes, pairs);
+ * "frontier_tiles" / "frontier_tiles_x" / "frontier_tiles_y" / "frontier_border" / "frontier_segs" /
+ * "frontier_query_bytes" (xw, yw), "frontier_lds" (radius), "frontier_chunk_queries" (budget in KiB, a query's bytes, B);
  * arguments a function does not take are ignored.  SLAM_ERR_INVALID for a name it does not know. */
 int slam_plan_query(const char *name, int a, int b, int c, int guard, int64_t *out);
 
@@ -493,6 +498,59 @@ int slam_grid_locate_dev(slam_ctx *ctx, slam_grid *grid, const float *ranges, in
                          const double *cos_t, const double *sin_t, int n, const double *rot_cs, int K, const int32_t *region,
                          int levels, float max_range, int cap, int32_t *best_out, int32_t *best_cost_out, int32_t *used_out,
                          int64_t *stats_out);
+
+/* ---- map frontiers: clustered exploration goals --------------------------------------------- */
+/* slam_grid_frontiers: "where should the robot go next to see more of this map?" in the sense of Yamauchi - the free
+ * cells that border unexplored space, grouped into 8-connected clusters, one member cell per cluster as a goal; integer
+ * end to end, batched over maps.  The reference has no counterpart.  The call changes nothing in the grid, leaves the
+ * context's sticky status untouched, sees every update enqueued before it on the context's stream and keeps nothing
+ * between calls.  Under slam_timing_* the field counts as SLAM_K_FINALIZE, everything else as SLAM_K_GRID.
+ *
+ * Which map.  Query b reads map gi = grid_of_batch[b]; with grid_of_batch NULL gi = b, and B <= G is required (the
+ * same map B times over is pointless, so NULL does not mean map 0 here).
+ *
+ * Which values.  pmap is what slam_grid_finalize_dev would give NOW: 0 free, 50 unknown, 100 occupied.
+ *
+ * Frontier cell.  F(x, y) iff all of
+ *   - pmap[x][y] == 0;
+ *   - at least one of the four neighbours (x+-1, y), (x, y+-1) that lie inside the map is 50 (a neighbour outside the
+ *     map is not unknown; a cell with only a diagonal unknown neighbour does not qualify);
+ *   - min_unknown == 0, or the number of cells equal to 50 among the cells of the (2*radius+1)^2 window centred on
+ *     (x, y) that lie inside the map is at least min_unknown (a scan's rays leave unknown gaps between them: the plain
+ *     rule alone marks thousands of cells inside explored space);
+ *   - min_clear2 == 0, or field[gi][x][y] >= min_clear2, the field slam_grid_distance_field gives NOW at `cap`.
+ * With min_clear2 == 0 no field is built and cap is ignored.  Otherwise the field is rebuilt for ALL G maps, as
+ * slam_grid_match does: a grid of many maps pays for all of them, whatever B is.
+ *
+ * Clusters.  The 8-connected components of F; the label of a component is the smallest flat index x*yw + y of its
+ * cells.  Of each: size; sx, sy the sums of x and of y (int64); the box x0, y0, x1, y1, inclusive; the rounded centroid
+ * cxr = (2*sx + size) / (2*size), cyr likewise (integer division); the representative: the member with the smallest
+ * (x-cxr)^2 + (y-cyr)^2, ties to the lowest flat index.  (The centroid of a crescent is no frontier cell and may lie in
+ * a wall; the representative always is a frontier cell.)
+ *
+ * Outputs.  count_out [B][2]: the number of clusters with size >= min_size - the TRUE number, also beyond
+ * max_clusters - and the number of frontier cells.  clusters_out [B][M][8], M = max_clusters, rows (label, size, rep_x,
+ * rep_y, x0, y0, x1, y1), and sums_out [B][M][2], rows (sx, sy): the kept clusters in ASCENDING LABEL order, the first
+ * min(count, M) of them; every later row is -1.  labels_out (nullable) [B][xw][yw]: the label of every frontier cell,
+ * those of clusters below min_size included, -1 elsewhere.  With M == 0 the two tables may be NULL.  clusters_out must
+ * be 8-byte aligned (the device form).  A query whose map entry is outside [0, G) gets counts (-1, -1), rows of -1 and
+ * labels of -1, in both forms; the others are unaffected.  Every query gets the same outputs alone, in any batch, in
+ * any order and under any chunking (below).
+ *
+ * Workspace.  In the context's workspace, 4 bytes per cell per query of labels and 8 bytes per 1024 cells of counts,
+ * bounded by the context option "frontier_ws_mb"; the queries are taken in chunks that fit and no result depends on the
+ * cut.
+ *
+ * B >= 1; 0 <= radius <= 8; 0 <= min_unknown <= (2*radius+1)^2; min_clear2 >= 0, and 1 <= cap <= 32767 and
+ * min_clear2 <= cap when min_clear2 > 0; min_size >= 1; 0 <= max_clusters <= 65536; B * max(M, 1) < 2^31; a map of at
+ * most 32768 cells in either axis; the workspace of ONE query within "frontier_ws_mb"; anything else is
+ * SLAM_ERR_INVALID, enqueues nothing and leaves the context as it was. */
+int slam_grid_frontiers(slam_ctx *ctx, slam_grid *grid, int B, const int32_t *grid_of_batch, int radius, int min_unknown,
+                        int min_clear2, int cap, int min_size, int max_clusters, int32_t *count_out, int32_t *clusters_out,
+                        int64_t *sums_out, int32_t *labels_out);
+int slam_grid_frontiers_dev(slam_ctx *ctx, slam_grid *grid, int B, const int32_t *grid_of_batch, int radius, int min_unknown,
+                            int min_clear2, int cap, int min_size, int max_clusters, int32_t *count_out, int32_t *clusters_out,
+                            int64_t *sums_out, int32_t *labels_out);
 
 /* ---- Monte Carlo localisation on the distance field ----------------------------------------- */
 /* F particle filters of P particles each, weighed against their filter's scan on the field above and resampled on
