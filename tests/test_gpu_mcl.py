@@ -13,6 +13,7 @@ import match_ref as M
 import mcl_ref as X
 import raycast_ref as R
 from conftest import pkg
+from mcl_checks import check_resample, check_weigh, fields_of, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -75,55 +76,6 @@ def room(slam, ctx, syn):
                                                abi.ptr(np.ascontiguousarray(room["poses"])), None, 6, 120))
     assert np.array_equal(g.read()["pmap"], case["pmap"])
     return g, case
-
-
-def fields_of(pm, cap):
-    pm = pm if pm.ndim == 3 else pm[None]
-    return np.stack([M.field(p, cap) for p in pm])
-
-
-def same_bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
-
-
-def check_weigh(slam, g, pm, geom, poses, ranges, ct, st, max_range=19.0, cap=64, motion=None, noise=None, maps=None, acc=None,
-                field=None):
-    """One slam_mcl_weigh against the restatement; returns (poses, cost, acc, used) of the device."""
-    fields = fields_of(pm, cap)
-    poses = np.ascontiguousarray(poses, dtype=np.float64)
-    gp, gc, ga, gu = slam.mcl_weigh_host(g, poses, ranges, ct, st, motion=motion, noise=noise, max_range=max_range, cap=cap,
-                                         grid_of_filter=maps, field=field, acc=acc)
-    assert gc.dtype == np.int32 and gu.dtype == np.int32 and (ga is None) == (acc is None)
-    if motion is None:
-        assert same_bits(gp, poses)
-    else:
-        assert np.allclose(gp, X.move(poses, motion, noise), rtol=0.0, atol=1e-9, equal_nan=True)
-    ref = X.weigh(fields, *geom, gp, ranges, ct, st, max_range, cap, maps=maps, acc=acc)      # the cost of the device's own moved poses
-    assert np.array_equal(gu, ref["used"])
-    diff = gc != ref["cost"]
-    F, P = gc.shape
-    for f, p in np.argwhere(diff):
-        gi = 0 if maps is None else int(maps[f])
-        beams = X.used_beams(np.asarray(ranges, dtype=np.float32).reshape(F, -1)[f], ct, st, max_range)
-        assert gc[f, p] >= 0 and ref["cost"][f, p] >= 0 and X.is_unsure(fields[gi], *geom, beams, gp[f, p], cap), (f, p)
-    assert diff.sum() <= 0.02 * F * P
-    if acc is not None:
-        assert ga.dtype == np.int32 and np.array_equal(ga[~diff], ref["acc"][~diff])
-        tot = np.minimum(np.asarray(acc, dtype=np.int64).reshape(F, P) + gc, X.ACC_MAX)
-        assert np.array_equal(ga[diff], tot[diff])
-    return gp, gc, ga, gu
-
-
-def check_resample(slam, ctx, poses, acc, table, u0, shift=0, ess_frac=np.inf):
-    got = slam.mcl_resample_host(ctx, poses, acc, table, u0, shift=shift, ess_frac=ess_frac)
-    ref = X.resample(poses, acc, table, shift, u0, ess_frac)
-    assert same_bits(got[0], ref["poses"])
-    for a, k in zip(got[1:3], ("acc", "ancestors")):
-        assert a.dtype == np.int32 and np.array_equal(a, ref[k]), k
-    assert np.allclose(got[3], ref["est"], rtol=0.0, atol=1e-9, equal_nan=True)
-    assert got[4].dtype == np.int32 and np.array_equal(got[4], ref["info"])
-    assert np.array_equal(got[3][:, 3], ref["est"][:, 3])              # ESS: one multiply and one divide on exact integers
-    return got
 
 
 # ------------------------------------------------------------------ particle counts, beam counts
