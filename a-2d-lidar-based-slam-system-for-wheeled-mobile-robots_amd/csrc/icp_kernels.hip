@@ -455,8 +455,8 @@ struct PolarGeo {
 };
 
 // ---------------------------------------------------------------------------------
-// A float32 pre-filter for the beam-window scan of the one-wave shape's later iterations (context option
-// "icp_f32_filter"): the trips of nn_polar are nine float64-class instructions a candidate, and nearly every query has ONE
+// A float32 pre-filter for the beam-window scans of the one-wave shape (context option "icp_f32_filter"; every iteration:
+// the lanes' own windows, and in the first one the probe and the windows of the listed queries, nn_listed_wave): the trips of nn_polar are nine float64-class instructions a candidate, and nearly every query has ONE
 // candidate that is nearest by far more than float32 can blur.  The trips run on a float32 image of the target and keep
 // the smallest square, the runner-up and the winner's index; float64 still decides: a lane is SETTLED when the smallest
 // square beats the runner-up by more than both can be wrong, then the winner's float64 square is formed from tarP as the
@@ -620,12 +620,24 @@ __device__ __forceinline__ void nn_polar(const double2 *__restrict__ tarP, int n
         // it: the surface the query lies on is usually seen a few beams away (1.5 % of the lanes, 18 % of the
         // wave-queries remain for the box search).  Any index is a valid guess: it only supplies the bound.
         const bool need = active && !fits;
-        Best pb;
-        pb.start();
-        pb.j = seed;
-        scan(need ? max(seed - kPolarProbe, 0) : 1, need ? min(seed + kPolarProbe, n_tar - 1) : 0, pb);
+        const int p0 = need ? max(seed - kPolarProbe, 0) : 1, p1 = need ? min(seed + kPolarProbe, n_tar - 1) : 0;
+        int pj = seed;
+        if (F32) {
+            // (in float32 without a proof: whatever index wins here only supplies the bound, the window that follows
+            // holds the nearest target for every guess)
+            F32Best pf;
+            pf.start();
+            scan32(f32.img, n_tar, fsx, fsy, p0, p1, pf);
+            pj = pf.m < kF32Inf ? pf.index() : seed;
+        } else {
+            Best pb;
+            pb.start();
+            pb.j = seed;
+            scan(p0, p1, pb);
+            pj = pb.j;
+        }
         int lo1, hi1;
-        const bool fits1 = window(pb.j, lo1, hi1) && need;
+        const bool fits1 = window(pj, lo1, hi1) && need;
         lo = fits1 ? lo1 : lo;
         hi = fits1 ? hi1 : hi;
         fits = fits || fits1;
@@ -1008,9 +1020,9 @@ struct NNTarget {
     int nblocks, n_tar;
     bool has_p;
     double2 *qlist;            // the list of first-iteration queries without a usable beam window (nn_listed),
-    int *qseed;                // their guesses,
+    int *qseed;                // their guesses (neither in the one-wave shape with the float32 image: its list is in registers),
     int cap;                   // its room; 0: no list
-    F32Image f32 = F32Image{nullptr, 0.0f};   // the float32 image of the one-wave shape's later iterations, or none
+    F32Image f32 = F32Image{nullptr, 0.0f};   // the float32 image of the one-wave shape's beam windows, or none
     __device__ __forceinline__ double2 at(int j) const { return has_p ? tarP[j] : tarB[tslot(j)]; }
 };
 struct NNQuery {
@@ -1027,7 +1039,8 @@ __device__ __forceinline__ double match_distance(double d2) { return (d2 < INFIN
 // from the reference's order of distances (see "Best") is added to amb_mask, the wave-wide mask of lanes that saw one:
 // kept in scalar registers (a per-lane flag cost four vector instructions a query); amb_mask != 0 -> the pair is re-done
 // with EXACT.  note_big(big): the diagnostic build's counter of queries left to the box search.
-template <int UNROLL, int STRIDE, bool EXACT, bool F32 = false, typename Place, typename NoteBig>
+// REGLIST: the list is not in LDS - the caller deals the listed queries (slot >= 0) to its lanes itself (icp_pair_wave).
+template <int UNROLL, int STRIDE, bool EXACT, bool F32 = false, bool REGLIST = false, typename Place, typename NoteBig>
 __device__ __forceinline__ NNQuery nn_query(const NNTarget &t, const PolarGeo &pg, const double sx, const double sy, const int seed, const bool okq,
                                             const bool first, const bool listing, Place &&place, NoteBig &&note_big, unsigned long long &amb_mask)
 {
@@ -1049,8 +1062,10 @@ __device__ __forceinline__ NNQuery nn_query(const NNTarget &t, const PolarGeo &p
                 const int pos = place(bm) + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bm, 0u));
                 if (big && pos < t.cap) {
                     h.slot = pos;
-                    t.qlist[pos] = make_double2(sx, sy);
-                    t.qseed[pos] = seed;
+                    if (!REGLIST) {
+                        t.qlist[pos] = make_double2(sx, sy);
+                        t.qseed[pos] = seed;
+                    }
                     big = false;                                     // (a list that is full leaves the rest to the box search)
                 }
             }
@@ -1508,8 +1523,8 @@ __device__ __forceinline__ bool icp_pair(const IcpArgs &a, const int b, char *sm
 // queries' search: the square of the distance is that of the query to the match as the search computed it, the same
 // operations on the same bits); the originals are formed again from the source for the final transform.  LDS holds the
 // unpadded image of the target (NaN points up to a whole block and behind the last beam), the boxes and a list for a
-// quarter of the queries: 8.6 KB for 360 beams, so that registers (128: four waves per SIMD) and not LDS bound the pairs
-// resident on a CU.  The box search (1.3 % of the queries) reads the unpadded image.  Sums are added in another order than
+// quarter of the queries: 8.6 KB for 360 beams - 9.6 KB with the float32 image in the list's place and the list in
+// registers (F32) - so that registers (128: four waves per SIMD) and not LDS bound the pairs resident on a CU.  The box search (1.3 % of the queries) reads the unpadded image.  Sums are added in another order than
 // in the workgroup shape; everything else is the shared pieces above.
 // ---------------------------------------------------------------------------------
 // (kWaveQpt, kWaveRound, icp_wave_points, icp_wave_lds_bytes: launch_shapes.h)
@@ -1543,6 +1558,92 @@ __device__ __forceinline__ double match_distance_wave(double d2)       // by the
     return sqrt_unscaled(d2);
 }
 
+// The list of this shape with the float32 image (F32Image), which takes the list's LDS: the list lives in REGISTERS.  Entry e
+// belongs to lane e % 64 in round e / 64 (a list holds at most a quarter of 384 queries: two rounds), one word: in, the
+// query's index + 1 - before the first update query i is pc.source(i) and its guess beam min(i, n_tar - 1), formed again by
+// the lane that works on it, the same operations on the same bits; out, the match's index, the tie flag in its sign bit
+// (the owner forms the square again from query and match).
+constexpr int kWaveListRounds = 2;
+static_assert((kWave * kWaveQpt + 3) / 4 <= kWaveListRounds * kWave, "the register list holds a quarter of the queries");
+
+// Deal the queries a slot has just listed (listed: this lane's query went to place first + its rank among them) to the
+// lanes that will work on them: ONE forward lane exchange.  Every lane sends - an exchange leaves a lane nobody sends to
+// with 0, and one inside a branch would not reach the lanes outside it - the listed ones their index to lane place % 64,
+// the others a 0 to the lanes that are left, in order: a permutation, no two lanes send to one.
+__device__ __forceinline__ void wave_list_deal(const bool listed, const int first, const int qi, int (&work)[kWaveListRounds])
+{
+    const unsigned long long pm = __ballot(listed);
+    if (pm == 0ull) return;                                          // wave-uniform
+    const int lane = threadIdx.x, cnt = (int)__popcll(pm);
+    const int rank = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(pm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)pm, 0u));
+    const int dest = listed ? first + rank : first + cnt + (lane - rank);         // (lane - rank: its rank among the others)
+    const int got = __builtin_amdgcn_ds_permute((dest & (kWave - 1)) << 2, listed ? qi + 1 : 0);
+    const int rel = (lane - first) & (kWave - 1), place = first + rel;
+    if (rel < cnt) {
+        if (place < kWave) work[0] = got;
+        else work[1] = got;
+    }
+}
+
+// nn_listed over that list, nq entries: probe and listed window go through the float32 image; the row search takes its
+// query from the worker lane by a lane exchange and stays float64.
+template <typename T>
+__device__ __forceinline__ void nn_listed_wave(const PairClouds<T> &pc, const double2 *__restrict__ tarP, int n_tar, const PolarGeo &geo,
+                                               const F32Image f32, int (&work)[kWaveListRounds], int nq)
+{
+    const int lane = threadIdx.x, row = lane >> 4;
+#pragma unroll
+    for (int r = 0; r < kWaveListRounds; ++r) {
+        if (r * kWave >= nq) break;                                  // wave-uniform
+        const bool act = r * kWave + lane < nq;
+        const int i = act ? work[r] - 1 : 0;                         // (a lane without an entry: any query, it searches nothing)
+        const double2 qp = pc.source(i, true);
+        double d2;
+        int j;
+        bool big, amb;
+        unsigned long long ambm;
+        nn_polar<4, true, true>(tarP, n_tar, qp.x, qp.y, min(i, n_tar - 1), act, geo, kPolarMaxListed, d2, j, big, amb, ambm, f32);
+        int res = j | (amb ? (int)0x80000000 : 0);
+        unsigned long long left = __ballot(big);
+        while (left != 0ull) {                                       // four of the remaining queries, one per row
+            int src = 0, cnt = 0, whose[4] = {0, 0, 0, 0};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if (left != 0ull) {
+                    const int l = __ffsll((long long)left) - 1;
+                    left &= left - 1ull;
+                    src = row == k ? l : src;
+                    whose[k] = l;
+                    cnt = k + 1;
+                }
+            }
+            double bd;
+            int jf;
+            nn_row(tarP, n_tar, make_double2(__shfl(qp.x, src), __shfl(qp.y, src)), bd, jf);   // (rows without a query repeat lane 0's)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int found = __shfl(jf, 16 * k);                // (every lane of row k holds its query's result)
+                if (k < cnt && lane == whose[k]) res = found;
+            }
+        }
+        work[r] = res;
+    }
+}
+
+// What nn_listed_wave left for the query listed at `slot` (none: slot < 0, j stays); the flag goes to amb_mask.  Called by
+// the whole wave; two_rounds (wave-uniform): the list went into the second round.
+__device__ __forceinline__ void listed_index(const int (&work)[kWaveListRounds], const bool two_rounds, const int slot, int &j, unsigned long long &amb_mask)
+{
+    const int r0 = __shfl(work[0], slot & (kWave - 1)), r1 = two_rounds ? __shfl(work[1], slot & (kWave - 1)) : 0;
+    bool flagged = false;
+    if (slot >= 0) {
+        const int jf = slot < kWave ? r0 : r1;
+        flagged = jf < 0;
+        j = jf & 0x7fffffff;
+    }
+    amb_mask |= __ballot(flagged);
+}
+
 template <typename T, bool EXACT, bool F32>
 __device__ __forceinline__ bool icp_pair_wave(const IcpArgs &a, const int b, char *smem)
 {
@@ -1551,9 +1652,12 @@ __device__ __forceinline__ bool icp_pair_wave(const IcpArgs &a, const int b, cha
     double2 *tarP = reinterpret_cast<double2 *>(smem);                                           // [icp_wave_points]
     Box *boxes = reinterpret_cast<Box *>(tarP + icp_wave_points(n_tar));                         // [padded to x4]
     Box *boxes4 = boxes + nn_boxes_padded(n_tar);                                                // one per 4 blocks
-    double2 *qlist = reinterpret_cast<double2 *>(boxes4 + nn_boxes4(n_tar));                     // [a.team_cap] nn_listed
-    int *qseed = reinterpret_cast<int *>(qlist + a.team_cap);                                    // [a.team_cap]
-    float2 *tarF = reinterpret_cast<float2 *>(qlist);                                            // [icp_wave_points] F32: over the list, after the first iteration
+    // behind the boxes: the list of nn_listed, [a.team_cap] queries and [a.team_cap] guesses - or, F32, the float32 image
+    // [icp_wave_points] (the list of that form is in registers: wave_list_deal)
+    double2 *qlist = reinterpret_cast<double2 *>(boxes4 + nn_boxes4(n_tar));
+    int *qseed = reinterpret_cast<int *>(qlist + a.team_cap);
+    float2 *tarF = reinterpret_cast<float2 *>(qlist);
+    if constexpr (F32) qlist = nullptr, qseed = nullptr;
     char *guard = smem + icp_wave_lds_bytes(n_tar, a.team_cap, F32);
     lds_guard_fill(guard);
 
@@ -1592,6 +1696,20 @@ __device__ __forceinline__ bool icp_pair_wave(const IcpArgs &a, const int b, cha
     wave_sync();
     stage_boxes<kNNBlock, true>(n_tar, tarP, boxes, boxes4);
     wave_sync();
+    // the float32 image of the target for every iteration's beam windows (F32Image), beside the list
+    if constexpr (F32 && !EXACT) if (pg.inv_db > 0.0f && a.max_iter > 0) {
+        float tm = 0.0f;
+        for (int j = lane; j < icp_wave_points(n_tar); j += kWave) {
+            const double2 t = tarP[j];                               // (NaN behind the last beam)
+            const float fx = t.x == t.x ? (float)t.x : INFINITY, fy = t.y == t.y ? (float)t.y : INFINITY;
+            tarF[j] = make_float2(fx, fy);
+            if (t.x == t.x && t.y == t.y) tm = fmaxf(tm, fabsf(fx) + fabsf(fy));
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) tm = fmaxf(tm, __shfl_xor(tm, off));
+        nt.f32 = F32Image{tarF, __uint_as_float((unsigned)__builtin_amdgcn_readfirstlane((int)__float_as_uint(tm * 1.000001f)))};
+        wave_sync();
+    }
 
     const double dn = (double)n_src;
     const LaneSel ls = lane_sel(lane);
@@ -1608,21 +1726,28 @@ __device__ __forceinline__ bool icp_pair_wave(const IcpArgs &a, const int b, cha
     // the first iteration: centroids, then centred products, as the reference (icp.py:154-160); the only one that lists queries
     auto first_iteration = [&]() __attribute__((always_inline)) -> bool {
         const bool listing = !EXACT && a.team_cap > 0 && pg.inv_db > 0.0f;
+        int work[kWaveListRounds] = {0, 0};                           // F32: the list (wave_list_deal)
+        (void)work;
 #pragma unroll
         for (int q = 0; q < QPT; ++q) {
             if (q * kWave >= n_src) continue;                        // wave-uniform
-            const NNQuery h = nn_query<4, kNNBlock, EXACT>(nt, pg, sx[q], sy[q], seed[q], lane + q * kWave < n_src, true, listing, place, no_note, amb_mask);
+            const int first = nlisted;
+            const NNQuery h = nn_query<4, kNNBlock, EXACT, F32 && !EXACT, F32 && !EXACT>(nt, pg, sx[q], sy[q], seed[q], lane + q * kWave < n_src, true, listing, place,
+                                                                                         no_note, amb_mask);
             seed[q] = h.slot >= 0 ? -1 - h.slot : h.j;               // (a listed query keeps its place on the list here)
+            if constexpr (F32 && !EXACT) if (listing) wave_list_deal(h.slot >= 0, first, lane + q * kWave, work);
         }
         if (listing) {
             wave_sync();
-            nn_listed<4>(tarP, n_tar, pg, qlist, qseed, min(nlisted, a.team_cap));
+            if constexpr (F32) nn_listed_wave(pc, tarP, n_tar, pg, nt.f32, work, min(nlisted, a.team_cap));
+            else nn_listed<4>(tarP, n_tar, pg, qlist, qseed, min(nlisted, a.team_cap));
             wave_sync();
 #pragma unroll
             for (int q = 0; q < QPT; ++q) {
                 if (q * kWave >= n_src) continue;
                 double d2 = 0.0;                                     // (formed again below from query and match)
-                listed_result(qlist, -1 - seed[q], d2, seed[q], amb_mask);
+                if constexpr (F32) listed_index(work, min(nlisted, a.team_cap) > kWave, -1 - seed[q], seed[q], amb_mask);
+                else listed_result(qlist, -1 - seed[q], d2, seed[q], amb_mask);
             }
         }
         double v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -1672,23 +1797,7 @@ __device__ __forceinline__ bool icp_pair_wave(const IcpArgs &a, const int b, cha
         advance(rigid_from_w(o.c, o.A, 0.0, o.B, 0.0, !same.wave_differs() || src_collapsed, lane), o.c.bx, o.c.by, sx, sy, s);
         return converged(s, a.tol);
     };
-    // the float32 image of the target for the later iterations' beam windows (F32Image), over the list the first one is done with
-    auto stage_f32 = [&]() __attribute__((always_inline)) {
-        wave_sync();
-        float tm = 0.0f;
-        for (int j = lane; j < icp_wave_points(n_tar); j += kWave) {
-            const double2 t = tarP[j];                               // (NaN behind the last beam)
-            const float fx = t.x == t.x ? (float)t.x : INFINITY, fy = t.y == t.y ? (float)t.y : INFINITY;
-            tarF[j] = make_float2(fx, fy);
-            if (t.x == t.x && t.y == t.y) tm = fmaxf(tm, fabsf(fx) + fabsf(fy));
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) tm = fmaxf(tm, __shfl_xor(tm, off));
-        nt.f32 = F32Image{tarF, __uint_as_float((unsigned)__builtin_amdgcn_readfirstlane((int)__float_as_uint(tm * 1.000001f)))};
-        wave_sync();
-    };
     if (a.max_iter > 0 && !first_iteration()) {
-        if (F32 && !EXACT && pg.inv_db > 0.0f && a.max_iter > 1) stage_f32();
         for (int it = 1; it < a.max_iter; ++it)
             if (iteration()) break;
     }
@@ -1755,7 +1864,7 @@ __global__ void __launch_bounds__(1024) k_icp(IcpArgs a)
 // k_icp<T>: one WAVE per pair (icp_pair_wave); at most 128 registers, so that four pairs are resident per SIMD.  An overload
 // of the name on purpose: kernel traces, counter summaries and the benchmark's roofline file the scan matcher under k_icp
 // whatever its launch shape, and tell the shapes apart by their template arguments.
-// F32: the later iterations' beam windows are scanned in float32 first (F32Image; context option "icp_f32_filter").
+// F32: the beam windows of every iteration are scanned in float32 first (F32Image; context option "icp_f32_filter").
 template <typename T, bool F32>
 __global__ void __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(4))) k_icp(IcpArgs a)
 {

@@ -321,14 +321,14 @@ SLAM_HD inline int icp_wave_points(int n_tar)
     const int whole = nn_blocks(n_tar) * kNNBlock, tail = n_tar + kPolarTail;
     return whole > tail ? whole : tail;
 }
-// (f32: the float32 image of the later iterations lies over the first iteration's list, which is dead by then - 360 beams:
-// 8 768 B with a list of 96, 9 792 B with the image of 368 points over it, 16 pairs a CU either way; side by side they
-// would be 11 712 B and 13)
+// (f32: the float32 image serves the first iteration too, so it cannot lie over the list as it first did - the list of that
+// form is kept in registers instead, a word a query dealt to the lanes by a lane exchange, and takes no LDS.  360 beams:
+// 8 768 B with a list of 96 slots of 20 B, 9 792 B with the image of 368 points, 16 pairs a CU either way; image and
+// 20-byte slots side by side would be 11 712 B and 13)
 SLAM_HD inline size_t icp_wave_lds_bytes(int n_tar, int cap, bool f32)   // (without the guard: the kernel puts it behind)
 {
-    const size_t list = (size_t)cap * kListSlotBytes, image = f32 ? (size_t)icp_wave_points(n_tar) * kFloat2Bytes : 0;
-    return (size_t)icp_wave_points(n_tar) * kDouble2Bytes + (size_t)(nn_boxes_padded(n_tar) + nn_boxes4(n_tar)) * kBoxBytes +
-           (list > image ? list : image);
+    const size_t behind = f32 ? (size_t)icp_wave_points(n_tar) * kFloat2Bytes : (size_t)cap * kListSlotBytes;
+    return (size_t)icp_wave_points(n_tar) * kDouble2Bytes + (size_t)(nn_boxes_padded(n_tar) + nn_boxes4(n_tar)) * kBoxBytes + behind;
 }
 SLAM_HD inline int icp_block(int n_src, int qpt)
 {
@@ -400,7 +400,7 @@ inline IcpShape plan_icp(const IcpRequest &a)
     // (context option "icp_one_wave").
     {
         const int cap = (a.is_scan && a.team_mode == 0) ? ((a.n_src + 3) / 4 + 15) / 16 * 16 : 0;   // the list: a quarter of the queries (a fifth is listed on the benchmark scans)
-        // a.f32_filter: -1 / 1 = the float32 pre-filter of the later iterations' beam windows (scans only: a point cloud has no
+        // a.f32_filter: -1 / 1 = the float32 pre-filter of every iteration's beam windows (scans only: a point cloud has no
         // windows), 0 = the float64 scan alone (context option "icp_f32_filter"; no result depends on it)
         const bool f32 = a.f32_filter != 0 && a.is_scan;
         const size_t lds = icp_wave_lds_bytes(a.n_tar, cap, f32) + a.guard;

@@ -90,7 +90,7 @@ struct IcpArgs {
     int team_cap = 0;          // set by launch_icp: room in the LDS list of first-iteration queries without a beam window (nn_listed), 0: none
     int team_mode = 0;         // context option "icp_team": 0 = on where it applies, 1 = off (the box search takes every such query)
     int one_wave = -1;         // context option "icp_one_wave": -1 = one wave per pair where a full-chip launch allows it, 0 = never, 1 = wherever a pair fits
-    int f32_filter = -1;       // context option "icp_f32_filter": the one-wave shape scans its later iterations' beam windows in float32 first, float64 decides: -1 = on, 0 = off, 1 = on
+    int f32_filter = -1;       // context option "icp_f32_filter": the one-wave shape scans its beam windows in float32 first, float64 decides: -1 = on, 0 = off, 1 = on
     int batch_invariant = 0;   // 1: launch_icp picks a shape that does not depend on B (the node replay: results independent of the batch)
 };
 

@@ -105,7 +105,7 @@ int slam_check_status(slam_ctx *ctx);
  *   launch holds at least 16 384 pairs (four rounds of the pairs resident in this shape), the clouds
  *   are scans and 16 pairs fit a compute unit's LDS; 0 = never; 1 = wherever a pair fits.  Same matches and iteration counts;
  *   transforms agree with the other shapes to rounding, as above.
- * "icp_f32_filter": the one-wave shape scans the beam windows of its iterations after the first in float32
+ * "icp_f32_filter": the one-wave shape scans the beam windows of its iterations, the first included, in float32
  *   first and forms in float64 only the winner's distance, wherever every lane of the wave has PROVED its
  *   nearest target (it beats the runner-up by more than float32 can be wrong); any other wave runs the
  *   float64 scan as before.  -1 = the library's choice (default: on), 0 = off, 1 = on.  No result depends
