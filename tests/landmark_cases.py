@@ -65,14 +65,14 @@ def filter_states(ekf, u, z, x0=None):
 
 def nudge_stability(ekf, drive, eps=1e-12, runs=4, seed=99):
     """(states of the drive, worst move of x and P over `runs` re-runs with every observation row moved by a uniform
-    +-eps; inf if a landmark count or the status changes).  The pattern is loc_ref.stable: association and the
-    append rule are discontinuous, and a drive is usable when nothing jumps."""
-    ref = filter_states(ekf, drive["u"], drive["z"])
+    +-eps; inf if a landmark count or the status changes); the drive may carry its start pose as "x0".  The pattern is
+    loc_ref.stable: association and the append rule are discontinuous, and a drive is usable when nothing jumps."""
+    ref = filter_states(ekf, drive["u"], drive["z"], drive.get("x0"))
     rng = np.random.default_rng(seed)
     worst = 0.0
     for _ in range(runs):
         z = [zs + rng.uniform(-eps, eps, size=zs.shape) for zs in drive["z"]]
-        got = filter_states(ekf, drive["u"], z)
+        got = filter_states(ekf, drive["u"], z, drive.get("x0"))
         if len(got) != len(ref):
             return ref, float("inf")
         for (x, P, nlm, st), (xr, Pr, nr, sr) in zip(got, ref):

@@ -51,8 +51,8 @@ def host_node(slam, scans):
 def assert_matches_host(out, l, ref, pmap=None):
     c, done = len(ref["kept"]), len(ref["nlm"])
     assert out["kept"][l, :c].tolist() == ref["kept"]
-    if ref["raised"]:                             # the device stops where the reference raises, with the state before
-        assert out["status"][l] == 1 and out["kept_count"][l] >= c
+    if ref["raised"] or ref.get("stop"):          # the device stops where the reference raises, with the state before; "stop":
+        assert out["status"][l] == (ref.get("stop") or 1) and out["kept_count"][l] >= c      # on a cap, `ref` being the scans before
     else:
         assert out["status"][l] == 0 and out["kept_count"][l] == c and np.all(out["kept"][l, c:] == -1)
     assert out["nlm"][l, :done].tolist() == ref["nlm"] and np.all(out["nlm"][l, done:] == -1)
