@@ -12,7 +12,9 @@ zjwzcx/A-2D-LiDAR-based-SLAM-System-for-Wheeled-Mobile-Robots:
                DeviceGrid.locate, grid_locate_host, locate_rotations, locate_pose; MCL.init_global starts from it);
                frontiers / next_goal: where to go next to see more of the map - clustered frontier cells, one goal per
                cluster (batched: DeviceGrid.frontiers, grid_frontiers_host, frontier_points; GridSLAM / DeviceGridSLAM
-               .frontiers on the best particle's map)
+               .frontiers on the best particle's map); travel_field / travel_path / next_goal(by="travel"): what it
+               costs to drive to every cell, the way there, and the frontier that is nearest to drive to (batched:
+               DeviceGrid.travel, grid_travel_host; DeviceGridSLAM.travel / .next_goals)
     bresenham  (start, end).path
     SLAM_EKF   laserCallback glue (scan matching + map building); landmarks=True: the whole W12
                node with Extraction and the landmark EKF on the host; batched on the device
@@ -36,6 +38,7 @@ libslamhip.so or the GPU is missing (there is no CPU implementation in the produ
 """
 from . import _abi, dist, param, synthetic
 from ._abi import Context, LibraryMissing, SlamError, default_context
+from ._abi import TRAVEL_DIAGONAL, TRAVEL_STRAIGHT, TRAVEL_TRIPS
 from ._abi import RAY_BAD, RAY_BLOCKED, RAY_CLASSES, RAY_EMPTY, RAY_FREE, RAY_HIT, RAY_NAMES, RAY_OUT, RAY_UNKNOWN
 from . import dwa
 from .bresenham import bresenham, rasterize
@@ -55,7 +58,7 @@ from .replay import DeviceGrid, DeviceReplay, grid_raycast_host, grid_score_host
 from .replay import grid_distance_field_host, grid_match_host, match_pose, match_rotations
 from .replay import grid_copy_maps_host, grid_update_particles_host
 from .replay import grid_locate_host, locate_pose, locate_rotations
-from .replay import frontier_points, grid_frontiers_host
+from .replay import frontier_points, grid_frontiers_host, grid_travel_host
 from .grid_slam import DeviceGridSLAM, GridSLAM
 from .slam_ekf import SLAM_EKF
 from .synthetic import LaserScan
@@ -67,7 +70,8 @@ __all__ = ["ICP", "Mapping", "Localization", "EKF", "Extraction", "LandMarkSet",
            "DeviceNodeReplay", "node_replay_host", "landmarks_host", "ekf_lm_host",
            "DeviceLocalizationReplay", "loc_replay_host", "grid_raycast_host", "grid_score_host",
            "grid_distance_field_host", "grid_match_host", "match_pose", "match_rotations",
-           "grid_locate_host", "locate_pose", "locate_rotations", "grid_frontiers_host", "frontier_points",
+           "grid_locate_host", "locate_pose", "locate_rotations", "grid_frontiers_host", "frontier_points", "grid_travel_host",
+           "TRAVEL_STRAIGHT", "TRAVEL_DIAGONAL", "TRAVEL_TRIPS",
            "MCL", "DeviceMCL", "MCL_DEAD", "mcl_weight_table", "mcl_weigh_host", "mcl_resample_host",
            "GridSLAM", "DeviceGridSLAM", "mcl_settle_host", "grid_copy_maps_host", "grid_update_particles_host",
            "RAY_EMPTY", "RAY_HIT", "RAY_BLOCKED", "RAY_FREE", "RAY_UNKNOWN", "RAY_OUT", "RAY_BAD", "RAY_CLASSES", "RAY_NAMES"]

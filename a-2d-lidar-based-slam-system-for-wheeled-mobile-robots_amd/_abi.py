@@ -87,6 +87,8 @@ _SIGS = {
     "slam_grid_locate_dev": ([_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, C.c_float, _i, _vp, _vp, _vp, _vp], _i),
     "slam_grid_frontiers": ([_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
     "slam_grid_frontiers_dev": ([_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
+    "slam_grid_travel": ([_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp], _i),
+    "slam_grid_travel_dev": ([_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp], _i),
     "slam_mcl_weigh": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, C.c_float, _i, _vp, _vp, _vp, _vp], _i),
     "slam_mcl_weigh_dev": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, C.c_float, _i, _vp, _vp, _vp, _vp], _i),
     "slam_mcl_resample": ([_vp, _vp, _vp, _vp, _i, _i, _vp, _d, _i, _i, _vp, _vp, _vp, _vp], _i),
@@ -145,6 +147,7 @@ EKF_MAX_LM = 32
 RAY_EMPTY, RAY_HIT, RAY_BLOCKED, RAY_FREE, RAY_UNKNOWN, RAY_OUT, RAY_BAD = range(7)
 RAY_CLASSES = 7
 MCL_DEAD = 2 ** 31 - 1             # SLAM_MCL_DEAD: a dead particle's accumulated cost
+TRAVEL_STRAIGHT, TRAVEL_DIAGONAL, TRAVEL_TRIPS = 10, 14, 1      # SLAM_TRAVEL_*: the two move costs and the trip-bound status
 RAY_NAMES = ("empty", "hit", "blocked", "free", "unknown", "out", "bad")
 
 

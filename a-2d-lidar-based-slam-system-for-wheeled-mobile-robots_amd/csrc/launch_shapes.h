@@ -610,4 +610,66 @@ inline FrontierShape plan_frontiers(const FrontierRequest &r)
     return p;
 }
 
+// ---------------------------------------------------------------------------------
+// Travel-cost field (travel_kernels.hip, slam_grid_travel)
+// ---------------------------------------------------------------------------------
+// One query = one map and its sources.  The map's cells are cut into tiles of kTravelTile x kTravelTile; the bits of the
+// traversable set T lie in rows padded to whole tiles of y, one 64-bit word per (row, tile column).  ONE workgroup owns
+// the whole relaxation of a query: it takes the dirty tile with the lowest pending border cost, relaxes it with a one-cell
+// halo in LDS until nothing changes and marks the neighbours whose facing border went down.  With that order a tile's
+// pending keys rise strictly and each is the final cost of one of the 4 * kTravelTile + 4 cells around it (DESIGN.md
+// section 19), which bounds the activations of a query by tiles * kTravelTripsPerTile.
+// Workspace of a query (context option "travel_ws_mb"): 4 bytes per cell of costs unless cost_out takes them, 8 bytes
+// per (row, tile column) of T, 4 bytes per tile of pending keys; queries are taken in chunks that fit.
+constexpr int kTravelTile = 64;
+constexpr int kTravelThreads = 1024;
+constexpr int kTravelStraight = 10, kTravelDiagonal = 14;
+constexpr int kTravelMaxSources = 64, kTravelMaxFoot = 8, kTravelMaxGoals = 65536;
+constexpr int kTravelTripsPerTile = 4 * kTravelTile + 6;      // the first activation, one per cell around the tile, one to spare
+constexpr long kTravelMaxBlocks = 1L << 20;   // workgroups of a launch; more groups are taken grid-stride
+
+// dynamic LDS of the relaxation: costs int32 [(Tile + 2)^2], T bytes [(Tile + 2)^2] rounded up to 16, 64 words of
+// selection keys and marks, then the guard
+SLAM_HD inline size_t travel_lds_bytes(int guard = kLdsGuard)
+{
+    const size_t halo = (size_t)(kTravelTile + 2) * (kTravelTile + 2);
+    return halo * 4 + (halo + 15) / 16 * 16 + 64 * 4 + (size_t)guard;
+}
+
+struct TravelRequest {
+    long B = 0;
+    int xw = 0, yw = 0;
+    bool own_costs = true;       // cost_out is NULL: the costs live in the workspace
+    long ws_bytes = 0;
+    int guard = kLdsGuard;
+};
+struct TravelShape {
+    bool ok = false;             // false: one query's workspace does not fit the budget
+    int tiles_x = 0, tiles_y = 0;
+    long tiles = 0;
+    long mask_words = 0;         // 64-bit words of T per query: xw * tiles_y
+    long trips = 0;              // bound on the tile activations of a query
+    long query_bytes = 0;
+    long chunk_queries = 0, chunks = 0;
+    int lds = 0, threads = kTravelThreads;
+};
+inline TravelShape plan_travel(const TravelRequest &r)
+{
+    TravelShape p;
+    if (r.B < 1 || r.xw < 1 || r.yw < 1) return p;
+    const long cells = (long)r.xw * r.yw;
+    p.tiles_x = (r.xw + kTravelTile - 1) / kTravelTile;
+    p.tiles_y = (r.yw + kTravelTile - 1) / kTravelTile;
+    p.tiles = (long)p.tiles_x * p.tiles_y;
+    p.mask_words = (long)r.xw * p.tiles_y;
+    p.trips = p.tiles * kTravelTripsPerTile;
+    p.query_bytes = (r.own_costs ? cells * 4 : 0) + p.mask_words * 8 + (p.tiles * 4 + 7) / 8 * 8;
+    p.lds = (int)travel_lds_bytes(r.guard);
+    p.chunk_queries = std::min(r.B, r.ws_bytes / p.query_bytes);
+    if (p.chunk_queries < 1) return p;
+    p.chunks = (r.B + p.chunk_queries - 1) / p.chunk_queries;
+    p.ok = true;
+    return p;
+}
+
 }  // namespace slam

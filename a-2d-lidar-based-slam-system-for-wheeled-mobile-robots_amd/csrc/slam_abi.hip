@@ -106,6 +106,7 @@ struct slam_ctx {
     int mcl_shape = -1;   // slam_mcl_weigh: -1 = the library's choice by beam count, 0 = lanes over particles, 1 = a wave per particle, lanes over beams; changes no result
     long locate_ws_bytes = 64L << 20; // slam_grid_locate: bytes its node lists may take ("locate_ws_mb"); pairs are cut into chunks that fit; changes no result
     long frontier_ws_bytes = 256L << 20; // slam_grid_frontiers: bytes its labels may take ("frontier_ws_mb"); queries are cut into chunks that fit; changes no result
+    long travel_ws_bytes = 256L << 20; // slam_grid_travel: bytes its costs, traversable bits and tile keys may take ("travel_ws_mb"); queries are cut into chunks that fit; changes no result
     int icp_team = 0;     // first-iteration queries without a beam window: 0 = listed and searched apart from their lanes (nn_listed), 1 = box search
     // "pipeline" option: the map stage of slam_replay_dev (reset -> ray cast -> finalize) runs on
     // a second stream, so the map stage of one replay overlaps the scan matching of the next.
@@ -716,6 +717,7 @@ static const OptionRange kOptionRanges[] = {
     {"mcl_shape", [](double v) { return v == -1 || v == 0 || v == 1; }, "mcl_shape is -1, 0 or 1"},
     {"locate_ws_mb", [](double v) { return v > 0 && v <= 1048576; }, "locate_ws_mb in (0, 1048576]"},
     {"frontier_ws_mb", [](double v) { return v > 0 && v <= 1048576; }, "frontier_ws_mb in (0, 1048576]"},
+    {"travel_ws_mb", [](double v) { return v > 0 && v <= 1048576; }, "travel_ws_mb in (0, 1048576]"},
 };
 
 int slam_set_option(slam_ctx *c, const char *name, double value)
@@ -741,6 +743,7 @@ int slam_set_option(slam_ctx *c, const char *name, double value)
     else if (!strcmp(name, "mcl_shape")) c->mcl_shape = (int)value;
     else if (!strcmp(name, "locate_ws_mb")) c->locate_ws_bytes = (long)(value * 1048576.0);
     else if (!strcmp(name, "frontier_ws_mb")) c->frontier_ws_bytes = (long)(value * 1048576.0);
+    else if (!strcmp(name, "travel_ws_mb")) c->travel_ws_bytes = (long)(value * 1048576.0);
     else if (!strcmp(name, "pipeline")) {
         TRY(join_from_grid(c));
         if (value == 1 && !c->gstream) {
@@ -867,6 +870,22 @@ static FrontierShape frontier_plan_for(int xw, int yw, int radius, long B, long 
     return plan_frontiers(r);
 }
 
+static TravelShape travel_plan_for(int xw, int yw, bool own_costs, long B, long ws_bytes, int guard)
+{
+    TravelRequest r;
+    r.B = B; r.xw = xw; r.yw = yw; r.own_costs = own_costs; r.ws_bytes = ws_bytes; r.guard = guard;
+    return plan_travel(r);
+}
+// a budget of `kib` KiB, queries of `bytes` bytes, B of them, as plan_travel cuts them: the queries of a chunk (chunks:
+// their number); 0 when one query does not fit
+static int64_t travel_plan_chunk(long kib, long bytes, long B, bool chunks)
+{
+    if (bytes <= 0 || B < 1) return 0;
+    const long per = std::min(B, kib * 1024 / bytes);
+    if (per < 1) return 0;
+    return chunks ? (B + per - 1) / per : per;
+}
+
 int slam_plan_query(const char *name, int a, int b, int c, int guard, int64_t *out)
 {
     if (!name || !out) return fail(SLAM_ERR_INVALID, "slam_plan_query: null pointer");
@@ -911,6 +930,15 @@ int slam_plan_query(const char *name, int a, int b, int c, int guard, int64_t *o
         {"frontier_segs", frontier_plan_for(a, b, 0, 1, 1L << 40, g).segs}, {"frontier_query_bytes", frontier_plan_for(a, b, 0, 1, 1L << 40, g).query_bytes},
         {"frontier_lds", (a >= 0 && a <= kFrontierMaxRadius) ? (int64_t)frontier_lds_bytes(a, g) : 0},
         {"frontier_chunk_queries", (b > 0 && c >= 1) ? std::min((int64_t)c, (int64_t)a * 1024 / b) : 0},
+        // slam_grid_travel: a = xw, b = yw (travel_tiles*, travel_mask_words, travel_trips; travel_query_bytes: c != 0 = the costs
+        // live in the workspace); travel_chunk_queries / travel_chunks: a = the budget in KiB, b = travel_query_bytes, c = B
+        {"kTravelTile", kTravelTile}, {"kTravelThreads", kTravelThreads}, {"kTravelTripsPerTile", kTravelTripsPerTile},
+        {"kTravelMaxSources", kTravelMaxSources}, {"kTravelMaxFoot", kTravelMaxFoot}, {"kTravelMaxGoals", kTravelMaxGoals},
+        {"travel_tiles_x", travel_plan_for(a, b, true, 1, 1L << 40, g).tiles_x}, {"travel_tiles_y", travel_plan_for(a, b, true, 1, 1L << 40, g).tiles_y},
+        {"travel_tiles", travel_plan_for(a, b, true, 1, 1L << 40, g).tiles}, {"travel_mask_words", travel_plan_for(a, b, true, 1, 1L << 40, g).mask_words},
+        {"travel_trips", travel_plan_for(a, b, true, 1, 1L << 40, g).trips},
+        {"travel_query_bytes", travel_plan_for(a, b, c != 0, 1, 1L << 40, g).query_bytes}, {"travel_lds", (int64_t)travel_lds_bytes(g)},
+        {"travel_chunk_queries", travel_plan_chunk(a, b, c, false)}, {"travel_chunks", travel_plan_chunk(a, b, c, true)},
     };
     for (const Entry &e : table)
         if (!strcmp(e.name, name)) { *out = e.value; return SLAM_OK; }
@@ -1868,6 +1896,106 @@ int slam_grid_frontiers(slam_ctx *c, slam_grid *g, int B, const int32_t *grid_of
         .out(d_lab, labels_out, (size_t)B * g->d.xw * g->d.yw);
     TRY(s.upload());
     TRY(frontiers_dev(__func__, c, g, B, d_g, radius, min_unknown, min_clear2, cap, min_size, max_clusters, d_cnt, d_cl, d_sums, d_lab));
+    return s.download();
+}
+
+// ---- travel-cost field (travel_kernels.hip) ---------------------------------------------------------------------------
+static int check_travel(const char *fn, const slam_ctx *c, const slam_grid *g, int B, const int32_t *grid_of_batch, const int32_t *sources,
+                        int S, int foot, int min_clear2, int cap, const int32_t *goals, int Q, int path_cap, const int32_t *status_out,
+                        const int32_t *cost_out, const int8_t *dir_out, const int32_t *goal_cost_out, const int32_t *path_len_out,
+                        const int32_t *path_out, TravelShape &plan)
+{
+    REQUIRE_IN(fn, g && sources && status_out, "null pointer");
+    REQUIRE_IN(fn, B >= 1, "B < 1");
+    REQUIRE_IN(fn, grid_of_batch || B <= g->d.G, "B > G without grid_of_batch (query b reads map b)");
+    REQUIRE_IN(fn, S >= 1 && S <= kTravelMaxSources, "S outside [1, 64]");
+    REQUIRE_IN(fn, foot >= 0 && foot <= kTravelMaxFoot, "foot outside [0, 8]");
+    REQUIRE_IN(fn, min_clear2 >= 0, "min_clear2 < 0");
+    if (min_clear2 > 0) {
+        REQUIRE_IN(fn, cap >= 1 && cap <= 32767, "cap outside [1, 32767]");
+        REQUIRE_IN(fn, min_clear2 <= cap, "min_clear2 > cap");
+    }
+    const long cells = (long)g->d.xw * g->d.yw;
+    REQUIRE_IN(fn, Q >= 0 && Q <= kTravelMaxGoals, "Q outside [0, 65536]");
+    REQUIRE_IN(fn, path_cap >= 0 && path_cap <= cells, "path_cap outside [0, xw * yw]");
+    REQUIRE_IN(fn, (long)B * std::max(Q, 1) * std::max(path_cap, 1) < (1L << 31), "B * max(Q, 1) * max(path_cap, 1) >= 2^31");
+    REQUIRE_IN(fn, (long)kTravelDiagonal * cells < (1L << 31), "a map of 2^31 / 14 cells or more: a cost may overflow");
+    const bool with_goals = goals && Q > 0;
+    REQUIRE_IN(fn, !with_goals || (goal_cost_out && path_len_out && (path_cap == 0 || path_out)), "goals without their outputs");
+    REQUIRE_IN(fn, cost_out || dir_out || with_goals, "no output asked for");
+    plan = travel_plan_for(g->d.xw, g->d.yw, cost_out == nullptr, B, c->travel_ws_bytes, kLdsGuard);
+    if (!plan.ok)
+        return fail(SLAM_ERR_INVALID, "%s: the workspace of one query (%ld bytes) does not fit the context option travel_ws_mb (%ld bytes)",
+                    fn, plan.query_bytes, c->travel_ws_bytes);
+    return SLAM_OK;
+}
+
+static int travel_dev(const char *fn, slam_ctx *c, slam_grid *g, int B, const int32_t *grid_of_batch, const int32_t *sources, int S,
+                      int foot, int through_unknown, int min_clear2, int cap, const int32_t *goals, int Q, int path_cap,
+                      int32_t *status_out, int32_t *cost_out, int8_t *dir_out, int32_t *goal_cost_out, int32_t *path_len_out,
+                      int32_t *path_out)
+{
+    TravelShape plan;
+    TRY(check_travel(fn, c, g, B, grid_of_batch, sources, S, foot, min_clear2, cap, goals, Q, path_cap, status_out, cost_out, dir_out,
+                     goal_cost_out, path_len_out, path_out, plan));
+    const size_t cells = (size_t)g->d.xw * g->d.yw;
+    const size_t cost_words = cost_out ? 0 : (size_t)plan.chunk_queries * cells, mask_words = (size_t)plan.chunk_queries * plan.mask_words;
+    const size_t dirty_words = (size_t)plan.chunk_queries * plan.tiles;
+    const size_t ws = align_up(cost_words * 4) + align_up(mask_words * 8) + align_up(dirty_words * 4);
+    TravelArgs a;
+    if (min_clear2 > 0) {       // the field of all G maps, as slam_grid_match builds it
+        int16_t *field = nullptr;
+        TRY(build_field(c, g, fn, cap, ws, field));
+        a.field = field;
+    } else {
+        TRY(grid_on_main(c));
+        TRY(arena_reserve(c, c->scratch, ws + 1024));
+    }
+    a.mask = carve<unsigned long long>(c->scratch, mask_words);
+    a.dirty = carve<int32_t>(c->scratch, dirty_words);
+    if (!cost_out) a.ws_cost = carve<int32_t>(c->scratch, cost_words);
+    REQUIRE_IN(fn, a.mask && a.dirty && (cost_out || a.ws_cost), "internal: workspace");
+    a.g = g->d;
+    a.maps = grid_of_batch;
+    a.sources = sources;
+    a.goals = Q > 0 ? goals : nullptr;
+    a.B = B; a.S = S; a.foot = foot; a.through_unknown = through_unknown != 0; a.min_clear2 = min_clear2; a.Q = Q; a.path_cap = path_cap;
+    a.status_out = status_out; a.cost_out = cost_out; a.dir_out = dir_out;
+    a.goal_cost_out = goal_cost_out; a.path_len_out = path_len_out; a.path_out = path_out;
+    Timed t(c, SLAM_K_GRID);
+    for (long b0 = 0; b0 < B; b0 += plan.chunk_queries)
+        HIPCHK(launch_travel(a, plan, b0, std::min(plan.chunk_queries, (long)B - b0), c->stream));
+    return SLAM_OK;
+}
+
+int slam_grid_travel_dev(slam_ctx *c, slam_grid *g, int B, const int32_t *grid_of_batch, const int32_t *sources, int S, int foot,
+                         int through_unknown, int min_clear2, int cap, const int32_t *goals, int Q, int path_cap, int32_t *status_out,
+                         int32_t *cost_out, int8_t *dir_out, int32_t *goal_cost_out, int32_t *path_len_out, int32_t *path_out)
+{
+    TRY(use(c));
+    return travel_dev(__func__, c, g, B, grid_of_batch, sources, S, foot, through_unknown, min_clear2, cap, goals, Q, path_cap, status_out,
+                      cost_out, dir_out, goal_cost_out, path_len_out, path_out);
+}
+
+int slam_grid_travel(slam_ctx *c, slam_grid *g, int B, const int32_t *grid_of_batch, const int32_t *sources, int S, int foot,
+                     int through_unknown, int min_clear2, int cap, const int32_t *goals, int Q, int path_cap, int32_t *status_out,
+                     int32_t *cost_out, int8_t *dir_out, int32_t *goal_cost_out, int32_t *path_len_out, int32_t *path_out)
+{
+    TRY(use(c));
+    TravelShape plan;
+    TRY(check_travel(__func__, c, g, B, grid_of_batch, sources, S, foot, min_clear2, cap, goals, Q, path_cap, status_out, cost_out,
+                     dir_out, goal_cost_out, path_len_out, path_out, plan));
+    const size_t cells = (size_t)B * g->d.xw * g->d.yw, rows = (size_t)B * Q;
+    const bool with_goals = goals && Q > 0;
+    int32_t *d_g, *d_src, *d_goals, *d_status, *d_cost, *d_gc, *d_len, *d_path; int8_t *d_dir;
+    Staging s(c);
+    s.in(d_g, grid_of_batch, B).in(d_src, sources, (size_t)B * S * 2).in(d_goals, with_goals ? goals : nullptr, rows * 2)
+        .out(d_status, status_out, B).out(d_cost, cost_out, cells).out(d_dir, dir_out, cells)
+        .out(d_gc, with_goals ? goal_cost_out : nullptr, rows).out(d_len, with_goals ? path_len_out : nullptr, rows)
+        .out(d_path, with_goals ? path_out : nullptr, rows * path_cap * 2);
+    TRY(s.upload());
+    TRY(travel_dev(__func__, c, g, B, d_g, d_src, S, foot, through_unknown, min_clear2, cap, d_goals, Q, path_cap, d_status, d_cost, d_dir,
+                   d_gc, d_len, d_path));
     return s.download();
 }
 

@@ -289,6 +289,31 @@ struct FrontierArgs {
 // every phase of queries b0 .. b0 + nb - 1 (nb <= p.chunk_queries), enqueued on s
 hipError_t launch_frontiers(const FrontierArgs &a, const FrontierShape &p, long b0, long nb, hipStream_t s);
 
+// ---- travel-cost field: reachable cells, costs and paths (travel_kernels.hip) --------------
+// A cost word through the phases: kTravelUnreached until a source reaches the cell, then the least cost found so far
+// (only ever lowered); k_travel_finish turns what is left of kTravelUnreached into -1.
+constexpr int32_t kTravelUnreached = 0x3fffffff;     // + kTravelDiagonal does not overflow
+constexpr int32_t kTravelClean = INT32_MAX;          // the pending key of a tile that is not dirty
+struct TravelArgs {
+    GridDev g;
+    const int16_t *field = nullptr;          // [G][xw][yw] when min_clear2 > 0
+    const int32_t *maps = nullptr;           // nullable [B]: NULL = query b reads map b
+    const int32_t *sources = nullptr;        // [B][S][2]
+    const int32_t *goals = nullptr;          // nullable [B][Q][2]
+    int B = 0, S = 0, foot = 0, through_unknown = 0, min_clear2 = 0, Q = 0, path_cap = 0;
+    int32_t *ws_cost = nullptr;              // workspace [chunk queries][xw * yw] when cost_out is NULL
+    unsigned long long *mask = nullptr;      // workspace [chunk queries][xw][tiles_y]: bit y % 64 of word y / 64 of row x
+    int32_t *dirty = nullptr;                // workspace [chunk queries][tiles]: the pending key, kTravelClean for none
+    int32_t *status_out = nullptr;           // [B]
+    int32_t *cost_out = nullptr;             // nullable [B][xw][yw]: the relaxation runs in it
+    int8_t *dir_out = nullptr;               // nullable [B][xw][yw]
+    int32_t *goal_cost_out = nullptr;        // [B][Q] with goals
+    int32_t *path_len_out = nullptr;         // [B][Q] with goals
+    int32_t *path_out = nullptr;             // [B][Q][path_cap][2], nullable when path_cap == 0
+};
+// every phase of queries b0 .. b0 + nb - 1 (nb <= p.chunk_queries), enqueued on s
+hipError_t launch_travel(const TravelArgs &a, const TravelShape &p, long b0, long nb, hipStream_t s);
+
 // ---- Monte Carlo localisation on the distance field (mcl_kernels.hip) ---------------------
 constexpr int kMclScanBlock = 1024;          // particles per workgroup of the prefix sum: fixed, so a filter's sums do not depend on the batch
 inline int mcl_scan_blocks(int P) { return (P + kMclScanBlock - 1) / kMclScanBlock; }

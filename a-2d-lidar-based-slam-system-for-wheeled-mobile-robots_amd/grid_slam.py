@@ -211,6 +211,63 @@ class DeviceGridSLAM:
         self._held = (maps,) + out
         return out
 
+    def _best_maps(self):
+        """int32 [F] on the device: map ``f * P + info[f, 0]`` of every filter, -1 for a filter with no live particle."""
+        torch = self.torch
+        best = self.info[:, 0]
+        return torch.where(best >= 0, torch.arange(self.F, dtype=torch.int32, device=self.dev) * self.P + best,
+                           torch.full_like(best, -1)).to(torch.int32).contiguous()
+
+    def _best_cells(self):
+        """int32 [F, 1, 2] on the device: the cell of every filter's best particle by the map's rule, ``int(scale * (v +
+        off))`` truncated toward zero; (-1, -1) for a filter with no live particle."""
+        torch = self.torch
+        best = self.info[:, 0].to(torch.int64)
+        xy = self.poses[torch.arange(self.F, device=self.dev), best.clamp(min=0), :2]
+        off = torch.tensor([self.grid.off_x, self.grid.off_y], dtype=torch.float64, device=self.dev)
+        cell = (self.grid.scale * (xy + off)).clamp(-2.0 ** 30, 2.0 ** 30).trunc().to(torch.int32)
+        return torch.where((best >= 0).reshape(-1, 1), cell, torch.full_like(cell, -1)).reshape(self.F, 1, 2).contiguous()
+
+    def travel(self, goals=None, foot=0, through_unknown=False, min_clear2=0, cap=64, path_cap=0, cost=True, dirs=False):
+        """The travel-cost field (:meth:`DeviceGrid.travel`) of every filter's best particle's map from that particle's
+        cell, one query per filter on map ``f * P + info[f, 0]``; source and map index are formed on the device, and a
+        filter with no live particle asks for no map: its status is -1.  goals: int32 [F, Q, 2] device tensor or None.
+        Returns the dict of device tensors; no synchronise."""
+        self._begin()
+        maps, src = self._best_maps(), self._best_cells()
+        self.ctx.stream_order(self._torch_stream(), 1)
+        out = self.grid.travel(src, maps, goals=goals, foot=foot, through_unknown=through_unknown, min_clear2=min_clear2, cap=cap,
+                               path_cap=path_cap, cost=cost, dirs=dirs)
+        self._held = (maps, src, goals) + tuple(out.values())
+        return out
+
+    def next_goals(self, foot=0, through_unknown=False, radius=2, min_unknown=13, min_clear2=0, cap=64, min_size=5, max_clusters=256):
+        """Every filter's next exploration goal by travel cost: the frontiers of its best particle's map
+        (:meth:`frontiers`), their representatives passed device to device as the goals of :meth:`travel`, and of the
+        kept clusters the one with the smallest cost >= 0, ties to the lowest label - chosen with torch ops.  Returns
+        (cell int32 [F, 2], cost int32 [F], status int32 [F]) on the device; cell (-1, -1) and cost -1 where no kept
+        cluster is reachable.  No synchronise."""
+        torch = self.torch
+        table = self.frontiers(radius=radius, min_unknown=min_unknown, min_clear2=min_clear2, cap=cap, min_size=min_size,
+                               max_clusters=max_clusters)[1]
+        held = self._held
+        self.ctx.stream_order(self._torch_stream(), 0)           # torch's copy of the representatives waits for the table
+        reps = table[:, :, 2:4].contiguous()
+        maps, src = self._best_maps(), self._best_cells()
+        self.ctx.stream_order(self._torch_stream(), 1)
+        out = self.grid.travel(src, maps, goals=reps, foot=foot, through_unknown=through_unknown, min_clear2=min_clear2, cap=cap,
+                               cost=False)
+        self.ctx.stream_order(self._torch_stream(), 0)
+        gc = out["goal_cost"].to(torch.int64)
+        key = torch.where(gc >= 0, gc, torch.full_like(gc, 2 ** 62))
+        k = torch.argmin(key, dim=1)                  # the first of equal costs: the lowest label
+        rows = torch.arange(self.F, device=self.dev)
+        ok = gc[rows, k] >= 0
+        cell = torch.where(ok.reshape(-1, 1), reps[rows, k], torch.full((self.F, 2), -1, dtype=torch.int32, device=self.dev))
+        costs = torch.where(ok, out["goal_cost"][rows, k], torch.full((self.F,), -1, dtype=torch.int32, device=self.dev))
+        self._held = held + (maps, src, reps) + tuple(out.values())
+        return cell, costs, out["status"]
+
     @property
     def trajectory(self):
         """The per-step estimates [S, F, 3] of the last :meth:`run` (or [1, F, 3] of the last :meth:`step`); synchronises."""
@@ -279,10 +336,27 @@ class GridSLAM:
                                                     cap=cap, min_size=min_size, max_clusters=max_clusters)
         return frontier_dict(count[0], clusters[0], sums[0], self.grid.scale, self.grid.off_x, self.grid.off_y)
 
-    def next_goal(self, **kw):
-        """The nearest-frontier rule from the best particle's pose on its map (:meth:`Mapping.next_goal`)."""
-        from .replay import nearest_goal
-        return nearest_goal(self.frontiers(**kw), self.best_pose)
+    def next_goal(self, by="distance", **kw):
+        """The nearest-frontier rule from the best particle's pose on its map, in a straight line or with ``by="travel"``
+        by travel cost (:meth:`Mapping.next_goal`)."""
+        import math
+        from .replay import grid_travel_host, nearest_goal, travel_goal
+        if by == "distance":
+            return nearest_goal(self.frontiers(**kw), self.best_pose)
+        if by != "travel":
+            raise ValueError("by must be 'distance' or 'travel'")
+        foot, through = kw.pop("foot", 0), kw.pop("through_unknown", False)
+        fr = self.frontiers(**kw)
+        if fr["point"].shape[0] == 0 or self.best < 0:
+            return None
+        clearance, cap = kw.get("clearance", 0.0), kw.get("cap", 64)
+        c2 = int(math.ceil((float(clearance) * self.grid.scale) ** 2)) if clearance > 0 else 0
+        p = self.best_pose
+        src = np.array([[[int(self.grid.scale * (p[0] + self.grid.off_x)), int(self.grid.scale * (p[1] + self.grid.off_y))]]], dtype=np.int32)
+        got = grid_travel_host(self.grid, src, [self.best], goals=fr["cell"].reshape(1, -1, 2), foot=foot, through_unknown=through,
+                               min_clear2=c2, cap=cap, cost=False)
+        k = travel_goal(fr, got["goal_cost"][0])
+        return None if k is None else fr["point"][k].copy()
 
     @property
     def best_pose(self):

@@ -228,11 +228,67 @@ class Mapping:
                                                   _abi.ptr(sums) if M > 0 else None, None))
         return frontier_dict(count[0], clusters[0], sums[0], self.index_scale, self.index_offset_x, self.index_offset_y)
 
-    def next_goal(self, pose, **kw):
-        """The nearest-frontier rule: the representative point [2] of the kept cluster (:meth:`frontiers`, ``**kw``) whose
-        point is nearest to the pose's (x, y); None when no cluster is kept - exploration is complete."""
-        from .replay import nearest_goal
-        return nearest_goal(self.frontiers(**kw), pose)
+    def next_goal(self, pose, by="distance", **kw):
+        """``by="distance"``, the nearest-frontier rule: the representative point [2] of the kept cluster
+        (:meth:`frontiers`, ``**kw``) whose point is nearest to the pose's (x, y); None when no cluster is kept -
+        exploration is complete.  ``by="travel"``: the representative of the kept cluster with the smallest travel cost
+        >= 0 from the pose's cell (:meth:`travel_field`), ties to the lowest label; None when no kept cluster is
+        reachable - exploration is complete for this robot, even if frontiers exist behind walls.  ``foot``,
+        ``through_unknown`` and ``clearance`` are taken from ``kw``; the clearance is shared with the frontier call."""
+        from .replay import nearest_goal, travel_goal
+        if by == "distance":
+            return nearest_goal(self.frontiers(**kw), pose)
+        if by != "travel":
+            raise ValueError("by must be 'distance' or 'travel'")
+        foot, through = kw.pop("foot", 0), kw.pop("through_unknown", False)
+        fr = self.frontiers(**kw)
+        if fr["point"].shape[0] == 0:
+            return None
+        got = self._travel(pose, kw.get("clearance", 0.0), foot, through, kw.get("cap", 64), goals=fr["cell"], cost=False)
+        k = travel_goal(fr, got["goal_cost"][0])
+        return None if k is None else fr["point"][k].copy()
+
+    def pose_cell(self, pose):
+        """The cell (x, y) of a pose by the map's own rule, ``int(scale * (v + off))``, truncated toward zero."""
+        p = np.asarray(pose, dtype=np.float64).reshape(-1)
+        return (int(self.index_scale * (p[0] + self.index_offset_x)), int(self.index_scale * (p[1] + self.index_offset_y)))
+
+    def _travel(self, pose, clearance, foot, through_unknown, cap, goals=None, path_cap=0, cost=True):
+        import math
+        from types import SimpleNamespace
+        from .replay import grid_travel_host
+        c2 = int(math.ceil((float(clearance) * self.index_scale) ** 2)) if clearance > 0 else 0
+        if c2 > int(cap):
+            raise ValueError("clearance of %g m is %d squared cells, beyond cap = %d" % (clearance, c2, cap))
+        grid = SimpleNamespace(_ctx=self._ctx, _h=self._grid, G=1, xw=self.xw, yw=self.yw)
+        src = np.array([[self.pose_cell(pose)]], dtype=np.int32)
+        gl = None if goals is None else np.asarray(goals, dtype=np.int32).reshape(1, -1, 2)
+        return grid_travel_host(grid, src, goals=gl, foot=foot, through_unknown=through_unknown, min_clear2=c2, cap=cap,
+                                path_cap=path_cap, cost=cost)
+
+    def travel_field(self, pose, clearance=0.0, foot=0, through_unknown=False, cap=64):
+        """What it costs to drive from the pose's cell (:meth:`pose_cell`) to every cell (``slam_grid_travel``): int32
+        [xw, yw], 10 a straight move and 14 a diagonal one, no corner cutting, -1 where the robot cannot go.  Free cells
+        are travelable, unknown ones with ``through_unknown``, both only ``clearance`` metres from every occupied cell
+        (``min_clear2 = ceil((clearance * scale)^2)``, an error beyond ``cap``); the cells within ``foot`` of the robot
+        are, whatever the map says."""
+        return self._travel(pose, clearance, foot, through_unknown, cap)["cost"][0]
+
+    def travel_path(self, pose, goal_xy, clearance=0.0, foot=0, through_unknown=False, cap=64, path_cap=256):
+        """The cheapest way from the pose to the cell of the world point ``goal_xy``: (points float64 [len, 2] - the cell
+        centres (:func:`frontier_points`), the robot's cell first - and the cost), or None when the goal is unreachable.
+        ``path_cap`` is grown and the call repeated when the path is longer."""
+        from .replay import frontier_points
+        goal = self.pose_cell(goal_xy)
+        while True:
+            got = self._travel(pose, clearance, foot, through_unknown, cap, goals=[goal], path_cap=path_cap, cost=False)
+            n = int(got["path_len"][0, 0])
+            if n == 0:
+                return None
+            if n <= int(path_cap):
+                cells = got["path"][0, 0, :n]
+                return frontier_points(cells, self.index_scale, self.index_offset_x, self.index_offset_y), int(got["goal_cost"][0, 0])
+            path_cap = n
 
     def counters(self):
         """(pass, hit) uint32 [xw, yw]: the integer evidence behind ``datamap``."""

@@ -288,6 +288,62 @@ def nearest_goal(fr, pose):
     return fr["point"][int(np.argmin(d))].copy()
 
 
+def _travel_shapes(grid, sources, grid_of_batch, goals):
+    """(B, S, Q) of a travel call from the shapes of its arguments: sources [B, S, 2] (or [S, 2] for B = 1), goals
+    [B, Q, 2] or None."""
+    if sources.ndim == 2:
+        sources = sources.reshape((1,) + tuple(sources.shape))
+    if sources.ndim != 3 or sources.shape[2] != 2:
+        raise ValueError("sources must be [B, S, 2]")
+    B, S = int(sources.shape[0]), int(sources.shape[1])
+    if grid_of_batch is not None and int(grid_of_batch.shape[0]) != B:
+        raise ValueError("grid_of_batch must be [B]")
+    Q = 0
+    if goals is not None:
+        if goals.ndim == 2:
+            goals = goals.reshape((1,) + tuple(goals.shape))
+        if goals.ndim != 3 or goals.shape[0] != B or goals.shape[2] != 2:
+            raise ValueError("goals must be [B, Q, 2]")
+        Q = int(goals.shape[1])
+    return sources, goals, B, S, Q
+
+
+def grid_travel_host(grid, sources, grid_of_batch=None, goals=None, foot=0, through_unknown=False, min_clear2=0, cap=64, path_cap=0,
+                     cost=True, dirs=False):
+    """The travel-cost field (``slam_grid_travel``) on NumPy arrays: sources int32 [B, S, 2] cells, query b on map
+    ``grid_of_batch[b]`` (None: map b), goals int32 [B, Q, 2] or None.  Returns a dict: ``status`` int32 [B], with ``cost``
+    ``cost`` int32 [B, xw, yw], with ``dirs`` ``dir`` int8 [B, xw, yw], with goals ``goal_cost`` and ``path_len`` int32
+    [B, Q] and, when ``path_cap`` > 0, ``path`` int32 [B, Q, path_cap, 2]."""
+    gob = None if grid_of_batch is None else np.ascontiguousarray(np.asarray(grid_of_batch, dtype=np.int32).reshape(-1))
+    src = np.ascontiguousarray(np.asarray(sources, dtype=np.int32))
+    gl = None if goals is None else np.ascontiguousarray(np.asarray(goals, dtype=np.int32))
+    src, gl, B, S, Q = _travel_shapes(grid, src, gob, gl)
+    P = int(path_cap)
+    out = dict(status=np.empty((B,), dtype=np.int32))
+    if cost:
+        out["cost"] = np.empty((B, grid.xw, grid.yw), dtype=np.int32)
+    if dirs:
+        out["dir"] = np.empty((B, grid.xw, grid.yw), dtype=np.int8)
+    if gl is not None:
+        out["goal_cost"], out["path_len"] = np.empty((B, Q), dtype=np.int32), np.empty((B, Q), dtype=np.int32)
+        if P > 0:
+            out["path"] = np.empty((B, Q, P, 2), dtype=np.int32)
+    ptr = lambda k: _abi.ptr(out[k]) if k in out and out[k].size else None
+    _abi.check(_abi.lib().slam_grid_travel(grid._ctx.handle, grid._h, B, _abi.ptr(gob), _abi.ptr(src), S, int(foot), int(bool(through_unknown)),
+                                           int(min_clear2), int(cap), _abi.ptr(gl) if Q > 0 else None, Q, P, _abi.ptr(out["status"]),
+                                           ptr("cost"), ptr("dir"), ptr("goal_cost"), ptr("path_len"), ptr("path")))
+    return out
+
+
+def travel_goal(fr, goal_cost):
+    """Index of the kept cluster of ``fr`` (:func:`frontier_dict`) with the smallest travel cost >= 0 in ``goal_cost``
+    [K], ties to the lowest label (the rows are in label order); None when none is reachable."""
+    c = np.asarray(goal_cost)[:fr["point"].shape[0]].astype(np.int64)
+    if c.size == 0 or not np.any(c >= 0):
+        return None
+    return int(np.argmin(np.where(c >= 0, c, np.iinfo(np.int64).max)))
+
+
 def grid_copy_maps_host(grid, src, first=0):
     """``slam_grid_copy_maps`` on a NumPy array: map ``first + k`` of ``grid`` becomes a copy of map ``src[k]``.  Returns
     int32 [count]: 1 copied, 0 kept (its own map, or no map).  A source that is itself a destination raises."""
@@ -504,6 +560,37 @@ class DeviceGrid:
                                                       int(min_unknown), int(min_clear2), int(cap), int(min_size), M, _abi.ptr(out[0]),
                                                       _abi.ptr(out[1]) if M > 0 else None, _abi.ptr(out[2]) if M > 0 else None,
                                                       _abi.ptr(lab)))
+        return out
+
+    def travel(self, sources, grid_of_batch=None, goals=None, foot=0, through_unknown=False, min_clear2=0, cap=64, path_cap=0,
+               cost=True, dirs=False, out=None):
+        """``slam_grid_travel_dev`` on torch device tensors: sources int32 [B, S, 2] cells, grid_of_batch int32 [B] or None
+        (query b reads map b), goals int32 [B, Q, 2] or None (rows of -1 are legal: the ``rep_x, rep_y`` columns of
+        :meth:`frontiers`' table go straight in once made contiguous).  Writes into the tensors of the dict ``out`` or
+        into fresh ones and returns the dict: ``status`` int32 [B], with ``cost`` ``cost`` int32 [B, xw, yw], with
+        ``dirs`` ``dir`` int8 [B, xw, yw], with goals ``goal_cost`` / ``path_len`` int32 [B, Q] and, when ``path_cap``
+        > 0, ``path`` int32 [B, Q, path_cap, 2].  No synchronise."""
+        import torch
+        sources, goals, B, S, Q = _travel_shapes(self, sources, grid_of_batch, goals)
+        P = int(path_cap)
+        if not sources.is_contiguous() or (goals is not None and not goals.is_contiguous()):
+            raise ValueError("sources and goals must be contiguous")
+        if out is None:
+            new = lambda dtype, *shape: torch.empty(shape, dtype=dtype, device=sources.device)
+            out = dict(status=new(torch.int32, B))
+            if cost:
+                out["cost"] = new(torch.int32, B, self.xw, self.yw)
+            if dirs:
+                out["dir"] = new(torch.int8, B, self.xw, self.yw)
+            if goals is not None:
+                out["goal_cost"], out["path_len"] = new(torch.int32, B, Q), new(torch.int32, B, Q)
+                if P > 0:
+                    out["path"] = new(torch.int32, B, Q, P, 2)
+        ptr = lambda k: _abi.ptr(out[k]) if k in out and out[k].numel() else None
+        _abi.check(_abi.lib().slam_grid_travel_dev(self._ctx.handle, self._h, B, _abi.ptr(grid_of_batch), _abi.ptr(sources), S, int(foot),
+                                                   int(bool(through_unknown)), int(min_clear2), int(cap),
+                                                   _abi.ptr(goals) if Q > 0 else None, Q, P, _abi.ptr(out["status"]), ptr("cost"),
+                                                   ptr("dir"), ptr("goal_cost"), ptr("path_len"), ptr("path")))
         return out
 
     def copy_maps(self, src, first=0, out=None):

@@ -144,7 +144,10 @@ int slam_check_status(slam_ctx *ctx);
  *   lists fit; a call whose single pair does not fit is SLAM_ERR_INVALID.  No result depends on it.
  * "frontier_ws_mb": MiB that the labels of slam_grid_frontiers may take in the context's workspace, in (0, 2^20],
  *   fractions allowed; default 256.  The queries of a call are cut into chunks that fit; a call whose single query
- *   does not fit is SLAM_ERR_INVALID.  No result depends on it. */
+ *   does not fit is SLAM_ERR_INVALID.  No result depends on it.
+ * "travel_ws_mb": MiB that the costs, the traversable bits and the tile keys of slam_grid_travel may take in the
+ *   context's workspace, in (0, 2^20], fractions allowed; default 256.  The queries of a call are cut into chunks that
+ *   fit; a call whose single query does not fit is SLAM_ERR_INVALID.  No result depends on it. */
 int slam_set_option(slam_ctx *ctx, const char *name, double value);
 /* Per-kernel-family timing with HIP events on the context's stream (bench.py roofline).
  * on: 0 = off, 1 = every family, 2 * mask = only the families in mask (bit SLAM_K_*): events on a
@@ -217,6 +220,9 @@ int slam_plan_icp(int B, int n_src, int n_tar, int is_scan, int qpt_pref, int ba
  * "locate_dense_lds" (n), "locate_dense_threads" (nodes), "locate_chunk_pairs" (budget in KiB, a pair's bytes, pairs);
  * "frontier_tiles" / "frontier_tiles_x" / "frontier_tiles_y" / "frontier_border" / "frontier_segs" /
  * "frontier_query_bytes" (xw, yw), "frontier_lds" (radius), "frontier_chunk_queries" (budget in KiB, a query's bytes, B);
+ * "travel_tiles" / "travel_tiles_x" / "travel_tiles_y" / "travel_mask_words" / "travel_trips" (xw, yw),
+ * "travel_query_bytes" (xw, yw, 1 when the costs live in the workspace), "travel_lds", "travel_chunk_queries" / "travel_chunks"
+ * (budget in KiB, a query's bytes, B);
  * arguments a function does not take are ignored.  SLAM_ERR_INVALID for a name it does not know. */
 int slam_plan_query(const char *name, int a, int b, int c, int guard, int64_t *out);
 
@@ -551,6 +557,72 @@ int slam_grid_frontiers(slam_ctx *ctx, slam_grid *grid, int B, const int32_t *gr
 int slam_grid_frontiers_dev(slam_ctx *ctx, slam_grid *grid, int B, const int32_t *grid_of_batch, int radius, int min_unknown,
                             int min_clear2, int cap, int min_size, int max_clusters, int32_t *count_out, int32_t *clusters_out,
                             int64_t *sums_out, int32_t *labels_out);
+
+/* ---- travel-cost field: reachable cells, costs and paths -------------------------------------- */
+/* slam_grid_travel: "what does it cost to drive from here to every cell of this map, and how?" - the cost-to-go field
+ * from the robot's cell over the traversable cells, the move back from every cell and the paths to a list of goals (the
+ * representatives of slam_grid_frontiers, say); integer end to end, one answer, batched over maps.  The reference has no
+ * counterpart.  The call changes nothing in the grid, leaves the context's sticky status untouched, sees every update
+ * enqueued before it on the context's stream and keeps nothing between calls.  Under slam_timing_* the field counts as
+ * SLAM_K_FINALIZE, everything else as SLAM_K_GRID.
+ *
+ * Which map.  Query b reads map gi = grid_of_batch[b]; with grid_of_batch NULL gi = b, and B <= G is required, as for
+ * the frontiers.
+ *
+ * Which values.  pmap is what slam_grid_finalize_dev would give NOW: 0 free, 50 unknown, 100 occupied.
+ *
+ * Sources.  sources [B][S][2], cells (x, y).  An entry outside the map is skipped; a query with no source inside its
+ * map answers -1 everywhere with status 0.
+ *
+ * Traversable set T of a query.  A cell of the map is in T iff
+ *   (a) it lies within Chebyshev distance `foot` of a source of the query that lies inside the map - the robot stands
+ *       there, whatever the map says (its own cell turns occupied once enough rays have started in it) - or
+ *   (b) its class is travelable: pmap == 0, or with through_unknown != 0 also pmap == 50; AND its clearance is enough:
+ *       min_clear2 == 0, or field[gi][x][y] >= min_clear2, the field slam_grid_distance_field gives NOW at `cap`.
+ * With min_clear2 == 0 no field is built and cap is ignored.  Otherwise the field is rebuilt for ALL G maps, as the
+ * frontiers and the matcher do.
+ *
+ * Moves.  Direction codes d = 0..7 = (1,0), (0,1), (-1,0), (0,-1), (1,1), (-1,1), (-1,-1), (1,-1); codes 0 to 3 cost
+ * SLAM_TRAVEL_STRAIGHT, codes 4 to 7 SLAM_TRAVEL_DIAGONAL.  A move from u to v is allowed iff both cells are in T; a
+ * diagonal move also needs the two cells it passes between, (ux+dx, uy) and (ux, uy+dy), in T: no corner cutting, two
+ * occupied cells that touch diagonally are a wall.  The graph is undirected.
+ *
+ * Outputs.  cost_out (nullable) [B][xw][yw], pmap's cell order: the least sum of move costs from any source; a source
+ * has 0; a cell that no source reaches, or that is not in T, has -1.  dir_out (nullable) int8 [B][xw][yw]: the LOWEST
+ * code d such that the move from the cell in direction d is allowed and cost[neighbour] + w_d == cost[cell]; sources
+ * and unreached cells have -1.  dir_out is defined from the final costs, not from the order anything ran in, so both
+ * arrays are unique, and every query answers the same alone, in any batch, in any order and under any chunking (below).
+ *
+ * Goals (optional).  goals (nullable) [B][Q][2]; goal_cost_out [B][Q]: the goal cell's cost, -1 for a goal outside the
+ * map or unreached; path_len_out [B][Q]: the TRUE number of cells of the path that follows dir from the goal to a
+ * source, both ends included - 1 for a goal on a source, 0 where the cost is -1; path_out (nullable when path_cap == 0)
+ * [B][Q][path_cap][2]: the path source first, min(len, path_cap) cells of it, every later row -1.  Entries of -1 are
+ * legal goals and answer -1 / 0, so the rep_x, rep_y columns of slam_grid_frontiers' table go straight in.  With goals
+ * NULL or Q == 0 the three goal outputs are not touched.
+ *
+ * status_out [B]: 0 answered; -1 the map entry is outside [0, G) - then every output of the query is -1 and the lengths
+ * are 0, in both forms, the others unaffected; SLAM_TRAVEL_TRIPS a hard trip bound of the relaxation was reached - the
+ * query's outputs are then not answers.  (Costs only decrease, so the relaxation ends; the tile with the lowest pending
+ * cost goes first, which bounds the activations of a tile by the cells around it: DESIGN.md section 19.)
+ *
+ * Workspace.  In the context's workspace per query: 4 bytes per cell of costs when cost_out is NULL (otherwise the
+ * relaxation runs in cost_out), the bits of T in rows padded to 64, 4 bytes per tile of 64 x 64 cells; bounded by the
+ * context option "travel_ws_mb"; the queries are taken in chunks that fit and no result depends on the cut.
+ *
+ * B >= 1; 1 <= S <= 64; 0 <= foot <= 8; min_clear2 >= 0, and 1 <= cap <= 32767 and min_clear2 <= cap when
+ * min_clear2 > 0; 0 <= Q <= 65536; 0 <= path_cap <= xw*yw; B * max(Q, 1) * max(path_cap, 1) < 2^31; 14 * xw * yw <
+ * 2^31; B <= G without routing; the workspace of ONE query within "travel_ws_mb"; status_out and sources not NULL; at
+ * least one of cost_out, dir_out and the goal outputs (goals with Q > 0, goal_cost_out, path_len_out, and path_out
+ * when path_cap > 0) asked for; anything else is SLAM_ERR_INVALID, enqueues nothing and leaves the context as it was. */
+#define SLAM_TRAVEL_STRAIGHT 10
+#define SLAM_TRAVEL_DIAGONAL 14
+#define SLAM_TRAVEL_TRIPS 1
+int slam_grid_travel(slam_ctx *ctx, slam_grid *grid, int B, const int32_t *grid_of_batch, const int32_t *sources, int S, int foot,
+                     int through_unknown, int min_clear2, int cap, const int32_t *goals, int Q, int path_cap, int32_t *status_out,
+                     int32_t *cost_out, int8_t *dir_out, int32_t *goal_cost_out, int32_t *path_len_out, int32_t *path_out);
+int slam_grid_travel_dev(slam_ctx *ctx, slam_grid *grid, int B, const int32_t *grid_of_batch, const int32_t *sources, int S, int foot,
+                         int through_unknown, int min_clear2, int cap, const int32_t *goals, int Q, int path_cap, int32_t *status_out,
+                         int32_t *cost_out, int8_t *dir_out, int32_t *goal_cost_out, int32_t *path_len_out, int32_t *path_out);
 
 /* ---- Monte Carlo localisation on the distance field ----------------------------------------- */
 /* F particle filters of P particles each, weighed against their filter's scan on the field above and resampled on
