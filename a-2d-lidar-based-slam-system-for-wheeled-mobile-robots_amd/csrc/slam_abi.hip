@@ -932,7 +932,7 @@ int slam_plan_query(const char *name, int a, int b, int c, int guard, int64_t *o
         {"frontier_chunk_queries", (b > 0 && c >= 1) ? std::min((int64_t)c, (int64_t)a * 1024 / b) : 0},
         // slam_grid_travel: a = xw, b = yw (travel_tiles*, travel_mask_words, travel_trips; travel_query_bytes: c != 0 = the costs
         // live in the workspace); travel_chunk_queries / travel_chunks: a = the budget in KiB, b = travel_query_bytes, c = B
-        {"kTravelTile", kTravelTile}, {"kTravelThreads", kTravelThreads}, {"kTravelTripsPerTile", kTravelTripsPerTile},
+        {"kTravelTile", kTravelTile}, {"kTravelMaxBlocks", (int64_t)kTravelMaxBlocks}, {"kTravelThreads", kTravelThreads}, {"kTravelTripsPerTile", kTravelTripsPerTile},
         {"kTravelMaxSources", kTravelMaxSources}, {"kTravelMaxFoot", kTravelMaxFoot}, {"kTravelMaxGoals", kTravelMaxGoals},
         {"travel_tiles_x", travel_plan_for(a, b, true, 1, 1L << 40, g).tiles_x}, {"travel_tiles_y", travel_plan_for(a, b, true, 1, 1L << 40, g).tiles_y},
         {"travel_tiles", travel_plan_for(a, b, true, 1, 1L << 40, g).tiles}, {"travel_mask_words", travel_plan_for(a, b, true, 1, 1L << 40, g).mask_words},

@@ -1,8 +1,8 @@
 """slam_grid_travel on the device against tests/travel_ref.py, every output with array_equal (dtype, shape and the -1
 padding included) and status 0 wherever a map is named: the patterns at which a relaxation by tiles can go wrong, written
 straight into the counters at the smallest shapes where it can - one cell, one row, one column, one tile of 64 x 64
-exactly and one more in each axis, 130 x 67 and 67 x 130 whose walls cross every multiple of 8, 16, 32 and 64; the rule
-clause by clause; sources; goals and paths; the room built by update_scans; one map of 1 000 x 1 000; and every Python
+exactly and one more in each axis, 130 x 67 and 67 x 130 whose walls cross every multiple of 8, 16, 32 and 64; 260 x 200
+and 200 x 260, where interior tiles have all eight neighbours; sources on a tile's border, by hand; the rule clause by clause; sources; goals and paths; the room built by update_scans; one map of 1 000 x 1 000; and every Python
 surface."""
 import numpy as np
 import pytest
@@ -94,6 +94,119 @@ def test_diagonal_blobs_are_walls_at_every_residue(slam, ctx):
     got = TC.check(slam, g, pm, src)
     assert (got["cost"][0] >= 0).sum() == 64 * 4                          # the second blob of a pair touches only diagonally
     TC.check(slam, g, pm, src, through_unknown=True)
+    g.close()
+
+
+# ------------------------------------------------------------------ many tiles
+def walled_rooms(shape):
+    """Free, cut by walls two cells thick ON the rows each side of a tile border - 63 | 64 and 127 | 128 - with one-cell
+    doors through both rows at y = 0 and at the tile's corner cells y = 63 (first wall), y = 64 and the last column (second)."""
+    pm = np.zeros(shape, dtype=np.int8)
+    for rows, doors in (((63, 64), (0, 63)), ((127, 128), (64, shape[1] - 1))):
+        for x in rows:
+            pm[x, :] = 100
+            pm[x, list(doors)] = 0
+    return pm
+
+
+def staircase(shape):
+    """Occupied but for the band |x - y| <= 1: the diagonal steps (63, 63) -> (64, 64) and (127, 127) -> (128, 128) go
+    through the corner shared by four tiles, between two cells that lie in the other two."""
+    xs, ys = np.indices(shape)
+    return np.where(np.abs(xs - ys) <= 1, 0, 100).astype(np.int8)
+
+
+def in_tile(pm, tx, ty):
+    """The first free cell of tile (tx, ty), or the tile's first cell."""
+    free = np.argwhere(pm[tx * TILE:(tx + 1) * TILE, ty * TILE:(ty + 1) * TILE] == 0)
+    return np.array([tx * TILE, ty * TILE]) + (free[0] if len(free) else 0)
+
+
+@pytest.mark.parametrize("shape", ((260, 200), (200, 260)), ids=lambda s: "%dx%d" % s)
+def test_many_tiles_with_every_interior_tile_loaded(slam, ctx, shape):
+    """5 x 4 and 4 x 5 tiles, the last ones 4 and 8 cells wide: interior tiles have all eight neighbours.  Six maps in one
+    grid, each queried three times in one routed call: from one end of its path, from the centre tile's corner cell, and
+    from three sources in three different tiles."""
+    xw, yw = shape
+    names = ["serpentine", "serpentine_t", "spiral", "random_0.6", "rooms", "staircase"]
+    maps = [FC.serpentine(xw, yw), np.ascontiguousarray(FC.serpentine(yw, xw).T), TC.spiral(xw, yw), FC.random_map(shape, 0.6, 19),
+            walled_rooms(shape), staircase(shape)]
+    g, pm = FC.grid_of(slam, ctx, np.stack(maps))
+    G = len(pm)
+    centre = np.array([(xw // TILE // 2) * TILE, (yw // TILE // 2) * TILE])           # the first cell of the centre tile
+    src = np.empty((3 * G, 3, 2), dtype=np.int32)
+    for k, p in enumerate(pm):
+        src[k] = first_free(p)                                                        # S = 3 with one cell three times is S = 1
+        src[G + k] = centre
+        src[2 * G + k] = [in_tile(p, 0, 0), in_tile(p, 1, 2), in_tile(p, 2, 1)]
+    assert all(len({(int(x) // TILE, int(y) // TILE) for x, y in s}) == 3 for s in src[2 * G:])
+    goals = np.stack([spread_goals(p) for p in pm] * 3)
+    got = TC.check(slam, g, pm, src, maps=np.tile(np.arange(G, dtype=np.int32), 3), goals=goals, path_cap=64)
+    cost = dict(zip(names, got["cost"][:G]))
+    assert cost["serpentine"].max() == 10 * ((pm[0] == 0).sum() - 1) and cost["serpentine_t"].max() == 10 * ((pm[1] == 0).sum() - 1)
+    assert np.array_equal(cost["spiral"] >= 0, pm[2] == 0) and np.all(cost["rooms"][pm[4] == 0] >= 0)
+    stairs = cost["staircase"]
+    assert stairs[64, 64] - stairs[63, 63] == 14 and stairs[128, 128] - stairs[127, 127] == 14 and stairs[0, 0] == 0
+    assert got["path_len"].max() > 64                                                  # paths longer than path_cap among them
+    g.close()
+
+
+# ------------------------------------------------------------------ the ring rule
+def corridors():
+    """name -> (cells [n, 2] in walking order, the index of the last cell before the tile border): occupied maps of
+    130 x 130 with one corridor one cell wide across a tile border."""
+    line = lambda lo, hi: np.arange(lo, hi + 1)
+    along_x = lambda lo, hi, y: np.stack([line(lo, hi), np.full(hi - lo + 1, y)], axis=1)
+    along_y = lambda x, lo, hi: np.stack([np.full(hi - lo + 1, x), line(lo, hi)], axis=1)
+    return {"x 63|64": (along_x(60, 70, 20), 3), "x 127|128": (along_x(121, 129, 90), 6), "y 63|64": (along_y(20, 60, 70), 3),
+            "y 127|128": (along_y(90, 121, 129), 6)}
+
+
+def test_a_source_on_a_tile_border_tells_the_tile_across_it(slam, ctx):
+    """The ring rule by hand: a source in the last or first row or column of its tile never goes down, so the tile across
+    the border is dirty from the start or never hears of it.  Straight corridors with the source on either side of the
+    border, an L whose corner (63, 63) is the source and whose way out is (64, 63), and a foot square that lies in two
+    tiles with nothing else free."""
+    cor = corridors()
+    names = list(cor)
+    pm = np.full((len(names) + 2, 130, 130), 100, dtype=np.int8)
+    for k, n in enumerate(names):
+        pm[k][tuple(cor[n][0].T)] = 0
+    L = np.concatenate([np.stack([np.full(9, 63), np.arange(55, 64)], axis=1), np.stack([np.arange(64, 71), np.full(7, 63)], axis=1)])
+    pm[len(names)][tuple(L.T)] = 0                                                    # map len(names) + 1 stays occupied throughout
+    g, pm = FC.grid_of(slam, ctx, pm)
+    maps, src = [], []
+    for k, n in enumerate(names):
+        cells, last = cor[n]
+        maps += [k, k]
+        src += [[cells[last]], [cells[last + 1]]]
+    maps.append(len(names))
+    src.append([[63, 63]])
+    maps, src = np.array(maps, dtype=np.int32), np.array(src, dtype=np.int32)
+    got = TC.check(slam, g, pm, src, maps=maps, goals=np.stack([cor[names[min(m, len(names) - 1)]][0][[0, -1]] for m in maps]), path_cap=16)
+    for b, (m, s) in enumerate(zip(maps[:-1], src[:-1])):
+        cells = cor[names[m]][0]
+        assert np.array_equal(got["cost"][b][tuple(cells.T)], 10 * np.abs(cells - s[0]).sum(axis=1)), (names[m], s)
+        assert (got["cost"][b] >= 0).sum() == len(cells)
+    assert np.array_equal(got["cost"][-1][tuple(L.T)], 10 * np.abs(L - [63, 63]).sum(axis=1)) and (got["cost"][-1] >= 0).sum() == len(L)
+    # the foot square across a border: the source two cells from it, in the corridors and on the map with nothing free
+    blank = len(names) + 1
+    fmaps, fsrc = [], []
+    for k, n in enumerate(names):
+        cells, last = cor[n]
+        for s in (cells[last - 1], cells[last + 2]):
+            fmaps += [k, blank]
+            fsrc += [[s], [s]]
+    fmaps, fsrc = np.array(fmaps, dtype=np.int32), np.array(fsrc, dtype=np.int32)
+    got = TC.check(slam, g, pm, fsrc, maps=fmaps, foot=2)
+    for b, m in enumerate(fmaps):
+        reached = got["cost"][b] >= 0
+        if m == blank:
+            lo, hi = np.maximum(fsrc[b, 0] - 2, 0), np.minimum(fsrc[b, 0] + 2, 129)
+            assert reached.sum() == np.prod(hi - lo + 1), (b, fsrc[b])                # the whole square, clipped by the map alone
+            assert len({(x // TILE, y // TILE) for x, y in np.argwhere(reached)}) == 2
+        else:
+            assert np.all(reached[tuple(cor[names[m]][0].T)]), (b, fsrc[b])
     g.close()
 
 

@@ -1,14 +1,17 @@
 """slam_grid_travel at the edges of its arguments and its workspace: batches routed, alone, reversed and with entries that
 name no map; NULL routing; the budget ("travel_ws_mb") cut to one, two and three queries a chunk and the query that fits
 no budget; every argument set the library rejects - each followed by a good call - and the context: the device form back
-to back, a call enqueued right behind an update, the counters before and after, the sticky status.  Against
-tests/travel_ref.py with array_equal, through the C ABI."""
+to back, a call enqueued right behind an update, the counters before and after, the sticky status; the routed batch under a
+clearance - whole, in chunks, with its costs in the workspace and in the device form around a call without one; more
+queries than a launch has workgroups, so that the kernels take their grid-stride loops; and the map whose costs
+could overflow.  Against tests/travel_ref.py with array_equal, through the C ABI."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 import frontier_cases as FC
+import match_ref as M
 import raycast_ref as R
 import travel_cases as TC
 import travel_ref as T
@@ -207,3 +210,156 @@ def test_device_form_back_to_back_behind_an_update_and_counters_untouched(slam, 
     assert (seen["cost"] >= 0).sum().item() > 1000
     ctx.check_status()
     m.close()
+
+
+# ------------------------------------------------------------------ routing, chunks and the workspace with a clearance
+CLEAR_CAP = 16
+
+
+@pytest.fixture(scope="module")
+def cleared(slam, case):
+    """The module's case under min_clear2 = 1 and 4: the fields of the three maps read back, and the restatement on them."""
+    fields = np.stack([M.field(p, CLEAR_CAP) for p in case["pm"]])
+    assert np.array_equal(slam.grid_distance_field_host(case["g"], CLEAR_CAP), fields)
+    want = {c2: T.batch(case["pm"], case["src"], maps=case["maps"], fields=fields, goals=case["goals"], min_clear2=c2, **KW) for c2 in (1, 4)}
+    return dict(fields=fields, want=want)
+
+
+@pytest.mark.parametrize("c2", (1, 4))
+def test_clearance_routed_in_chunks_in_the_workspace_and_back_to_back(slam, ctx, case, cleared, c2):
+    import torch
+    pm, maps, fields, want = case["pm"], case["maps"], cleared["fields"], cleared["want"][c2]
+    # the field must be the MAP's, not the query's: under map b's field some routed query would see another T
+    other = [b for b, gi in enumerate(maps) if 0 <= gi < 3 and b < 3 and gi != b
+             and not np.array_equal(T.traversable(pm[gi], fields[gi], case["src"][b], KW["foot"], False, c2),
+                                    T.traversable(pm[gi], fields[b], case["src"][b], KW["foot"], False, c2))]
+    assert other, "the maps' fields do not tell routing by query from routing by map"
+    assert (c2 == 1) == np.array_equal(want["cost"], case["want"]["cost"])   # 1 closes no free cell under its own map's field, 4 does
+    kw = dict(min_clear2=c2, cap=CLEAR_CAP)
+    got = call(slam, case, **kw)
+    TC.same(got, want)
+    assert got["status"].tolist() == [0, 0, 0, 0, -1, -1, 0]
+    no_cost = {k: v for k, v in want.items() if k != "cost"}
+    TC.same(call(slam, case, cost=False, **kw), no_cost)                  # the costs in the workspace, beside the field
+    try:
+        for own in (0, 1):
+            qb = query("travel_query_bytes", *SHAPE, own)
+            for per_chunk in (1, 2, 3):
+                kib = -(-per_chunk * (qb + 256) // 1024)
+                assert query("travel_chunk_queries", kib, qb, 7) == per_chunk
+                ctx.set_option("travel_ws_mb", kib / 1024.0)
+                TC.same(call(slam, case, cost=not own, **kw), no_cost if own else want)
+    finally:
+        ctx.set_option("travel_ws_mb", 256)
+    # the device form twice, a call WITHOUT a clearance and with its costs in the workspace in between: the field is
+    # rebuilt and the arena carved at another layout, all three enqueued without a synchronise
+    dev = torch.device("cuda", 0)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
+    d_maps, d_src, d_goals = up(maps), up(case["src"]), up(case["goals"])
+    torch.cuda.synchronize()
+    o1 = case["g"].travel(d_src, d_maps, goals=d_goals, dirs=True, **kw, **KW)
+    o2 = case["g"].travel(d_src, d_maps, goals=d_goals, dirs=True, cost=False, **KW)
+    o3 = case["g"].travel(d_src, d_maps, goals=d_goals, dirs=True, **kw, **KW)
+    ctx.synchronize()
+    host = lambda o: {k: v.cpu().numpy() for k, v in o.items()}
+    TC.same(host(o1), want)
+    TC.same(host(o2), {k: v for k, v in case["want"].items() if k != "cost"})
+    TC.same(host(o3), want)
+    ctx.check_status()
+
+
+# ------------------------------------------------------------------ past the block cap
+def pocket_room():
+    """17 x 16, free, with a wall that closes the rows behind it off, a stub of a wall and a few unknown cells."""
+    pm = np.zeros((17, 16), dtype=np.int8)
+    pm[10, :] = 100
+    pm[0:6, 5] = 100
+    pm[3:5, 9:12] = 50
+    pm[13, 2:7] = 50
+    return pm
+
+
+def test_more_queries_than_the_block_cap_in_one_chunk(slam, ctx):
+    """B = kTravelMaxBlocks + 3 queries in ONE chunk: k_travel_classes and k_travel_relax take their grid-stride loops, and
+    with 272 cells a query k_travel_finish does at 256 cells a block (k_travel_paths, a lane per goal at 256 a block, would
+    need 2^28 goals in a chunk; here it only runs past 2^21 rows).  The queries cycle through 7
+    combinations of (map, sources, goals), one of them without a map; 7 does not divide the cap, so a workgroup's second
+    query differs from its first.  Compared on the device, combination by combination."""
+    import torch
+    if torch.cuda.mem_get_info(0)[0] < 6 << 30:
+        pytest.skip("needs 6 GB of free device memory")
+    cap = query("kTravelMaxBlocks")
+    B, K, S, Q, P = cap + 3, 7, 2, 2, 4
+    assert cap % K != 0 and B * 17 * 16 > 256 * cap
+    g, pm = FC.grid_of(slam, ctx, np.stack([FC.random_map((17, 16), 0.8, 23), pocket_room()]))
+    free = np.argwhere(T.answer(pm[0], None, [[0, 0]], foot=1)["cost"] > 0)       # what (0, 0) reaches on the random map
+    cmaps = np.array([0, 1, -1, 1, 0, 1, 0], dtype=np.int32)
+    csrc = np.array([[[0, 0], [16, 15]], [[2, 2], [2, 2]], [[1, 1], [3, 3]], [[14, 3], [20, 3]], [free[3], free[-2]], [[9, 9], [11, 9]],
+                     [[16, 0], [0, 15]]], dtype=np.int32)
+    cgoals = np.array([[[8, 8], [3, 12]], [[16, 15], [0, 15]], [[1, 1], [2, 2]], [[12, 12], [2, 2]], [free[0], [-1, -1]], [[16, 0], [0, 0]],
+                       [free[len(free) // 2], [17, 0]]], dtype=np.int32)
+    kw = dict(foot=1, path_cap=P)
+    want = T.batch(pm, csrc, maps=cmaps, goals=cgoals, **kw)
+    assert len({want["cost"][k].tobytes() for k in range(K)}) == K and len(free) > 100
+    assert np.all((want["goal_cost"] >= 0).sum(axis=1)[cmaps >= 0] >= 1) and (want["goal_cost"] < 0).any() and want["path_len"].max() > P
+    assert query("travel_chunks", 256 * 1024, query("travel_query_bytes", 17, 16, 0), B) == 1
+    dev = torch.device("cuda", 0)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    which = torch.arange(B, device=dev) % K
+    maps, src, goals = up(cmaps)[which].contiguous(), up(csrc)[which].contiguous(), up(cgoals)[which].contiguous()
+    torch.cuda.synchronize()
+    out = g.travel(src, maps, goals=goals, dirs=True, **kw)
+    ctx.synchronize()
+    assert sorted(out) == sorted(TC.KEYS) and out["cost"].shape == (B, 17, 16) and out["path"].shape == (B, Q, P, 2)
+    for key in TC.KEYS:
+        for k in range(K):
+            rows, w = out[key][k::K], up(want[key][k])
+            assert rows.dtype == w.dtype and bool((rows == w).all()), (key, k, torch.nonzero((rows != w).reshape(rows.shape[0], -1).any(1))[:4].flatten().tolist())
+    # the last queries alone, in the host form: the same rows
+    tail = np.arange(B - 5, B) % K
+    alone = slam.grid_travel_host(g, csrc[tail], grid_of_batch=cmaps[tail], goals=cgoals[tail], dirs=True, **kw)
+    TC.same(alone, {k: v[B - 5:].cpu().numpy() for k, v in out.items()})
+    TC.same(alone, {k: v[tail] for k, v in want.items()})
+    ctx.check_status()
+    del out, maps, src, goals, which, rows, w
+    g.close()
+    torch.cuda.empty_cache()
+
+
+# ------------------------------------------------------------------ the overflow rejection
+def test_a_map_whose_costs_could_overflow_is_rejected_and_one_cell_row_less_is_not(slam, ctx):
+    """14 * xw * yw >= 2^31 at 12 386 x 12 385 cells and not at 12 385 x 12 385.  The smaller grid is not relaxed: with the
+    budget at 1 MB it is refused by the LATER clause, which shows that the overflow clause let it pass."""
+    import torch
+    if torch.cuda.mem_get_info(0)[0] < 4 << 30:
+        pytest.skip("needs 4 GB of free device memory")
+    abi = pkg("_abi")
+    assert 14 * 12386 * 12385 >= 2 ** 31 > 14 * 12385 * 12385
+    src, goals = np.array([[[5, 5]]], dtype=np.int32), np.array([[[7, 7]]], dtype=np.int32)
+    out = [np.full(1, -7, np.int32) for _ in range(3)]                   # status, goal_cost, path_len
+
+    def raw(g):
+        return abi.lib().slam_grid_travel(ctx.handle, g._h, 1, None, abi.ptr(src), 1, 0, 0, 0, 64, abi.ptr(goals), 1, 0, abi.ptr(out[0]), None,
+                                          None, abi.ptr(out[1]), abi.ptr(out[2]), None)
+
+    g = slam.DeviceGrid(1, 12386, 12385, 1.0, 0.0, 0.0, context=ctx)
+    try:
+        assert raw(g) == abi.ERR_INVALID
+        assert "overflow" in abi.lib().slam_last_error().decode() and all(v[0] == -7 for v in out)
+        with pytest.raises(slam.SlamError, match="overflow"):
+            slam.grid_travel_host(g, src, goals=goals, cost=False)
+        ctx.check_status()
+    finally:
+        g.close()
+    g = slam.DeviceGrid(1, 12385, 12385, 1.0, 0.0, 0.0, context=ctx)
+    try:
+        ctx.set_option("travel_ws_mb", 1)
+        assert raw(g) == abi.ERR_INVALID
+        assert "travel_ws_mb" in abi.lib().slam_last_error().decode() and all(v[0] == -7 for v in out)
+        with pytest.raises(slam.SlamError, match="travel_ws_mb"):
+            slam.grid_travel_host(g, src, goals=goals, cost=False)
+        ctx.check_status()
+    finally:
+        ctx.set_option("travel_ws_mb", 256)
+        g.close()
+    torch.cuda.empty_cache()

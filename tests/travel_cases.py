@@ -2,6 +2,10 @@
 tests/map_cases.py:
 
     case_of('travel', seed)     one query: a pmap, sources, the rule's arguments, goals and a path_cap
+    case_of('travel_batch', seed)  B queries routed over G maps of one shape - the 'travel' case's map of that seed, its
+                                mirror and a fresh random map - with entries that name no map, a map queried twice and,
+                                on a third of the seeds, a clearance; drawn from a generator of its own, so the 'travel'
+                                cases stay what they were
     answer(case, pmap, field)   what tests/travel_ref.py says of it (the map read back from a device, or the case's own)
     seeds()                     range(SLAM_HYP_EXAMPLES), default 60
 
@@ -108,16 +112,101 @@ def make(rng, seed):
                 min_clear2=int(pick((0, 0, 0, 1, 2, 4))), cap=CAP, goals=goals, path_cap=min(int(pick((0, 1, 5, 40, 300))), xw * yw), family=family)
 
 
+BATCH_CELLS = 40000      # B * cells of a batch case, but for every tenth seed
+
+
+def ring_cells(T):
+    """[n, 2]: the cells of T on the last or first row or column of their tile with a cell of T straight across the border."""
+    xw, yw = T.shape
+    out = np.zeros(T.shape, dtype=bool)
+    xs, ys = np.indices(T.shape)
+    out[:-1] |= T[:-1] & T[1:] & (xs[:-1] % TILE == TILE - 1)
+    out[1:] |= T[1:] & T[:-1] & (xs[1:] % TILE == 0)
+    out[:, :-1] |= T[:, :-1] & T[:, 1:] & (ys[:, :-1] % TILE == TILE - 1)
+    out[:, 1:] |= T[:, 1:] & T[:, :-1] & (ys[:, 1:] % TILE == 0)
+    return np.argwhere(out)
+
+
+def make_batch(rng, seed):
+    pick = lambda seq: seq[int(rng.integers(0, len(seq)))]
+    one = make(np.random.default_rng([19, seed]), seed)
+    pm0 = one["pmap"]
+    xw, yw = pm0.shape
+    G = int(rng.integers(1, 4))
+    pmaps = np.stack([pm0, pm0[::-1], random_map(rng, pm0.shape)][:G])
+    B = int(rng.integers(1, 7))
+    if seed % 10:
+        B = max(1, min(B, BATCH_CELLS // (xw * yw)))
+    maps = rng.integers(0, G, B).astype(np.int32)
+    if B >= 2 and rng.random() < 0.5:
+        maps[int(rng.integers(1, B))] = maps[0]                                            # one map queried twice
+    if rng.random() < 0.35:
+        maps[int(rng.integers(0, B))] = pick((-1, G))                                      # entries that name no map
+        if B >= 3:
+            maps[int(rng.integers(0, B))] = pick((-1, G, G + 5))
+    through, min_clear2 = bool(rng.random() < 0.3), int(pick((0, 0, 0, 0, 1, 4)))
+    if min_clear2 > 0 and G >= 2 and rng.random() < 0.7:
+        maps[0] = int(rng.integers(1, G))                                                  # query 0 under another map's field
+    S = int(pick((1, 1, 2, 3, 64)))
+    src = np.empty((B, S, 2), dtype=np.int32)
+    goals = np.empty((B, 6, 2), dtype=np.int32)
+    for b in range(B):
+        pm = pmaps[min(max(int(maps[b]), 0), G - 1)]
+        free, occupied = np.argwhere(pm == 0), np.argwhere(pm == 100)
+        for s in range(S):
+            u = rng.random()
+            if u < 0.1:
+                src[b, s] = pick(((-1, 0), (xw, 0), (0, yw), (xw + 3, yw - 1)))
+            elif u < 0.2 and len(occupied):
+                src[b, s] = pick(occupied)
+            elif len(free):
+                src[b, s] = pick(free)
+            else:
+                src[b, s] = (int(rng.integers(0, xw)), int(rng.integers(0, yw)))
+        ring = ring_cells((pm == 0) | (through & (pm == 50)))
+        if len(ring) and rng.random() < 0.5:
+            src[b, 0] = pick(ring)                                                         # on a tile's border, with a way across it
+        goals[b] = [pick(free) if len(free) else (0, 0) for _ in range(3)] + [src[b, 0], (-1, -1), (xw - 1, yw - 1)]
+    return dict(pmaps=pmaps, maps=maps, sources=src, foot=int(pick((0, 0, 0, 1, 2, 8))), through_unknown=through,
+                min_clear2=min_clear2, cap=CAP, goals=goals, path_cap=min(int(pick((0, 1, 5, 40, 300))), xw * yw), family=one["family"])
+
+
 def case_of(kind, seed):
     """The case of (kind, seed): a dict of plain Python values and NumPy arrays, with "kind" and "seed" in it."""
-    assert kind == "travel"
-    c = make(np.random.default_rng([19, int(seed)]), int(seed))
+    assert kind in ("travel", "travel_batch")
+    if kind == "travel":
+        c = make(np.random.default_rng([19, int(seed)]), int(seed))
+    else:
+        c = make_batch(np.random.default_rng([19, int(seed), 1]), int(seed))
     c.update(kind=kind, seed=int(seed))
     return c
 
 
+def rule_of(case, **kw):
+    """The rule's arguments of a case as keywords, for travel_ref.batch and grid_travel_host alike."""
+    out = dict(foot=case["foot"], through_unknown=case["through_unknown"], min_clear2=case["min_clear2"], path_cap=case["path_cap"])
+    out.update(kw)
+    return out
+
+
+def answer_batch(case, pmaps=None, fields=None, with_T=False):
+    """tests/travel_ref.py on a 'travel_batch' case: the arrays of grid_travel_host, stacked over the queries; ``with_T``:
+    also the list of each query's traversable set (None where it names no map)."""
+    pm = case["pmaps"] if pmaps is None else pmaps
+    if fields is None and case["min_clear2"] > 0:
+        fields = np.stack([M.field(p, case["cap"]) for p in pm])
+    out = T.batch(pm, case["sources"], maps=case["maps"], fields=fields, goals=case["goals"], **rule_of(case))
+    if with_T:
+        out["T"] = [T.traversable(pm[g], None if fields is None else fields[g], case["sources"][b], case["foot"], case["through_unknown"],
+                                  case["min_clear2"]) if 0 <= g < len(pm) else None for b, g in enumerate(case["maps"])]
+        out["fields"] = fields
+    return out
+
+
 def answer(case, pmap=None, field=None):
     """tests/travel_ref.py on the case; ``pmap`` / ``field``: the map and its field read back from a device."""
+    if case["kind"] == "travel_batch":
+        return answer_batch(case, pmap, field, with_T=True)
     pm = case["pmap"] if pmap is None else pmap
     if field is None and case["min_clear2"] > 0:
         field = M.field(pm, case["cap"])
@@ -134,8 +223,35 @@ def tile_runs(cells):
     return runs
 
 
+def batch_edges_of(case, ans):
+    """The names of the edges a 'travel_batch' case reaches (``ans``: answer_batch(case, with_T=True))."""
+    pm, maps, src = case["pmaps"], case["maps"], case["sources"]
+    G, (xw, yw) = len(pm), pm.shape[1:]
+    named = [b for b, g in enumerate(maps) if 0 <= g < G]
+    out = set()
+    if len(named) < len(maps):
+        out.add("a query that names no map")
+    for i, b in enumerate(named):
+        if any(maps[b] == maps[c] and not np.array_equal(src[b], src[c]) for c in named[:i]):
+            out.add("one map queried twice")
+    for b in named:
+        g = int(maps[b])
+        if case["min_clear2"] > 0 and g != b and b < G:
+            other = T.traversable(pm[g], ans["fields"][b], src[b], case["foot"], case["through_unknown"], case["min_clear2"])
+            if not np.array_equal(other, ans["T"][b]):
+                out.add("a routed query under a clearance whose map's field differs from map b's")
+        Tm = ans["T"][b]
+        for x, y in T.valid_sources((xw, yw), src[b]):
+            for dx, dy, on in ((1, 0, x % TILE == TILE - 1), (-1, 0, x % TILE == 0), (0, 1, y % TILE == TILE - 1), (0, -1, y % TILE == 0)):
+                if on and 0 <= x + dx < xw and 0 <= y + dy < yw and Tm[x + dx, y + dy]:
+                    out.add("a source on the last or first row or column of its tile with a traversable cell across the border")
+    return out
+
+
 def edges_of(case, ans):
     """The names of the edges this case reaches."""
+    if case["kind"] == "travel_batch":
+        return batch_edges_of(case, ans)
     pm, src = case["pmap"], case["sources"]
     xw, yw = pm.shape
     inside = [(x, y) for x, y in src if 0 <= x < xw and 0 <= y < yw]
