@@ -37,6 +37,7 @@
 #include "slam_internal.h"
 #include "slam_stamps.h"
 #include "grid_walk.h"
+#include "workspace.h"
 
 namespace slam {
 
@@ -2015,10 +2016,10 @@ __global__ void __launch_bounds__(1024) k_tile_cast(GridDev g, TileScratch ts, i
     lds_guard_check(guard, g.status);
 }
 
-static size_t tile_scratch_bytes(long rays, long groups)
+// the pieces of a tile cast, bound to the members of `ts`
+static Layout tile_pieces(TileScratch &ts, long rays, long groups)
 {
-    // (groups: an upper bound is enough - one per scan)
-    return (size_t)rays * (sizeof(RayRec) + kTileWords * 4 + kTileWords * 2) + (size_t)groups * 16 + 1024;
+    return Layout().add(ts.recs, rays).add(ts.bits, (size_t)rays * kTileWords).add(ts.prefix, (size_t)rays * kTileWords).add(ts.gbox, (size_t)groups * 4);
 }
 
 // The casts for large maps take at most kMaxLaunchGroups groups of scans in one launch (k_tile_cast: a row of gridDim.y per
@@ -2052,7 +2053,7 @@ static hipError_t launch_in_chunks(const Src &src, int L, int scans, int G, cons
 }
 
 template <class Src>
-static hipError_t launch_tiles(const GridDev &g, const Src &src, int L, int scans, int n, int group, void *scratch, hipStream_t s)
+static hipError_t launch_tiles(const GridDev &g, const Src &src, int L, int scans, int n, int group, void *scratch, size_t cap, hipStream_t s)
 {
     if (scans < 1) return hipSuccess;
     // scans per (tile, group) workgroup: 16 by default (1080 beams, 2000 x 2000 cells, three overlapping replays:
@@ -2067,14 +2068,10 @@ static hipError_t launch_tiles(const GridDev &g, const Src &src, int L, int scan
     const long groups = (long)L * groups_per_traj, rays = (long)L * scans * n;
     if (groups > kMaxLaunchGroups)
         return launch_in_chunks(src, L, scans, G, nullptr, [&](const Src &cs, int cl, int cscans, const int32_t *) {
-            return launch_tiles(g, cs, cl, cscans, n, G, scratch, s);
+            return launch_tiles(g, cs, cl, cscans, n, G, scratch, cap, s);
         });
     TileScratch ts;
-    char *p = static_cast<char *>(scratch);
-    ts.recs = reinterpret_cast<RayRec *>(p); p += (size_t)rays * sizeof(RayRec);
-    ts.bits = reinterpret_cast<uint32_t *>(p); p += (size_t)rays * kTileWords * 4;
-    ts.prefix = reinterpret_cast<unsigned short *>(p); p += (size_t)rays * kTileWords * 2;
-    ts.gbox = reinterpret_cast<int *>(p);
+    if (!tile_pieces(ts, rays, groups).place(scratch, cap)) return hipErrorInvalidValue;
     if (g.pmap_live && g.live_dirty) *g.live_dirty = true;
     // the family is three launches: bracket it with recorded events when timing is armed
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -2126,7 +2123,7 @@ struct WedgeScratch {
     unsigned short *list;      // [rays] ray numbers inside their group, sorted by (class, length descending)
     int *offs;                 // [groups][kWedgeClasses + 1] class boundaries in the group's list
     uint32_t *cost;            // [groups][kWedgeClasses] cells the class's rays pass (from the length bins: to +-8 cells a ray)
-    uint32_t *order;           // [groups * kWedgeClasses] units (group * kWedgeClasses + class), the most cells first
+    uint32_t *order;           // [1 + groups * kWedgeClasses + rays / kWedgePartMin] parts listed, then the parts (unit | part << 20), the most cells first
     const int32_t *got;        // nullable [L]: map of trajectory l (null: every trajectory casts into map 0)
 };
 
@@ -2506,13 +2503,15 @@ __global__ void __launch_bounds__(kWedgeThreads, 2 * kWedgeThreads / 256) k_wedg
     lds_guard_check(guard, g.status);
 }
 
-static size_t wedge_scratch_bytes(long rays, long scans, long groups)
+// the pieces of a wedge cast, bound to the members of `ws`
+static Layout wedge_pieces(WedgeScratch &ws, long rays, long scans, long groups)
 {
-    return (size_t)rays * 6 + (size_t)scans * 4 + (size_t)groups * (kWedgeClasses + 1) * 4 + (size_t)groups * kWedgeClasses * 8 + (size_t)(rays / kWedgePartMin + 1) * 4 + 4096;
+    return Layout().add(ws.ends, rays).add(ws.orgs, scans).add(ws.offs, (size_t)groups * (kWedgeClasses + 1)).add(ws.cost, (size_t)groups * kWedgeClasses)
+        .add(ws.order, 1 + (size_t)groups * kWedgeClasses + (size_t)rays / kWedgePartMin).add(ws.list, rays);
 }
 
 template <class Src>
-static hipError_t launch_wedges(const GridDev &g, const Src &src, int L, int scans, int n, int group, void *scratch, hipStream_t s, const int32_t *got)
+static hipError_t launch_wedges(const GridDev &g, const Src &src, int L, int scans, int n, int group, void *scratch, size_t cap, hipStream_t s, const int32_t *got)
 {
     if (scans < 1) return hipSuccess;
     int G = group > 0 ? group : 16;
@@ -2524,16 +2523,10 @@ static hipError_t launch_wedges(const GridDev &g, const Src &src, int L, int sca
     const long groups = (long)L * groups_per_traj, rays = (long)L * scans * n;
     if (groups > kMaxLaunchGroups)
         return launch_in_chunks(src, L, scans, G, got, [&](const Src &cs, int cl, int cscans, const int32_t *cgot) {
-            return launch_wedges(g, cs, cl, cscans, n, G, scratch, s, cgot);
+            return launch_wedges(g, cs, cl, cscans, n, G, scratch, cap, s, cgot);
         });
     WedgeScratch ws;
-    char *p = static_cast<char *>(scratch);
-    ws.ends = reinterpret_cast<uint32_t *>(p); p += (size_t)rays * 4;
-    ws.orgs = reinterpret_cast<uint32_t *>(p); p += (size_t)L * scans * 4;
-    ws.offs = reinterpret_cast<int *>(p); p += (size_t)groups * (kWedgeClasses + 1) * 4;
-    ws.cost = reinterpret_cast<uint32_t *>(p); p += (size_t)groups * kWedgeClasses * 4;
-    ws.order = reinterpret_cast<uint32_t *>(p); p += ((size_t)groups * kWedgeClasses + (size_t)rays / kWedgePartMin + 1) * 4;
-    ws.list = reinterpret_cast<unsigned short *>(p);
+    if (!wedge_pieces(ws, rays, (long)L * scans, groups).place(scratch, cap)) return hipErrorInvalidValue;
     ws.got = got;
     if (g.pmap_live && g.live_dirty) *g.live_dirty = true;
     const size_t lds_a = win_sc_bytes(G) + (size_t)(kWedgeClasses * kWedgeLenBins + kWinMaxGroup) * 4 + (size_t)G * n * 2;
@@ -2585,21 +2578,28 @@ CastPath plan_cast(const GridDev &g, int mode, const CastRequest &r)
     return mode != 0 && r.n <= 65535 ? CastPath::Window : CastPath::Direct;
 }
 
-size_t cast_scratch_bytes(CastPath p, const CastRequest &r)
+size_t cast_layout_bytes(CastPath p, long rays, long scans, long groups)
 {
-    // the wedges keep 6 bytes per ray (end cell, sorted ray number), the recorded walks ~400; groups: one per scan bounds them
-    const long rays = (long)r.L * r.scans * r.n, groups = (long)r.L * r.scans;
-    if (p == CastPath::Wedges) return wedge_scratch_bytes(rays, groups, groups);
-    if (p == CastPath::Tiles) return tile_scratch_bytes(rays, groups);
+    TileScratch ts;
+    WedgeScratch ws;
+    if (p == CastPath::Wedges) return wedge_pieces(ws, rays, scans, groups).bytes();
+    if (p == CastPath::Tiles) return tile_pieces(ts, rays, groups).bytes();
     return 0;
 }
 
+size_t cast_scratch_bytes(CastPath p, const CastRequest &r)
+{
+    // the wedges keep 6 bytes per ray (end cell, sorted ray number), the recorded walks ~400; groups: one per scan bounds them
+    const long scans = (long)r.L * r.scans;
+    return cast_layout_bytes(p, scans * r.n, scans, scans);
+}
+
 template <class Src>
-static hipError_t launch_cast(const GridDev &g, CastPath p, const Src &src, const CastRequest &r, void *scratch, hipStream_t s)
+static hipError_t launch_cast(const GridDev &g, CastPath p, const Src &src, const CastRequest &r, void *scratch, size_t cap, hipStream_t s)
 {
     switch (p) {
-    case CastPath::Wedges: return launch_wedges(g, src, r.L, r.scans, r.n, r.group, scratch, s, r.maps);
-    case CastPath::Tiles: return launch_tiles(g, src, r.L, r.scans, r.n, r.group, scratch, s);
+    case CastPath::Wedges: return launch_wedges(g, src, r.L, r.scans, r.n, r.group, scratch, cap, s, r.maps);
+    case CastPath::Tiles: return launch_tiles(g, src, r.L, r.scans, r.n, r.group, scratch, cap, s);
     case CastPath::Window:
         return launch_win(g, src, r.L, r.scans, r.n, pick_group(r.group, (long)r.L * r.scans, r.scans, r.n), r.maps, s, r.split, r.lds_hits);
     case CastPath::Direct: break;
@@ -2610,17 +2610,17 @@ static hipError_t launch_cast(const GridDev &g, CastPath p, const Src &src, cons
     return hipGetLastError();
 }
 
-hipError_t launch_cast(const GridDev &g, CastPath p, const CastRequest &r, void *scratch, hipStream_t s)
+hipError_t launch_cast(const GridDev &g, CastPath p, const CastRequest &r, void *scratch, size_t scratch_bytes, hipStream_t s)
 {
-    if (r.ox) return launch_cast(g, p, ExplicitSource{r.ox, r.oy, r.cx, r.cy, r.scans, r.n}, r, scratch, s);
+    if (r.ox) return launch_cast(g, p, ExplicitSource{r.ox, r.oy, r.cx, r.cy, r.scans, r.n}, r, scratch, scratch_bytes, s);
     if (r.per_filter) {
         ParticleSource src(r.ranges, r.cos_t, r.sin_t, r.poses, r.acc, r.n, r.per_filter);
         src.l0 = r.first_particle;
-        return launch_cast(g, p, src, r, scratch, s);
+        return launch_cast(g, p, src, r, scratch, scratch_bytes, s);
     }
     const ReplaySource src{r.ranges, r.cos_t, r.sin_t, r.poses, r.scans + 1, r.n, r.particles ? 0L : (long)(r.scans + 1) * r.n,
                            r.particles, r.centres, r.heading_cs};
-    return launch_cast(g, p, src, r, scratch, s);
+    return launch_cast(g, p, src, r, scratch, scratch_bytes, s);
 }
 
 __global__ void __launch_bounds__(256) k_grid_finalize(const uint32_t *__restrict__ pass, const uint32_t *__restrict__ hit,

@@ -16,6 +16,7 @@
 
 #include "slam_internal.h"
 #include "slam_stamps.h"
+#include "workspace.h"
 
 using namespace slam;
 
@@ -67,7 +68,7 @@ size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 
 struct Arena {
     char *base = nullptr;
-    size_t cap = 0, used = 0;
+    size_t cap = 0;
 };
 
 struct Pending {
@@ -173,7 +174,6 @@ namespace {
 
 int arena_reserve(slam_ctx *c, Arena &a, size_t bytes)
 {
-    a.used = 0;
     if (bytes <= a.cap) return SLAM_OK;
     HIPCHK(hipStreamSynchronize(c->stream));
     if (a.base) HIPCHK(hipFree(a.base));
@@ -186,20 +186,13 @@ int arena_reserve(slam_ctx *c, Arena &a, size_t bytes)
     return SLAM_OK;
 }
 
-// Next piece of a reserved arena.  A piece that does not fit (a reservation computed too small:
-// an internal error) comes back null, which the entry point's null checks / the first copy
-// into it turn into an error code instead of a silent overrun.
-template <typename T>
-T *carve(Arena &a, size_t count)
+// The arena sized for a call's layout and the layout placed in it: every pointer bound to a piece is set.  A layout that
+// does not fit is an error code here, before the entry point has enqueued anything.
+int reserve(slam_ctx *c, Arena &a, const Layout &ws)
 {
-    size_t off = align_up(a.used);
-    if (off + count * sizeof(T) > a.cap) {
-        a.used = a.cap + 1;
-        (void)fail(SLAM_ERR_NOMEM, "internal: workspace reservation too small (%zu > %zu bytes)", off + count * sizeof(T), a.cap);
-        return nullptr;
-    }
-    a.used = off + count * sizeof(T);
-    return reinterpret_cast<T *>(a.base + off);
+    TRY(arena_reserve(c, a, ws.bytes()));
+    if (ws.place(a.base, a.cap)) return SLAM_OK;
+    return fail(SLAM_ERR_NOMEM, "internal: a workspace of %zu bytes (more than %d pieces?) in an arena of %zu", ws.bytes(), Layout::kMaxPieces, a.cap);
 }
 
 // RAII bracket around the kernel launch(es) of a family: every SLAM_LAUNCH inside it draws a
@@ -299,8 +292,8 @@ bool ensure_pinned(slam_ctx *c)
 }
 
 // Device copies of the arguments of a host-pointer entry point.  The entry point declares its
-// pieces once, in order; upload() reserves exactly their aligned sum in the staging arena, sets
-// every device pointer and copies the inputs in; download() copies the outputs back and ends with
+// pieces once, in order (a Layout, workspace.h); upload() reserves exactly their aligned sum in the staging
+// arena, sets every device pointer and copies the inputs in; download() copies the outputs back and ends with
 // a stream synchronise (so the page-locked block is free at the next call).  The pieces lie in
 // ONE arena in ascending order, so when those of one direction are small (a drop-in call: one
 // scan pair, one scan) they cross the bus in one copy through the page-locked block, laid out
@@ -321,20 +314,18 @@ public:
 
     int upload()
     {
-        if (overflow_) return fail(SLAM_ERR_NOMEM, "internal: more than %d staging pieces", kMaxPieces);
-        TRY(arena_reserve(c_, c_->staging, size_));
+        TRY(reserve(c_, c_->staging, ws_));
         char *d = c_->staging.base;
-        for (int i = 0; i < n_; ++i) p_[i].set(p_[i].dev, d + p_[i].off);
         size_t lo, hi;
         if (!span(true, lo, hi)) return SLAM_OK;
         if (hi - lo <= kPinnedBytes / 2 && ensure_pinned(c_)) {
-            for (int i = 0; i < n_; ++i)
-                if (p_[i].src) memcpy(c_->pinned + (p_[i].off - lo), p_[i].src, p_[i].bytes);
+            for (int i = 0; i < ws_.count(); ++i)
+                if (h_[i].src) memcpy(c_->pinned + (ws_.offset(i) - lo), h_[i].src, ws_.size(i));
             HIPCHK(hipMemcpyAsync(d + lo, c_->pinned, hi - lo, hipMemcpyHostToDevice, c_->stream));
             return SLAM_OK;
         }
-        for (int i = 0; i < n_; ++i)
-            if (p_[i].src) HIPCHK(hipMemcpyAsync(d + p_[i].off, p_[i].src, p_[i].bytes, hipMemcpyHostToDevice, c_->stream));
+        for (int i = 0; i < ws_.count(); ++i)
+            if (h_[i].src) HIPCHK(hipMemcpyAsync(d + ws_.offset(i), h_[i].src, ws_.size(i), hipMemcpyHostToDevice, c_->stream));
         return SLAM_OK;
     }
 
@@ -346,56 +337,47 @@ public:
             char *h = c_->pinned + kPinnedBytes / 2;
             HIPCHK(hipMemcpyAsync(h, d + lo, hi - lo, hipMemcpyDeviceToHost, c_->stream));
             HIPCHK(hipStreamSynchronize(c_->stream));
-            for (int i = 0; i < n_; ++i)
-                if (p_[i].dst) memcpy(p_[i].dst, h + (p_[i].off - lo), p_[i].bytes);
+            for (int i = 0; i < ws_.count(); ++i)
+                if (h_[i].dst) memcpy(h_[i].dst, h + (ws_.offset(i) - lo), ws_.size(i));
             return SLAM_OK;
         }
-        for (int i = 0; i < n_; ++i)
-            if (p_[i].dst) HIPCHK(hipMemcpyAsync(p_[i].dst, d + p_[i].off, p_[i].bytes, hipMemcpyDeviceToHost, c_->stream));
+        for (int i = 0; i < ws_.count(); ++i)
+            if (h_[i].dst) HIPCHK(hipMemcpyAsync(h_[i].dst, d + ws_.offset(i), ws_.size(i), hipMemcpyDeviceToHost, c_->stream));
         HIPCHK(hipStreamSynchronize(c_->stream));
         return SLAM_OK;
     }
 
 private:
-    struct Piece {
-        void *dev;                            // the entry point's device pointer (a T *), set by upload()
-        void (*set)(void *dev, char *p);
+    struct Host {
         const void *src;                      // host source of an input (null: nothing to copy in)
         void *dst;                            // host destination of an output (null: nothing to copy back)
-        size_t off, bytes;
     };
-    static constexpr int kMaxPieces = 24;
 
-    template <typename T> static void set_ptr(void *dev, char *p) { *static_cast<T **>(dev) = reinterpret_cast<T *>(p); }
     template <typename T> Staging &add(T *&dev, size_t n, const void *src, void *dst, bool absent)
     {
         dev = nullptr;
         if (absent) return *this;
-        if (n_ == kMaxPieces) overflow_ = true;
-        if (overflow_) return *this;
-        const size_t bytes = n * sizeof(T);
-        p_[n_++] = Piece{&dev, &set_ptr<T>, bytes ? src : nullptr, bytes ? dst : nullptr, size_, bytes};
-        size_ += align_up(bytes);
+        const int i = ws_.count();
+        ws_.add(dev, n);
+        if (ws_.count() > i) h_[i] = Host{n ? src : nullptr, n ? dst : nullptr};
         return *this;
     }
     // byte range [lo, hi) of the arena that the copies of one direction cover; false: nothing to copy
     bool span(bool in, size_t &lo, size_t &hi) const
     {
-        lo = size_;
+        lo = ws_.bytes();
         hi = 0;
-        for (int i = 0; i < n_; ++i)
-            if (in ? p_[i].src != nullptr : p_[i].dst != nullptr) {
-                lo = std::min(lo, p_[i].off);
-                hi = std::max(hi, p_[i].off + p_[i].bytes);
+        for (int i = 0; i < ws_.count(); ++i)
+            if (in ? h_[i].src != nullptr : h_[i].dst != nullptr) {
+                lo = std::min(lo, ws_.offset(i));
+                hi = std::max(hi, ws_.offset(i) + ws_.size(i));
             }
         return lo < hi;
     }
 
     slam_ctx *c_;
-    Piece p_[kMaxPieces];
-    int n_ = 0;
-    bool overflow_ = false;
-    size_t size_ = 0;
+    Layout ws_;                               // the device pieces, in the order they were declared
+    Host h_[Layout::kMaxPieces];              // piece i of ws_: where its bytes come from and go to
 };
 
 // entry points that touch a map on the MAIN stream call this first
@@ -537,8 +519,6 @@ int astar_run(slam_ctx *c, const int8_t *maps, int G, int H, int W, int wire, in
     TRY(grid_on_main(c));
     const size_t cells = (size_t)H * W;
     const size_t dil_words = (size_t)G * span * ((span + 63) / 64);     // trigger rows: G x span rows of 64-column words
-    const size_t dil = dil_words * sizeof(unsigned long long);
-    const size_t infl = inflated ? 0 : (size_t)G * cells;
     long slots = 0;
     if (a) {
         slots = a->B < kAstarMaxSlots ? a->B : kAstarMaxSlots;
@@ -546,22 +526,16 @@ int astar_run(slam_ctx *c, const int8_t *maps, int G, int H, int W, int wire, in
         if (slots > fit) slots = fit > 0 ? fit : 1;
     }
     const size_t sc = (size_t)slots * cells;
-    TRY(arena_reserve(c, c->scratch, align_up(dil) + align_up(infl) + align_up(sc) + 4 * align_up(sc * 4) +
-                                         align_up(sc * 8) + 4096));
-    unsigned long long *d_dil = carve<unsigned long long>(c->scratch, dil_words);
-    if (!inflated) inflated = carve<int8_t>(c->scratch, infl);
-    if (!d_dil || !inflated) return SLAM_ERR_NOMEM;
+    unsigned long long *d_dil;
+    Layout ws;
+    ws.add(d_dil, dil_words);
+    if (!inflated) ws.add(inflated, (size_t)G * cells);
+    if (a) ws.add(a->state, sc).add(a->pos, sc).add(a->ocell, sc).add(a->og, sc).add(a->closed, sc).add(a->okey, sc);
+    TRY(reserve(c, c->scratch, ws));
     HIPCHK(launch_astar_inflate(maps, G, H, W, wire, span, r, d_dil, inflated, c->status, c->stream));
     if (!a) return SLAM_OK;
     a->imaps = inflated;
     a->slots = (int)slots;
-    a->state = carve<uint8_t>(c->scratch, sc);
-    a->pos = carve<int32_t>(c->scratch, sc);
-    a->ocell = carve<int32_t>(c->scratch, sc);
-    a->og = carve<int32_t>(c->scratch, sc);
-    a->closed = carve<int32_t>(c->scratch, sc);
-    a->okey = carve<unsigned long long>(c->scratch, sc);
-    if (!a->state || !a->pos || !a->ocell || !a->og || !a->closed || !a->okey) return SLAM_ERR_NOMEM;
     HIPCHK(hipMemsetAsync(a->state, 0, sc, c->stream));
     HIPCHK(launch_astar(*a, c->stream));
     return SLAM_OK;
@@ -939,6 +913,9 @@ int slam_plan_query(const char *name, int a, int b, int c, int guard, int64_t *o
         {"travel_trips", travel_plan_for(a, b, true, 1, 1L << 40, g).trips},
         {"travel_query_bytes", travel_plan_for(a, b, c != 0, 1, 1L << 40, g).query_bytes}, {"travel_lds", (int64_t)travel_lds_bytes(g)},
         {"travel_chunk_queries", travel_plan_chunk(a, b, c, false)}, {"travel_chunks", travel_plan_chunk(a, b, c, true)},
+        // the ray casts of large maps: a = scans of the cast (L * scans), b = beams, c = groups: where the engine's layout ends
+        {"wedge_ws_bytes", (int64_t)cast_layout_bytes(CastPath::Wedges, (long)a * b, a, c)},
+        {"tile_ws_bytes", (int64_t)cast_layout_bytes(CastPath::Tiles, (long)a * b, a, c)},
     };
     for (const Entry &e : table)
         if (!strcmp(e.name, name)) { *out = e.value; return SLAM_OK; }
@@ -1277,7 +1254,7 @@ int slam_grid_update_dev(slam_ctx *c, slam_grid *g, const double *ox, const doub
     const CastPath path = plan_cast(g->d, c->grid_mode, r);
     const size_t need = cast_scratch_bytes(path, r);
     if (need > c->tiles.cap) TRY(arena_reserve(c, c->tiles, need));
-    HIPCHK(launch_cast(g->d, path, r, c->tiles.base, c->stream));
+    HIPCHK(launch_cast(g->d, path, r, c->tiles.base, c->tiles.cap, c->stream));
     return SLAM_OK;
 }
 
@@ -1315,7 +1292,7 @@ static int cast_replay(slam_ctx *c, slam_grid *g, const float *ranges, const dou
         if (c->gstream) HIPCHK(hipStreamSynchronize(c->gstream));
         TRY(arena_reserve(c, c->tiles, need));
     }
-    HIPCHK(launch_cast(g->d, path, r, c->tiles.base, st));
+    HIPCHK(launch_cast(g->d, path, r, c->tiles.base, c->tiles.cap, st));
     return SLAM_OK;
 }
 
@@ -1454,8 +1431,8 @@ int slam_grid_occupancy_data(slam_ctx *c, slam_grid *g, int gi, int8_t *data)
     REQUIRE(g && data, "null pointer");
     REQUIRE(gi >= 0 && gi < g->d.G, "grid index out of range");
     size_t per = (size_t)g->d.xw * g->d.yw;
-    TRY(arena_reserve(c, c->scratch, align_up(per) + 1024));
-    int8_t *d_data = carve<int8_t>(c->scratch, per);
+    int8_t *d_data;
+    TRY(reserve(c, c->scratch, Layout().add(d_data, per)));
     const int8_t *pm = g->pmap_one;
     if (g->pmap_live) {                       // kept current by the ray casts: no finalize pass
         TRY(refresh_live(c, g, c->stream));
@@ -1509,9 +1486,8 @@ static int run_raycast(slam_ctx *c, slam_grid *g, RaycastArgs &a)
 {
     TRY(grid_on_main(c));
     const size_t words = raycast_mask_words(g->d);
-    TRY(arena_reserve(c, c->scratch, align_up(words * 4) + 1024));
-    uint32_t *mask = carve<uint32_t>(c->scratch, words);
-    REQUIRE_IN(a.counts_out ? "slam_grid_scan_score" : "slam_grid_raycast", mask, "internal: workspace");
+    uint32_t *mask;
+    TRY(reserve(c, c->scratch, Layout().add(mask, words)));
     a.g = g->d;
     a.mask = mask;
     {
@@ -1589,18 +1565,17 @@ int slam_grid_scan_score(slam_ctx *c, slam_grid *g, const float *ranges, int sha
 }
 
 // ---- distance field and window matcher (match_kernels.hip) --------------------------------------------------------
-// The occupied bits packed as the counters stand on the stream now, then the field of all G maps: the mask and the
-// row distances in arena scratch, carved first; `field` null: carved behind them (the matcher's own copy).
-static int build_field(slam_ctx *c, slam_grid *g, const char *fn, int cap, size_t extra_bytes, int16_t *&field)
+// The occupied bits packed as the counters stand on the stream now, then the field of all G maps.  `ws` holds the caller's
+// own pieces of the scratch arena (a copy: the pointers they are bound to are the caller's); the mask, the row distances
+// and, with `field` null, the field (the matcher's own copy) join them, and the arena is reserved for all of them at once.
+static int build_field(slam_ctx *c, slam_grid *g, int cap, Layout ws, int16_t *&field)
 {
     TRY(grid_on_main(c));
-    const size_t words = raycast_mask_words(g->d), cells = (size_t)g->d.G * g->d.xw * g->d.yw;
-    TRY(arena_reserve(c, c->scratch, align_up(words * 4) + align_up(field_rowd_bytes(g->d)) + (field ? 0 : align_up(cells * 2)) +
-                                         align_up(extra_bytes) + 1024));
-    uint32_t *mask = carve<uint32_t>(c->scratch, words);
-    uint8_t *rowd = carve<uint8_t>(c->scratch, field_rowd_bytes(g->d));
-    if (!field) field = carve<int16_t>(c->scratch, cells);
-    REQUIRE_IN(fn, mask && rowd && field, "internal: workspace");
+    uint32_t *mask;
+    uint8_t *rowd;
+    ws.add(mask, raycast_mask_words(g->d)).add(rowd, field_rowd_bytes(g->d));
+    if (!field) ws.add(field, (size_t)g->d.G * g->d.xw * g->d.yw);
+    TRY(reserve(c, c->scratch, ws));
     Timed t(c, SLAM_K_FINALIZE);          // the threshold rule over every cell, as a finalize pass is
     HIPCHK(launch_raycast_pack(g->d, mask, c->stream));
     HIPCHK(launch_distance_field(g->d, mask, cap, rowd, field, c->stream));
@@ -1618,7 +1593,7 @@ int slam_grid_distance_field_dev(slam_ctx *c, slam_grid *g, int cap, int16_t *fi
 {
     TRY(use(c));
     TRY(check_field(__func__, g, cap, field_out));
-    return build_field(c, g, __func__, cap, 0, field_out);
+    return build_field(c, g, cap, Layout(), field_out);
 }
 
 int slam_grid_distance_field(slam_ctx *c, slam_grid *g, int cap, int16_t *field_out)
@@ -1661,10 +1636,8 @@ int slam_grid_match_dev(slam_ctx *c, slam_grid *g, const float *ranges, int shar
     TRY(check_match(__func__, g, ranges, centres, B, cos_t, sin_t, n, rot_cs, K, nx, ny, step, max_range, cap, best_out,
                     best_cost_out));
     int16_t *field = nullptr;
-    TRY(build_field(c, g, __func__, cap, (size_t)B * 8, field));
     MatchArgs a;
-    a.keys = carve<unsigned long long>(c->scratch, B);
-    REQUIRE(a.keys, "internal: workspace");
+    TRY(build_field(c, g, cap, Layout().add(a.keys, B), field));
     a.g = g->d; a.field = field;
     a.ranges = ranges; a.range_stride = shared ? 0 : n;
     a.centres = centres; a.maps = grid_of_batch; a.cos_t = cos_t; a.sin_t = sin_t; a.rot_cs = rot_cs;
@@ -1732,27 +1705,18 @@ static int locate_dev(const char *fn, slam_ctx *c, slam_grid *g, const float *ra
                      best_cost_out, plan));
     const int H = levels;
     const size_t pyr_cells = locate_pyramid_cells(g->d, H), keys = 2 * (size_t)B, evals = (size_t)B * (H + 1);
-    size_t extra = align_up(pyr_cells * 2) + align_up((keys + evals) * 8) + 2 * align_up((size_t)B * 4) + align_up(64);
-    for (int h = 1; h <= H; ++h) extra += align_up((size_t)plan.chunk_pairs * plan.level_nodes[h] * kLocateNodeBytes);
     const size_t rows = H ? (size_t)plan.chunk_pairs : 0;
-    extra += align_up(rows * n * kLocateOffsetBytes) + align_up(rows * 8);
-    int16_t *field = nullptr;
-    TRY(build_field(c, g, fn, cap, extra, field));
     LocateArgs a;
-    int16_t *pyr = carve<int16_t>(c->scratch, pyr_cells);
-    unsigned long long *words = carve<unsigned long long>(c->scratch, keys + evals);
-    a.bound = carve<int32_t>(c->scratch, B);
-    a.used = carve<int32_t>(c->scratch, B);
-    a.list_len = carve<unsigned>(c->scratch, kLocateMaxLevels + 1);
-    bool carved = pyr && words && a.bound && a.used && a.list_len;
+    int16_t *pyr, *field = nullptr;
+    unsigned long long *words;
+    Layout ws;
+    ws.add(pyr, pyr_cells).add(words, keys + evals).add(a.bound, B).add(a.used, B).add(a.list_len, kLocateMaxLevels + 1);
     for (int h = 1; h <= H; ++h) {
         a.list_cap[h] = plan.chunk_pairs * plan.level_nodes[h];
-        a.list[h] = carve<int32_t>(c->scratch, (size_t)a.list_cap[h] * 2);
-        carved = carved && a.list[h];
+        ws.add(a.list[h], (size_t)a.list_cap[h] * 2);
     }
-    a.table = carve<int32_t>(c->scratch, rows * n * 2);
-    a.table_cnt = carve<int32_t>(c->scratch, rows * 2);
-    REQUIRE_IN(fn, carved && a.table && a.table_cnt, "internal: workspace");
+    ws.add(a.table, rows * n * 2).add(a.table_cnt, rows * 2);
+    TRY(build_field(c, g, cap, ws, field));
     a.key_top = words; a.key_leaf = words + B; a.evaluated = words + keys;
     a.g = g->d;
     a.ranges = ranges; a.range_stride = shared ? 0 : n;
@@ -1849,19 +1813,17 @@ static int frontiers_dev(const char *fn, slam_ctx *c, slam_grid *g, int B, const
                         clusters_out, sums_out, plan));
     const size_t cells = (size_t)g->d.xw * g->d.yw;
     const size_t lab_words = (size_t)plan.chunk_queries * cells, seg_words = (size_t)plan.chunk_queries * plan.segs * 2;
-    const size_t ws = align_up(lab_words * 4) + align_up(seg_words * 4);
     FrontierArgs a;
+    Layout ws;
+    ws.add(a.lab, lab_words).add(a.seg, seg_words);
     if (min_clear2 > 0) {       // the field of all G maps, as slam_grid_match builds it
         int16_t *field = nullptr;
-        TRY(build_field(c, g, fn, cap, ws, field));
+        TRY(build_field(c, g, cap, ws, field));
         a.field = field;
     } else {
         TRY(grid_on_main(c));
-        TRY(arena_reserve(c, c->scratch, ws + 1024));
+        TRY(reserve(c, c->scratch, ws));
     }
-    a.lab = carve<int32_t>(c->scratch, lab_words);
-    a.seg = carve<int32_t>(c->scratch, seg_words);
-    REQUIRE_IN(fn, a.lab && a.seg, "internal: workspace");
     a.g = g->d;
     a.maps = grid_of_batch;
     a.B = B; a.radius = radius; a.min_unknown = min_unknown; a.min_clear2 = min_clear2; a.min_size = min_size; a.M = max_clusters;
@@ -1939,22 +1901,20 @@ static int travel_dev(const char *fn, slam_ctx *c, slam_grid *g, int B, const in
     TRY(check_travel(fn, c, g, B, grid_of_batch, sources, S, foot, min_clear2, cap, goals, Q, path_cap, status_out, cost_out, dir_out,
                      goal_cost_out, path_len_out, path_out, plan));
     const size_t cells = (size_t)g->d.xw * g->d.yw;
-    const size_t cost_words = cost_out ? 0 : (size_t)plan.chunk_queries * cells, mask_words = (size_t)plan.chunk_queries * plan.mask_words;
+    const size_t mask_words = (size_t)plan.chunk_queries * plan.mask_words;
     const size_t dirty_words = (size_t)plan.chunk_queries * plan.tiles;
-    const size_t ws = align_up(cost_words * 4) + align_up(mask_words * 8) + align_up(dirty_words * 4);
     TravelArgs a;
+    Layout ws;
+    ws.add(a.mask, mask_words).add(a.dirty, dirty_words);
+    if (!cost_out) ws.add(a.ws_cost, (size_t)plan.chunk_queries * cells);
     if (min_clear2 > 0) {       // the field of all G maps, as slam_grid_match builds it
         int16_t *field = nullptr;
-        TRY(build_field(c, g, fn, cap, ws, field));
+        TRY(build_field(c, g, cap, ws, field));
         a.field = field;
     } else {
         TRY(grid_on_main(c));
-        TRY(arena_reserve(c, c->scratch, ws + 1024));
+        TRY(reserve(c, c->scratch, ws));
     }
-    a.mask = carve<unsigned long long>(c->scratch, mask_words);
-    a.dirty = carve<int32_t>(c->scratch, dirty_words);
-    if (!cost_out) a.ws_cost = carve<int32_t>(c->scratch, cost_words);
-    REQUIRE_IN(fn, a.mask && a.dirty && (cost_out || a.ws_cost), "internal: workspace");
     a.g = g->d;
     a.maps = grid_of_batch;
     a.sources = sources;
@@ -2029,7 +1989,7 @@ int slam_mcl_weigh_dev(slam_ctx *c, slam_grid *g, double *poses, const double *m
     TRY(use(c));
     TRY(check_mcl_weigh(__func__, g, poses, motion, noise, ranges, cos_t, sin_t, F, P, n, max_range, cap));
     int16_t *built = nullptr;
-    if (!field) TRY(build_field(c, g, __func__, cap, 0, built));
+    if (!field) TRY(build_field(c, g, cap, Layout(), built));
     else TRY(grid_on_main(c));
     MclWeighArgs a;
     a.g = g->d; a.field = field ? field : built;
@@ -2078,17 +2038,10 @@ int slam_mcl_resample_dev(slam_ctx *c, const double *poses, int32_t *acc, const 
     TRY(use(c));
     TRY(check_mcl_resample(__func__, poses, acc, table, T, shift, u0, ess_frac, F, P, poses_out, est_out, info_out));
     const size_t FP = (size_t)F * P, FB = (size_t)F * mcl_scan_blocks(P);
-    TRY(arena_reserve(c, c->scratch, align_up((size_t)F * 8) + align_up((size_t)F * 4) + align_up(FP * 8) + 2 * align_up(FB * 8) +
-                                         align_up(FB * 32) + align_up((size_t)F * 16) + 1024));
     MclResampleArgs a;
-    a.keys = carve<unsigned long long>(c->scratch, F);
-    a.live = carve<int32_t>(c->scratch, F);
-    a.cum = carve<unsigned long long>(c->scratch, FP);
-    a.bsum = carve<unsigned long long>(c->scratch, FB);
-    a.bq = carve<unsigned long long>(c->scratch, FB);
-    a.bpart = carve<double>(c->scratch, FB * 4);
-    a.fpar = carve<unsigned long long>(c->scratch, (size_t)F * 2);
-    REQUIRE(a.keys && a.live && a.cum && a.bsum && a.bq && a.bpart && a.fpar, "internal: workspace");
+    Layout ws;
+    ws.add(a.keys, F).add(a.live, F).add(a.cum, FP).add(a.bsum, FB).add(a.bq, FB).add(a.bpart, FB * 4).add(a.fpar, (size_t)F * 2);
+    TRY(reserve(c, c->scratch, ws));
     a.poses = poses; a.acc = acc; a.table = table; a.T = T; a.shift = shift; a.u0 = u0; a.ess_frac = ess_frac; a.F = F; a.P = P;
     a.poses_out = poses_out; a.ancestors_out = ancestors_out; a.est_out = est_out; a.info_out = info_out;
     HIPCHK(hipMemsetAsync(a.keys, 0xff, (size_t)F * 8, c->stream));
@@ -2130,7 +2083,7 @@ int slam_mcl_weigh_maps_dev(slam_ctx *c, slam_grid *g, double *poses, const doub
     TRY(check_mcl_weigh(__func__, g, poses, motion, noise, ranges, cos_t, sin_t, F, P, n, max_range, cap));
     TRY(check_mcl_weigh_maps(__func__, g, grid_of_particle, F, P));
     int16_t *built = nullptr;
-    if (!field) TRY(build_field(c, g, __func__, cap, 0, built));
+    if (!field) TRY(build_field(c, g, cap, Layout(), built));
     else TRY(grid_on_main(c));
     MclWeighArgs a;
     a.g = g->d; a.field = field ? field : built;
@@ -2267,7 +2220,7 @@ int slam_grid_update_particles_dev(slam_ctx *c, slam_grid *g, const float *range
         r.ranges = ranges; r.cos_t = cos_t; r.sin_t = sin_t; r.poses = poses + 3 * (size_t)l0; r.acc = acc ? acc + l0 : nullptr;
         r.L = cnt; r.scans = 1; r.n = n; r.particles = true; r.per_filter = P; r.first_particle = l0; r.group = 1;
         r.lds_hits = c->win_lds_hits;
-        HIPCHK(launch_cast(d, plan_cast(d, c->grid_mode, r), r, nullptr, c->stream));
+        HIPCHK(launch_cast(d, plan_cast(d, c->grid_mode, r), r, nullptr, 0, c->stream));
     }
     return SLAM_OK;
 }
@@ -2352,8 +2305,7 @@ int slam_replay_dev(slam_ctx *c, const float *ranges, const double *cos_t, const
             }
             T = c->pipe_T[c->cast_pos];
         } else {
-            TRY(arena_reserve(c, c->scratch, align_up((size_t)pairs * 72) + 1024));
-            T = carve<double>(c->scratch, (size_t)pairs * 9);
+            TRY(reserve(c, c->scratch, Layout().add(T, (size_t)pairs * 9)));
         }
     }
     if (c->pipeline)        // is an earlier replay's compose / ray cast still reading these buffers?
@@ -2495,9 +2447,7 @@ int slam_particles_dev(slam_ctx *c, const float *ranges2, const double *cos_t, c
     }
     double *heading_cs = nullptr;               // cos / sin of the new headings: written by the pose step, read by the ray cast
     if (grid) {
-        const size_t need = align_up((size_t)P * 16) + 1024;
-        TRY(arena_reserve(c, c->scratch, need));
-        heading_cs = carve<double>(c->scratch, (size_t)P * 2);
+        TRY(reserve(c, c->scratch, Layout().add(heading_cs, (size_t)P * 2)));
         grid->pristine = false;
     }
     for (int k = 0; k < chunks; ++k) {
@@ -2538,7 +2488,7 @@ int slam_particles_dev(slam_ctx *c, const float *ranges2, const double *cos_t, c
             r.heading_cs = heading_cs + 2 * (size_t)p0;
             r.L = pc; r.scans = 1; r.n = n; r.particles = true; r.group = 1; r.lds_hits = c->win_lds_hits;
             Timed t(c, SLAM_K_GRID, nullptr, k == 0);
-            HIPCHK(launch_cast(d, plan_cast(d, c->grid_mode, r), r, nullptr, st));
+            HIPCHK(launch_cast(d, plan_cast(d, c->grid_mode, r), r, nullptr, 0, st));
             if (chunks > 1) HIPCHK(hipEventRecord(c->pev_cast[k], c->pstream));
         }
     }
@@ -3018,14 +2968,13 @@ int slam_node_replay_dev(slam_ctx *c, const float *ranges, const double *cos_t, 
     TRY(check_node_replay(__func__, ranges, cos_t, sin_t, L, n_scan, n, dtype, max_iter, lm_cap, max_lm, pose0, kept_out,
                           kept_count_out, xest_out, nlm_out, x_final_out, P_final_out, status_out));
     const size_t S = (size_t)L * n_scan, pairs = (size_t)L * (n_scan - 1), slots = S * lm_cap;
-    TRY(arena_reserve(c, c->scratch, align_up(S * 4) * 2 + align_up(slots * 4) + 2 * align_up(slots * 16) + align_up(S * n * 4) +
-                                         align_up(pairs * 24) + align_up(pairs * 72) + 4096));
-    int32_t *cnt = carve<int32_t>(c->scratch, S), *ovf = carve<int32_t>(c->scratch, S), *ids = carve<int32_t>(c->scratch, slots);
-    double *means = carve<double>(c->scratch, slots * 2), *z = carve<double>(c->scratch, slots * 2);
-    float *kr = carve<float>(c->scratch, S * n);
-    double *cast_poses = carve<double>(c->scratch, pairs * 3);
-    double *T = T_out ? T_out : carve<double>(c->scratch, pairs * 9);
-    REQUIRE(cnt && ovf && ids && means && z && kr && cast_poses && T, "internal: workspace");
+    int32_t *cnt, *ovf, *ids;
+    double *means, *z, *cast_poses, *T = T_out;
+    float *kr;
+    Layout ws;
+    ws.add(cnt, S).add(ovf, S).add(ids, slots).add(means, slots * 2).add(z, slots * 2).add(kr, S * n).add(cast_poses, pairs * 3);
+    if (!T) ws.add(T, pairs * 9);
+    TRY(reserve(c, c->scratch, ws));
     {   // 1. extraction of every scan (:79); 2. the kept scans of every trajectory (:74-82), moved to the front
         LandmarkArgs a{ranges, cos_t, sin_t, (long)S, n, range_threshold, radius_max_th, lm_cap, cnt, ovf, ids, means, z, nullptr, c->status};
         HIPCHK(launch_landmarks(a, c->stream));
@@ -3118,14 +3067,12 @@ int slam_loc_replay_dev(slam_ctx *c, const float *ranges, int S, int n_scan, int
     TRY(check_loc_replay(__func__, ranges, S, n_scan, n, stream_of_traj, ox, oy, obs_off, M, K, L, cos_t, sin_t, angle_min,
                          angle_increment, max_iter, xest_out, xodom_out, P_final_out, status_out));
     const size_t Lz = (size_t)L, pairs = (size_t)S * (2 * (size_t)n_scan - 1);
-    TRY(arena_reserve(c, c->scratch, align_up(pairs * 4 * n * 8) + align_up(pairs * 72) + 2 * align_up(Lz * 2 * n * 8) +
-                                         align_up(Lz * 72) + align_up(Lz * 4) + align_up(Lz * kLocStateDoubles * 8) + 4096));
-    double *pair_pts = carve<double>(c->scratch, pairs * 4 * n), *T_stream = carve<double>(c->scratch, pairs * 9);
-    double *tar = carve<double>(c->scratch, Lz * 2 * n), *src = carve<double>(c->scratch, Lz * 2 * n);
-    double *T_step = carve<double>(c->scratch, Lz * 9);
-    int32_t *it_step = carve<int32_t>(c->scratch, Lz);
-    double *state = carve<double>(c->scratch, Lz * kLocStateDoubles);
-    REQUIRE(pair_pts && T_stream && tar && src && T_step && it_step && state, "internal: workspace");
+    double *pair_pts, *T_stream, *tar, *src, *T_step, *state;
+    int32_t *it_step;
+    Layout ws;
+    ws.add(pair_pts, pairs * 4 * n).add(T_stream, pairs * 9).add(tar, Lz * 2 * n).add(src, Lz * 2 * n).add(T_step, Lz * 9)
+        .add(it_step, Lz).add(state, Lz * kLocStateDoubles);
+    TRY(reserve(c, c->scratch, ws));
     IcpArgs icp;
     icp.prior = nullptr; icp.ranges = nullptr; icp.cos_t = icp.sin_t = nullptr; icp.tar_scan_stride = icp.src_scan_stride = 0;
     icp.ppt = 0; icp.n_tar = n; icp.n_src = n; icp.max_iter = max_iter; icp.tol = tol; icp.err_out = nullptr;

@@ -144,8 +144,11 @@ struct GridDev {
     double free_inc, hit_inc;
 };
 
-// A ray cast of a batch of scans: plan_cast picks the engine, cast_scratch_bytes is the device scratch launch_cast then needs
-// at `scratch` (0 for Direct and Window).  The request holds either explicit world-frame endpoints (ox != nullptr:
+// A ray cast of a batch of scans: plan_cast picks the engine and launch_cast places that engine's pieces (grid_kernels.hip:
+// TileScratch, WedgeScratch; none for Direct and Window) in the `scratch_bytes` bytes at `scratch`, or fails with
+// hipErrorInvalidValue before its first kernel when they end beyond them.  cast_layout_bytes is where the pieces of a launch of
+// `rays` rays in `scans` scans and `groups` groups end, and cast_scratch_bytes that of a whole request with one group per scan:
+// no piece shrinks as a count grows, so it covers every launch of the request and every chunk of an oversize one.  The request holds either explicit world-frame endpoints (ox != nullptr:
 // Mapping.update's own arguments, `scans` scans of one stream) or a replay: scan k of trajectory l is
 // ranges[(l * (scans + 1) + k + 1) * n], cast from poses[l][k] (slam_ekf.py:89).
 enum class CastPath { Direct, Window, Tiles, Wedges };
@@ -167,8 +170,9 @@ struct CastRequest {
     int lds_hits = -1;                     // context option "win_lds_hits": hits of sorted window rays counted in LDS, one add per end cell: -1 = in chip-filling launches, 0 = off, 1 = on
 };
 CastPath plan_cast(const GridDev &g, int grid_mode, const CastRequest &r);
+size_t cast_layout_bytes(CastPath p, long rays, long scans, long groups);
 size_t cast_scratch_bytes(CastPath p, const CastRequest &r);
-hipError_t launch_cast(const GridDev &g, CastPath p, const CastRequest &r, void *scratch, hipStream_t s);
+hipError_t launch_cast(const GridDev &g, CastPath p, const CastRequest &r, void *scratch, size_t scratch_bytes, hipStream_t s);
 hipError_t launch_grid_finalize(const GridDev &g, int g0, int gcount, int8_t *pmap, hipStream_t s);
 // slam_grid_copy_maps: map first + k becomes a copy of map src[k], counters and (when kept) live pmap; copied_out nullable [count]
 hipError_t launch_grid_copy_maps(const GridDev &g, const int32_t *src, int first, int count, int32_t *copied_out, hipStream_t s);

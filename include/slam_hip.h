@@ -223,6 +223,8 @@ int slam_plan_icp(int B, int n_src, int n_tar, int is_scan, int qpt_pref, int ba
  * "travel_tiles" / "travel_tiles_x" / "travel_tiles_y" / "travel_mask_words" / "travel_trips" (xw, yw),
  * "travel_query_bytes" (xw, yw, 1 when the costs live in the workspace), "travel_lds", "travel_chunk_queries" / "travel_chunks"
  * (budget in KiB, a query's bytes, B);
+ * "wedge_ws_bytes" / "tile_ws_bytes" (scans of the cast = L * scans, beams, groups): the bytes at which the device workspace
+ * of the wedge / tile ray cast ends, every piece on a 256-byte boundary, computed in 64 bits;
  * arguments a function does not take are ignored.  SLAM_ERR_INVALID for a name it does not know. */
 int slam_plan_query(const char *name, int a, int b, int c, int guard, int64_t *out);
 
