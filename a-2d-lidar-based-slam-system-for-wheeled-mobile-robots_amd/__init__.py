@@ -14,7 +14,10 @@ zjwzcx/A-2D-LiDAR-based-SLAM-System-for-Wheeled-Mobile-Robots:
                cluster (batched: DeviceGrid.frontiers, grid_frontiers_host, frontier_points; GridSLAM / DeviceGridSLAM
                .frontiers on the best particle's map); travel_field / travel_path / next_goal(by="travel"): what it
                costs to drive to every cell, the way there, and the frontier that is nearest to drive to (batched:
-               DeviceGrid.travel, grid_travel_host; DeviceGridSLAM.travel / .next_goals)
+               DeviceGrid.travel, grid_travel_host; DeviceGridSLAM.travel / .next_goals); view_gain /
+               next_goal(by="gain"): the cells a scan from a pose would reveal, and the frontier that reveals the most
+               unknown cells per unit of travel (batched: DeviceGrid.view_gain, grid_view_gain_host, view_poses,
+               gain_goal; GridSLAM / DeviceGridSLAM .view_gain, DeviceGridSLAM.next_goals(by="gain"))
     bresenham  (start, end).path
     SLAM_EKF   laserCallback glue (scan matching + map building); landmarks=True: the whole W12
                node with Extraction and the landmark EKF on the host; batched on the device
@@ -40,6 +43,7 @@ from . import _abi, dist, param, synthetic
 from ._abi import Context, LibraryMissing, SlamError, default_context
 from ._abi import TRAVEL_DIAGONAL, TRAVEL_STRAIGHT, TRAVEL_TRIPS
 from ._abi import RAY_BAD, RAY_BLOCKED, RAY_CLASSES, RAY_EMPTY, RAY_FREE, RAY_HIT, RAY_NAMES, RAY_OUT, RAY_UNKNOWN
+from ._abi import VIEW_COUNTS, VIEW_FREE, VIEW_OCCUPIED, VIEW_OPEN, VIEW_UNKNOWN
 from . import dwa
 from .bresenham import bresenham, rasterize
 from .dwa import DeviceDWA, dwa_batch_host, dwa_control
@@ -59,6 +63,7 @@ from .replay import grid_distance_field_host, grid_match_host, match_pose, match
 from .replay import grid_copy_maps_host, grid_update_particles_host
 from .replay import grid_locate_host, locate_pose, locate_rotations
 from .replay import frontier_points, grid_frontiers_host, grid_travel_host
+from .replay import gain_goal, grid_view_gain_host, view_poses, view_tables
 from .grid_slam import DeviceGridSLAM, GridSLAM
 from .slam_ekf import SLAM_EKF
 from .synthetic import LaserScan
@@ -74,4 +79,5 @@ __all__ = ["ICP", "Mapping", "Localization", "EKF", "Extraction", "LandMarkSet",
            "TRAVEL_STRAIGHT", "TRAVEL_DIAGONAL", "TRAVEL_TRIPS",
            "MCL", "DeviceMCL", "MCL_DEAD", "mcl_weight_table", "mcl_weigh_host", "mcl_resample_host",
            "GridSLAM", "DeviceGridSLAM", "mcl_settle_host", "grid_copy_maps_host", "grid_update_particles_host",
-           "RAY_EMPTY", "RAY_HIT", "RAY_BLOCKED", "RAY_FREE", "RAY_UNKNOWN", "RAY_OUT", "RAY_BAD", "RAY_CLASSES", "RAY_NAMES"]
+           "RAY_EMPTY", "RAY_HIT", "RAY_BLOCKED", "RAY_FREE", "RAY_UNKNOWN", "RAY_OUT", "RAY_BAD", "RAY_CLASSES", "RAY_NAMES",
+           "grid_view_gain_host", "view_poses", "view_tables", "gain_goal", "VIEW_UNKNOWN", "VIEW_FREE", "VIEW_OCCUPIED", "VIEW_OPEN", "VIEW_COUNTS"]

@@ -77,6 +77,8 @@ _SIGS = {
     "slam_grid_visits": ([_vp, _vp, C.POINTER(C.c_uint64)], _i),
     "slam_grid_raycast": ([_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, C.c_float, _i, _vp, _vp], _i),
     "slam_grid_raycast_dev": ([_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, C.c_float, _i, _vp, _vp], _i),
+    "slam_grid_view_gain": ([_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, C.c_float, _i, _vp, _vp], _i),
+    "slam_grid_view_gain_dev": ([_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, C.c_float, _i, _vp, _vp], _i),
     "slam_grid_scan_score": ([_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp], _i),
     "slam_grid_scan_score_dev": ([_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp], _i),
     "slam_grid_distance_field": ([_vp, _vp, _i, _vp], _i),
@@ -146,6 +148,9 @@ EKF_MAX_LM = 32
 # classes of slam_grid_scan_score (SLAM_RAY_*)
 RAY_EMPTY, RAY_HIT, RAY_BLOCKED, RAY_FREE, RAY_UNKNOWN, RAY_OUT, RAY_BAD = range(7)
 RAY_CLASSES = 7
+# columns of slam_grid_view_gain's counts (SLAM_VIEW_*)
+VIEW_UNKNOWN, VIEW_FREE, VIEW_OCCUPIED, VIEW_OPEN = range(4)
+VIEW_COUNTS = 4
 MCL_DEAD = 2 ** 31 - 1             # SLAM_MCL_DEAD: a dead particle's accumulated cost
 TRAVEL_STRAIGHT, TRAVEL_DIAGONAL, TRAVEL_TRIPS = 10, 14, 1      # SLAM_TRAVEL_*: the two move costs and the trip-bound status
 RAY_NAMES = ("empty", "hit", "blocked", "free", "unknown", "out", "bad")

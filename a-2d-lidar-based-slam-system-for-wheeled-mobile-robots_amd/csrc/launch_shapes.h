@@ -672,4 +672,85 @@ inline TravelShape plan_travel(const TravelRequest &r)
     return p;
 }
 
+// ---------------------------------------------------------------------------------
+// View gain (view_kernels.hip, slam_grid_view_gain)
+// ---------------------------------------------------------------------------------
+// One view = one pose and its beams.  Its BOX is the bounding box of its start and end cells, clipped to the map and
+// padded to whole 32-cell words in y: box_rows rows of box_words words.  One workgroup owns a view: it keeps one bit per
+// cell of the box (the WINDOW), sets the bits of the cells its beams see and counts them against the map's class bits.
+// The window lies in LDS when it is at most kViewLdsBytes (the bound of the staged ray cast: two workgroups share a
+// compute unit's 160 KiB), else in the call's workspace, one slot of a whole map's words per workgroup of the global
+// engine (context option "gain_ws_mb"): chunk_views slots, over which the views are taken grid-stride in `chunks` passes.
+constexpr size_t kViewLdsBytes = 64 * 1024;
+constexpr int kViewThreads = 256;
+constexpr long kViewMaxBlocks = 16384;       // workgroups of a launch; more views are taken grid-stride
+
+// Which engine takes a view whose window has `window_words` words ("gain_lds": -1 automatic, 0 global, 1 LDS wherever
+// the window fits): the ONE place that decides, asked by plan_view and by both kernels.
+// The automatic rule follows tools/bench_gain.py (profiles/gain_bench.json): automatic means LDS
+// wherever the window fits.  Course map at 400 x 400, views at its 60 frontier representatives, 360 beams to 30 m, ms
+// per call, LDS / global:
+//     B          1            64           256          8 192        1 024 maps x 256
+//     gain    0.349/0.414  0.348/0.423  0.347/0.455  5.45/6.14    172.7/186.1         global 8 - 31 % slower everywhere
+// Nothing measured speaks for the global engine where LDS fits.  (Supposed, not measured: the marks of a view land in
+// few words - beams share their cells near the origin - and an OR at the L2 costs more than one in LDS.)
+SLAM_HD inline bool view_fits_lds(long window_words) { return window_words * 4 <= (long)kViewLdsBytes; }
+SLAM_HD inline bool choose_view_lds(long window_words, int lds_mode)
+{
+    if (!view_fits_lds(window_words) || lds_mode == 0) return false;
+    return true;                             // 1, and automatic
+}
+
+struct ViewRequest {
+    long B = 0;
+    int xw = 0, yw = 0;
+    int box_rows = 0, box_words = 0;     // the box asked about (0: the whole map)
+    int lds_mode = -1;
+    long ws_bytes = 0;
+    int guard = kLdsGuard;
+};
+struct ViewShape {
+    bool ok = false;             // false: the global engine may be needed and one view's slot does not fit the budget
+    int row_words = 0;           // words per map row: ceil(yw / 32)
+    long map_words = 0;          // xw * row_words: seen_out words of a view, and the words of a global slot
+    long window_words = 0;       // of the box asked about
+    long lds_bytes = 0;          // of that window in LDS, guard included
+    bool engine_lds = false;     // the engine that box takes
+    bool needs_global = false;   // some box of this map may go to the global engine
+    bool needs_lds = false;      // ... to the LDS engine
+    long launch_lds = 0;         // dynamic LDS of the LDS engine's launch: the largest window that can fit, and the guard
+    long view_bytes = 0;         // bytes of a global slot
+    long chunk_views = 0, chunks = 0;
+    long grid_lds = 0, grid_global = 0;
+    int threads = kViewThreads;
+};
+inline ViewShape plan_view(const ViewRequest &r)
+{
+    ViewShape p;
+    if (r.B < 1 || r.xw < 1 || r.yw < 1) return p;
+    p.row_words = (r.yw + 31) / 32;
+    p.map_words = (long)r.xw * p.row_words;
+    const int rows = r.box_rows > 0 ? std::min(r.box_rows, r.xw) : r.xw;
+    const int words = r.box_words > 0 ? std::min(r.box_words, p.row_words) : p.row_words;
+    p.window_words = (long)rows * words;
+    p.lds_bytes = p.window_words * 4 + r.guard;
+    p.engine_lds = choose_view_lds(p.window_words, r.lds_mode);
+    p.needs_lds = r.lds_mode != 0;
+    p.needs_global = !choose_view_lds(p.map_words, r.lds_mode);
+    p.launch_lds = std::min(p.map_words * 4, (long)kViewLdsBytes) + r.guard;
+    p.view_bytes = p.map_words * 4;
+    p.chunk_views = std::min(r.B, r.ws_bytes / p.view_bytes);
+    p.grid_lds = p.needs_lds ? std::min(r.B, kViewMaxBlocks) : 0;
+    if (p.chunk_views < 1) {
+        p.chunk_views = 0;
+        p.ok = !p.needs_global;
+        return p;
+    }
+    p.chunk_views = std::min(p.chunk_views, kViewMaxBlocks);
+    p.chunks = (r.B + p.chunk_views - 1) / p.chunk_views;
+    p.grid_global = p.needs_global ? p.chunk_views : 0;
+    p.ok = true;
+    return p;
+}
+
 }  // namespace slam

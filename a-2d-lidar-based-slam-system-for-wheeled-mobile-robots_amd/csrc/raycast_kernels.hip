@@ -1,7 +1,8 @@
 // The read side of the occupancy grid for gfx950 (MI355X): rays traced THROUGH a map.
 //
 //   trace(map, start, end, skip)   the first occupied cell, in PATH order, of bresenham(start, end).path
-//                                  (W12m/bresenham.py:2-58) from path index `skip` on
+//                                  (W12m/bresenham.py:2-58) from path index `skip` on (ray_trace.h, shared with
+//                                  the view gain of view_kernels.hip)
 //   slam_grid_raycast              the scan the map would give: every beam cast to max_range from a pose
 //   slam_grid_scan_score           a measured scan against the map: every beam traced to its own end cell and
 //                                  put into one of seven classes (SLAM_RAY_*), tallied per hypothesis
@@ -29,6 +30,7 @@
 
 #include "slam_internal.h"
 #include "grid_walk.h"
+#include "ray_trace.h"
 
 namespace slam {
 
@@ -50,36 +52,6 @@ __global__ void __launch_bounds__(256) k_raycast_pack(const uint32_t *__restrict
             }
         }
     }
-}
-
-// trace(): path index of the first occupied in-bounds cell at path index >= skip, or -1; Lp = path length;
-// (fx, fy) the cell found.  `mask` is the map's own [xw][wpr] words, in global memory or in LDS.  A mask word is
-// kept while the walk stays inside it (32 cells of a row: a steep line changes word every 32nd step).
-__device__ __forceinline__ int trace(const uint32_t *mask, int xw, int yw, int wpr, int sx, int sy, int ex, int ey, int skip,
-                                     int &Lp, int &fx, int &fy)
-{
-    Ray r;
-    Lp = 0; fx = fy = -1;
-    if (!ray_setup(sx, sy, ex, ey, r)) return -1;                   // identical cells: empty path (bresenham.py:10-11)
-    Lp = r.dx + 1;
-    // walk steps whose cell is tested: path index j = k, or dx - k on a reversed line (bresenham.py:57-58)
-    const int k0 = r.flag ? 0 : skip, k1 = r.flag ? r.dx - skip : r.dx;
-    if (k0 > k1) return -1;
-    CellWalk w(r);
-    int found = -1, cur = -1;
-    uint32_t word = 0;
-    for (int k = 0; k <= k1; ++k) {
-        if (k >= k0 && (unsigned)w.lx < (unsigned)xw && (unsigned)w.ly < (unsigned)yw) {
-            const int wi = w.lx * wpr + (w.ly >> 5);
-            if (wi != cur) { cur = wi; word = mask[wi]; }
-            if ((word >> (w.ly & 31)) & 1u) {
-                found = k; fx = w.lx; fy = w.ly;
-                if (!r.flag) break;
-            }
-        }
-        (void)w.next();
-    }
-    return found < 0 ? -1 : r.flag ? r.dx - found : found;
 }
 
 // Per-hypothesis tallies of a wave's classes: for every hypothesis the wave holds, lane c < 7 adds the number of
@@ -115,13 +87,7 @@ __device__ __forceinline__ int one_ray(const RaycastArgs &a, const uint32_t *mas
         const double c = cos(pose[2]), s = sin(pose[2]);
         double rr = SCORE ? (double)a.ranges[(size_t)b * a.range_stride + i] : (double)a.max_range;
         if (SCORE && rr == INFINITY) rr = 30.0;                      // slam_ekf.py:119
-        const double lx = a.cos_t[i] * rr, ly = a.sin_t[i] * rr;     // :122
-        const double x = c * lx + (-s) * ly + px * 1.0;              // u2T(pose).dot(pc), :89
-        const double y = s * lx + c * ly + py * 1.0;
-        pcx = to_cell(px, g.scale, g.off_x, bad);
-        pcy = to_cell(py, g.scale, g.off_y, bad);
-        pox = to_cell(x, g.scale, g.off_x, bad);                     // (an infinite or NaN coordinate is flagged here:
-        poy = to_cell(y, g.scale, g.off_y, bad);                     //  every way a pose or a range can be non-finite)
+        beam_cells(g, px, py, c, s, a.cos_t[i], a.sin_t[i], rr, pcx, pcy, pox, poy, bad);
     }
     int Lp = 0, fx = -1, fy = -1, j = -1;
     if (!bad) j = trace(mask, g.xw, g.yw, a.wpr, pcx, pcy, pox, poy, a.skip, Lp, fx, fy);

@@ -108,6 +108,8 @@ struct slam_ctx {
     long locate_ws_bytes = 64L << 20; // slam_grid_locate: bytes its node lists may take ("locate_ws_mb"); pairs are cut into chunks that fit; changes no result
     long frontier_ws_bytes = 256L << 20; // slam_grid_frontiers: bytes its labels may take ("frontier_ws_mb"); queries are cut into chunks that fit; changes no result
     long travel_ws_bytes = 256L << 20; // slam_grid_travel: bytes its costs, traversable bits and tile keys may take ("travel_ws_mb"); queries are cut into chunks that fit; changes no result
+    int gain_lds = -1;    // slam_grid_view_gain: -1 = automatic, 0 = every bit window in the workspace, 1 = in LDS wherever a view's window fits; changes no result
+    long gain_ws_bytes = 256L << 20; // slam_grid_view_gain: bytes the window slots of its global engine may take ("gain_ws_mb"); changes no result
     int icp_team = 0;     // first-iteration queries without a beam window: 0 = listed and searched apart from their lanes (nn_listed), 1 = box search
     // "pipeline" option: the map stage of slam_replay_dev (reset -> ray cast -> finalize) runs on
     // a second stream, so the map stage of one replay overlaps the scan matching of the next.
@@ -692,6 +694,8 @@ static const OptionRange kOptionRanges[] = {
     {"locate_ws_mb", [](double v) { return v > 0 && v <= 1048576; }, "locate_ws_mb in (0, 1048576]"},
     {"frontier_ws_mb", [](double v) { return v > 0 && v <= 1048576; }, "frontier_ws_mb in (0, 1048576]"},
     {"travel_ws_mb", [](double v) { return v > 0 && v <= 1048576; }, "travel_ws_mb in (0, 1048576]"},
+    {"gain_lds", [](double v) { return v == -1 || v == 0 || v == 1; }, "gain_lds is -1, 0 or 1"},
+    {"gain_ws_mb", [](double v) { return v > 0 && v <= 1048576; }, "gain_ws_mb in (0, 1048576]"},
 };
 
 int slam_set_option(slam_ctx *c, const char *name, double value)
@@ -718,6 +722,8 @@ int slam_set_option(slam_ctx *c, const char *name, double value)
     else if (!strcmp(name, "locate_ws_mb")) c->locate_ws_bytes = (long)(value * 1048576.0);
     else if (!strcmp(name, "frontier_ws_mb")) c->frontier_ws_bytes = (long)(value * 1048576.0);
     else if (!strcmp(name, "travel_ws_mb")) c->travel_ws_bytes = (long)(value * 1048576.0);
+    else if (!strcmp(name, "gain_lds")) c->gain_lds = (int)value;
+    else if (!strcmp(name, "gain_ws_mb")) c->gain_ws_bytes = (long)(value * 1048576.0);
     else if (!strcmp(name, "pipeline")) {
         TRY(join_from_grid(c));
         if (value == 1 && !c->gstream) {
@@ -860,6 +866,26 @@ static int64_t travel_plan_chunk(long kib, long bytes, long B, bool chunks)
     return chunks ? (B + per - 1) / per : per;
 }
 
+// the view gain's plan for a map of xw x yw, B views and a box of `rows` rows of `words` words (0: the whole map)
+static ViewShape view_plan_for(int xw, int yw, int rows, int words, int lds_mode, long B, long ws_bytes, int guard)
+{
+    ViewRequest r;
+    r.B = B; r.xw = xw; r.yw = yw; r.box_rows = rows; r.box_words = words; r.lds_mode = lds_mode; r.ws_bytes = ws_bytes; r.guard = guard;
+    return plan_view(r);
+}
+// a box of a rows x b words on a map large enough to hold it
+static ViewShape view_box_plan(int a, int b, int mode, int guard)
+{
+    return view_plan_for(std::max(a, 1), 32 * std::max(b, 1), a, b, mode, 1, 1L << 40, guard);
+}
+// a budget of `kib` KiB, slots of `bytes` bytes (a multiple of 4), B views, as plan_view cuts them (global engine)
+static int64_t view_plan_chunk(long kib, long bytes, long B, bool chunks)
+{
+    if (bytes < 4 || B < 1) return 0;
+    const ViewShape p = view_plan_for((int)(bytes / 4), 1, 0, 0, 0, B, kib * 1024, 0);
+    return !p.ok ? 0 : chunks ? p.chunks : p.chunk_views;
+}
+
 int slam_plan_query(const char *name, int a, int b, int c, int guard, int64_t *out)
 {
     if (!name || !out) return fail(SLAM_ERR_INVALID, "slam_plan_query: null pointer");
@@ -913,6 +939,15 @@ int slam_plan_query(const char *name, int a, int b, int c, int guard, int64_t *o
         {"travel_trips", travel_plan_for(a, b, true, 1, 1L << 40, g).trips},
         {"travel_query_bytes", travel_plan_for(a, b, c != 0, 1, 1L << 40, g).query_bytes}, {"travel_lds", (int64_t)travel_lds_bytes(g)},
         {"travel_chunk_queries", travel_plan_chunk(a, b, c, false)}, {"travel_chunks", travel_plan_chunk(a, b, c, true)},
+        // slam_grid_view_gain: view_row_words: a = yw; view_bytes: a = xw, b = yw (a global slot, and seen_out, of one view);
+        // view_window_words, view_lds_bytes, view_engine (1 = LDS, 0 = global): a box of a rows x b words, c = "gain_lds";
+        // view_chunk_views / view_chunks: a = the budget in KiB, b = view_bytes, c = B, as plan_view cuts them
+        {"kViewLdsBytes", (int64_t)kViewLdsBytes}, {"kViewThreads", kViewThreads}, {"kViewMaxBlocks", (int64_t)kViewMaxBlocks},
+        {"view_row_words", view_plan_for(1, std::max(a, 1), 0, 0, -1, 1, 1L << 40, g).row_words},
+        {"view_bytes", view_plan_for(std::max(a, 1), std::max(b, 1), 0, 0, -1, 1, 1L << 40, g).view_bytes},
+        {"view_window_words", view_box_plan(a, b, c, g).window_words}, {"view_lds_bytes", view_box_plan(a, b, c, g).lds_bytes},
+        {"view_engine", view_box_plan(a, b, c, g).engine_lds ? 1 : 0},
+        {"view_chunk_views", view_plan_chunk(a, b, c, false)}, {"view_chunks", view_plan_chunk(a, b, c, true)},
         // the ray casts of large maps: a = scans of the cast (L * scans), b = beams, c = groups: where the engine's layout ends
         {"wedge_ws_bytes", (int64_t)cast_layout_bytes(CastPath::Wedges, (long)a * b, a, c)},
         {"tile_ws_bytes", (int64_t)cast_layout_bytes(CastPath::Tiles, (long)a * b, a, c)},
@@ -1561,6 +1596,71 @@ int slam_grid_scan_score(slam_ctx *c, slam_grid *g, const float *ranges, int sha
         .in(d_s, sin_t, n).out(d_cnt, counts_out, (size_t)B * SLAM_RAY_CLASSES).out(d_cls, class_out, rays);
     TRY(s.upload());
     TRY(slam_grid_scan_score_dev(c, g, d_r, shared, d_p, B, d_g, d_c, d_s, n, skip, d_cnt, d_cls));
+    return s.download();
+}
+
+// ---- view gain (view_kernels.hip) -----------------------------------------------------------------------------------
+static int check_view(const char *fn, const slam_ctx *c, const slam_grid *g, const double *poses, int B, const double *cos_t,
+                      const double *sin_t, int n, float max_range, int skip, const int32_t *counts_out, const uint32_t *seen_out,
+                      ViewShape &plan)
+{
+    TRY(check_raycast(fn, g, poses, B, cos_t, sin_t, n, skip, counts_out));
+    REQUIRE_IN(fn, std::isfinite(max_range) && max_range > 0, "max_range must be finite and > 0");
+    const long map_words = (long)g->d.xw * ((g->d.yw + 31) / 32);
+    REQUIRE_IN(fn, map_words < (1L << 31), "xw * ceil(yw / 32) >= 2^31");
+    REQUIRE_IN(fn, !seen_out || (long)B * map_words < (1L << 31), "B * xw * ceil(yw / 32) >= 2^31 with seen_out");
+    plan = view_plan_for(g->d.xw, g->d.yw, 0, 0, c->gain_lds, B, c->gain_ws_bytes, kLdsGuard);
+    if (!plan.ok)
+        return fail(SLAM_ERR_INVALID, "%s: the bit window of one view (%ld bytes) does not fit the context option gain_ws_mb (%ld bytes)",
+                    fn, plan.view_bytes, c->gain_ws_bytes);
+    return SLAM_OK;
+}
+
+// pack the two class planes of every map as the counters stand on the stream now, then the views.  The counters are
+// only read.
+static int view_dev(const char *fn, slam_ctx *c, slam_grid *g, const double *poses, int B, const int32_t *grid_of_batch,
+                    const double *cos_t, const double *sin_t, int n, float max_range, int skip, int32_t *counts_out, uint32_t *seen_out)
+{
+    ViewShape plan;
+    TRY(check_view(fn, c, g, poses, B, cos_t, sin_t, n, max_range, skip, counts_out, seen_out, plan));
+    TRY(grid_on_main(c));
+    const size_t plane = raycast_mask_words(g->d);
+    uint32_t *occ, *unk, *slots;
+    TRY(reserve(c, c->scratch, Layout().add(occ, plane).add(unk, plane).add(slots, (size_t)plan.grid_global * plan.map_words)));
+    ViewArgs a;
+    a.g = g->d; a.occ = occ; a.unk = unk; a.wpr = plan.row_words;
+    a.poses = poses; a.maps = grid_of_batch; a.cos_t = cos_t; a.sin_t = sin_t;
+    a.B = B; a.n = n; a.skip = skip; a.max_range = max_range; a.lds_mode = c->gain_lds;
+    a.slots = slots; a.counts_out = counts_out; a.seen_out = seen_out;
+    {
+        Timed t(c, SLAM_K_FINALIZE);      // the threshold rule over every cell, as a finalize pass is
+        HIPCHK(launch_view_pack(g->d, occ, unk, c->stream));
+    }
+    Timed t(c, SLAM_K_GRID);
+    HIPCHK(launch_view(a, plan, c->stream));
+    return SLAM_OK;
+}
+
+int slam_grid_view_gain_dev(slam_ctx *c, slam_grid *g, const double *poses, int B, const int32_t *grid_of_batch, const double *cos_t,
+                            const double *sin_t, int n, float max_range, int skip, int32_t *counts_out, uint32_t *seen_out)
+{
+    TRY(use(c));
+    return view_dev(__func__, c, g, poses, B, grid_of_batch, cos_t, sin_t, n, max_range, skip, counts_out, seen_out);
+}
+
+int slam_grid_view_gain(slam_ctx *c, slam_grid *g, const double *poses, int B, const int32_t *grid_of_batch, const double *cos_t,
+                        const double *sin_t, int n, float max_range, int skip, int32_t *counts_out, uint32_t *seen_out)
+{
+    TRY(use(c));
+    ViewShape plan;
+    TRY(check_view(__func__, c, g, poses, B, cos_t, sin_t, n, max_range, skip, counts_out, seen_out, plan));
+    TRY(check_grid_of_batch(__func__, g, grid_of_batch, B));
+    double *d_p, *d_c, *d_s; int32_t *d_g, *d_cnt; uint32_t *d_seen;
+    Staging s(c);
+    s.in(d_p, poses, (size_t)B * 3).in(d_g, grid_of_batch, B).in(d_c, cos_t, n).in(d_s, sin_t, n)
+        .out(d_cnt, counts_out, (size_t)B * SLAM_VIEW_COUNTS).out(d_seen, seen_out, (size_t)B * plan.map_words);
+    TRY(s.upload());
+    TRY(view_dev(__func__, c, g, d_p, B, d_g, d_c, d_s, n, max_range, skip, d_cnt, d_seen));
     return s.download();
 }
 

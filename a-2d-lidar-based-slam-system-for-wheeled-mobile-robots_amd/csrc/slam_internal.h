@@ -205,6 +205,27 @@ bool choose_raycast_path(const GridDev &g, int lds_mode, long B, int n);
 hipError_t launch_raycast_pack(const GridDev &g, uint32_t *mask, hipStream_t s);
 hipError_t launch_raycast(RaycastArgs a, bool staged, hipStream_t s);
 
+// ---- view gain: the cells a scan from a pose would reveal (view_kernels.hip) --------------
+struct ViewArgs {
+    GridDev g;
+    const uint32_t *occ = nullptr;           // [G][xw][wpr]: bit ly % 32 of word [lx][ly / 32] = pmap == 100 (launch_view_pack)
+    const uint32_t *unk = nullptr;           // the same for pmap == 50
+    int wpr = 0;                             // words per map row
+    const double *poses = nullptr;           // [B][3]
+    const int32_t *maps = nullptr;           // nullable [B]: NULL = every view reads map 0 (an entry outside [0, G): a row of -1)
+    const double *cos_t = nullptr, *sin_t = nullptr;
+    int B = 0, n = 0, skip = 0;
+    float max_range = 0.f;
+    int lds_mode = -1;                       // context option "gain_lds"
+    uint32_t *slots = nullptr;               // global engine: [its workgroups][xw * wpr] window words
+    int32_t *counts_out = nullptr;           // [B][SLAM_VIEW_COUNTS]
+    uint32_t *seen_out = nullptr;            // nullable [B][xw][wpr]
+};
+// occ, unk: the two planes, raycast_mask_words(g) words each
+hipError_t launch_view_pack(const GridDev &g, uint32_t *occ, uint32_t *unk, hipStream_t s);
+// the LDS engine over the views it takes, then the global engine over the rest, as p says
+hipError_t launch_view(const ViewArgs &a, const ViewShape &p, hipStream_t s);
+
 // ---- distance field of the grid and the window matcher on it (match_kernels.hip) ---------
 struct MatchArgs {
     GridDev g;

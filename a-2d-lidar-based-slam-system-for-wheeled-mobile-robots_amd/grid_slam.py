@@ -241,12 +241,49 @@ class DeviceGridSLAM:
         self._held = (maps, src, goals) + tuple(out.values())
         return out
 
-    def next_goals(self, foot=0, through_unknown=False, radius=2, min_unknown=13, min_clear2=0, cap=64, min_size=5, max_clusters=256):
+    def view_gain(self, reps, n=360, max_range=None, skip=1, return_seen=False):
+        """What a scan from each cell of ``reps`` (int32 [F, M, 2] device tensor, e.g. the representatives of
+        :meth:`frontiers`' table) would reveal of its filter's best particle's map (:meth:`DeviceGrid.view_gain`): the
+        views stand at the cell centres, heading 0, with the ``n`` beams of :func:`view_tables` over the full circle to
+        ``max_range`` (default: the filter's).  Poses and map indices are formed on the device.  Returns counts int32
+        [F, M, 4] (``_abi.VIEW_*``), rows of -1 for a cell with a negative coordinate and for a filter with no live
+        particle, and with ``return_seen`` also the bit words [F, M, xw, ceil(yw / 32)].  No synchronise."""
+        from .replay import view_poses, view_tables
+        torch = self.torch
+        self._begin()
+        F, M = int(reps.shape[0]), int(reps.shape[1])
+        if F != self.F or reps.dim() != 3 or int(reps.shape[2]) != 2:
+            raise ValueError("reps must be [F, M, 2]")
+        tables = self._view_tables = getattr(self, "_view_tables", None) or {}
+        if int(n) not in tables:
+            tables[int(n)] = tuple(torch.from_numpy(t).to(self.dev) for t in view_tables(int(n)))
+        ct, st = tables[int(n)]
+        poses = view_poses(reps, self.grid.scale, self.grid.off_x, self.grid.off_y)
+        poses = torch.where((reps >= 0).all(dim=-1, keepdim=True), poses, torch.full_like(poses, float("nan"))).reshape(F * M, 3).contiguous()
+        maps = self._best_maps().reshape(F, 1).expand(F, M).reshape(F * M).contiguous()
+        self.ctx.stream_order(self._torch_stream(), 1)
+        out = self.grid.view_gain(poses, ct, st, max_range=self.max_range if max_range is None else max_range, skip=skip,
+                                  grid_of_batch=maps, return_seen=return_seen)
+        self._held = (reps, poses, maps, ct, st) + (out if return_seen else (out,))
+        if return_seen:
+            return out[0].reshape(F, M, -1), out[1].reshape(F, M, self.grid.xw, -1)
+        return out.reshape(F, M, -1)
+
+    def next_goals(self, foot=0, through_unknown=False, radius=2, min_unknown=13, min_clear2=0, cap=64, min_size=5, max_clusters=256,
+                   by="travel", bias=100, n=360, max_range=None, skip=1):
         """Every filter's next exploration goal by travel cost: the frontiers of its best particle's map
         (:meth:`frontiers`), their representatives passed device to device as the goals of :meth:`travel`, and of the
         kept clusters the one with the smallest cost >= 0, ties to the lowest label - chosen with torch ops.  Returns
         (cell int32 [F, 2], cost int32 [F], status int32 [F]) on the device; cell (-1, -1) and cost -1 where no kept
-        cluster is reachable.  No synchronise."""
+        cluster is reachable.  No synchronise.
+        ``by="gain"``, next-best-view: the representatives also go device to device into :meth:`view_gain` (``n``,
+        ``max_range``, ``skip``), and of the kept clusters with cost c >= 0 and u > 0 unknown cells in view the one with
+        the largest u / (c + ``bias``) wins, compared exactly in int64 (u_k * (c_l + bias) > u_l * (c_k + bias)), ties to
+        the lower cost, then to the lower label (:func:`gain_goal`).  Returns (cell, cost, status, unknown int32 [F]);
+        cell (-1, -1), cost -1 and unknown -1 where there is no candidate.  ``bias`` (default 100) is in travel-cost
+        units; it is a starting value, not a tuned one."""
+        if by not in ("travel", "gain"):
+            raise ValueError("by must be 'travel' or 'gain'")
         torch = self.torch
         table = self.frontiers(radius=radius, min_unknown=min_unknown, min_clear2=min_clear2, cap=cap, min_size=min_size,
                                max_clusters=max_clusters)[1]
@@ -257,6 +294,8 @@ class DeviceGridSLAM:
         self.ctx.stream_order(self._torch_stream(), 1)
         out = self.grid.travel(src, maps, goals=reps, foot=foot, through_unknown=through_unknown, min_clear2=min_clear2, cap=cap,
                                cost=False)
+        if by == "gain":
+            return self._gain_goals(reps, out, held + (maps, src), int(bias), n, max_range, skip)
         self.ctx.stream_order(self._torch_stream(), 0)
         gc = out["goal_cost"].to(torch.int64)
         key = torch.where(gc >= 0, gc, torch.full_like(gc, 2 ** 62))
@@ -267,6 +306,40 @@ class DeviceGridSLAM:
         costs = torch.where(ok, out["goal_cost"][rows, k], torch.full((self.F,), -1, dtype=torch.int32, device=self.dev))
         self._held = held + (maps, src, reps) + tuple(out.values())
         return cell, costs, out["status"]
+
+    def _gain_goals(self, reps, travel, held, bias, n, max_range, skip):
+        """The rule of ``next_goals(by="gain")`` on the device: a knock-out over the clusters in label order, so the left
+        of every pair has the lower label and keeps a full tie."""
+        torch = self.torch
+        if bias < 1:
+            raise ValueError("bias must be >= 1")
+        counts = self.view_gain(reps, n=n, max_range=max_range, skip=skip)
+        held = held + self._held + tuple(travel.values())
+        self.ctx.stream_order(self._torch_stream(), 0)           # torch reads the costs and the counts after the kernels
+        F, M = int(reps.shape[0]), int(reps.shape[1])
+        width = 1
+        while width < max(M, 1):
+            width *= 2
+        c = torch.full((F, width), -1, dtype=torch.int64, device=self.dev)
+        u = torch.zeros((F, width), dtype=torch.int64, device=self.dev)
+        c[:, :M] = travel["goal_cost"].to(torch.int64)
+        u[:, :M] = counts[:, :, _abi.VIEW_UNKNOWN].to(torch.int64)
+        ok = (c >= 0) & (u > 0)                       # (a row beyond the kept clusters is (-1, -1): no cost, no view)
+        k = torch.arange(width, dtype=torch.int64, device=self.dev).reshape(1, -1).expand(F, width)
+        while width > 1:
+            cl, cr, ul, ur, okl, okr, kl, kr = c[:, 0::2], c[:, 1::2], u[:, 0::2], u[:, 1::2], ok[:, 0::2], ok[:, 1::2], k[:, 0::2], k[:, 1::2]
+            lhs, rhs = ur * (cl + bias), ul * (cr + bias)
+            right = okr & (~okl | (lhs > rhs) | ((lhs == rhs) & (cr < cl)))
+            c, u, ok, k = torch.where(right, cr, cl), torch.where(right, ur, ul), okl | okr, torch.where(right, kr, kl)
+            width //= 2
+        rows = torch.arange(F, device=self.dev)
+        ok, k = ok[:, 0], k[:, 0].clamp(max=max(M - 1, 0))
+        neg = torch.full((F,), -1, dtype=torch.int32, device=self.dev)
+        cell = torch.where(ok.reshape(-1, 1), reps[rows, k], torch.full((F, 2), -1, dtype=torch.int32, device=self.dev))
+        costs = torch.where(ok, c[:, 0].to(torch.int32), neg)
+        unknown = torch.where(ok, u[:, 0].to(torch.int32), neg)
+        self._held = held + (counts,)
+        return cell, costs, travel["status"], unknown
 
     @property
     def trajectory(self):
@@ -335,6 +408,19 @@ class GridSLAM:
         count, clusters, sums = grid_frontiers_host(self.grid, [max(self.best, 0)], radius=radius, min_unknown=min_unknown, min_clear2=c2,
                                                     cap=cap, min_size=min_size, max_clusters=max_clusters)
         return frontier_dict(count[0], clusters[0], sums[0], self.grid.scale, self.grid.off_x, self.grid.off_y)
+
+    def view_gain(self, pose_or_poses, angle_min, angle_max, n, max_range=30.0, skip=1, return_seen=False):
+        """:meth:`Mapping.view_gain` on the best particle's map."""
+        from .replay import grid_view_gain_host
+        p = np.asarray(pose_or_poses, dtype=np.float64)
+        one = p.ndim == 1
+        p = p.reshape(-1, 3)
+        ct, st = _abi.trig_tables(angle_min, angle_max, int(n))
+        out = grid_view_gain_host(self.grid, p, ct, st, max_range=max_range, skip=skip, grid_of_batch=[max(self.best, 0)] * p.shape[0],
+                                  return_seen=return_seen)
+        if not one:
+            return out
+        return (out[0][0], out[1][0]) if return_seen else out[0]
 
     def next_goal(self, by="distance", **kw):
         """The nearest-frontier rule from the best particle's pose on its map, in a straight line or with ``by="travel"``

@@ -234,12 +234,19 @@ class Mapping:
         exploration is complete.  ``by="travel"``: the representative of the kept cluster with the smallest travel cost
         >= 0 from the pose's cell (:meth:`travel_field`), ties to the lowest label; None when no kept cluster is
         reachable - exploration is complete for this robot, even if frontiers exist behind walls.  ``foot``,
-        ``through_unknown`` and ``clearance`` are taken from ``kw``; the clearance is shared with the frontier call."""
+        ``through_unknown`` and ``clearance`` are taken from ``kw``; the clearance is shared with the frontier call.
+        ``by="gain"``, next-best-view: among the kept clusters with travel cost c >= 0 and u > 0 unknown cells in view
+        from their representative's cell centre (heading 0, the ``n`` beams (default 360) of :func:`view_tables` over the
+        full circle to ``max_range`` (default 30 m)), the one with the largest u / (c + ``bias``), compared exactly as
+        integers (:func:`gain_goal`), ties to the lower cost, then to the lower label; None when there is none.
+        ``bias`` (default 100) is in travel-cost units; it is a starting value, not a tuned one."""
         from .replay import nearest_goal, travel_goal
         if by == "distance":
             return nearest_goal(self.frontiers(**kw), pose)
+        if by == "gain":
+            return self._gain_goal(pose, **kw)
         if by != "travel":
-            raise ValueError("by must be 'distance' or 'travel'")
+            raise ValueError("by must be 'distance', 'travel' or 'gain'")
         foot, through = kw.pop("foot", 0), kw.pop("through_unknown", False)
         fr = self.frontiers(**kw)
         if fr["point"].shape[0] == 0:
@@ -247,6 +254,38 @@ class Mapping:
         got = self._travel(pose, kw.get("clearance", 0.0), foot, through, kw.get("cap", 64), goals=fr["cell"], cost=False)
         k = travel_goal(fr, got["goal_cost"][0])
         return None if k is None else fr["point"][k].copy()
+
+    def _gain_goal(self, pose, bias=100, n=360, max_range=30.0, skip=1, **kw):
+        from types import SimpleNamespace
+        from .replay import gain_goal, grid_view_gain_host, view_poses, view_tables
+        foot, through = kw.pop("foot", 0), kw.pop("through_unknown", False)
+        fr = self.frontiers(**kw)
+        if fr["point"].shape[0] == 0:
+            return None
+        got = self._travel(pose, kw.get("clearance", 0.0), foot, through, kw.get("cap", 64), goals=fr["cell"], cost=False)
+        views = view_poses(fr["cell"], self.index_scale, self.index_offset_x, self.index_offset_y)
+        grid = SimpleNamespace(_ctx=self._ctx, _h=self._grid, G=1, xw=self.xw, yw=self.yw)
+        counts = grid_view_gain_host(grid, views, *view_tables(n), max_range=max_range, skip=skip)
+        k = gain_goal(fr, got["goal_cost"][0], counts[:, _abi.VIEW_UNKNOWN], bias)
+        return None if k is None else fr["point"][k].copy()
+
+    def view_gain(self, pose_or_poses, angle_min, angle_max, n, max_range=30.0, skip=1, return_seen=False):
+        """What a scan from a pose would reveal of this map (``slam_grid_view_gain``): ``n`` beams of
+        ``linspace(angle_min, angle_max, n)`` cast to ``max_range`` as :meth:`raycast` casts them, and the SET of map cells
+        they see - path indices ``skip`` up to and including each beam's first occupied cell, or to its end - counted:
+        int32 [4] = (unknown, free, occupied cells, beams that found nothing) (``_abi.VIEW_*``), a row of -1 for a pose
+        the index rule rejects.  poses [B, 3] give [B, 4].  With ``return_seen`` also the set as bit words uint32
+        [xw, ceil(yw / 32)] ([B, ...]): bit ``y & 31`` of word ``y >> 5`` in row x."""
+        from types import SimpleNamespace
+        from .replay import grid_view_gain_host
+        p = np.asarray(pose_or_poses, dtype=np.float64)
+        one = p.ndim == 1
+        ct, st = _abi.trig_tables(angle_min, angle_max, int(n))
+        grid = SimpleNamespace(_ctx=self._ctx, _h=self._grid, G=1, xw=self.xw, yw=self.yw)
+        out = grid_view_gain_host(grid, p.reshape(-1, 3), ct, st, max_range=max_range, skip=skip, return_seen=return_seen)
+        if not one:
+            return out
+        return (out[0][0], out[1][0]) if return_seen else out[0]
 
     def pose_cell(self, pose):
         """The cell (x, y) of a pose by the map's own rule, ``int(scale * (v + off))``, truncated toward zero."""

@@ -143,6 +143,43 @@ def grid_score_host(grid, ranges, poses, cos_t, sin_t, skip=1, grid_of_batch=Non
     return (counts, cls) if return_classes else counts
 
 
+def grid_view_gain_host(grid, poses, cos_t, sin_t, max_range=30.0, skip=1, grid_of_batch=None, return_seen=False):
+    """What a scan from each pose would reveal (``slam_grid_view_gain``): the beams of every pose [B, 3] are cast to
+    ``max_range`` as :func:`grid_raycast_host` casts them, and the SET of in-bounds cells they see - up to and
+    including each beam's first occupied cell, or to its end - is counted against the map.  ``grid_of_batch`` None:
+    every view reads map 0.  Returns counts int32 [B, 4] = (unknown, free, occupied cells of the set, beams that found
+    nothing) (``_abi.VIEW_*``; a row of -1 for a pose the index rule rejects) and with ``return_seen`` also the set as
+    bit words uint32 [B, xw, ceil(yw / 32)], bit ``y & 31`` of word ``y >> 5`` in row x."""
+    p, gob = _batch_args(poses, grid_of_batch)
+    ct, st = _tables(cos_t, sin_t)
+    B, n = p.shape[0], ct.shape[0]
+    counts = np.empty((B, _abi.VIEW_COUNTS), dtype=np.int32)
+    seen = np.empty((B, grid.xw, (grid.yw + 31) // 32), dtype=np.uint32) if return_seen else None
+    _abi.check(_abi.lib().slam_grid_view_gain(grid._ctx.handle, grid._h, _abi.ptr(p), B, _abi.ptr(gob), _abi.ptr(ct), _abi.ptr(st),
+                                              n, float(max_range), int(skip), _abi.ptr(counts), _abi.ptr(seen)))
+    return (counts, seen) if return_seen else counts
+
+
+def view_poses(cells, scale, off_x, off_y):
+    """Poses [..., 3] at the CENTRES of cells [..., 2], heading 0, on a grid of index rule (scale, off_x, off_y): x =
+    (i + 0.5) / scale - off_x, y alike (:func:`frontier_points`).  A torch tensor gives a float64 tensor on its device
+    (no synchronise); anything else a NumPy array."""
+    if type(cells).__module__.split(".")[0] == "torch":
+        import torch
+        c = cells.to(torch.float64)
+        return torch.stack([(c[..., 0] + 0.5) / float(scale) - float(off_x), (c[..., 1] + 0.5) / float(scale) - float(off_y),
+                            torch.zeros_like(c[..., 0])], dim=-1).contiguous()
+    pts = frontier_points(cells, scale, off_x, off_y)
+    return np.ascontiguousarray(np.concatenate([pts, np.zeros(pts.shape[:-1] + (1,))], axis=-1))
+
+
+def view_tables(n):
+    """(cos_t, sin_t) float64 [n] of ``n`` beams over the full circle, theta_i = -pi + i * 2 pi / n
+    (:func:`locate_rotations`): the beams a goal's view is counted with."""
+    rot = locate_rotations(n)[1]
+    return np.ascontiguousarray(rot[:, 0]), np.ascontiguousarray(rot[:, 1])
+
+
 def _window_ok(K, nx, ny):
     """The window sizes ``slam_grid_match`` takes (a cost volume is only allocated for those; the library rejects the rest)."""
     return K >= 1 and nx >= 0 and ny >= 0 and K * (2 * int(nx) + 1) * (2 * int(ny) + 1) <= 1 << 24
@@ -344,6 +381,32 @@ def travel_goal(fr, goal_cost):
     return int(np.argmin(np.where(c >= 0, c, np.iinfo(np.int64).max)))
 
 
+def gain_goal(fr, goal_cost, unknown, bias=100):
+    """Index of the kept cluster of ``fr`` (:func:`frontier_dict`) that reveals the most unknown cells per unit of
+    travel, or None.  Candidates are the clusters with travel cost c >= 0 in ``goal_cost`` [K] and u > 0 in
+    ``unknown`` [K] (the ``VIEW_UNKNOWN`` count of a view from the cluster's representative); k beats l iff
+    u_k * (c_l + bias) > u_l * (c_k + bias), in exact Python integers; ties go to the lower cost, then to the lower
+    label (the rows are in label order).  ``bias`` is in travel-cost units (10 per straight cell step); its default of
+    100 is a starting value, not a tuned one."""
+    K = fr["point"].shape[0]
+    c = [int(v) for v in np.asarray(goal_cost).reshape(-1)[:K]]
+    u = [int(v) for v in np.asarray(unknown).reshape(-1)[:K]]
+    bias = int(bias)
+    if bias < 1:
+        raise ValueError("bias must be >= 1")
+    best = None
+    for k in range(min(K, len(c), len(u))):
+        if c[k] < 0 or u[k] <= 0:
+            continue
+        if best is None:
+            best = k
+            continue
+        lhs, rhs = u[k] * (c[best] + bias), u[best] * (c[k] + bias)
+        if lhs > rhs or (lhs == rhs and c[k] < c[best]):
+            best = k
+    return best
+
+
 def grid_copy_maps_host(grid, src, first=0):
     """``slam_grid_copy_maps`` on a NumPy array: map ``first + k`` of ``grid`` becomes a copy of map ``src[k]``.  Returns
     int32 [count]: 1 copied, 0 kept (its own map, or no map).  A source that is itself a destination raises."""
@@ -485,6 +548,23 @@ class DeviceGrid:
                                                        _abi.ptr(poses), B, _abi.ptr(grid_of_batch), _abi.ptr(cos_t),
                                                        _abi.ptr(sin_t), n, int(skip), _abi.ptr(counts_out), _abi.ptr(class_out)))
         return counts_out if class_out is None else (counts_out, class_out)
+
+    def view_gain(self, poses, cos_t, sin_t, max_range=30.0, skip=1, grid_of_batch=None, counts_out=None, seen_out=None,
+                  return_seen=False):
+        """``slam_grid_view_gain_dev`` on torch device tensors: poses float64 [B, 3], cos_t / sin_t float64 [n],
+        grid_of_batch int32 [B] or None (every view reads map 0).  Writes counts int32 [B, 4] (``_abi.VIEW_*``; and the
+        seen set as int32 bit words [B, xw, ceil(yw / 32)]) into the tensors given or into fresh ones; enqueued on the
+        context's stream, no synchronise."""
+        import torch
+        B, n = int(poses.shape[0]), int(cos_t.shape[0])
+        if counts_out is None:
+            counts_out = torch.empty((B, _abi.VIEW_COUNTS), dtype=torch.int32, device=poses.device)
+        if seen_out is None and return_seen:
+            seen_out = torch.empty((B, self.xw, (self.yw + 31) // 32), dtype=torch.int32, device=poses.device)
+        _abi.check(_abi.lib().slam_grid_view_gain_dev(self._ctx.handle, self._h, _abi.ptr(poses), B, _abi.ptr(grid_of_batch),
+                                                      _abi.ptr(cos_t), _abi.ptr(sin_t), n, float(max_range), int(skip),
+                                                      _abi.ptr(counts_out), _abi.ptr(seen_out)))
+        return counts_out if seen_out is None else (counts_out, seen_out)
 
     def distance_field(self, cap=64, out=None):
         """``slam_grid_distance_field_dev``: the capped squared cell distance to the nearest occupied cell of every

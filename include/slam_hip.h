@@ -147,7 +147,8 @@ int slam_check_status(slam_ctx *ctx);
  *   does not fit is SLAM_ERR_INVALID.  No result depends on it.
  * "travel_ws_mb": MiB that the costs, the traversable bits and the tile keys of slam_grid_travel may take in the
  *   context's workspace, in (0, 2^20], fractions allowed; default 256.  The queries of a call are cut into chunks that
- *   fit; a call whose single query does not fit is SLAM_ERR_INVALID.  No result depends on it. */
+ *   fit; a call whose single query does not fit is SLAM_ERR_INVALID.  No result depends on it.
+ * "gain_lds", "gain_ws_mb": the engine and the workspace of slam_grid_view_gain (see there). */
 int slam_set_option(slam_ctx *ctx, const char *name, double value);
 /* Per-kernel-family timing with HIP events on the context's stream (bench.py roofline).
  * on: 0 = off, 1 = every family, 2 * mask = only the families in mask (bit SLAM_K_*): events on a
@@ -391,6 +392,41 @@ int slam_grid_scan_score(slam_ctx *ctx, slam_grid *grid, const float *ranges, in
 int slam_grid_scan_score_dev(slam_ctx *ctx, slam_grid *grid, const float *ranges, int shared, const double *poses, int B,
                              const int32_t *grid_of_batch, const double *cos_t, const double *sin_t, int n, int skip,
                              int32_t *counts_out, int8_t *class_out);
+
+/* ---- view gain: the cells a scan from a pose would reveal ---------------------------------- */
+/* What a robot would SEE from a pose, as a set of cells; the reference has no counterpart.  View b is poses[b] and
+ * n beams formed exactly as slam_grid_raycast forms them (every range max_range, finite and > 0; the origin at the
+ * pose; both cells through int(scale * (v + off))).  grid_of_batch as for the ray cast: NULL = every view reads
+ * map 0.  For beam i with path = bresenham(start, end).path and (j, Lp) = trace(map, start, end, skip) the beam sees
+ * the path indices skip <= k <= j when j >= 0 (the found cell included) and skip <= k < Lp when j == -1; a path cell
+ * outside the map is seen by nobody.  S(b) is the set of in-bounds cells seen by any beam of the view. */
+#define SLAM_VIEW_UNKNOWN 0   /* |S| with pmap == 50                                               */
+#define SLAM_VIEW_FREE 1      /* |S| with pmap == 0                                                */
+#define SLAM_VIEW_OCCUPIED 2  /* |S| with pmap == 100: the distinct first-hit cells                */
+#define SLAM_VIEW_OPEN 3      /* beams with a valid end cell and j == -1                           */
+#define SLAM_VIEW_COUNTS 4
+/* counts_out [B][SLAM_VIEW_COUNTS] int32, pmap as slam_grid_finalize_dev would give it now.  seen_out (nullable)
+ * uint32 [B][xw][ceil(yw / 32)]: bit y & 31 of word y >> 5 in row x is set iff (x, y) is in S(b); bits at y >= yw
+ * are 0.  A beam whose end cell the index rule rejects (NaN, beyond 2^20) is skipped and not counted as OPEN.  A view
+ * with a non-finite pose or a start index beyond 2^20 gets a row of -1 and zero seen words; so does, in the device
+ * form, a view whose map entry is outside [0, G) (the host form rejects such an entry).  Neither raises the sticky
+ * status.  Every view answers the same alone, in any batch, in any order, under any chunking and under either engine
+ * (integer counts of a set).  The call sees every update enqueued before it on the context's stream, changes
+ * nothing in the grid, keeps nothing between calls and leaves the sticky status untouched.
+ * 1 <= n <= 4096, B >= 1, B * n < 2^31, 0 <= skip <= 2^20; with seen_out B * xw * ceil(yw / 32) < 2^31.
+ * Context options: "gain_lds" - where a view's bit window lies: 1 = in LDS wherever the window of its box (the
+ *   bounding box of its start and end cells, clipped to the map, whole words in y) fits 64 KiB, else in the
+ *   workspace; 0 = always in the workspace (global atomics); -1 = automatic (default).  Same bits either way.
+ *   "gain_ws_mb" - MiB the workspace windows may take, in (0, 2^20], fractions allowed; default 256.  One window slot
+ *   holds a whole map's words; the views are taken over the slots that fit and no result depends on the cut; a call
+ *   that may need a slot and whose single slot does not fit is SLAM_ERR_INVALID.
+ * Under slam_timing_* the pass that packs the class bits counts as SLAM_K_FINALIZE, the rest as SLAM_K_GRID. */
+int slam_grid_view_gain(slam_ctx *ctx, slam_grid *grid, const double *poses, int B, const int32_t *grid_of_batch,
+                        const double *cos_t, const double *sin_t, int n, float max_range, int skip, int32_t *counts_out,
+                        uint32_t *seen_out);
+int slam_grid_view_gain_dev(slam_ctx *ctx, slam_grid *grid, const double *poses, int B, const int32_t *grid_of_batch,
+                            const double *cos_t, const double *sin_t, int n, float max_range, int skip, int32_t *counts_out,
+                            uint32_t *seen_out);
 
 /* ---- distance field of the map and the window scan-to-map matcher --------------------------- */
 /* Where a scan fits a map best; the reference has no counterpart.  Both calls see every update enqueued before
