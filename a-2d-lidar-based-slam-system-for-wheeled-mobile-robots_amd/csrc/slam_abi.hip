@@ -391,6 +391,12 @@ int grid_on_main(slam_ctx *c)
     return join_from_grid(c);
 }
 
+// entry points that take NO map and enqueue on the MAIN stream call this first: their device arguments may be results of
+// the pipelined stages (poses_out, pmap_dev) or buffers those stages still read.  The map stream waits for the pose
+// stream, so joining it joins both; no map work is marked (the map stream need not fork again).  Pipeline off, no chunked
+// particle batch in flight: two flag tests.
+int streams_on_main(slam_ctx *c) { return join_from_grid(c); }
+
 int status_to_code(int st)
 {
     if (st & kStatusGuard) return fail(SLAM_ERR_HIP, "internal: a kernel wrote past its LDS regions (SLAM_LDS_GUARD build)");
@@ -1006,6 +1012,7 @@ int slam_scan_to_points_dev(slam_ctx *c, const float *ranges, const double *cos_
                             int clip_inf, int dtype, void *pts_out)
 {
     TRY(use(c));
+    TRY(streams_on_main(c));
     TRY(check_scan_to_points(__func__, ranges, cos_t, sin_t, B, n, dtype, pts_out));
     Timed t(c, SLAM_K_POINTS);
     HIPCHK(launch_scan_to_points(ranges, cos_t, sin_t, (long)B * n, n, clip_inf, dtype, pts_out, c->stream));
@@ -1040,6 +1047,7 @@ int slam_nn_dev(slam_ctx *c, const void *src, const void *tar, int B, int n_src,
                 int32_t *idx)
 {
     TRY(use(c));
+    TRY(streams_on_main(c));
     TRY(check_nn(__func__, src, tar, B, n_src, n_tar, dtype, dist, idx));
     Timed t(c, SLAM_K_NN);
     HIPCHK(launch_nn(src, tar, B, n_src, n_tar, dtype, dist, idx, c->stream));
@@ -1071,6 +1079,7 @@ static int check_kabsch2d(const char *fn, const double *src, const double *tar, 
 int slam_kabsch2d_dev(slam_ctx *c, const double *src, const double *tar, int B, int n, double *T_out)
 {
     TRY(use(c));
+    TRY(streams_on_main(c));
     TRY(check_kabsch2d(__func__, src, tar, B, n, T_out));
     Timed t(c, SLAM_K_KABSCH);
     HIPCHK(launch_kabsch(src, tar, B, n, T_out, c->stream));
@@ -1106,6 +1115,7 @@ int slam_icp_batch_dev(slam_ctx *c, const void *tar, const void *src, int B, int
                        int32_t *iters_out, double *mean_err_out)
 {
     TRY(use(c));
+    TRY(streams_on_main(c));
     TRY(check_icp_batch(__func__, tar, src, B, n_tar, n_src, dtype, max_iter, T_out));
     IcpArgs a;
     a.tar = tar; a.src = src; a.prior = prior;
@@ -1149,6 +1159,7 @@ static int check_pose_compose(const char *fn, const double *T, const double *pos
 int slam_pose_compose_dev(slam_ctx *c, const double *T, const double *pose0, int L, int n, double *poses_out)
 {
     TRY(use(c));
+    TRY(streams_on_main(c));
     TRY(check_pose_compose(__func__, T, pose0, L, n, poses_out));
     Timed t(c, SLAM_K_COMPOSE);
     HIPCHK(launch_pose_compose(T, pose0, L, n, poses_out, c->stream));
@@ -2136,6 +2147,7 @@ int slam_mcl_resample_dev(slam_ctx *c, const double *poses, int32_t *acc, const 
                           int32_t *info_out)
 {
     TRY(use(c));
+    TRY(streams_on_main(c));
     TRY(check_mcl_resample(__func__, poses, acc, table, T, shift, u0, ess_frac, F, P, poses_out, est_out, info_out));
     const size_t FP = (size_t)F * P, FB = (size_t)F * mcl_scan_blocks(P);
     MclResampleArgs a;
@@ -2230,6 +2242,7 @@ int slam_mcl_settle_dev(slam_ctx *c, const int32_t *ancestors, const double *pos
                         double *poses_out, int32_t *map_src_out, int32_t *moved_out)
 {
     TRY(use(c));
+    TRY(streams_on_main(c));
     TRY(check_mcl_settle(__func__, ancestors, poses_src, F, P, map0, settled_out, poses_out));
     MclSettleArgs a;
     a.ancestors = ancestors; a.poses_src = poses_src; a.F = F; a.P = P; a.map0 = map0;
@@ -2388,6 +2401,7 @@ int slam_replay_dev(slam_ctx *c, const float *ranges, const double *cos_t, const
     (void)pts_ws;   // kept in the ABI; the point buffers are no longer materialised
     const long pairs = (long)L * (n_scan - 1);
     const bool piped = c->pipeline && grid;     // three stages on three streams: ICP | compose | map
+    if (!piped) TRY(streams_on_main(c));        // everything on the main stream: pose0 may be a row of a piped replay's poses_out
     double *T = T_out;
     if (!T) {
         if (piped) {                            // two alternating buffers: compose of replay k reads T while ICP k+1 runs
@@ -2657,6 +2671,7 @@ int slam_map_obstacles_dev(slam_ctx *c, const int8_t *map, int width, int height
                            double origin_x, double origin_y, double *ox, double *oy, int cap, int *count_dev)
 {
     TRY(use(c));
+    TRY(streams_on_main(c));
     TRY(check_map_obstacles(__func__, map, width, height, ox, oy, cap, count_dev));
     HIPCHK(launch_map_obstacles(map, width, height, wire_layout, resolution, origin_x, origin_y, ox, oy, cap, count_dev, c->stream));
     return SLAM_OK;
@@ -2675,6 +2690,7 @@ int slam_virtual_scan_dev(slam_ctx *c, const double *ox, const double *oy, int K
                           double angle_min, double angle_increment, int n, double *ranges_out)
 {
     TRY(use(c));
+    TRY(streams_on_main(c));
     REQUIRE(ranges_out, "null pointer");
     TRY(check_virtual_scan(__func__, ox, oy, K, poses, B, angle_min, angle_increment, n));
     HIPCHK(launch_virtual_scan(ox, oy, K, poses, B, angle_min, angle_increment, n, ranges_out, c->stream));
@@ -2707,6 +2723,7 @@ int slam_scan_to_points_f64_dev(slam_ctx *c, const double *ranges, const double 
                                 double *pts_out)
 {
     TRY(use(c));
+    TRY(streams_on_main(c));
     TRY(check_scan_to_points_f64(__func__, ranges, cos_t, sin_t, B, n, pts_out));
     HIPCHK(launch_ranges64_to_points(ranges, cos_t, sin_t, B, n, pts_out, c->stream));
     return SLAM_OK;
@@ -2740,6 +2757,7 @@ int slam_map_observation_dev(slam_ctx *c, const double *ox, const double *oy, in
                              double *T_out, int32_t *iters_out)
 {
     TRY(use(c));
+    TRY(streams_on_main(c));
     REQUIRE(vranges_ws && vpts_ws, "null pointer");
     TRY(check_map_observation(__func__, ox, oy, K, poses, src, B, n, cos_t, sin_t, angle_min, angle_increment, max_iter, T_out));
     TRY(slam_virtual_scan_dev(c, ox, oy, K, poses, B, angle_min, angle_increment, n, vranges_ws));
@@ -2786,6 +2804,7 @@ int slam_dwa_dev(slam_ctx *c, const double *states, const double *goals, const d
                  int32_t *counts_out, double *costs_out, int s_cap, double *traj_out)
 {
     TRY(use(c));
+    TRY(streams_on_main(c));
     const DwaOut o{u_out, cost_out, index_out, counts_out, costs_out, s_cap, traj_out};
     DwaArgs a;
     TRY(check_dwa_obstacles(__func__, states, goals, obstacles, M, config, B, o, a));
@@ -2843,6 +2862,7 @@ int slam_dwa_scans_dev(slam_ctx *c, const double *states, const double *goals, c
                        int s_cap, double *traj_out)
 {
     TRY(use(c));
+    TRY(streams_on_main(c));
     const DwaOut o{u_out, cost_out, index_out, counts_out, costs_out, s_cap, traj_out};
     DwaArgs a;
     TRY(check_dwa_scans(__func__, states, goals, ranges, n, cos_t, sin_t, threshold, config, B, o, a));
@@ -2972,6 +2992,7 @@ int slam_landmarks_dev(slam_ctx *c, const float *ranges, const double *cos_t, co
                        int32_t *ids_out, double *means_out, double *z_out, int32_t *labels_out)
 {
     TRY(use(c));
+    TRY(streams_on_main(c));
     TRY(check_landmarks(__func__, ranges, cos_t, sin_t, S, n, lm_cap, count_out, overflow_out, ids_out, means_out, z_out));
     LandmarkArgs a{ranges, cos_t, sin_t, S, n, range_threshold, radius_max_th, lm_cap, count_out, overflow_out, ids_out,
                    means_out, z_out, labels_out, c->status};
@@ -3013,6 +3034,7 @@ int slam_ekf_lm_dev(slam_ctx *c, const double *x0, const double *u, const int32_
                     int32_t *nlm_out, int32_t *status_out)
 {
     TRY(use(c));
+    TRY(streams_on_main(c));
     TRY(check_ekf_lm(__func__, u, step_counts, z_off, z, nz, B, steps, max_lm, x_out, P_out, nlm_out, status_out));
     EkfArgs a{};
     a.B = B; a.steps_max = steps; a.max_lm = max_lm;
@@ -3065,6 +3087,7 @@ int slam_node_replay_dev(slam_ctx *c, const float *ranges, const double *cos_t, 
                          double *T_out, int32_t *iters_out, int32_t *status_out)
 {
     TRY(use(c));
+    TRY(streams_on_main(c));      // (pose0 and the scans are read before the map is touched)
     TRY(check_node_replay(__func__, ranges, cos_t, sin_t, L, n_scan, n, dtype, max_iter, lm_cap, max_lm, pose0, kept_out,
                           kept_count_out, xest_out, nlm_out, x_final_out, P_final_out, status_out));
     const size_t S = (size_t)L * n_scan, pairs = (size_t)L * (n_scan - 1), slots = S * lm_cap;
@@ -3164,6 +3187,7 @@ int slam_loc_replay_dev(slam_ctx *c, const float *ranges, int S, int n_scan, int
                         int32_t *iters_obs_out, double *T_odom_out, double *tar_pts_out)
 {
     TRY(use(c));
+    TRY(streams_on_main(c));
     TRY(check_loc_replay(__func__, ranges, S, n_scan, n, stream_of_traj, ox, oy, obs_off, M, K, L, cos_t, sin_t, angle_min,
                          angle_increment, max_iter, xest_out, xodom_out, P_final_out, status_out));
     const size_t Lz = (size_t)L, pairs = (size_t)S * (2 * (size_t)n_scan - 1);
