@@ -35,8 +35,8 @@ zjwzcx/A-2D-LiDAR-based-SLAM-System-for-Wheeled-Mobile-Robots:
     global_planner  find_path(...).start_find() / GlobalPlanner (course_agv_nav A*), batched as
                DeviceAStar / astar_host
 
-plus the batched forms used by bench.py (``replay``) and the multi-GPU sharding helper
-(``dist``).  Importing the package never computes anything; every operator raises if
+plus the batched forms used by bench.py (``replay``), the maps and their queries (``grid``: DeviceGrid and every
+grid_*_host) and the multi-GPU sharding helper (``dist``).  Importing the package never computes anything; every operator raises if
 libslamhip.so or the GPU is missing (there is no CPU implementation in the product).
 """
 from . import _abi, dist, param, synthetic
@@ -58,12 +58,13 @@ from .loc_replay import DeviceLocalizationReplay, loc_replay_host
 from .mapping import Mapping
 from .mcl import MCL, MCL_DEAD, DeviceMCL, mcl_resample_host, mcl_settle_host, mcl_weigh_host, mcl_weight_table
 from .node_replay import DeviceNodeReplay, ekf_lm_host, landmarks_host, node_replay_host
-from .replay import DeviceGrid, DeviceReplay, grid_raycast_host, grid_score_host, icp_batch_host, particles_host, prior_matrices, replay_host
-from .replay import grid_distance_field_host, grid_match_host, match_pose, match_rotations
-from .replay import grid_copy_maps_host, grid_update_particles_host
-from .replay import grid_locate_host, locate_pose, locate_rotations
-from .replay import frontier_points, grid_frontiers_host, grid_travel_host
-from .replay import gain_goal, grid_view_gain_host, view_poses, view_tables
+from .grid import DeviceGrid, grid_raycast_host, grid_score_host
+from .grid import grid_distance_field_host, grid_match_host, match_pose, match_rotations
+from .grid import grid_copy_maps_host, grid_update_particles_host
+from .grid import grid_locate_host, locate_pose, locate_rotations
+from .grid import frontier_points, grid_frontiers_host, grid_travel_host
+from .grid import gain_goal, grid_view_gain_host, view_poses, view_tables
+from .replay import DeviceReplay, icp_batch_host, particles_host, prior_matrices, replay_host
 from .grid_slam import DeviceGridSLAM, GridSLAM
 from .slam_ekf import SLAM_EKF
 from .synthetic import LaserScan

@@ -40,108 +40,46 @@ class LibraryMissing(ImportError):
 _lib = None
 _lib_lock = threading.Lock()
 
-_vp, _i, _d = C.c_void_p, C.c_int, C.c_double
-_SIGS = {
-    "slam_abi_version": ([], _i),
-    "slam_last_error": ([], C.c_char_p),
-    "slam_create": ([_i, _vp, C.POINTER(_vp)], _i),
-    "slam_destroy": ([_vp], _i),
-    "slam_synchronize": ([_vp], _i),
-    "slam_stream_order": ([_vp, _vp, _i], _i),
-    "slam_check_status": ([_vp], _i),
-    "slam_set_option": ([_vp, C.c_char_p, _d], _i),
-    "slam_timing_enable": ([_vp, _i], _i),
-    "slam_timing_read": ([_vp, _vp, _vp], _i),
-    "slam_plan_win": ([_i] * 16 + [_vp], _i),
-    "slam_plan_icp": ([_i] * 10 + [_vp], _i),
-    "slam_plan_win_phases": ([_vp, _vp, _i, _i, _i, _i, _i, _i, _vp], _i),
-    "slam_plan_query": ([C.c_char_p, _i, _i, _i, _i, C.POINTER(C.c_int64)], _i),
-    "slam_scan_to_points": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
-    "slam_scan_to_points_dev": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
-    "slam_nn": ([_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp], _i),
-    "slam_nn_dev": ([_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp], _i),
-    "slam_kabsch2d": ([_vp, _vp, _vp, _i, _i, _vp], _i),
-    "slam_kabsch2d_dev": ([_vp, _vp, _vp, _i, _i, _vp], _i),
-    "slam_icp_batch": ([_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _d, _vp, _vp, _vp], _i),
-    "slam_icp_batch_dev": ([_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _d, _vp, _vp, _vp], _i),
-    "slam_pose_compose": ([_vp, _vp, _vp, _i, _i, _vp], _i),
-    "slam_pose_compose_dev": ([_vp, _vp, _vp, _i, _i, _vp], _i),
-    "slam_grid_create": ([_vp, _i, _i, _i, _d, _d, _d, _d, _d, _d, C.POINTER(_vp)], _i),
-    "slam_grid_destroy": ([_vp, _vp], _i),
-    "slam_grid_reset": ([_vp, _vp], _i),
-    "slam_grid_update": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp], _i),
-    "slam_grid_update_dev": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp], _i),
-    "slam_grid_read": ([_vp, _vp, _i, _vp, _vp, _vp, _vp], _i),
-    "slam_grid_finalize_dev": ([_vp, _vp, _vp], _i),
-    "slam_grid_occupancy_data": ([_vp, _vp, _i, _vp], _i),
-    "slam_grid_visits": ([_vp, _vp, C.POINTER(C.c_uint64)], _i),
-    "slam_grid_raycast": ([_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, C.c_float, _i, _vp, _vp], _i),
-    "slam_grid_raycast_dev": ([_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, C.c_float, _i, _vp, _vp], _i),
-    "slam_grid_view_gain": ([_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, C.c_float, _i, _vp, _vp], _i),
-    "slam_grid_view_gain_dev": ([_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, C.c_float, _i, _vp, _vp], _i),
-    "slam_grid_scan_score": ([_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp], _i),
-    "slam_grid_scan_score_dev": ([_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp], _i),
-    "slam_grid_distance_field": ([_vp, _vp, _i, _vp], _i),
-    "slam_grid_distance_field_dev": ([_vp, _vp, _i, _vp], _i),
-    "slam_grid_match": ([_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _d, C.c_float, _i, _vp, _vp, _vp, _vp], _i),
-    "slam_grid_match_dev": ([_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _d, C.c_float, _i, _vp, _vp, _vp, _vp], _i),
-    "slam_grid_locate": ([_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, C.c_float, _i, _vp, _vp, _vp, _vp], _i),
-    "slam_grid_locate_dev": ([_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, C.c_float, _i, _vp, _vp, _vp, _vp], _i),
-    "slam_grid_frontiers": ([_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
-    "slam_grid_frontiers_dev": ([_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
-    "slam_grid_travel": ([_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp], _i),
-    "slam_grid_travel_dev": ([_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp], _i),
-    "slam_mcl_weigh": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, C.c_float, _i, _vp, _vp, _vp, _vp], _i),
-    "slam_mcl_weigh_dev": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, C.c_float, _i, _vp, _vp, _vp, _vp], _i),
-    "slam_mcl_resample": ([_vp, _vp, _vp, _vp, _i, _i, _vp, _d, _i, _i, _vp, _vp, _vp, _vp], _i),
-    "slam_mcl_resample_dev": ([_vp, _vp, _vp, _vp, _i, _i, _vp, _d, _i, _i, _vp, _vp, _vp, _vp], _i),
-    "slam_mcl_weigh_maps": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, C.c_float, _i, _vp, _vp, _vp, _vp], _i),
-    "slam_mcl_weigh_maps_dev": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, C.c_float, _i, _vp, _vp, _vp, _vp], _i),
-    "slam_mcl_settle": ([_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
-    "slam_mcl_settle_dev": ([_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
-    "slam_grid_copy_maps": ([_vp, _vp, _vp, _i, _i, _vp], _i),
-    "slam_grid_copy_maps_dev": ([_vp, _vp, _vp, _i, _i, _vp], _i),
-    "slam_grid_update_particles": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i], _i),
-    "slam_grid_update_particles_dev": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i], _i),
-    "slam_bresenham_batch": ([_vp, _vp, _vp, _i, _vp, _vp, _vp, C.c_int64], _i),
-    "slam_replay": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp], _i),
-    "slam_particles": ([_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _d, _vp, _vp, _vp, _vp], _i),
-    "slam_particles_dev": ([_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _d, _vp, _vp, _vp, _vp, _vp], _i),
-    "slam_grid_counters_dev": ([_vp, _vp, C.POINTER(_vp), C.POINTER(_vp)], _i),
-    "slam_grid_live_pmap": ([_vp, _vp, C.POINTER(_vp)], _i),
-    "slam_grid_update_scans": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i], _i),
-    "slam_grid_update_scans_dev": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i], _i),
-    "slam_map_obstacles": ([_vp, _vp, _i, _i, _i, _d, _d, _d, _vp, _vp, _i, C.POINTER(_i)], _i),
-    "slam_map_obstacles_dev": ([_vp, _vp, _i, _i, _i, _d, _d, _d, _vp, _vp, _i, _vp], _i),
-    "slam_virtual_scan": ([_vp, _vp, _vp, _i, _vp, _i, _d, _d, _i, _vp], _i),
-    "slam_virtual_scan_dev": ([_vp, _vp, _vp, _i, _vp, _i, _d, _d, _i, _vp], _i),
-    "slam_scan_to_points_f64": ([_vp, _vp, _vp, _vp, _i, _i, _vp], _i),
-    "slam_scan_to_points_f64_dev": ([_vp, _vp, _vp, _vp, _i, _i, _vp], _i),
-    "slam_map_observation": ([_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _d, _d, _i, _d, _vp, _vp], _i),
-    "slam_map_observation_dev": ([_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _d, _d, _i, _d, _vp, _vp, _vp, _vp], _i),
-    "slam_replay_dev": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i),
-    "slam_dwa": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp], _i),
-    "slam_dwa_dev": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp], _i),
-    "slam_dwa_scans": ([_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _d, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp], _i),
-    "slam_dwa_scans_dev": ([_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _d, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp], _i),
-    "slam_dwa_shape": ([_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)], _i),
-    "slam_astar": ([_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp], _i),
-    "slam_astar_dev": ([_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp], _i),
-    "slam_astar_inflate": ([_vp, _vp, _i, _i, _i, _i, _i, _i, _vp], _i),
-    "slam_astar_inflate_dev": ([_vp, _vp, _i, _i, _i, _i, _i, _i, _vp], _i),
-    "slam_landmarks": ([_vp, _vp, _vp, _vp, _i, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp], _i),
-    "slam_landmarks_dev": ([_vp, _vp, _vp, _vp, _i, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp], _i),
-    "slam_ekf_lm": ([_vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
-    "slam_ekf_lm_dev": ([_vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
-    "slam_node_replay": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _d, _d, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                          _vp, _vp, _vp, _vp, _vp], _i),
-    "slam_node_replay_dev": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _d, _d, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                              _vp, _vp, _vp, _vp, _vp], _i),
-    "slam_loc_replay": ([_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _d, _d, _i, _d, _vp, _vp, _vp, _vp,
-                         _vp, _vp, _vp, _vp], _i),
-    "slam_loc_replay_dev": ([_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, C.c_int64, _vp, _vp, _i, _vp, _vp, _d, _d, _i, _d, _vp,
-                             _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i),
-}
+_vp = C.c_void_p
+_BY_VALUE = {"int": C.c_int, "double": C.c_double, "float": C.c_float, "int64_t": C.c_int64}
+
+
+def _ctype(decl, text):
+    """The ctypes type of one parameter or return type ``text`` of declaration ``decl``: ``int``, ``double``, ``float``
+    and ``int64_t`` by value, ``char *`` a ``c_char_p``, every other pointer or array a void pointer.  Anything else
+    raises: a width this binding does not know must not be passed as an ``int``."""
+    words = re.sub(r"\bconst\b", " ", text.replace("*", " * ")).split()
+    if "*" in text or "[" in text:
+        return C.c_char_p if re.fullmatch(r"char \*( \w+)?", " ".join(words)) else _vp
+    base = " ".join(words[:-1] if len(words) > 1 else words)       # (the last word of several is the parameter's name)
+    if base not in _BY_VALUE:
+        raise SlamError("%s: no ctypes rule for %r" % (decl, " ".join(text.split())))
+    return _BY_VALUE[base]
+
+
+def header_signatures(path=HEADER_PATH, text=None):
+    """{name: ([argtypes], restype)} of every function include/slam_hip.h declares (or ``text``, a header's contents),
+    by the type rule of :func:`_ctype`.  Comments and preprocessor lines are skipped; a statement with a parameter list
+    that does not read as ``type name(params)`` raises."""
+    if text is None:
+        with open(path) as f:
+            text = f.read()
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#.*$|\bextern\s+\"C\"\s*\{", " ", text, flags=re.M)
+    sigs = {}
+    for stmt in text.split(";"):
+        if "(" not in stmt:
+            continue
+        m = re.fullmatch(r"\s*([\w\s*]+?)\s*\b(\w+)\s*\(([^()]*)\)\s*", stmt)
+        if m is None:
+            raise SlamError("cannot read the declaration %r" % " ".join(stmt.split()))
+        res, name, params = m.groups()
+        params = [] if params.strip() in ("", "void") else params.split(",")
+        sigs[name] = ([_ctype(name, p) for p in params], _ctype(name, res))
+    return sigs
+
+
+_SIGS = header_signatures()
 NODE_OK, NODE_REF_RAISES, NODE_LM_CAP, NODE_OBS_CAP = 0, 1, 2, 3
 LOC_OK, LOC_NONFINITE, LOC_BAD_ROUTE = 0, 1, 2
 EKF_MAX_LM = 32
@@ -158,9 +96,7 @@ RAY_NAMES = ("empty", "hit", "blocked", "free", "unknown", "out", "bad")
 
 def header_symbols(path=HEADER_PATH):
     """Names of every function include/slam_hip.h declares."""
-    text = open(path).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(slam_[a-z0-9_]+)\s*\(", text)))
+    return sorted(header_signatures(path))
 
 
 def lib():

@@ -19,8 +19,10 @@ from __future__ import annotations
 import numpy as np
 
 from . import _abi
+from .grid import (DeviceGrid, _first, _one_or_many, clearance_cells2, frontier_dict, grid_copy_maps_host, grid_frontiers_host,
+                   grid_travel_host, grid_update_particles_host, grid_view_gain_host, nearest_goal, pose_cell, travel_goal,
+                   view_poses, view_tables)
 from .mcl import mcl_resample_host, mcl_settle_host, mcl_weigh_host, mcl_weight_table
-from .replay import DeviceGrid, grid_copy_maps_host, grid_update_particles_host
 
 
 class DeviceGridSLAM:
@@ -197,9 +199,7 @@ class DeviceGridSLAM:
         < 0``) asks for no map: its counts are (-1, -1).  Returns the device tensors; no synchronise."""
         torch = self.torch
         self._begin()
-        best = self.info[:, 0]
-        maps = torch.where(best >= 0, torch.arange(self.F, dtype=torch.int32, device=self.dev) * self.P + best,
-                           torch.full_like(best, -1)).to(torch.int32).contiguous()
+        maps = self._best_maps()
         out = (torch.empty((self.F, 2), dtype=torch.int32, device=self.dev),
                torch.empty((self.F, int(max_clusters), 8), dtype=torch.int32, device=self.dev),
                torch.empty((self.F, int(max_clusters), 2), dtype=torch.int64, device=self.dev))
@@ -224,8 +224,7 @@ class DeviceGridSLAM:
         torch = self.torch
         best = self.info[:, 0].to(torch.int64)
         xy = self.poses[torch.arange(self.F, device=self.dev), best.clamp(min=0), :2]
-        off = torch.tensor([self.grid.off_x, self.grid.off_y], dtype=torch.float64, device=self.dev)
-        cell = (self.grid.scale * (xy + off)).clamp(-2.0 ** 30, 2.0 ** 30).trunc().to(torch.int32)
+        cell = pose_cell(xy, self.grid.scale, self.grid.off_x, self.grid.off_y)
         return torch.where((best >= 0).reshape(-1, 1), cell, torch.full_like(cell, -1)).reshape(self.F, 1, 2).contiguous()
 
     def travel(self, goals=None, foot=0, through_unknown=False, min_clear2=0, cap=64, path_cap=0, cost=True, dirs=False):
@@ -248,7 +247,6 @@ class DeviceGridSLAM:
         ``max_range`` (default: the filter's).  Poses and map indices are formed on the device.  Returns counts int32
         [F, M, 4] (``_abi.VIEW_*``), rows of -1 for a cell with a negative coordinate and for a filter with no live
         particle, and with ``return_seen`` also the bit words [F, M, xw, ceil(yw / 32)].  No synchronise."""
-        from .replay import view_poses, view_tables
         torch = self.torch
         self._begin()
         F, M = int(reps.shape[0]), int(reps.shape[1])
@@ -400,33 +398,21 @@ class GridSLAM:
 
     def frontiers(self, radius=2, min_unknown=13, clearance=0.0, min_size=5, max_clusters=256, cap=64):
         """:meth:`Mapping.frontiers` on the best particle's map."""
-        import math
-        from .replay import frontier_dict, grid_frontiers_host
-        c2 = int(math.ceil((float(clearance) * self.grid.scale) ** 2)) if clearance > 0 else 0
-        if c2 > int(cap):
-            raise ValueError("clearance of %g m is %d squared cells, beyond cap = %d" % (clearance, c2, cap))
-        count, clusters, sums = grid_frontiers_host(self.grid, [max(self.best, 0)], radius=radius, min_unknown=min_unknown, min_clear2=c2,
-                                                    cap=cap, min_size=min_size, max_clusters=max_clusters)
-        return frontier_dict(count[0], clusters[0], sums[0], self.grid.scale, self.grid.off_x, self.grid.off_y)
+        c2 = clearance_cells2(clearance, self.grid.scale, cap)
+        got = grid_frontiers_host(self.grid, [max(self.best, 0)], radius=radius, min_unknown=min_unknown, min_clear2=c2, cap=cap,
+                                  min_size=min_size, max_clusters=max_clusters)
+        return frontier_dict(*_first(got), self.grid.scale, self.grid.off_x, self.grid.off_y)
 
     def view_gain(self, pose_or_poses, angle_min, angle_max, n, max_range=30.0, skip=1, return_seen=False):
         """:meth:`Mapping.view_gain` on the best particle's map."""
-        from .replay import grid_view_gain_host
-        p = np.asarray(pose_or_poses, dtype=np.float64)
-        one = p.ndim == 1
-        p = p.reshape(-1, 3)
+        p, one = _one_or_many(pose_or_poses)
         ct, st = _abi.trig_tables(angle_min, angle_max, int(n))
-        out = grid_view_gain_host(self.grid, p, ct, st, max_range=max_range, skip=skip, grid_of_batch=[max(self.best, 0)] * p.shape[0],
-                                  return_seen=return_seen)
-        if not one:
-            return out
-        return (out[0][0], out[1][0]) if return_seen else out[0]
+        return _first(grid_view_gain_host(self.grid, p, ct, st, max_range=max_range, skip=skip,
+                                          grid_of_batch=[max(self.best, 0)] * p.shape[0], return_seen=return_seen), one)
 
     def next_goal(self, by="distance", **kw):
         """The nearest-frontier rule from the best particle's pose on its map, in a straight line or with ``by="travel"``
         by travel cost (:meth:`Mapping.next_goal`)."""
-        import math
-        from .replay import grid_travel_host, nearest_goal, travel_goal
         if by == "distance":
             return nearest_goal(self.frontiers(**kw), self.best_pose)
         if by != "travel":
@@ -435,12 +421,10 @@ class GridSLAM:
         fr = self.frontiers(**kw)
         if fr["point"].shape[0] == 0 or self.best < 0:
             return None
-        clearance, cap = kw.get("clearance", 0.0), kw.get("cap", 64)
-        c2 = int(math.ceil((float(clearance) * self.grid.scale) ** 2)) if clearance > 0 else 0
-        p = self.best_pose
-        src = np.array([[[int(self.grid.scale * (p[0] + self.grid.off_x)), int(self.grid.scale * (p[1] + self.grid.off_y))]]], dtype=np.int32)
+        cap = kw.get("cap", 64)
+        src = np.array([[pose_cell(self.best_pose, self.grid.scale, self.grid.off_x, self.grid.off_y)]], dtype=np.int32)
         got = grid_travel_host(self.grid, src, [self.best], goals=fr["cell"].reshape(1, -1, 2), foot=foot, through_unknown=through,
-                               min_clear2=c2, cap=cap, cost=False)
+                               min_clear2=clearance_cells2(kw.get("clearance", 0.0), self.grid.scale, cap), cap=cap, cost=False)
         k = travel_goal(fr, got["goal_cost"][0])
         return None if k is None else fr["point"][k].copy()
 

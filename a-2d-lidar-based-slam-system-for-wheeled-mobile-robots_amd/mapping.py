@@ -25,11 +25,13 @@ Fidelity notes:
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
 from . import _abi
+from .grid import (DeviceGrid, _first, _one_or_many, clearance_cells2, frontier_dict, frontier_points, gain_goal,
+                   grid_distance_field_host, grid_frontiers_host, grid_locate_host, grid_match_host, grid_raycast_host,
+                   grid_score_host, grid_travel_host, grid_view_gain_host, locate_pose, locate_rotations, match_pose,
+                   match_rotations, nearest_goal, pose_cell, travel_goal, view_poses, view_tables)
 
 
 class Mapping:
@@ -50,28 +52,28 @@ class Mapping:
         self.index_scale = float(index_scale)
         self.index_offset_x = float(index_offset)
         self.index_offset_y = float(index_offset if index_offset_y is None else index_offset_y)
-        self._ctx = context or _abi.default_context()
-        h = C.c_void_p()
-        _abi.check(_abi.lib().slam_grid_create(self._ctx.handle, 1, self.xw, self.yw, self.index_scale,
-                                               self.index_offset_x, self.index_offset_y, float(free_inc),
-                                               float(hit_inc), float(thresh), C.byref(h)))
-        self._grid = h
+        self.grid = DeviceGrid(1, self.xw, self.yw, self.index_scale, self.index_offset_x, self.index_offset_y, free_inc, hit_inc,
+                               thresh, context)
+        self._ctx = self.grid._ctx
         self._p8 = np.empty((self.xw, self.yw), dtype=np.int8)
-        # one scan per call owns the map: the ray cast keeps pmap current on the device itself
-        live = C.c_void_p()
-        _abi.check(_abi.lib().slam_grid_live_pmap(self._ctx.handle, self._grid, C.byref(live)))
+        self.grid.live_pmap()       # one scan per call owns the map: the ray cast keeps pmap current on the device itself
+
+    @property
+    def _grid(self):
+        """The map's raw handle, ``grid._h``, under the name callers outside the package knew it by."""
+        return self.grid._h
 
     @property
     def datamap(self):
         """The evidence map of mapping.py:15 (float64 [xw, yw]).  ``update`` only brings ``pmap``
         back from the device; this view (8 bytes per cell) is read when it is asked for."""
         if self._datamap_stale:
-            _abi.check(_abi.lib().slam_grid_read(self._ctx.handle, self._grid, 0, None, _abi.ptr(self._datamap), None, None))
+            _abi.check(_abi.lib().slam_grid_read(self._ctx.handle, self.grid._h, 0, None, _abi.ptr(self._datamap), None, None))
             self._datamap_stale = False
         return self._datamap
 
     def _fetch_pmap(self):
-        _abi.check(_abi.lib().slam_grid_read(self._ctx.handle, self._grid, 0, _abi.ptr(self._p8), None, None, None))
+        _abi.check(_abi.lib().slam_grid_read(self._ctx.handle, self.grid._h, 0, _abi.ptr(self._p8), None, None, None))
         self.pmap[...] = self._p8
         self._datamap_stale = True
         return self.pmap
@@ -86,9 +88,7 @@ class Mapping:
 
     def __del__(self):
         try:
-            if getattr(self, "_grid", None) is not None and self._ctx._h is not None:
-                _abi.lib().slam_grid_destroy(self._ctx.handle, self._grid)
-            self._grid = None
+            self.grid.close()
         except Exception:
             pass
 
@@ -104,7 +104,7 @@ class Mapping:
         cy = np.array([float(np.asarray(center_y).reshape(-1)[0])])
         L = _abi.lib()
         try:
-            _abi.check(L.slam_grid_update(self._ctx.handle, self._grid, _abi.ptr(ox), _abi.ptr(oy), _abi.ptr(cx),
+            _abi.check(L.slam_grid_update(self._ctx.handle, self.grid._h, _abi.ptr(ox), _abi.ptr(oy), _abi.ptr(cx),
                                           _abi.ptr(cy), 1, n, None))
         finally:
             self._datamap_stale = True            # on a NaN / inf beam the beams before it were still applied
@@ -124,7 +124,7 @@ class Mapping:
         ct, st = _abi.trig_tables(angle_min, angle_max, n)
         L = _abi.lib()
         try:
-            _abi.check(L.slam_grid_update_scans(self._ctx.handle, self._grid, _abi.ptr(r), _abi.ptr(ct), _abi.ptr(st),
+            _abi.check(L.slam_grid_update_scans(self._ctx.handle, self.grid._h, _abi.ptr(r), _abi.ptr(ct), _abi.ptr(st),
                                                 _abi.ptr(p), _abi.ptr(c), S, n))
         finally:
             self._datamap_stale = True
@@ -136,32 +136,23 @@ class Mapping:
         [n] to the centre of the first occupied cell from path index ``skip`` on (1: not the robot's own cell) -
         inf where the ray meets none, NaN for a pose the reference's ``int()`` would raise on - and with
         ``return_cells`` also the cells int32 [n, 2], (-1, -1) where there is none."""
-        p = np.ascontiguousarray(np.asarray(pose, dtype=np.float64).reshape(3))
+        p = np.asarray(pose, dtype=np.float64).reshape(3)
         ct, st = _abi.trig_tables(angle_min, angle_max, int(n))
-        r = np.empty(int(n), dtype=np.float32)
-        cells = np.empty((int(n), 2), dtype=np.int32) if return_cells else None
-        _abi.check(_abi.lib().slam_grid_raycast(self._ctx.handle, self._grid, _abi.ptr(p), 1, None, _abi.ptr(ct), _abi.ptr(st),
-                                                int(n), float(max_range), int(skip), _abi.ptr(r), _abi.ptr(cells)))
-        return (r, cells) if return_cells else r
+        return _first(grid_raycast_host(self.grid, p, ct, st, max_range=max_range, skip=skip, return_cells=return_cells))
 
     def score_scan(self, ranges, angle_min, angle_max, pose, skip=1):
         """How a measured scan sits in this map seen from ``pose`` (``slam_grid_scan_score``): the seven counts
         int32 [7], indexed by ``_abi.RAY_EMPTY .. RAY_BAD``, of beams formed as ``update_scans`` forms them."""
-        r = np.ascontiguousarray(np.asarray(ranges, dtype=np.float32).reshape(-1))
-        p = np.ascontiguousarray(np.asarray(pose, dtype=np.float64).reshape(3))
+        r = np.asarray(ranges, dtype=np.float32).reshape(-1)
+        p = np.asarray(pose, dtype=np.float64).reshape(3)
         ct, st = _abi.trig_tables(angle_min, angle_max, r.shape[0])
-        counts = np.empty(_abi.RAY_CLASSES, dtype=np.int32)
-        _abi.check(_abi.lib().slam_grid_scan_score(self._ctx.handle, self._grid, _abi.ptr(r), 1, _abi.ptr(p), 1, None, _abi.ptr(ct),
-                                                   _abi.ptr(st), r.shape[0], int(skip), _abi.ptr(counts), None))
-        return counts
+        return _first(grid_score_host(self.grid, r, p, ct, st, skip=skip))
 
     def distance_field(self, cap=64):
         """The distance field of this map (``slam_grid_distance_field``): int16 [xw, yw], the squared cell distance
         to the nearest occupied cell, capped at ``cap`` (1 .. 32767); ``cap`` everywhere while nothing is occupied.
         Rebuilt from the live counters on every call."""
-        out = np.empty((self.xw, self.yw), dtype=np.int16)
-        _abi.check(_abi.lib().slam_grid_distance_field(self._ctx.handle, self._grid, int(cap), _abi.ptr(out)))
-        return out
+        return _first(grid_distance_field_host(self.grid, cap))
 
     def match_scan(self, ranges, angle_min, angle_max, pose, window=(4, 4), step=None, n_rot=11, rot_step=0.01,
                    max_range=30.0, cap=64, return_costs=False):
@@ -171,37 +162,26 @@ class Mapping:
         ``max_range`` of the distance-field value at the beam's end cell (``cap`` off the map).  Returns (pose [3],
         cost, used beams) of the cheapest candidate, ties to the lowest (rotation, x, y) index, and with
         ``return_costs`` also the cost volume int32 [n_rot, 2 window[0] + 1, 2 window[1] + 1]."""
-        from .replay import _window_ok, match_pose, match_rotations
-        r = np.ascontiguousarray(np.asarray(ranges, dtype=np.float32).reshape(-1))
+        r = np.asarray(ranges, dtype=np.float32).reshape(-1)
         p = np.asarray(pose, dtype=np.float64).reshape(3)
-        n, nx, ny = r.shape[0], int(window[0]), int(window[1])
+        nx, ny = int(window[0]), int(window[1])
         step = 1.0 / self.index_scale if step is None else float(step)
-        ct, st = _abi.trig_tables(angle_min, angle_max, n)
-        ctr = np.ascontiguousarray(p[None, :2])
+        ct, st = _abi.trig_tables(angle_min, angle_max, r.shape[0])
         th, rot = match_rotations(p[2:3], n_rot, rot_step)
-        best, cost, used = (np.empty(1, dtype=np.int32) for _ in range(3))
-        vol = np.empty((int(n_rot), 2 * nx + 1, 2 * ny + 1), dtype=np.int32) if return_costs and _window_ok(int(n_rot), nx, ny) else None
-        _abi.check(_abi.lib().slam_grid_match(self._ctx.handle, self._grid, _abi.ptr(r), 1, _abi.ptr(ctr), 1, None, _abi.ptr(ct),
-                                              _abi.ptr(st), n, _abi.ptr(rot), int(n_rot), nx, ny, step, float(max_range),
-                                              int(cap), _abi.ptr(best), _abi.ptr(cost), _abi.ptr(used), _abi.ptr(vol)))
-        out = (match_pose(ctr, th, best, nx, ny, step)[0], int(cost[0]), int(used[0]))
-        return out + (vol,) if return_costs else out
+        got = _first(grid_match_host(self.grid, r, p[None, :2], ct, st, rot, nx, ny, step, max_range=max_range, cap=cap,
+                                     return_costs=return_costs))
+        return (match_pose(p[None, :2], th, got[0], nx, ny, step)[0], int(got[1]), int(got[2])) + got[3:]
 
     def locate_scan(self, ranges, angle_min, angle_max, n_rot=256, levels=5, region=None, max_range=30.0, cap=64):
         """Where in this map a measured scan was taken (``slam_grid_locate``): the cheapest of ``n_rot`` rotations over the
         full circle x every cell of the map - or of ``region`` = (i0, j0, ni, nj) - as the robot's cell, found exactly by
         branch and bound on a ``levels``-deep pyramid of the distance field.  Returns (pose [3] at the cell's centre,
         cost, used beams)."""
-        from .replay import locate_pose, locate_rotations
-        r = np.ascontiguousarray(np.asarray(ranges, dtype=np.float32).reshape(-1))
+        r = np.asarray(ranges, dtype=np.float32).reshape(-1)
         ct, st = _abi.trig_tables(angle_min, angle_max, r.shape[0])
         _, rot = locate_rotations(n_rot)
-        reg = None if region is None else np.ascontiguousarray(np.asarray(region, dtype=np.int32).reshape(1, 4))
-        best = np.empty((1, 3), dtype=np.int32)
-        cost, used = (np.empty(1, dtype=np.int32) for _ in range(2))
-        _abi.check(_abi.lib().slam_grid_locate(self._ctx.handle, self._grid, _abi.ptr(r), 1, 1, None, _abi.ptr(ct), _abi.ptr(st),
-                                               r.shape[0], _abi.ptr(rot), rot.shape[0], _abi.ptr(reg), int(levels),
-                                               float(max_range), int(cap), _abi.ptr(best), _abi.ptr(cost), _abi.ptr(used), None))
+        reg = None if region is None else np.asarray(region, dtype=np.int32).reshape(1, 4)
+        best, cost, used = grid_locate_host(self.grid, r, ct, st, rot, levels=levels, region=reg, max_range=max_range, cap=cap, B=1)
         pose = locate_pose(best, self.index_scale, self.index_offset_x, self.index_offset_y, rot)[0]
         return pose, int(cost[0]), int(used[0])
 
@@ -214,19 +194,10 @@ class Mapping:
         world coordinates), ``centroid`` [K, 2] (world, from the sums), ``bbox`` [K, 4]; and ``count`` (the true number
         of kept clusters, also beyond ``max_clusters``) and ``n_frontier``.  The defaults (2, 13, 5) come from one
         experiment on the synthetic room; they are not tuned."""
-        import math
-        from .replay import frontier_dict
-        c2 = int(math.ceil((float(clearance) * self.index_scale) ** 2)) if clearance > 0 else 0
-        if c2 > int(cap):
-            raise ValueError("clearance of %g m is %d squared cells, beyond cap = %d" % (clearance, c2, cap))
-        M = int(max_clusters)
-        count = np.empty((1, 2), dtype=np.int32)
-        clusters = np.empty((1, max(M, 0), 8), dtype=np.int32)
-        sums = np.empty((1, max(M, 0), 2), dtype=np.int64)
-        _abi.check(_abi.lib().slam_grid_frontiers(self._ctx.handle, self._grid, 1, None, int(radius), int(min_unknown), c2, int(cap),
-                                                  int(min_size), M, _abi.ptr(count), _abi.ptr(clusters) if M > 0 else None,
-                                                  _abi.ptr(sums) if M > 0 else None, None))
-        return frontier_dict(count[0], clusters[0], sums[0], self.index_scale, self.index_offset_x, self.index_offset_y)
+        c2 = clearance_cells2(clearance, self.index_scale, cap)
+        got = grid_frontiers_host(self.grid, radius=radius, min_unknown=min_unknown, min_clear2=c2, cap=cap, min_size=min_size,
+                                  max_clusters=max_clusters)
+        return frontier_dict(*_first(got), self.index_scale, self.index_offset_x, self.index_offset_y)
 
     def next_goal(self, pose, by="distance", **kw):
         """``by="distance"``, the nearest-frontier rule: the representative point [2] of the kept cluster
@@ -240,7 +211,6 @@ class Mapping:
         full circle to ``max_range`` (default 30 m)), the one with the largest u / (c + ``bias``), compared exactly as
         integers (:func:`gain_goal`), ties to the lower cost, then to the lower label; None when there is none.
         ``bias`` (default 100) is in travel-cost units; it is a starting value, not a tuned one."""
-        from .replay import nearest_goal, travel_goal
         if by == "distance":
             return nearest_goal(self.frontiers(**kw), pose)
         if by == "gain":
@@ -256,16 +226,13 @@ class Mapping:
         return None if k is None else fr["point"][k].copy()
 
     def _gain_goal(self, pose, bias=100, n=360, max_range=30.0, skip=1, **kw):
-        from types import SimpleNamespace
-        from .replay import gain_goal, grid_view_gain_host, view_poses, view_tables
         foot, through = kw.pop("foot", 0), kw.pop("through_unknown", False)
         fr = self.frontiers(**kw)
         if fr["point"].shape[0] == 0:
             return None
         got = self._travel(pose, kw.get("clearance", 0.0), foot, through, kw.get("cap", 64), goals=fr["cell"], cost=False)
         views = view_poses(fr["cell"], self.index_scale, self.index_offset_x, self.index_offset_y)
-        grid = SimpleNamespace(_ctx=self._ctx, _h=self._grid, G=1, xw=self.xw, yw=self.yw)
-        counts = grid_view_gain_host(grid, views, *view_tables(n), max_range=max_range, skip=skip)
+        counts = grid_view_gain_host(self.grid, views, *view_tables(n), max_range=max_range, skip=skip)
         k = gain_goal(fr, got["goal_cost"][0], counts[:, _abi.VIEW_UNKNOWN], bias)
         return None if k is None else fr["point"][k].copy()
 
@@ -276,33 +243,19 @@ class Mapping:
         int32 [4] = (unknown, free, occupied cells, beams that found nothing) (``_abi.VIEW_*``), a row of -1 for a pose
         the index rule rejects.  poses [B, 3] give [B, 4].  With ``return_seen`` also the set as bit words uint32
         [xw, ceil(yw / 32)] ([B, ...]): bit ``y & 31`` of word ``y >> 5`` in row x."""
-        from types import SimpleNamespace
-        from .replay import grid_view_gain_host
-        p = np.asarray(pose_or_poses, dtype=np.float64)
-        one = p.ndim == 1
+        p, one = _one_or_many(pose_or_poses)
         ct, st = _abi.trig_tables(angle_min, angle_max, int(n))
-        grid = SimpleNamespace(_ctx=self._ctx, _h=self._grid, G=1, xw=self.xw, yw=self.yw)
-        out = grid_view_gain_host(grid, p.reshape(-1, 3), ct, st, max_range=max_range, skip=skip, return_seen=return_seen)
-        if not one:
-            return out
-        return (out[0][0], out[1][0]) if return_seen else out[0]
+        return _first(grid_view_gain_host(self.grid, p, ct, st, max_range=max_range, skip=skip, return_seen=return_seen), one)
 
     def pose_cell(self, pose):
         """The cell (x, y) of a pose by the map's own rule, ``int(scale * (v + off))``, truncated toward zero."""
-        p = np.asarray(pose, dtype=np.float64).reshape(-1)
-        return (int(self.index_scale * (p[0] + self.index_offset_x)), int(self.index_scale * (p[1] + self.index_offset_y)))
+        return pose_cell(pose, self.index_scale, self.index_offset_x, self.index_offset_y)
 
     def _travel(self, pose, clearance, foot, through_unknown, cap, goals=None, path_cap=0, cost=True):
-        import math
-        from types import SimpleNamespace
-        from .replay import grid_travel_host
-        c2 = int(math.ceil((float(clearance) * self.index_scale) ** 2)) if clearance > 0 else 0
-        if c2 > int(cap):
-            raise ValueError("clearance of %g m is %d squared cells, beyond cap = %d" % (clearance, c2, cap))
-        grid = SimpleNamespace(_ctx=self._ctx, _h=self._grid, G=1, xw=self.xw, yw=self.yw)
+        c2 = clearance_cells2(clearance, self.index_scale, cap)
         src = np.array([[self.pose_cell(pose)]], dtype=np.int32)
         gl = None if goals is None else np.asarray(goals, dtype=np.int32).reshape(1, -1, 2)
-        return grid_travel_host(grid, src, goals=gl, foot=foot, through_unknown=through_unknown, min_clear2=c2, cap=cap,
+        return grid_travel_host(self.grid, src, goals=gl, foot=foot, through_unknown=through_unknown, min_clear2=c2, cap=cap,
                                 path_cap=path_cap, cost=cost)
 
     def travel_field(self, pose, clearance=0.0, foot=0, through_unknown=False, cap=64):
@@ -317,7 +270,6 @@ class Mapping:
         """The cheapest way from the pose to the cell of the world point ``goal_xy``: (points float64 [len, 2] - the cell
         centres (:func:`frontier_points`), the robot's cell first - and the cost), or None when the goal is unreachable.
         ``path_cap`` is grown and the call repeated when the path is longer."""
-        from .replay import frontier_points
         goal = self.pose_cell(goal_xy)
         while True:
             got = self._travel(pose, clearance, foot, through_unknown, cap, goals=[goal], path_cap=path_cap, cost=False)
@@ -331,19 +283,13 @@ class Mapping:
 
     def counters(self):
         """(pass, hit) uint32 [xw, yw]: the integer evidence behind ``datamap``."""
-        p = np.empty((self.xw, self.yw), dtype=np.uint32)
-        h = np.empty((self.xw, self.yw), dtype=np.uint32)
-        _abi.check(_abi.lib().slam_grid_read(self._ctx.handle, self._grid, 0, None, None, _abi.ptr(p), _abi.ptr(h)))
-        return p, h
+        got = self.grid.read(0, want=("pass", "hit"))
+        return got["pass"], got["hit"]
 
     def occupancy_grid_data(self):
         """int8 [yw*xw] in the OccupancyGrid layout of publishMap
         (W12m/slam_ekf.py:270-271): data[y*width + x] = pmap[x][y]."""
-        out = np.empty(self.xw * self.yw, dtype=np.int8)
-        _abi.check(_abi.lib().slam_grid_occupancy_data(self._ctx.handle, self._grid, 0, _abi.ptr(out)))
-        return out
+        return self.grid.occupancy_grid_data(0)
 
     def visits(self):
-        v = C.c_uint64(0)
-        _abi.check(_abi.lib().slam_grid_visits(self._ctx.handle, self._grid, C.byref(v)))
-        return int(v.value)
+        return self.grid.visits()

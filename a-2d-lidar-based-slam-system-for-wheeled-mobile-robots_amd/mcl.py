@@ -32,8 +32,8 @@ def mcl_weight_table(sigma_cells, shift=0, T=4096, floor=0):
 
 
 def _handles(grid):
-    """(context handle, grid handle) of a DeviceGrid or a Mapping."""
-    return grid._ctx.handle, getattr(grid, "_h", None) or grid._grid
+    """(context handle, grid handle) of a DeviceGrid."""
+    return grid._ctx.handle, grid._h
 
 
 def _opt(a, dtype, shape):
@@ -314,7 +314,7 @@ class MCL:
         if u is not None:
             motion = np.asarray(u, dtype=np.float64).reshape(1, 3)
             noise = self.rng.normal(0.0, 1.0, (1, self.P, 3)) * self.noise_sigma
-        poses, _cost, acc, _used = mcl_weigh_host(self.mapping, self.particles[None], r, ct, st, motion=motion, noise=noise,
+        poses, _cost, acc, _used = mcl_weigh_host(self.mapping.grid, self.particles[None], r, ct, st, motion=motion, noise=noise,
                                                   max_range=self.max_range, cap=self.cap, field=self.field if self.static_map else None,
                                                   acc=self.acc[None])
         u0 = np.array([min(self.rng.uniform(), np.nextafter(1.0, 0.0))])

@@ -16,7 +16,7 @@ import numpy as np
 
 from . import _abi
 from .param import get_param
-from .replay import DeviceGrid
+from .grid import DeviceGrid
 
 NODE_OK, NODE_REF_RAISES, NODE_LM_CAP, NODE_OBS_CAP = _abi.NODE_OK, _abi.NODE_REF_RAISES, _abi.NODE_LM_CAP, _abi.NODE_OBS_CAP
 

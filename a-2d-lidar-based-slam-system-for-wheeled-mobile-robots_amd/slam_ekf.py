@@ -119,11 +119,11 @@ class SLAM_EKF:  # noqa: N801 (the reference's class name)
         tol = get_param('/icp/tolerance', 0.001)                   # icp.py:40
         _abi.check(_abi.lib().slam_replay(self._ctx.handle, _abi.ptr(pair), _abi.ptr(ct), _abi.ptr(st), 1, 2, n,
                                           _abi.F64, int(self.icp.max_iter), float(tol), _abi.ptr(pose0),
-                                          None if self.online else self.mapping._grid, None, _abi.ptr(pose),
+                                          None if self.online else self.mapping.grid._h, None, _abi.ptr(pose),
                                           _abi.ptr(T), _abi.ptr(it)))
         if self.online:                                            # W12o :102-104
             centre = np.array([[float(self.x_online), float(self.y_online)]])
-            _abi.check(_abi.lib().slam_grid_update_scans(self._ctx.handle, self.mapping._grid, _abi.ptr(ranges),
+            _abi.check(_abi.lib().slam_grid_update_scans(self._ctx.handle, self.mapping.grid._h, _abi.ptr(ranges),
                                                          _abi.ptr(ct), _abi.ptr(st), _abi.ptr(pose), _abi.ptr(centre),
                                                          1, n))
         self._prev_ranges = ranges                                 # calc_odometry :112
@@ -157,7 +157,7 @@ class SLAM_EKF:  # noqa: N801 (the reference's class name)
         centre = None
         if self.online:
             centre = np.array([[float(self.x_online), float(self.y_online)]])
-        _abi.check(_abi.lib().slam_grid_update_scans(self._ctx.handle, self.mapping._grid, _abi.ptr(ranges), _abi.ptr(ct),
+        _abi.check(_abi.lib().slam_grid_update_scans(self._ctx.handle, self.mapping.grid._h, _abi.ptr(ranges), _abi.ptr(ct),
                                                      _abi.ptr(st), _abi.ptr(pose), _abi.ptr(centre), 1, n))   # :88-90
         self.publishMap(self.mapping._fetch_pmap())                # :91
 

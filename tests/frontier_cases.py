@@ -148,7 +148,7 @@ class MapGrid:
     """A Mapping's one map seen as a grid of G = 1, for the helpers here and for grid_frontiers_host."""
 
     def __init__(self, m):
-        self._ctx, self._h, self.G, self.xw, self.yw = m._ctx, m._grid, 1, m.xw, m.yw
+        self._ctx, self._h, self.G, self.xw, self.yw = m._ctx, m.grid._h, 1, m.xw, m.yw
 
     def read(self, gi, want=("pmap",)):
         from conftest import pkg

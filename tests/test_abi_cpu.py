@@ -22,6 +22,70 @@ def test_library_exports_every_declared_symbol():
     assert L.slam_abi_version() == 1
 
 
+SYNTHETIC_HEADER = """
+/* int commented_out(int a); */
+// double also_commented_out(void);
+#ifdef __cplusplus
+extern "C" {
+#endif
+#define NOT_A_CALL(x) (x)
+typedef struct thing thing;
+enum { A = 0, B = 4 };
+int by_value(int a, double b, float c, int64_t d);
+int pointers(const double *in, thing **out, int32_t x[4], const int32_t y[2][2], void *raw);
+int no_arguments(void);
+const char *text(void);
+int takes_text(thing *t, const char *name, char **names);
+double wrapped(thing *t,   /* a comment inside the list */
+               const float *ranges, int n,
+               int64_t
+                   count);
+int unnamed(int, const float *, double);
+#ifdef __cplusplus
+}
+#endif
+"""
+
+
+def test_signatures_are_parsed_from_the_header_by_the_type_rule():
+    abi = pkg("_abi")
+    vp, i, d, f, i64, s = C.c_void_p, C.c_int, C.c_double, C.c_float, C.c_int64, C.c_char_p
+    assert abi.header_signatures(text=SYNTHETIC_HEADER) == {
+        "by_value": ([i, d, f, i64], i),
+        "pointers": ([vp, vp, vp, vp, vp], i),
+        "no_arguments": ([], i),
+        "text": ([], s),
+        "takes_text": ([vp, s, vp], i),
+        "wrapped": ([vp, vp, i, i64], d),
+        "unnamed": ([i, vp, d], i),
+    }
+    for bad in ("int f(long n);", "int f(unsigned int n);", "int f(size_t n);", "long f(int n);", "void f(int n);", "int f(int32_t n);",
+                "int f(int (*callback)(int));"):
+        with pytest.raises(abi.SlamError, match=r"\bf\b"):
+            abi.header_signatures(text="int good(int a);\n" + bad)
+
+
+def test_real_header_widths_where_a_slip_would_corrupt_arguments():
+    """Positions counted in include/slam_hip.h itself: a float bound as a double, or an int64_t bound as an int, shifts or
+    truncates every argument after it without any error."""
+    abi = pkg("_abi")
+    sig = abi.header_signatures()
+    assert sig == abi._SIGS and len(sig) == 95
+    vp, i, d, f, i64 = C.c_void_p, C.c_int, C.c_double, C.c_float, C.c_int64
+    for name in ("slam_grid_match", "slam_grid_match_dev"):
+        args = sig[name][0]
+        assert args[11:17] == [i, i, i, d, f, i], name              # K, nx, ny, double step, float max_range, cap
+    for name in ("slam_grid_raycast", "slam_grid_raycast_dev"):
+        assert sig[name][0][7:10] == [i, f, i], name                # n, float max_range, skip
+    assert sig["slam_bresenham_batch"][0] == [vp, vp, vp, i, vp, vp, vp, i64]                      # int64_t total_cells, last
+    for name in ("slam_ekf_lm", "slam_ekf_lm_dev"):
+        assert sig[name][0][5:8] == [vp, i64, i], name              # z, int64_t nz, B
+    assert sig["slam_loc_replay_dev"][0][9:12] == [i, i64, vp]      # M, int64_t K, map_of_traj
+    assert i64 not in sig["slam_loc_replay"][0]                     # (the host form reads K from obs_off[M])
+    assert sig["slam_last_error"] == ([], C.c_char_p) and sig["slam_set_option"][0] == [vp, C.c_char_p, d]
+    assert all(res is i for name, (_a, res) in sig.items() if name != "slam_last_error")
+
+
 def test_header_cites_reference_for_every_operator():
     text = open(os.path.join(ROOT, "include", "slam_hip.h")).read()
     for ref in ("icp.py:38-88", "icp.py:90-114", "icp.py:149-179", "mapping.py:22-51", "mapping.py:8-20",
