@@ -167,6 +167,7 @@ class Context:
         check(lib().slam_create(int(device), _vp(stream) if stream else None, C.byref(h)))
         self._h = h
         self.device = int(device)
+        self.options = {}              # what set_option last set, by name: the options live on the context, not on its users
 
     @property
     def handle(self):
@@ -200,6 +201,7 @@ class Context:
 
     def set_option(self, name, value):
         check(lib().slam_set_option(self.handle, name.encode(), float(value)))
+        self.options[name] = float(value)
 
     def timing_enable(self, on=True, only=None):
         """``only``: family names (K_NAMES) whose launches carry events; None: every family."""

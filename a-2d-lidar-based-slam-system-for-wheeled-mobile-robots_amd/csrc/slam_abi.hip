@@ -66,6 +66,13 @@ size_t dtype_size(int dtype)
 
 size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 
+// a grid object's state, one allocation [pass | hit | visit counter]: the two counter planes of all its cells, then the slots
+size_t grid_plane_bytes(size_t cells) { return align_up(cells * 4); }
+size_t grid_state_bytes(size_t cells)
+{
+    return grid_plane_bytes(cells) * 2 + align_up((size_t)kVisitSlots * kVisitStride * sizeof(unsigned long long));
+}
+
 struct Arena {
     char *base = nullptr;
     size_t cap = 0;
@@ -957,6 +964,9 @@ int slam_plan_query(const char *name, int a, int b, int c, int guard, int64_t *o
         // the ray casts of large maps: a = scans of the cast (L * scans), b = beams, c = groups: where the engine's layout ends
         {"wedge_ws_bytes", (int64_t)cast_layout_bytes(CastPath::Wedges, (long)a * b, a, c)},
         {"tile_ws_bytes", (int64_t)cast_layout_bytes(CastPath::Tiles, (long)a * b, a, c)},
+        // slam_grid_create: a = G, b = xw, c = yw: the bytes of the grid object's state, which a reset (slam_grid_reset, option
+        // "replay_reset") clears - pass and hit counters of every map and the visit slots
+        {"grid_state_bytes", (a > 0 && b > 0 && c > 0) ? (int64_t)grid_state_bytes((size_t)a * b * c) : 0},
     };
     for (const Entry &e : table)
         if (!strcmp(e.name, name)) { *out = e.value; return SLAM_OK; }
@@ -1221,11 +1231,11 @@ int slam_grid_create(slam_ctx *c, int G, int xw, int yw, double scale, double of
     for (uint32_t k = 0; k < (uint32_t)kMaxHitLevels; ++k) g->d.pass_thresh[k] = k < levels ? table[k] : 0;
     g->d.status = c->status;
     // one allocation [pass | hit | visit counter] so that a reset is a single memset
-    g->state_bytes = align_up(cells * 4) * 2 + align_up((size_t)kVisitSlots * kVisitStride * sizeof(unsigned long long));
+    g->state_bytes = grid_state_bytes(cells);
     hipError_t e = hipMalloc(reinterpret_cast<void **>(&g->d.pass), g->state_bytes);
     if (e == hipSuccess) {
-        g->d.hit = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(g->d.pass) + align_up(cells * 4));
-        g->visits = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(g->d.pass) + 2 * align_up(cells * 4));
+        g->d.hit = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(g->d.pass) + grid_plane_bytes(cells));
+        g->visits = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(g->d.pass) + 2 * grid_plane_bytes(cells));
     }
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&g->pmap_one), align_up((size_t)xw * yw));
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&g->datamap_one), (size_t)xw * yw * 8);

@@ -140,7 +140,6 @@ class DeviceReplay:
         if grid_of_traj is not None:
             self.got = torch.from_numpy(np.ascontiguousarray(np.asarray(grid_of_traj, dtype=np.int32))).to(self.dev)
         self.max_iter, self.tol = int(max_iter), float(tolerance)
-        self._reset_opt = 0
         torch.cuda.synchronize(self.dev)
 
     def make_grid(self, G, xw, yw, reso, **kw):
@@ -161,9 +160,9 @@ class DeviceReplay:
                 setattr(self, name, buf)
         if self.grid is not None:          # (the reset rides on the scan-matching launch: context option "replay_reset")
             want = 1 if reset_grid else 0
-            if want != self._reset_opt:
+            # the option is the CONTEXT's: another replay on it, or its owner, may have set it since this one ran last
+            if want != self.ctx.options.get("replay_reset", 0):
                 self.ctx.set_option("replay_reset", want)
-                self._reset_opt = want
         _abi.check(_abi.lib().slam_replay_dev(
             self.ctx.handle, self.ranges.data_ptr(), self.cos_t.data_ptr(), self.sin_t.data_ptr(), self.L, self.n_scan,
             self.n, self.code, self.max_iter, self.tol, self.pose0.data_ptr(),

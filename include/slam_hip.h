@@ -226,6 +226,7 @@ int slam_plan_icp(int B, int n_src, int n_tar, int is_scan, int qpt_pref, int ba
  * (budget in KiB, a query's bytes, B);
  * "wedge_ws_bytes" / "tile_ws_bytes" (scans of the cast = L * scans, beams, groups): the bytes at which the device workspace
  * of the wedge / tile ray cast ends, every piece on a 256-byte boundary, computed in 64 bits;
+ * "grid_state_bytes" (G, xw, yw): the bytes a reset of such a grid object clears (both counters of every map, the visit slots);
  * arguments a function does not take are ignored.  SLAM_ERR_INVALID for a name it does not know. */
 int slam_plan_query(const char *name, int a, int b, int c, int guard, int64_t *out);
 

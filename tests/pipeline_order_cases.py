@@ -50,6 +50,9 @@ LEGS = {
     "view_gain_poses": ("slam_grid_view_gain_dev", "P-in"),
     "replay_chain_map": ("slam_replay_dev", "P-in"),
     "replay_chain_no_map": ("slam_replay_dev", "P-in"),
+    "ekf_lm": ("slam_ekf_lm_dev", "P-in"),
+    "node_replay": ("slam_node_replay_dev", "P-in"),
+    "loc_replay": ("slam_loc_replay_dev", "P-in"),
     # P, written while the map stage reads it
     "pose_compose_out": ("slam_pose_compose_dev", "P-out"),
     "mcl_settle_out": ("slam_mcl_settle_dev", "P-out"),
@@ -60,10 +63,10 @@ LEGS = {
 # Entry points without a leg.  The first three are the pipeline's own stages: a join in them would undo the overlap the
 # option is for (the piped slam_replay_dev is exempt as a CONSUMER of the join; the replay_chain legs follow it with a
 # second and a third replay).  The others take no map and join the internal streams at their head exactly as the legs
-# of their kind do (streams_on_main, csrc/slam_abi.hip).  For most of them no argument has the type of a stage result -
+# of their kind do (streams_on_main, csrc/slam_abi.hip).  No argument of theirs has the type of a stage result -
 # poses_out is float64 [.][3] poses and pmap_dev an int8 map - so a leg would have to feed them bytes that mean something
-# else.  The last three do take a start pose: they are joined, and a leg for each (its node reference applied to B's last
-# pose) is still to be written.
+# else.  (The three nodes that take a start pose - the landmark filter, the landmark node and the localization node -
+# have their legs above: x0 / pose0 is the last row of the piped replay's poses_out.)
 EXEMPT = {
     "slam_replay_dev[piped]": "the pipeline itself: scan matching | pose composition | map stage, ordered by its own events",
     "slam_grid_reset": "first piece of the map stage: runs on the map stream, behind the previous map stage",
@@ -76,9 +79,6 @@ EXEMPT = {
     "slam_dwa_dev": "reads [B][5] planner states, goals and obstacle points only",
     "slam_dwa_scans_dev": "reads [B][5] planner states, goals and float32 ranges only",
     "slam_landmarks_dev": "reads float32 ranges and beam tables only",
-    "slam_ekf_lm_dev": "no leg: x0 [B][3] could be a row of poses_out; joined at its head like pose_compose_pose0",
-    "slam_node_replay_dev": "no leg: pose0 could be a row of poses_out; joined at its head like replay_chain_no_map",
-    "slam_loc_replay_dev": "no leg: pose0 could be a row of poses_out; joined at its head like replay_chain_no_map",
 }
 
 

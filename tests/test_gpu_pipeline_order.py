@@ -23,10 +23,12 @@ import numpy as np
 import pytest
 
 import astar_ref as AR
+import filter_cases as FLT
 import frontier_cases as FC
 import frontier_ref as F
 import gridslam_ref as GS
 import locate_cases as LC
+import loc_ref
 import locate_ref as L
 import match_ref as MR
 import mcl_checks as MC
@@ -40,6 +42,7 @@ from oracle import c_oracle as co
 from oracle import oracle_np as on
 from pipeline_order_cases import LEGS
 from test_gpu_match import same_match
+from test_gpu_node_replay import assert_matches_host, host_node
 from test_gpu_raycast import ref_raycast, same
 from test_gpu_view import check as check_view
 
@@ -706,6 +709,86 @@ def leg_replay_chain_map(e):
 
 def leg_replay_chain_no_map(e):
     chain_leg(e, False)
+
+
+# the three nodes that take a start pose: x0 / pose0 is the last row of P
+def leg_ekf_lm(e):
+    """slam_ekf_lm_dev from x0 = B's last pose: three steps of circle-drive odometry that see one landmark, then a second one
+    beside it, then both again (the first trajectory of test_ekf_past_the_group_count)."""
+    t = e.torch
+    max_lm, steps, N = 2, 3, 7
+    u = np.tile(FLT.ODOMETRY, (1, steps, 1))
+    rows = [[(3.0, 0.2)], [(3.1, 0.1), (4.0, 2.0)], [(3.0, -0.1), (4.1, 1.8)]]
+    z = np.array([r for s in rows for r in s], dtype=np.float64)
+    off = np.concatenate([[0], np.cumsum([len(s) for s in rows])]).astype(np.int64)
+
+    def ref(poses):
+        r = FLT.host_run(u[0], [np.array(s, dtype=np.float64).reshape(-1, 2) for s in rows], poses[-1], max_lm)
+        assert r["status"] == FLT.OK and r["nlm"] == [1, 2, 2]
+        return [r["x"], r["P"]]
+    want = e.pose_answers(ref, by=1e-3)
+    d_u, d_off, d_z, d_n = e.up(u), e.up(off), e.up(z), e.up(np.full(1, steps, dtype=np.int32))
+    x0 = e.tail(1)
+    x, P = t.empty((1, N), dtype=t.float64, device=e.dev), t.empty((1, N, N), dtype=t.float64, device=e.dev)
+    nlm, status = t.empty((1, steps), dtype=t.int32, device=e.dev), t.empty(1, dtype=t.int32, device=e.dev)
+    e.race(lambda: e.A.check(e.A.lib().slam_ekf_lm_dev(e.ctx.handle, x0.data_ptr(), d_u.data_ptr(), d_n.data_ptr(), d_off.data_ptr(),
+                                                       d_z.data_ptr(), len(z), 1, steps, max_lm, x.data_ptr(), P.data_ptr(),
+                                                       nlm.data_ptr(), status.data_ptr())))
+    assert status.cpu().numpy().tolist() == [FLT.OK] and nlm.cpu().numpy().tolist() == [[1, 2, 2]]
+    dx, dP = np.max(np.abs(x.cpu().numpy()[0] - want[0])), np.max(np.abs(P.cpu().numpy()[0] - want[1]))
+    assert dx < 1e-9 and dP < 1e-9, (dx, dP)              # the bar of test_ekf_past_the_group_count (and of check_trajectory)
+
+
+NODE_SCANS = (48, 49, 53, 56)                   # scans of B that show a landmark (a pillar seen edge-on): the node keeps them all
+
+
+def leg_node_replay(e):
+    """slam_node_replay_dev (no map) from pose0 = B's last pose, over four of B's scans."""
+    scans = np.ascontiguousarray(e.rep["B"].ranges[list(NODE_SCANS)])
+
+    def ref(poses):
+        class Started:                          # host_node builds its node itself: hand it one that starts at the pose
+            LaserScan = e.slam.LaserScan
+
+            @staticmethod
+            def SLAM_EKF(**kw):
+                node = e.slam.SLAM_EKF(**kw)
+                node.xEst = np.array(poses[-1], dtype=np.float64).reshape(3, 1)
+                return node
+        r = host_node(Started, scans)
+        assert r["kept"] == list(range(len(scans))) and not r["raised"] and len(r["nlm"]) == len(scans) - 1
+        return r
+    want = e.pose_answers(ref, by=1e-3)
+    rep = e.slam.DeviceNodeReplay(scans, AMIN, AMAX, max_lm=8)
+    rep.ctx.close()
+    rep.ctx, rep.pose0 = e.ctx, e.tail(1)
+    e.torch.cuda.synchronize()
+    e.race(rep.run)
+    assert_matches_host(rep.results(), 0, want)           # the bars of tests/test_gpu_node_replay.py: counts exact, states within 1e-9
+
+
+LOC_SCANS = (119, 118, 117)                     # B's last scans, backwards: the first was taken at B's last pose
+
+
+def leg_loc_replay(e):
+    """slam_loc_replay_dev from pose0 = B's last pose against the occupied cells of B's map, over B's last three scans."""
+    ranges = np.ascontiguousarray(e.rep["B"].ranges[list(LOC_SCANS)])
+    keys = ("xest", "xodom", "P", "T_obs", "T_odom")
+
+    def ref(poses):
+        r = loc_ref.chain(ranges, e.obst, AMIN, AMAX, poses[-1])
+        return [r[k] for k in keys] + [r["iters_obs"]]
+    want = e.pose_answers(ref, by=1e-3)
+    _, worst = loc_ref.stable(ranges, e.obst, AMIN, AMAX, e.want["B"]["poses"][-1])
+    assert worst < 1e-10                                  # B's last pose sits away from the chain's discontinuities
+    rep = e.slam.DeviceLocalizationReplay(ranges, AMIN, AMAX, e.obst, pose0=np.zeros((1, 3)), context=e.ctx)
+    rep.pose0 = e.tail(1)
+    e.race(rep.run)
+    o = rep.results()
+    assert o["status"].tolist() == [0] and o["iters_obs"][0].tolist() == want[-1].tolist()
+    for k, w in zip(keys, want):                          # the bars of test_against_oracle_chain
+        d = float(np.max(np.abs(o[k][0] - w)))
+        assert d < 1e-9, (k, d)
 
 
 # ------------------------------------------------------------------ P, written while the map stage reads it
