@@ -17,7 +17,10 @@ zjwzcx/A-2D-LiDAR-based-SLAM-System-for-Wheeled-Mobile-Robots:
                DeviceGrid.travel, grid_travel_host; DeviceGridSLAM.travel / .next_goals); view_gain /
                next_goal(by="gain"): the cells a scan from a pose would reveal, and the frontier that reveals the most
                unknown cells per unit of travel (batched: DeviceGrid.view_gain, grid_view_gain_host, view_poses,
-               gain_goal; GridSLAM / DeviceGridSLAM .view_gain, DeviceGridSLAM.next_goals(by="gain"))
+               gain_goal; GridSLAM / DeviceGridSLAM .view_gain, DeviceGridSLAM.next_goals(by="gain")); refine_scan /
+               match_scan(refine=k): a matched pose moved below the cell by damped Gauss-Newton steps on the smooth
+               distance field, with the 3 x 3 normal matrix of the fit (batched: DeviceGrid.refine, grid_refine_host,
+               refine_normal; include/slam_refine.h)
     bresenham  (start, end).path
     SLAM_EKF   laserCallback glue (scan matching + map building); landmarks=True: the whole W12
                node with Extraction and the landmark EKF on the host; batched on the device
@@ -44,6 +47,7 @@ from ._abi import Context, LibraryMissing, SlamError, default_context
 from ._abi import TRAVEL_DIAGONAL, TRAVEL_STRAIGHT, TRAVEL_TRIPS
 from ._abi import RAY_BAD, RAY_BLOCKED, RAY_CLASSES, RAY_EMPTY, RAY_FREE, RAY_HIT, RAY_NAMES, RAY_OUT, RAY_UNKNOWN
 from ._abi import VIEW_COUNTS, VIEW_FREE, VIEW_OCCUPIED, VIEW_OPEN, VIEW_UNKNOWN
+from ._abi import REFINE_BAD_POSE, REFINE_NO_MAP, REFINE_NORMAL_LEN, REFINE_OK
 from . import dwa
 from .bresenham import bresenham, rasterize
 from .dwa import DeviceDWA, dwa_batch_host, dwa_control
@@ -64,6 +68,7 @@ from .grid import grid_copy_maps_host, grid_update_particles_host
 from .grid import grid_locate_host, locate_pose, locate_rotations
 from .grid import frontier_points, grid_frontiers_host, grid_travel_host
 from .grid import gain_goal, grid_view_gain_host, view_poses, view_tables
+from .grid import grid_refine_host, refine_normal
 from .replay import DeviceReplay, icp_batch_host, particles_host, prior_matrices, replay_host
 from .grid_slam import DeviceGridSLAM, GridSLAM
 from .slam_ekf import SLAM_EKF
@@ -81,4 +86,5 @@ __all__ = ["ICP", "Mapping", "Localization", "EKF", "Extraction", "LandMarkSet",
            "MCL", "DeviceMCL", "MCL_DEAD", "mcl_weight_table", "mcl_weigh_host", "mcl_resample_host",
            "GridSLAM", "DeviceGridSLAM", "mcl_settle_host", "grid_copy_maps_host", "grid_update_particles_host",
            "RAY_EMPTY", "RAY_HIT", "RAY_BLOCKED", "RAY_FREE", "RAY_UNKNOWN", "RAY_OUT", "RAY_BAD", "RAY_CLASSES", "RAY_NAMES",
-           "grid_view_gain_host", "view_poses", "view_tables", "gain_goal", "VIEW_UNKNOWN", "VIEW_FREE", "VIEW_OCCUPIED", "VIEW_OPEN", "VIEW_COUNTS"]
+           "grid_view_gain_host", "view_poses", "view_tables", "gain_goal", "VIEW_UNKNOWN", "VIEW_FREE", "VIEW_OCCUPIED", "VIEW_OPEN", "VIEW_COUNTS",
+           "grid_refine_host", "refine_normal", "REFINE_OK", "REFINE_BAD_POSE", "REFINE_NO_MAP", "REFINE_NORMAL_LEN"]

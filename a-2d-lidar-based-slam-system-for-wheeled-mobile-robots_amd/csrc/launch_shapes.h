@@ -753,4 +753,31 @@ inline ViewShape plan_view(const ViewRequest &r)
     return p;
 }
 
+// ---------------------------------------------------------------------------------
+// Refinement of a scan-to-map pose (refine_kernels.hip, slam_grid_refine)
+// ---------------------------------------------------------------------------------
+// One WAVE owns a hypothesis through all its iterations: its lanes take the beams, its sums go through a butterfly and
+// every lane solves the same 3 x 3 system.  Four waves share a 256-thread workgroup (no LDS, no barrier: they only share
+// the launch), so a launch has ceil(B / 4) workgroups, kRefineMaxBlocks at most; the hypotheses beyond
+// kRefineMaxBlocks * kRefineWaves are taken grid-stride.  Nothing here depends on n: a hypothesis's sums must not
+// depend on the batch, so the shape may not either.
+constexpr int kRefineWaves = 4;              // hypotheses per workgroup
+constexpr int kRefineThreads = kRefineWaves * kWave;
+constexpr long kRefineMaxBlocks = 16384;     // workgroups of a launch: 64 waves a CU of a 256-CU chip, eight rounds of residency
+struct RefineShape {
+    long blocks = 0;             // workgroups the batch needs
+    long grid = 0;               // workgroups launched
+    long pass = 0;               // hypotheses one sweep of the launch takes: grid * kRefineWaves
+    int threads = kRefineThreads;
+};
+SLAM_HD inline RefineShape plan_refine(long B)
+{
+    RefineShape p;
+    if (B < 1) return p;
+    p.blocks = (B + kRefineWaves - 1) / kRefineWaves;
+    p.grid = p.blocks < kRefineMaxBlocks ? p.blocks : kRefineMaxBlocks;
+    p.pass = p.grid * kRefineWaves;
+    return p;
+}
+
 }  // namespace slam

@@ -156,19 +156,7 @@ __global__ void __launch_bounds__(256) k_mcl_weigh(MclWeighArgs a)
     lds_guard_check(guard, g.status);
 }
 
-// ---- 64-bit values across a wave ----------------------------------------------------------------------------------
-template <typename T>
-__device__ __forceinline__ T shfl64(T v, int src)
-{
-    static_assert(sizeof(T) == 8, "64-bit values");
-    unsigned long long u;
-    memcpy(&u, &v, 8);
-    const unsigned hi = __shfl((unsigned)(u >> 32), src, kWave), lo = __shfl((unsigned)u, src, kWave);
-    u = ((unsigned long long)hi << 32) | lo;
-    memcpy(&v, &u, 8);
-    return v;
-}
-
+// (shfl64, a 64-bit value across a wave: slam_internal.h)
 // The other shape: a wave per particle, lanes over the beams, the cost summed across the wave.  Group = (filter f,
 // kMclWaveRun particles of it), a quarter of them per wave.  First the lanes of a wave each move ONE of its particles and
 // take the cosine and sine of its heading (so that work is not repeated by 64 lanes); then the wave goes through its

@@ -961,6 +961,11 @@ int slam_plan_query(const char *name, int a, int b, int c, int guard, int64_t *o
         {"view_window_words", view_box_plan(a, b, c, g).window_words}, {"view_lds_bytes", view_box_plan(a, b, c, g).lds_bytes},
         {"view_engine", view_box_plan(a, b, c, g).engine_lds ? 1 : 0},
         {"view_chunk_views", view_plan_chunk(a, b, c, false)}, {"view_chunks", view_plan_chunk(a, b, c, true)},
+        // slam_grid_refine: a = B.  "refine": the workgroups of its launch; refine_blocks: those the batch needs; refine_pass:
+        // the hypotheses one sweep of the launch takes; refine_cap: the most a launch takes in one sweep, whatever B
+        {"kRefineWaves", kRefineWaves}, {"kRefineThreads", kRefineThreads}, {"kRefineMaxBlocks", (int64_t)kRefineMaxBlocks},
+        {"refine", (int64_t)plan_refine(a).grid}, {"refine_blocks", (int64_t)plan_refine(a).blocks},
+        {"refine_pass", (int64_t)plan_refine(a).pass}, {"refine_cap", (int64_t)(kRefineMaxBlocks * kRefineWaves)},
         // the ray casts of large maps: a = scans of the cast (L * scans), b = beams, c = groups: where the engine's layout ends
         {"wedge_ws_bytes", (int64_t)cast_layout_bytes(CastPath::Wedges, (long)a * b, a, c)},
         {"tile_ws_bytes", (int64_t)cast_layout_bytes(CastPath::Tiles, (long)a * b, a, c)},
@@ -1787,6 +1792,65 @@ int slam_grid_match(slam_ctx *c, slam_grid *g, const float *ranges, int shared, 
     TRY(s.upload());
     TRY(slam_grid_match_dev(c, g, d_r, shared, d_ctr, B, d_g, d_c, d_s, n, d_rot, K, nx, ny, step, max_range, cap, d_best,
                             d_cost, d_used, d_vol));
+    return s.download();
+}
+
+// ---- refinement of a scan-to-map pose below the cell (refine_kernels.hip, include/slam_refine.h) ---------------------
+static int check_refine(const char *fn, const slam_grid *g, const float *ranges, const double *poses, int B, const double *cos_t,
+                        const double *sin_t, int n, int iters, double damping, double step_cells, double step_rad, float max_range,
+                        int cap, const double *pose_out, const double *cost_out, const int32_t *status_out)
+{
+    REQUIRE_IN(fn, g && ranges && poses && cos_t && sin_t && pose_out && cost_out && status_out, "null pointer");
+    REQUIRE_IN(fn, cap >= 1 && cap <= 32767, "cap outside [1, 32767]");
+    REQUIRE_IN(fn, n >= 1 && n <= 4096, "n outside [1, 4096]");
+    REQUIRE_IN(fn, B >= 1 && (long)B * n < (1L << 31), "B < 1 or B * n >= 2^31");
+    REQUIRE_IN(fn, iters >= 0 && iters <= 64, "iters outside [0, 64]");
+    REQUIRE_IN(fn, std::isfinite(damping) && damping >= 0, "damping must be finite and >= 0");
+    REQUIRE_IN(fn, step_cells > 0 && step_rad > 0, "step_cells and step_rad must be > 0");
+    REQUIRE_IN(fn, max_range > 0, "max_range must be > 0");
+    return SLAM_OK;
+}
+
+int slam_grid_refine_dev(slam_ctx *c, slam_grid *g, const float *ranges, int shared, const double *poses, int B,
+                         const int32_t *grid_of_batch, const double *cos_t, const double *sin_t, int n, int iters, double damping,
+                         double step_cells, double step_rad, float max_range, int cap, const int16_t *field, double *pose_out,
+                         double *cost_out, int32_t *used_out, double *normal_out, int32_t *status_out)
+{
+    TRY(use(c));
+    TRY(check_refine(__func__, g, ranges, poses, B, cos_t, sin_t, n, iters, damping, step_cells, step_rad, max_range, cap, pose_out,
+                     cost_out, status_out));
+    int16_t *built = nullptr;
+    if (!field) TRY(build_field(c, g, cap, Layout(), built));      // (joins the internal streams first, as grid_on_main does)
+    else TRY(grid_on_main(c));
+    RefineArgs a;
+    a.g = g->d; a.field = field ? field : built;
+    a.ranges = ranges; a.range_stride = shared ? 0 : n;
+    a.poses = poses; a.maps = grid_of_batch; a.cos_t = cos_t; a.sin_t = sin_t;
+    a.B = B; a.n = n; a.iters = iters; a.damping = damping; a.step_xy = step_cells / g->d.scale; a.step_rad = step_rad;
+    a.max_range = max_range; a.cap = cap;
+    a.pose_out = pose_out; a.cost_out = cost_out; a.used_out = used_out; a.normal_out = normal_out; a.status_out = status_out;
+    Timed t(c, SLAM_K_GRID);
+    HIPCHK(launch_refine(a, c->stream));
+    return SLAM_OK;
+}
+
+int slam_grid_refine(slam_ctx *c, slam_grid *g, const float *ranges, int shared, const double *poses, int B,
+                     const int32_t *grid_of_batch, const double *cos_t, const double *sin_t, int n, int iters, double damping,
+                     double step_cells, double step_rad, float max_range, int cap, const int16_t *field, double *pose_out,
+                     double *cost_out, int32_t *used_out, double *normal_out, int32_t *status_out)
+{
+    TRY(use(c));
+    TRY(check_refine(__func__, g, ranges, poses, B, cos_t, sin_t, n, iters, damping, step_cells, step_rad, max_range, cap, pose_out,
+                     cost_out, status_out));
+    float *d_r; double *d_p, *d_c, *d_s, *d_po, *d_co, *d_no; int32_t *d_g, *d_used, *d_st; int16_t *d_f;
+    Staging s(c);
+    s.in(d_r, ranges, shared ? (size_t)n : (size_t)B * n).in(d_p, poses, (size_t)B * 3).in(d_g, grid_of_batch, B).in(d_c, cos_t, n)
+        .in(d_s, sin_t, n).in(d_f, field, (size_t)g->d.G * g->d.xw * g->d.yw).out(d_po, pose_out, (size_t)B * 3)
+        .out(d_co, cost_out, (size_t)B * 2).out(d_used, used_out, B).out(d_no, normal_out, (size_t)B * SLAM_REFINE_NORMAL_LEN)
+        .out(d_st, status_out, B);
+    TRY(s.upload());
+    TRY(slam_grid_refine_dev(c, g, d_r, shared, d_p, B, d_g, d_c, d_s, n, iters, damping, step_cells, step_rad, max_range, cap, d_f,
+                             d_po, d_co, d_used, d_no, d_st));
     return s.download();
 }
 

@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include "slam_hip.h"
+#include "slam_refine.h"
 #include "launch_shapes.h"
 
 #include <hip/hip_ext.h>
@@ -61,6 +62,19 @@ __device__ __forceinline__ void lds_guard_check(const char *p, int *status)
     bool bad = false;
     for (int i = threadIdx.x; i < kLdsGuard / 4; i += blockDim.x) bad |= reinterpret_cast<const unsigned *>(p)[i] != 0xA5A5A5A5u;
     if (bad && status) atomicOr(status, kStatusGuard);
+}
+
+// a 64-bit value across a wave: lane `src`'s v
+template <typename T>
+__device__ __forceinline__ T shfl64(T v, int src)
+{
+    static_assert(sizeof(T) == 8, "64-bit values");
+    unsigned long long u;
+    memcpy(&u, &v, 8);
+    const unsigned hi = __shfl((unsigned)(u >> 32), src, kWave), lo = __shfl((unsigned)u, src, kWave);
+    u = ((unsigned long long)hi << 32) | lo;
+    memcpy(&v, &u, 8);
+    return v;
 }
 #endif
 
@@ -250,6 +264,28 @@ size_t field_rowd_bytes(const GridDev &g);   // workspace of launch_distance_fie
 // mask: launch_raycast_pack's words; rowd: field_rowd_bytes(g) bytes of workspace; field [G][xw][yw]; 1 <= cap <= 32767
 hipError_t launch_distance_field(const GridDev &g, const uint32_t *mask, int cap, uint8_t *rowd, int16_t *field, hipStream_t s);
 hipError_t launch_match(MatchArgs a, hipStream_t s);
+
+// ---- refinement of a scan-to-map pose below the cell (refine_kernels.hip, include/slam_refine.h) ----
+struct RefineArgs {
+    GridDev g;
+    const int16_t *field = nullptr;          // [G][xw][yw] (launch_distance_field at the same cap)
+    const float *ranges = nullptr;           // [B][n], or one [n] with range_stride 0
+    long range_stride = 0;
+    const double *poses = nullptr;           // [B][3]
+    const int32_t *maps = nullptr;           // nullable [B]: the map of every hypothesis (an entry outside [0, G): SLAM_REFINE_NO_MAP)
+    const double *cos_t = nullptr, *sin_t = nullptr;
+    int B = 0, n = 0, iters = 0;
+    double damping = 0.0;
+    double step_xy = 0.0, step_rad = 0.0;    // the clamps of a step: step_cells / scale metres, radians
+    float max_range = 0.f;
+    int cap = 0;
+    double *pose_out = nullptr;              // [B][3]
+    double *cost_out = nullptr;              // [B][2]
+    int32_t *used_out = nullptr;             // nullable [B]
+    double *normal_out = nullptr;            // nullable [B][9]
+    int32_t *status_out = nullptr;           // [B]
+};
+hipError_t launch_refine(const RefineArgs &a, hipStream_t s);
 
 // ---- global scan localisation on a pyramid of the field (locate_kernels.hip) --------------
 // Level h of the pyramid: P_h[x][y] for -pad <= x < xw, -pad <= y < yw (pad = 2^h - 1) at base[(gi * X + x + pad) * Y + y + pad];

@@ -191,6 +191,41 @@ def grid_match_host(grid, ranges, centres, cos_t, sin_t, rot_cs, nx, ny, step, m
     return (best, cost, used, vol) if return_costs else (best, cost, used)
 
 
+def grid_refine_host(grid, ranges, poses, cos_t, sin_t, iters=10, damping=1e-3, step_cells=0.5, step_rad=0.02, max_range=30.0,
+                     cap=64, grid_of_batch=None, field=None, return_normal=False):
+    """Poses refined below the cell (``slam_grid_refine``, include/slam_refine.h): ``iters`` damped Gauss-Newton steps of
+    every pose [B, 3] on the bilinear interpolation of the square root of its map's distance field, each step clamped to
+    ``step_cells`` cells in x and y and ``step_rad`` radians.  ranges float32 [B, n] or one shared [n]; ``field`` None:
+    the field is rebuilt by the call, else int16 [G, xw, yw] of :func:`grid_distance_field_host` at the same ``cap``.
+    Returns (poses [B, 3], cost float64 [B, 2] at the start and at the end, used int32 [B], status int32 [B]
+    (``_abi.REFINE_*``)) and with ``return_normal`` also normal float64 [B, 9] = (Hxx, Hxy, Hxt, Hyy, Hyt, Htt, gx, gy,
+    gt) of the last evaluation.  The call never chooses between start and end; the costs let the caller."""
+    p, gob = _batch_args(poses, grid_of_batch)
+    ct, st = _tables(cos_t, sin_t)
+    B, n = p.shape[0], ct.shape[0]
+    r = np.ascontiguousarray(np.asarray(ranges, dtype=np.float32))
+    shared = r.ndim == 1
+    if r.shape != ((n,) if shared else (B, n)):
+        raise ValueError("ranges must be [n] or [B, n]")
+    f = None if field is None else np.ascontiguousarray(np.asarray(field, dtype=np.int16))
+    if f is not None and f.shape != (grid.G, grid.xw, grid.yw):
+        raise ValueError("field must be [G, xw, yw]")
+    out, cost = np.empty((B, 3), dtype=np.float64), np.empty((B, 2), dtype=np.float64)
+    used, status = np.empty(B, dtype=np.int32), np.empty(B, dtype=np.int32)
+    normal = np.empty((B, _abi.REFINE_NORMAL_LEN), dtype=np.float64) if return_normal else None
+    _abi.check(_abi.lib().slam_grid_refine(grid._ctx.handle, grid._h, _abi.ptr(r), int(shared), _abi.ptr(p), B, _abi.ptr(gob),
+                                           _abi.ptr(ct), _abi.ptr(st), n, int(iters), float(damping), float(step_cells),
+                                           float(step_rad), float(max_range), int(cap), _abi.ptr(f), _abi.ptr(out), _abi.ptr(cost),
+                                           _abi.ptr(used), _abi.ptr(normal), _abi.ptr(status)))
+    return (out, cost, used, status, normal) if return_normal else (out, cost, used, status)
+
+
+def refine_normal(normal):
+    """(H [..., 3, 3] symmetric, g [..., 3]) of ``normal`` [..., 9] = (Hxx, Hxy, Hxt, Hyy, Hyt, Htt, gx, gy, gt)."""
+    v = np.asarray(normal, dtype=np.float64)
+    return v[..., [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(v.shape[:-1] + (3, 3)), v[..., 6:9].copy()
+
+
 def grid_locate_host(grid, ranges, cos_t, sin_t, rot_cs, levels=5, region=None, max_range=30.0, cap=64, grid_of_batch=None,
                      B=None, return_stats=False):
     """Global scan localisation (``slam_grid_locate``): the best pose of every scan over its whole map, or over
@@ -561,6 +596,28 @@ class DeviceGrid:
                                                   int(cap), _abi.ptr(best_out), _abi.ptr(cost_out), _abi.ptr(used_out),
                                                   _abi.ptr(costs_out)))
         return (best_out, cost_out, used_out) if costs_out is None else (best_out, cost_out, used_out, costs_out)
+
+    def refine(self, ranges, poses, cos_t, sin_t, iters=10, damping=1e-3, step_cells=0.5, step_rad=0.02, max_range=30.0, cap=64,
+               grid_of_batch=None, field=None, out=None, return_normal=False):
+        """``slam_grid_refine_dev`` on torch device tensors: ranges float32 [B, n] or a shared [n], poses float64 [B, 3],
+        cos_t / sin_t float64 [n], grid_of_batch int32 [B] or None, field int16 [G, xw, yw] of :meth:`distance_field` at
+        the same ``cap`` or None (rebuilt by the call).  Writes poses float64 [B, 3], cost float64 [B, 2], used int32 [B]
+        and status int32 [B] (and normal float64 [B, 9]) into the tensors of ``out`` (a tuple in that order) or into fresh
+        ones and returns them; enqueued on the context's stream, no synchronise."""
+        import torch
+        B, n = int(poses.shape[0]), int(cos_t.shape[0])
+        if out is None:
+            new = lambda dtype, *shape: torch.empty(shape, dtype=dtype, device=poses.device)
+            out = (new(torch.float64, B, 3), new(torch.float64, B, 2), new(torch.int32, B), new(torch.int32, B))
+            if return_normal:
+                out += (new(torch.float64, B, _abi.REFINE_NORMAL_LEN),)
+        normal = out[4] if len(out) > 4 else None
+        _abi.check(_abi.lib().slam_grid_refine_dev(self._ctx.handle, self._h, _abi.ptr(ranges), int(ranges.dim() == 1), _abi.ptr(poses),
+                                                   B, _abi.ptr(grid_of_batch), _abi.ptr(cos_t), _abi.ptr(sin_t), n, int(iters),
+                                                   float(damping), float(step_cells), float(step_rad), float(max_range), int(cap),
+                                                   _abi.ptr(field), _abi.ptr(out[0]), _abi.ptr(out[1]), _abi.ptr(out[2]),
+                                                   _abi.ptr(normal), _abi.ptr(out[3])))
+        return out
 
     def locate(self, ranges, cos_t, sin_t, rot_cs, levels=5, region=None, max_range=30.0, cap=64, grid_of_batch=None, B=None,
                best_out=None, cost_out=None, used_out=None, stats_out=None, return_stats=False):

@@ -30,8 +30,8 @@ import numpy as np
 from . import _abi
 from .grid import (DeviceGrid, _first, _one_or_many, clearance_cells2, frontier_dict, frontier_points, gain_goal,
                    grid_distance_field_host, grid_frontiers_host, grid_locate_host, grid_match_host, grid_raycast_host,
-                   grid_score_host, grid_travel_host, grid_view_gain_host, locate_pose, locate_rotations, match_pose,
-                   match_rotations, nearest_goal, pose_cell, travel_goal, view_poses, view_tables)
+                   grid_refine_host, grid_score_host, grid_travel_host, grid_view_gain_host, locate_pose, locate_rotations,
+                   match_pose, match_rotations, nearest_goal, pose_cell, refine_normal, travel_goal, view_poses, view_tables)
 
 
 class Mapping:
@@ -154,14 +154,37 @@ class Mapping:
         Rebuilt from the live counters on every call."""
         return _first(grid_distance_field_host(self.grid, cap))
 
+    def refine_scan(self, ranges, angle_min, angle_max, pose, iters=10, damping=1e-3, max_step=(0.5, 0.02), max_range=30.0, cap=64,
+                    return_normal=False):
+        """``pose`` (x, y, theta) moved below the cell to where the scan fits this map (``slam_grid_refine``): ``iters``
+        damped Gauss-Newton steps on the smooth distance field, each clamped to ``max_step`` = (cells in x and y, radians).
+        The cost is the sum over the used beams of the squared interpolated distance, in cells.  Returns (pose [3], cost,
+        used beams) and with ``return_normal`` also H [3, 3] and g [3] of the fit at the returned pose: the information
+        matrix of the scan-to-map constraint, up to the measurement variance, and its gradient.  The device rule has no
+        decisions; THIS method adds one on the host: when the end costs more than the start, the start pose and its cost
+        (and, with ``return_normal``, its H and g, from a call of no iterations) are returned.  A pose the call cannot
+        answer (status 1) comes back unchanged with cost -1."""
+        r = np.asarray(ranges, dtype=np.float32).reshape(-1)
+        p = np.asarray(pose, dtype=np.float64).reshape(3)
+        ct, st = _abi.trig_tables(angle_min, angle_max, r.shape[0])
+        kw = dict(damping=damping, step_cells=max_step[0], step_rad=max_step[1], max_range=max_range, cap=cap, return_normal=return_normal)
+        got = _first(grid_refine_host(self.grid, r, p, ct, st, iters=iters, **kw))
+        if got[1][1] > got[1][0]:                   # the end costs more: keep the start
+            got = _first(grid_refine_host(self.grid, r, p, ct, st, iters=0, **kw)) if return_normal else (p.copy(), got[1][[0, 0]], got[2])
+        out = (got[0], float(got[1][1]), int(got[2]))
+        return out + refine_normal(got[4]) if return_normal else out
+
     def match_scan(self, ranges, angle_min, angle_max, pose, window=(4, 4), step=None, n_rot=11, rot_step=0.01,
-                   max_range=30.0, cap=64, return_costs=False):
+                   max_range=30.0, cap=64, return_costs=False, refine=0):
         """Where a measured scan fits this map best near ``pose`` (x, y, theta) (``slam_grid_match``): every pose of
         the window - ``n_rot`` rotations theta + (k - n_rot // 2) * rot_step, (2 window[0] + 1) x (2 window[1] + 1)
         translations of ``step`` (default: one cell, 1 / index_scale) - costs the sum over the beams shorter than
         ``max_range`` of the distance-field value at the beam's end cell (``cap`` off the map).  Returns (pose [3],
         cost, used beams) of the cheapest candidate, ties to the lowest (rotation, x, y) index, and with
-        ``return_costs`` also the cost volume int32 [n_rot, 2 window[0] + 1, 2 window[1] + 1]."""
+        ``return_costs`` also the cost volume int32 [n_rot, 2 window[0] + 1, 2 window[1] + 1].  ``refine`` = k > 0: the
+        winner is then moved below the cell by :meth:`refine_scan` with k iterations at the same ``max_range`` and
+        ``cap``, and (pose, cost, used) are that call's - the cost a float, in squared cells of the smooth field; a
+        window without a winner is returned as it is.  ``refine`` = 0: nothing but the window match."""
         r = np.asarray(ranges, dtype=np.float32).reshape(-1)
         p = np.asarray(pose, dtype=np.float64).reshape(3)
         nx, ny = int(window[0]), int(window[1])
@@ -170,7 +193,10 @@ class Mapping:
         th, rot = match_rotations(p[2:3], n_rot, rot_step)
         got = _first(grid_match_host(self.grid, r, p[None, :2], ct, st, rot, nx, ny, step, max_range=max_range, cap=cap,
                                      return_costs=return_costs))
-        return (match_pose(p[None, :2], th, got[0], nx, ny, step)[0], int(got[1]), int(got[2])) + got[3:]
+        out = (match_pose(p[None, :2], th, got[0], nx, ny, step)[0], int(got[1]), int(got[2]))
+        if int(refine) > 0 and got[0] >= 0:
+            out = self.refine_scan(r, angle_min, angle_max, out[0], iters=int(refine), max_range=max_range, cap=cap)
+        return out + got[3:]
 
     def locate_scan(self, ranges, angle_min, angle_max, n_rot=256, levels=5, region=None, max_range=30.0, cap=64):
         """Where in this map a measured scan was taken (``slam_grid_locate``): the cheapest of ``n_rot`` rotations over the
