@@ -33,6 +33,9 @@ zjwzcx/A-2D-LiDAR-based-SLAM-System-for-Wheeled-Mobile-Robots:
                resampling (in place; only the maps of particles that died are copied); batched and device-resident
                as DeviceGridSLAM, on NumPy arrays as mcl_weigh_host(own_maps=True) / mcl_settle_host /
                grid_copy_maps_host / grid_update_particles_host (DeviceGrid.copy_maps / .update_particles)
+    ScanTracker  scan-to-map tracking: every scan matched against the map so far, refined below the cell and, behind a
+               keyframe gate, integrated - one call per scan stream (include/slam_track.h); batched and
+               device-resident as DeviceTracker, on NumPy arrays as track_host (track_rotations, new_state)
     dwa        dwa_control / Config / RobotType (course_agv_nav DWA local planner), batched as
                DeviceDWA / dwa_batch_host; LocalPlanner: the local planner node without ROS
     global_planner  find_path(...).start_find() / GlobalPlanner (course_agv_nav A*), batched as
@@ -48,6 +51,7 @@ from ._abi import TRAVEL_DIAGONAL, TRAVEL_STRAIGHT, TRAVEL_TRIPS
 from ._abi import RAY_BAD, RAY_BLOCKED, RAY_CLASSES, RAY_EMPTY, RAY_FREE, RAY_HIT, RAY_NAMES, RAY_OUT, RAY_UNKNOWN
 from ._abi import VIEW_COUNTS, VIEW_FREE, VIEW_OCCUPIED, VIEW_OPEN, VIEW_UNKNOWN
 from ._abi import REFINE_BAD_POSE, REFINE_NO_MAP, REFINE_NORMAL_LEN, REFINE_OK
+from ._abi import TRACK_INTEGRATED, TRACK_LOST, TRACK_MATCHED, TRACK_REFINED
 from . import dwa
 from .bresenham import bresenham, rasterize
 from .dwa import DeviceDWA, dwa_batch_host, dwa_control
@@ -72,6 +76,7 @@ from .grid import grid_refine_host, refine_normal
 from .replay import DeviceReplay, icp_batch_host, particles_host, prior_matrices, replay_host
 from .grid_slam import DeviceGridSLAM, GridSLAM
 from .slam_ekf import SLAM_EKF
+from .tracker import DeviceTracker, ScanTracker, new_state, track_host, track_rotations
 from .synthetic import LaserScan
 
 __all__ = ["ICP", "Mapping", "Localization", "EKF", "Extraction", "LandMarkSet", "bresenham", "rasterize", "SLAM_EKF", "LaserScan", "Context", "default_context",
@@ -87,4 +92,6 @@ __all__ = ["ICP", "Mapping", "Localization", "EKF", "Extraction", "LandMarkSet",
            "GridSLAM", "DeviceGridSLAM", "mcl_settle_host", "grid_copy_maps_host", "grid_update_particles_host",
            "RAY_EMPTY", "RAY_HIT", "RAY_BLOCKED", "RAY_FREE", "RAY_UNKNOWN", "RAY_OUT", "RAY_BAD", "RAY_CLASSES", "RAY_NAMES",
            "grid_view_gain_host", "view_poses", "view_tables", "gain_goal", "VIEW_UNKNOWN", "VIEW_FREE", "VIEW_OCCUPIED", "VIEW_OPEN", "VIEW_COUNTS",
-           "grid_refine_host", "refine_normal", "REFINE_OK", "REFINE_BAD_POSE", "REFINE_NO_MAP", "REFINE_NORMAL_LEN"]
+           "grid_refine_host", "refine_normal", "REFINE_OK", "REFINE_BAD_POSE", "REFINE_NO_MAP", "REFINE_NORMAL_LEN",
+           "DeviceTracker", "ScanTracker", "track_host", "track_rotations", "new_state",
+           "TRACK_MATCHED", "TRACK_REFINED", "TRACK_INTEGRATED", "TRACK_LOST"]

@@ -22,6 +22,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SLAM_HIP_LIB") or os.path.join(_HERE, "libslamhip.so")   # override: A/B builds
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "slam_hip.h")
 REFINE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "slam_refine.h")     # the second header: slam_grid_refine(_dev)
+TRACK_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "slam_track.h")       # the third header: slam_track(_dev)
 
 SLAM_OK, ERR_INVALID, ERR_HIP, ERR_NOMEM, ERR_NAN, ERR_OVERFLOW, ERR_NODEVICE = 0, -1, -2, -3, -4, -5, -6
 F64, F32, F16 = 0, 1, 2
@@ -82,6 +83,7 @@ def header_signatures(path=HEADER_PATH, text=None):
 
 _SIGS = header_signatures()
 _SIGS_REFINE = header_signatures(REFINE_HEADER_PATH)
+_SIGS_TRACK = header_signatures(TRACK_HEADER_PATH)
 NODE_OK, NODE_REF_RAISES, NODE_LM_CAP, NODE_OBS_CAP = 0, 1, 2, 3
 LOC_OK, LOC_NONFINITE, LOC_BAD_ROUTE = 0, 1, 2
 EKF_MAX_LM = 32
@@ -93,6 +95,9 @@ VIEW_UNKNOWN, VIEW_FREE, VIEW_OCCUPIED, VIEW_OPEN = range(4)
 VIEW_COUNTS = 4
 REFINE_OK, REFINE_BAD_POSE, REFINE_NO_MAP = 0, 1, 2            # status_out of slam_grid_refine (SLAM_REFINE_*)
 REFINE_NORMAL_LEN = 9              # normal_out: Hxx, Hxy, Hxt, Hyy, Hyt, Htt, gx, gy, gt
+# flag bits of slam_track's info_out (SLAM_TRACK_*) and the row lengths of its state, info and trace
+TRACK_MATCHED, TRACK_REFINED, TRACK_INTEGRATED, TRACK_LOST = 1, 2, 4, 8
+TRACK_STATE_LEN, TRACK_INFO_LEN, TRACK_TRACE_LEN = 8, 4, 13
 MCL_DEAD = 2 ** 31 - 1             # SLAM_MCL_DEAD: a dead particle's accumulated cost
 TRAVEL_STRAIGHT, TRAVEL_DIAGONAL, TRAVEL_TRIPS = 10, 14, 1      # SLAM_TRAVEL_*: the two move costs and the trip-bound status
 RAY_NAMES = ("empty", "hit", "blocked", "free", "unknown", "out", "bad")
@@ -123,7 +128,7 @@ def lib():
                 except ImportError:
                     pass
             L = C.CDLL(LIB_PATH)
-            for sigs in (_SIGS, _SIGS_REFINE):
+            for sigs in (_SIGS, _SIGS_REFINE, _SIGS_TRACK):
                 for name, (args, res) in sigs.items():
                     fn = getattr(L, name)
                     fn.argtypes, fn.restype = args, res

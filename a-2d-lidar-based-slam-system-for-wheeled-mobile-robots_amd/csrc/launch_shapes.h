@@ -780,4 +780,27 @@ SLAM_HD inline RefineShape plan_refine(long B)
     return p;
 }
 
+// ---------------------------------------------------------------------------------
+// The scan-to-map tracker's own steps (track_kernels.hip, slam_track)
+// ---------------------------------------------------------------------------------
+// Two shapes for L trajectories.  "Rows": one workgroup of a wave per trajectory, whose lanes copy the scan's n ranges
+// and form the K rotations while lane 0 predicts (k_track_predict).  "Lanes": one lane per trajectory, 256 to a workgroup
+// (k_track_seed, k_track_decide).  Both take the trajectories beyond kTrackMaxBlocks workgroups grid-stride.
+constexpr int kTrackRowThreads = kWave;
+constexpr int kTrackThreads = 256;
+constexpr long kTrackMaxBlocks = 65536;
+struct TrackShape {
+    long row_grid = 0, lane_grid = 0;        // workgroups of the two shapes
+    int row_threads = kTrackRowThreads, lane_threads = kTrackThreads;
+};
+SLAM_HD inline TrackShape plan_track(long L)
+{
+    TrackShape p;
+    if (L < 1) return p;
+    p.row_grid = L < kTrackMaxBlocks ? L : kTrackMaxBlocks;
+    const long lanes = (L + kTrackThreads - 1) / kTrackThreads;
+    p.lane_grid = lanes < kTrackMaxBlocks ? lanes : kTrackMaxBlocks;
+    return p;
+}
+
 }  // namespace slam

@@ -966,6 +966,10 @@ int slam_plan_query(const char *name, int a, int b, int c, int guard, int64_t *o
         {"kRefineWaves", kRefineWaves}, {"kRefineThreads", kRefineThreads}, {"kRefineMaxBlocks", (int64_t)kRefineMaxBlocks},
         {"refine", (int64_t)plan_refine(a).grid}, {"refine_blocks", (int64_t)plan_refine(a).blocks},
         {"refine_pass", (int64_t)plan_refine(a).pass}, {"refine_cap", (int64_t)(kRefineMaxBlocks * kRefineWaves)},
+        // slam_track: a = L.  track_rows: the workgroups of its predict step (one per trajectory); track_lanes: those of its seed
+        // and decide steps (one lane per trajectory)
+        {"kTrackRowThreads", kTrackRowThreads}, {"kTrackThreads", kTrackThreads}, {"kTrackMaxBlocks", (int64_t)kTrackMaxBlocks},
+        {"track_rows", (int64_t)plan_track(a).row_grid}, {"track_lanes", (int64_t)plan_track(a).lane_grid},
         // the ray casts of large maps: a = scans of the cast (L * scans), b = beams, c = groups: where the engine's layout ends
         {"wedge_ws_bytes", (int64_t)cast_layout_bytes(CastPath::Wedges, (long)a * b, a, c)},
         {"tile_ws_bytes", (int64_t)cast_layout_bytes(CastPath::Tiles, (long)a * b, a, c)},
@@ -1694,18 +1698,34 @@ int slam_grid_view_gain(slam_ctx *c, slam_grid *g, const double *poses, int B, c
 // The occupied bits packed as the counters stand on the stream now, then the field of all G maps.  `ws` holds the caller's
 // own pieces of the scratch arena (a copy: the pointers they are bound to are the caller's); the mask, the row distances
 // and, with `field` null, the field (the matcher's own copy) join them, and the arena is reserved for all of them at once.
+// The field's own pieces (field_layout) and its launches in pieces already placed (enqueue_field) are apart for the call
+// that builds the field many times in one workspace (slam_track_dev).
+struct FieldPieces {
+    uint32_t *mask = nullptr;
+    uint8_t *rowd = nullptr;
+};
+
+static void field_layout(const slam_grid *g, Layout &ws, FieldPieces &p, int16_t *&field)
+{
+    ws.add(p.mask, raycast_mask_words(g->d)).add(p.rowd, field_rowd_bytes(g->d));
+    if (!field) ws.add(field, (size_t)g->d.G * g->d.xw * g->d.yw);
+}
+
+static int enqueue_field(slam_ctx *c, slam_grid *g, int cap, const FieldPieces &p, int16_t *field)
+{
+    Timed t(c, SLAM_K_FINALIZE);          // the threshold rule over every cell, as a finalize pass is
+    HIPCHK(launch_raycast_pack(g->d, p.mask, c->stream));
+    HIPCHK(launch_distance_field(g->d, p.mask, cap, p.rowd, field, c->stream));
+    return SLAM_OK;
+}
+
 static int build_field(slam_ctx *c, slam_grid *g, int cap, Layout ws, int16_t *&field)
 {
     TRY(grid_on_main(c));
-    uint32_t *mask;
-    uint8_t *rowd;
-    ws.add(mask, raycast_mask_words(g->d)).add(rowd, field_rowd_bytes(g->d));
-    if (!field) ws.add(field, (size_t)g->d.G * g->d.xw * g->d.yw);
+    FieldPieces p;
+    field_layout(g, ws, p, field);
     TRY(reserve(c, c->scratch, ws));
-    Timed t(c, SLAM_K_FINALIZE);          // the threshold rule over every cell, as a finalize pass is
-    HIPCHK(launch_raycast_pack(g->d, mask, c->stream));
-    HIPCHK(launch_distance_field(g->d, mask, cap, rowd, field, c->stream));
-    return SLAM_OK;
+    return enqueue_field(c, g, cap, p, field);
 }
 
 static int check_field(const char *fn, const slam_grid *g, int cap, const void *out)
@@ -2386,14 +2406,12 @@ static int check_update_particles(const char *fn, const slam_grid *g, const floa
     return SLAM_OK;
 }
 
-int slam_grid_update_particles_dev(slam_ctx *c, slam_grid *g, const float *ranges, const double *cos_t, const double *sin_t,
-                                   const double *poses, const int32_t *acc, int F, int P, int n, int map0)
+// One scan per particle into its own map, through the window path as slam_particles_dev casts its hypotheses: a live
+// pmap stays current.  A launch takes at most 65 535 particles (one workgroup row each).  The caller has checked the
+// arguments and joined the internal streams (slam_grid_update_particles_dev, and slam_track_dev once per scan).
+static int cast_particles(slam_ctx *c, slam_grid *g, const float *ranges, const double *cos_t, const double *sin_t,
+                          const double *poses, const int32_t *acc, int F, int P, int n, int map0)
 {
-    TRY(use(c));
-    TRY(check_update_particles(__func__, g, ranges, cos_t, sin_t, poses, F, P, n, map0));
-    TRY(grid_on_main(c));
-    // One scan per particle into its own map, through the window path as slam_particles_dev casts its hypotheses: a live
-    // pmap stays current.  A launch takes at most 65 535 particles (one workgroup row each).
     g->pristine = false;
     const long L = (long)F * P, span = 65535;
     Timed t(c, SLAM_K_GRID);
@@ -2412,6 +2430,15 @@ int slam_grid_update_particles_dev(slam_ctx *c, slam_grid *g, const float *range
     return SLAM_OK;
 }
 
+int slam_grid_update_particles_dev(slam_ctx *c, slam_grid *g, const float *ranges, const double *cos_t, const double *sin_t,
+                                   const double *poses, const int32_t *acc, int F, int P, int n, int map0)
+{
+    TRY(use(c));
+    TRY(check_update_particles(__func__, g, ranges, cos_t, sin_t, poses, F, P, n, map0));
+    TRY(grid_on_main(c));
+    return cast_particles(c, g, ranges, cos_t, sin_t, poses, acc, F, P, n, map0);
+}
+
 int slam_grid_update_particles(slam_ctx *c, slam_grid *g, const float *ranges, const double *cos_t, const double *sin_t,
                                const double *poses, const int32_t *acc, int F, int P, int n, int map0)
 {
@@ -2423,6 +2450,95 @@ int slam_grid_update_particles(slam_ctx *c, slam_grid *g, const float *ranges, c
     s.in(d_r, ranges, (size_t)F * n).in(d_c, cos_t, n).in(d_s, sin_t, n).in(d_p, poses, FP * 3).in(d_a, acc, FP);
     TRY(s.upload());
     TRY(slam_grid_update_particles_dev(c, g, d_r, d_c, d_s, d_p, d_a, F, P, n, map0));
+    return check_status_sync(c);
+}
+
+// ---- the scan-to-map tracker: match, refine, integrate per scan (track_kernels.hip, include/slam_track.h) -----------
+static int check_track(const char *fn, const slam_grid *g, const float *ranges, int L, int S, const double *cos_t, const double *sin_t,
+                       int n, const double *rot_off, const double *rot_off_cs, int K, int nx, int ny, double step, int iters,
+                       double damping, double step_cells, double step_rad, float max_range, int cap, int min_used, double gate_dist,
+                       double gate_turn, int map0, const double *state, const double *poses_out, const int32_t *info_out)
+{
+    REQUIRE_IN(fn, g && rot_off && state && poses_out && info_out, "null pointer");
+    REQUIRE_IN(fn, L >= 1 && S >= 1, "L < 1 or S < 1");
+    REQUIRE_IN(fn, n >= 1 && (long)L * S * n < (1L << 31), "n < 1 or L * S * n >= 2^31");
+    // (the matcher's and the refinement's own checks, on the arrays they will be given: the outputs are workspace)
+    TRY(check_match(fn, g, ranges, state, L, cos_t, sin_t, n, rot_off_cs, K, nx, ny, step, max_range, cap, info_out, info_out));
+    TRY(check_refine(fn, g, ranges, state, L, cos_t, sin_t, n, iters, damping, step_cells, step_rad, max_range, cap, poses_out, poses_out,
+                     info_out));
+    REQUIRE_IN(fn, map0 >= 0 && (long)map0 + L <= g->d.G, "map0 < 0 or map0 + L > G");
+    REQUIRE_IN(fn, min_used >= 1, "min_used < 1");
+    REQUIRE_IN(fn, gate_dist >= 0 && gate_turn >= 0, "gate_dist and gate_turn must be >= 0 (+inf: never)");      // (false for NaN)
+    return SLAM_OK;
+}
+
+int slam_track_dev(slam_ctx *c, slam_grid *g, const float *ranges, const double *motion, int L, int S, const double *cos_t,
+                   const double *sin_t, int n, const double *rot_off, const double *rot_off_cs, int K, int nx, int ny, double step,
+                   int iters, double damping, double step_cells, double step_rad, float max_range, int cap, int min_used,
+                   double gate_dist, double gate_turn, int map0, double *state, double *poses_out, int32_t *info_out, double *trace_out)
+{
+    TRY(use(c));
+    TRY(check_track(__func__, g, ranges, L, S, cos_t, sin_t, n, rot_off, rot_off_cs, K, nx, ny, step, iters, damping, step_cells,
+                    step_rad, max_range, cap, min_used, gate_dist, gate_turn, map0, state, poses_out, info_out));
+    TRY(grid_on_main(c));
+    // Every piece of every scan's workspace, reserved ONCE: growing the arena synchronises and frees, which nothing may do
+    // while the loop's kernels are in flight.
+    TrackArgs a;
+    FieldPieces fp;
+    int16_t *field = nullptr;
+    Layout ws;
+    field_layout(g, ws, fp, field);
+    ws.add(a.scan, (size_t)L * n).add(a.pred, (size_t)L * 5).add(a.centres, (size_t)L * 2).add(a.rot_cs, (size_t)L * K * 2)
+        .add(a.match_maps, L).add(a.keys, L).add(a.best, L).add(a.best_cost, L).add(a.used, L).add(a.start, (size_t)L * 3)
+        .add(a.refine_maps, L).add(a.refined, (size_t)L * 3).add(a.refine_cost, (size_t)L * 2).add(a.refine_status, L).add(a.acc, L)
+        .add(a.cast_pose, (size_t)L * 3);
+    TRY(reserve(c, c->scratch, ws));
+    a.ranges = ranges; a.motion = motion; a.rot_off = rot_off; a.rot_off_cs = rot_off_cs;
+    a.L = L; a.S = S; a.n = n; a.K = K; a.nx = nx; a.ny = ny; a.step = step; a.min_used = min_used; a.map0 = map0;
+    a.gate_dist = gate_dist; a.gate_turn = gate_turn; a.scale = g->d.scale; a.off_x = g->d.off_x; a.off_y = g->d.off_y;
+    a.state = state; a.poses_out = poses_out; a.info_out = info_out; a.trace_out = trace_out;
+    MatchArgs m;
+    m.g = g->d; m.field = field; m.ranges = a.scan; m.range_stride = n; m.centres = a.centres; m.maps = a.match_maps;
+    m.cos_t = cos_t; m.sin_t = sin_t; m.rot_cs = a.rot_cs; m.B = L; m.n = n; m.K = K; m.nx = nx; m.ny = ny; m.step = step;
+    m.max_range = max_range; m.cap = cap; m.keys = a.keys; m.best_out = a.best; m.best_cost_out = a.best_cost; m.used_out = a.used;
+    RefineArgs r;
+    r.g = g->d; r.field = field; r.ranges = a.scan; r.range_stride = n; r.poses = a.start; r.maps = a.refine_maps;
+    r.cos_t = cos_t; r.sin_t = sin_t; r.B = L; r.n = n; r.iters = iters; r.damping = damping; r.step_xy = step_cells / g->d.scale;
+    r.step_rad = step_rad; r.max_range = max_range; r.cap = cap; r.pose_out = a.refined; r.cost_out = a.refine_cost;
+    r.status_out = a.refine_status;
+    for (int s = 0; s < S; ++s) {
+        TRY(enqueue_field(c, g, cap, fp, field));                     // the map as every earlier scan left it
+        {
+            Timed t(c, SLAM_K_GRID);
+            HIPCHK(launch_track_predict(a, s, c->stream));
+            HIPCHK(launch_match(m, c->stream));
+            HIPCHK(launch_track_seed(a, c->stream));
+            HIPCHK(launch_refine(r, c->stream));
+            HIPCHK(launch_track_decide(a, s, c->stream));
+        }
+        TRY(cast_particles(c, g, a.scan, cos_t, sin_t, a.cast_pose, a.acc, L, 1, n, map0));
+    }
+    return SLAM_OK;
+}
+
+int slam_track(slam_ctx *c, slam_grid *g, const float *ranges, const double *motion, int L, int S, const double *cos_t,
+               const double *sin_t, int n, const double *rot_off, const double *rot_off_cs, int K, int nx, int ny, double step, int iters,
+               double damping, double step_cells, double step_rad, float max_range, int cap, int min_used, double gate_dist,
+               double gate_turn, int map0, double *state, double *poses_out, int32_t *info_out, double *trace_out)
+{
+    TRY(use(c));
+    TRY(check_track(__func__, g, ranges, L, S, cos_t, sin_t, n, rot_off, rot_off_cs, K, nx, ny, step, iters, damping, step_cells,
+                    step_rad, max_range, cap, min_used, gate_dist, gate_turn, map0, state, poses_out, info_out));
+    const size_t LS = (size_t)L * S;
+    float *d_r; double *d_m, *d_c, *d_s, *d_ro, *d_rc, *d_st, *d_po, *d_tr; int32_t *d_in;
+    Staging s(c);
+    s.in(d_r, ranges, LS * n).in(d_m, motion, LS * 3).in(d_c, cos_t, n).in(d_s, sin_t, n).in(d_ro, rot_off, K)
+        .in(d_rc, rot_off_cs, (size_t)K * 2).inout(d_st, state, (size_t)L * SLAM_TRACK_STATE_LEN).out(d_po, poses_out, LS * 3)
+        .out(d_in, info_out, LS * SLAM_TRACK_INFO_LEN).out(d_tr, trace_out, LS * SLAM_TRACK_TRACE_LEN);
+    TRY(s.upload());
+    TRY(slam_track_dev(c, g, d_r, d_m, L, S, d_c, d_s, n, d_ro, d_rc, K, nx, ny, step, iters, damping, step_cells, step_rad, max_range,
+                       cap, min_used, gate_dist, gate_turn, map0, d_st, d_po, d_in, d_tr));
+    TRY(s.download());
     return check_status_sync(c);
 }
 

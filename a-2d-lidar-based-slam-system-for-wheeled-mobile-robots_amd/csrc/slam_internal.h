@@ -8,6 +8,7 @@
 
 #include "slam_hip.h"
 #include "slam_refine.h"
+#include "slam_track.h"
 #include "launch_shapes.h"
 
 #include <hip/hip_ext.h>
@@ -286,6 +287,40 @@ struct RefineArgs {
     int32_t *status_out = nullptr;           // [B]
 };
 hipError_t launch_refine(const RefineArgs &a, hipStream_t s);
+
+// ---- the scan-to-map tracker's steps around the matcher, the refinement and the cast (track_kernels.hip, include/slam_track.h) ----
+// Everything but the caller's arrays is workspace of slam_track_dev, [L] rows each, rewritten for every scan.
+struct TrackArgs {
+    const float *ranges = nullptr;           // [L][S][n]
+    const double *motion = nullptr;          // nullable [L][S][3]
+    const double *rot_off = nullptr;         // [K]
+    const double *rot_off_cs = nullptr;      // [K][2]
+    int L = 0, S = 0, n = 0, K = 0, nx = 0, ny = 0;
+    double step = 0.0;
+    int min_used = 1, map0 = 0;
+    double gate_dist = 0.0, gate_turn = 0.0;
+    double scale = 0.0, off_x = 0.0, off_y = 0.0;            // the grid's index rule
+    double *state = nullptr;                 // [L][8], in and out
+    double *poses_out = nullptr;             // [L][S][3]
+    int32_t *info_out = nullptr;             // [L][S][4]
+    double *trace_out = nullptr;             // nullable [L][S][13]
+    float *scan = nullptr;                   // [L][n]: this scan's rows
+    double *pred = nullptr;                  // [L][5]: pred, c0, s0
+    double *centres = nullptr;               // [L][2]      the matcher's inputs ...
+    double *rot_cs = nullptr;                // [L][K][2]
+    int32_t *match_maps = nullptr;           // [L]: map0 + l, or -1 for a first scan
+    unsigned long long *keys = nullptr;      // [L]
+    int32_t *best = nullptr, *best_cost = nullptr, *used = nullptr;      // ... and its outputs
+    double *start = nullptr;                 // [L][3]      the refinement's start poses (the matched poses) ...
+    int32_t *refine_maps = nullptr;          // [L]: map0 + l, or -1 where nothing is refined
+    double *refined = nullptr, *refine_cost = nullptr;       // [L][3], [L][2]: ... and its outputs
+    int32_t *refine_status = nullptr;        // [L]
+    int32_t *acc = nullptr;                  // [L]: the cast's skip marks (SLAM_MCL_DEAD: not integrated)
+    double *cast_pose = nullptr;             // [L][3]: the pose each scan is cast from
+};
+hipError_t launch_track_predict(const TrackArgs &a, int s, hipStream_t st);
+hipError_t launch_track_seed(const TrackArgs &a, hipStream_t st);
+hipError_t launch_track_decide(const TrackArgs &a, int s, hipStream_t st);
 
 // ---- global scan localisation on a pyramid of the field (locate_kernels.hip) --------------
 // Level h of the pyramid: P_h[x][y] for -pad <= x < xw, -pad <= y < yw (pad = 2^h - 1) at base[(gi * X + x + pad) * Y + y + pad];
